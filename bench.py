@@ -4,8 +4,13 @@ pre-extracted 36x2048 region features, V=10k, length 20, sentiment-word attentio
 (BASELINE.json metric). One "step" = one greedy roll-out of a batch of B captions per GPU,
 inputs resident in HBM, weights random-init of the reference architecture.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --scaling weak|strong]
+    python bench.py [--gpus N --steps K --warmup W --batch B --scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last
+timed roll-out returned (rank 0's shard) as DIR/<name>.npy.  Everything else - the CPU baseline and the side
+measurements in `extra` (other engines, batches, beam search, training and RL iterations, scans, epochs) - runs only
+with `--full`.
 
 Images are independent, so multi-GPU is a pure shard of the batch (no data-path collective):
 weak scaling (default), value = N*B*K captions / max-over-ranks time; `--scaling strong` keeps the GLOBAL batch at B.
@@ -13,15 +18,15 @@ weak scaling (default), value = N*B*K captions / max-over-ranks time; `--scaling
 torch.distributed.run, 127.0.0.1 rendezvous) BEFORE this process makes any GPU call, relays rank 0's one JSON line and
 exits with the launcher's code; it refuses (exit 2) when the box has fewer than N GPUs, and a launcher whose WORLD_SIZE
 differs from --gpus is an error - a line can never say n_gpus: 1 for a --gpus 8 request.
-With N > 1 the line's `extra` carries the training curves of BASELINE configs[3] / [4]: `xe_train` (fixed 128 captions per
-GPU: weak), `xe_train_strong` (fixed GLOBAL batch 1024 -> 1024/N per GPU), `rl_iteration` (Detector.forward under DP, global
-B=512) and `grad_allreduce` (the 88 MB arena all-reduce alone, RCCL over xGMI).
+With N > 1 and `--full` the line's `extra` carries the training curves of BASELINE configs[3] / [4]: `xe_train` (fixed
+128 captions per GPU: weak), `xe_train_strong` (fixed GLOBAL batch 1024 -> 1024/N per GPU), `rl_iteration`
+(Detector.forward under DP, global B=512) and `grad_allreduce` (the 88 MB arena all-reduce alone, RCCL over xGMI).
 
 Extra objects on the JSON line:
   roofline      dominant kernel (largest share of the decode step): achieved algorithmic
                 FLOP/s (or B/s) from HIP events recorded inside the timed region
   roofline_kernels   the same for every kernel of the step (incl. the HBM-bound attention scan)
-  cpu_baseline  the CPU oracle (a port of the reference, oracle/) timed on this box's host
+  cpu_baseline  (--full) the CPU oracle (a port of the reference, oracle/) timed on this box's host
                 cores on a bounded sample of the same workload
 """
 import argparse
@@ -82,7 +87,14 @@ def parse():
     ap.add_argument('--extras-deadline', type=float, default=420.0,
                     help='under a process group: seconds the side measurements may take before rank 0 writes the line '
                          'with what it has and leaves (HeadlineGuard)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the CPU baseline and the side measurements (extra); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one returned as DIR/<name>.npy (float32 / float64)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 import contextlib
@@ -105,6 +117,26 @@ def device_inputs(B, seed, dev, regions=R):
     d = synth.make_inputs(B, V, synth.DEFAULT_SETTINGS, regions=regions, seq_len=T, seed=seed)
     keys = ('fc_feats', 'att_feats', 'cpt_words', 'senti_words', 'senti_labels')
     return [torch.from_numpy(d[k]).to(dev) for k in keys], d
+
+
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, seq, seq_logprobs, seq_masks):
+    """--dump-outputs: what the roll-out handed its caller - tokens (as float64, exact), log-probabilities and masks, all
+    [B, T] - as <path>/<name>.npy.  Above DUMP_BYTES a fixed seeded sample of rows (ascending, written as rows.npy)
+    stands for the batch."""
+    arrs = {'seq': seq.cpu().numpy().astype(np.float64), 'seq_logprobs': seq_logprobs.cpu().numpy().astype(np.float32),
+            'seq_masks': seq_masks.cpu().numpy().astype(np.float32)}
+    B = arrs['seq'].shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrs.values())
+    if B * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_BYTES // (row_bytes + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs['rows'] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def usable_cores():
@@ -1051,6 +1083,8 @@ def run(args):
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         el = float(tt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, seq, lp, mk)
     # ---- the line's own part: everything the headline's measurements determine, BEFORE any side measurement runs
     total = world * B * args.steps
     summ = ops.TIMER.summary()
@@ -1115,7 +1149,7 @@ def run(args):
             'roofline_kernels': rest if scan is not None else entries[1:],
             'extra': ex,
         }
-        if not args.no_cpu_baseline and world == 1 and note is None:
+        if args.full and not args.no_cpu_baseline and world == 1 and note is None:
             out['cpu_baseline'] = cpu_baseline(weights, args.cpu_seconds)
         # LAST key: the driver's record keeps the tail of this line - the other half of BASELINE's metric (beam-5 p50) and
         # the training figures in one compact object
@@ -1183,7 +1217,7 @@ def run(args):
         run_jobs(jobs, extra, at)
 
     grouped = world > 1 or under_launcher
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if grouped and rank == 0:
             # the headline must reach stdout even if a side measurement fails or hangs on ANY rank (HeadlineGuard)
             guard = HeadlineGuard(compose, args.extras_deadline)

@@ -151,3 +151,47 @@ def test_a_rank_fatal_failure_is_not_swallowed_by_the_side_measurement_loop():
             "s.loader.exec_module(m); m.run_jobs([('c', lambda: (_ for _ in ()).throw(m.FatalUnderGroup('x')))], {})" % BENCH)
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and 'FatalUnderGroup' in r.stderr
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_rows_above_the_cap(tmp_path):
+    """--dump-outputs: the roll-out's tokens, log-probabilities and masks as float .npy files; a batch above the cap is
+    represented by a fixed seeded sample of rows (rows.npy), the same on every run.  A plain run has --full off."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location('bench_mod3', BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.np = np
+    g = torch.Generator().manual_seed(0)
+    seq, lp = torch.randint(0, 10000, (6, 20), generator=g), torch.randn(6, 20, generator=g)
+    mk = (torch.rand(6, 20, generator=g) > 0.3).float()
+    bench.dump_outputs(str(tmp_path / 'small'), seq, lp, mk)
+    got = {f[:-4]: np.load(str(tmp_path / 'small' / f)) for f in os.listdir(str(tmp_path / 'small'))}
+    assert sorted(got) == ['seq', 'seq_logprobs', 'seq_masks']
+    assert got['seq'].dtype == np.float64 and (got['seq'] == seq.numpy()).all()
+    assert got['seq_logprobs'].dtype == np.float32 and (got['seq_logprobs'] == lp.numpy()).all()
+    assert got['seq_masks'].dtype == np.float32 and (got['seq_masks'] == mk.numpy()).all()
+    B = bench.DUMP_BYTES // (20 * 16) + 1000                     # just over the cap
+    big = torch.arange(B * 20, dtype=torch.int64).reshape(B, 20)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), big, big.float(), big.float())
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == ['rows.npy', 'seq.npy', 'seq_logprobs.npy', 'seq_masks.npy']
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= 64 * 10 ** 6
+    rows = np.load(str(tmp_path / 'a' / 'rows.npy')).astype(np.int64)
+    assert (np.diff(rows) > 0).all() and (np.load(str(tmp_path / 'a' / 'seq.npy')) == big.numpy()[rows]).all()
+    for f in files:
+        assert (np.load(str(tmp_path / 'a' / f)) == np.load(str(tmp_path / 'b' / f))).all()
+    saved = sys.argv
+    try:
+        sys.argv = ['bench.py']
+        a = bench.parse()
+    finally:
+        sys.argv = saved
+    assert a.full is False and a.dump_outputs is None
+
+
+def test_steps_below_one_are_refused():
+    r = _run(['--steps', '0'])
+    assert r.returncode == 2 and '--steps' in r.stderr and '"metric"' not in r.stdout

@@ -289,3 +289,40 @@ def test_config4_rl_training_iteration_at_full_size_vs_reference(golden):
         if gk in g.files and float(g[gk][0]) > 1e-6:          # (the alpha biases' true gradient is 0: Adam steps on noise)
             assert np.median(d) <= 1e-6, (k, float(np.median(d)))
             assert (d > 4e-6).mean() <= 0.1, (k, float((d > 4e-6).mean()))
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_what_the_last_one_returned(tmp_path):
+    """`bench.py` without --full: the headline only (no extra / cpu_baseline), `steps` timed steps, and with
+    --dump-outputs the last timed roll-out's arrays - equal to a direct greedy roll-out of the same seeded weights and
+    inputs (the roll-out is deterministic: tests/test_gpu_determinism.py)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    B, out = 64, tmp_path / 'dump'
+    r = subprocess.run([sys.executable, bench.__file__, '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', str(B),
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0
+    assert d['unit'] == 'captions/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['extra'] == {} and 'cpu_baseline' not in d
+    got = {k: np.load(str(out / (k + '.npy'))) for k in ('seq', 'seq_logprobs', 'seq_masks')}
+    assert sorted(os.listdir(str(out))) == ['seq.npy', 'seq_logprobs.npy', 'seq_masks.npy']
+    st = synth.DEFAULT_SETTINGS
+    cap = Captioner(synth.make_idx2word(bench.V), synth.SENTIMENT_CATEGORIES, st)
+    cap.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(bench.V, st, seed=0).items()})
+    cap.to(dev()).eval()
+    din = synth.make_inputs(B, bench.V, st, regions=bench.R, seq_len=bench.T, seed=100)
+    prev = ops.set_h3_mode(1)                                        # (bench.py's default engine selection)
+    try:
+        with torch.no_grad():
+            seq, lp, mk = cap(*[torch.from_numpy(din[k]).to(dev()) for k in KEYS], bench.T, 1, mode='rl')
+    finally:
+        ops.set_h3_mode(prev)
+    assert got['seq'].dtype == np.float64 and got['seq'].shape == (B, bench.T)
+    assert (got['seq'] == seq.cpu().numpy()).all() and (got['seq_masks'] == mk.cpu().numpy()).all()
+    np.testing.assert_allclose(got['seq_logprobs'], lp.cpu().numpy(), rtol=0, atol=1e-5)

@@ -22,5 +22,5 @@ echo mfma done
 timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/clk -- python3 $R/bench.py --steps 2 --warmup 1 $ARGS > $O/clk.log 2>&1 || echo clk pass failed
 echo clk done
 python3 $R/tools/pmc_summary.py $O/fetch $O/write $B $O/mfma $O/clk $O/stats > $O/pmc_summary.json
-cd $R && python3 bench.py --batch $B > $O/bench.json 2> $O/bench.err
+cd $R && python3 bench.py --full --batch $B > $O/bench.json 2> $O/bench.err
 echo bench done
