@@ -120,6 +120,7 @@ class BeamSelectArgs(C.Structure):
 
 
 ISC_COLSUM_MAX_JOBS, ISC_COLSUM_MAX_OUT = 24, 3
+ISC_SCALE_SRC_MAX = 4
 
 
 class ColsumJob(C.Structure):

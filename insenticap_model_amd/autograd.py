@@ -10,9 +10,11 @@ time-stacked buffers [T(+1), B, ...], and its backward is a reverse sweep in whi
     - weights are shared across time, so nothing is lost by deferring them.
 torch is used for memory, the autograd hook-up and (train mode) random numbers only.
 """
+import math
+
 import torch
 
-from . import ops
+from . import _lib, ops
 
 NN, TN = ops.NN, ops.TN
 
@@ -233,117 +235,384 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     return out, S
 
 
+# ------------------------------------------------------------------------------ backward: stages of both forms
+# (_backward below and autograd_pair._pair_backward: one reverse sweep each, the same stages around it)
+# gradients that start from zero: the attention scores' biases (softmax is shift invariant) and the two embeddings
+# (accumulated into, row by row)
+_ZEROED = ('attention.cont_att.att_alpha.bias', 'attention.senti_att.word_alpha.bias', 'senti_label_embed.0.weight',
+           'word_embed.0.weight')
+
+
+def _dims(cap):
+    st = cap.settings
+    return st['feat_emb_dim'], st['att_hid_dim'], st['rnn_hid_dim'], st['word_emb_dim'], cap.vocab_size
+
+
+def _nn(segs, out, acc=False):
+    return ops.gemm_problem(segs, out, NN, accumulate=acc)
+
+
+def _tn(segs, out, acc=False):
+    return ops.gemm_problem(segs, out, TN, accumulate=acc)
+
+
+class _Grads:
+    """Where a backward pass puts its parameter gradients.  Without a sink they fill the {param name: gradient}
+    dictionary the backward returns.  With one (`cap._grad_sink`, dp.GradSink: the data-parallel step) every gradient is
+    written straight into its view of the flat arena (zeroed before the backward), and bucket_done(b) starts bucket b's
+    all-reduce as soon as its last contraction is enqueued.  Bias gradients are column sums, deferred: every sum of a
+    bucket goes out in one isc_colsum_multi.
+    Gradient scale: the sweep is linear in what enters it, so everything entering is multiplied by a power of two S
+    (isc_grad_scale: the largest entering |gradient| -> 2^-4..2^-3) and the parameter gradients by 1/S at the end - both
+    exact - which keeps the f16 planes of the split-f16 contractions in their normal range."""
+
+    def __init__(self, cap, p, sink=None):
+        self.cap, self.p, self.sink = cap, p, sink
+        self.G, self.sums, self.gs, self.zeroed = {}, [], None, {}
+
+    def fill(self, specs, zeroed=_ZEROED):
+        """Zero tensors for (shape, dtype) `specs` and for the gradients named in `zeroed` out of ONE fill (each fill is a
+        launch of its own, ~4.5 us at any size); under a sink those gradients are the arena's."""
+        names = list(zeroed) if self.sink is None else []
+        out = self.cap._zeros_many(*specs, *[(self.p[n].shape, torch.float32) for n in names])
+        self.zeroed = dict(zip(names, out[len(specs):]))
+        return out[:len(specs)]
+
+    def scale(self, gs_z, sources, feats, dense=()):
+        """Picks S from `sources`, the attribute gradients `feats` and the dense log-prob gradients `dense` (their
+        maxima: one extra pass each) into the zeroed float32[4] gs_z.  Returns (S as a [1] device tensor or None when
+        scaling is off, `feats` times S)."""
+        if not getattr(self.cap, 'grad_scaling', True):
+            return None, feats
+        srcs = list(sources) + [x.contiguous() if x is not None else None for x in feats]
+        ops.grad_scale(srcs, gs_z, [d.abs().amax().reshape(1) for d in dense if d is not None])
+        self.gs = gs_z
+        return gs_z[0:1], [x * gs_z[0] if x is not None else None for x in feats]
+
+    def gout(self, name, *shape):
+        """The tensor parameter `name`'s gradient is computed into, viewed as `shape` (default: the parameter's); zero
+        for the fill's `zeroed`."""
+        if self.sink is not None:
+            t = self.sink.out(name)
+        else:                           # (parameter-shaped: autograd checks the shape of what the node returns)
+            t = self.G[name] = self.zeroed.pop(name) if name in self.zeroed else self.cap._new(*self.p[name].shape)
+        if not shape:
+            return t
+        assert t.numel() == math.prod(shape), (name, tuple(t.shape), shape)
+        return t.view(*shape)
+
+    def put(self, name, t):
+        """Gradient `name` computed elsewhere: t itself, or under a sink a copy in the arena."""
+        if self.sink is not None:
+            self.sink.out(name).copy_(t)
+        else:
+            self.G[name] = t
+
+    def tn(self, a, w, name):
+        out = self.gout(name, a.shape[1], w.shape[1])
+        ops.gemm_bwd([_tn([(a, w)], out)], TN)
+        return out
+
+    def csum(self, x, *names):
+        """Column sum of x into the gradient(s) `names` (several: tied biases share one reduction), deferred."""
+        self.sums.append((x, [self.gout(n, x.shape[1]) for n in names], False))
+
+    def bucket_done(self, b):
+        """Every gradient of bucket b (dp.GradSink.STARTS) is enqueued: its bias sums go out, then - under a sink - the
+        bucket is unscaled in one launch and its all-reduce starts."""
+        ops.colsum_multi(self.sums)
+        del self.sums[:]
+        if self.sink is not None:
+            self.sink.ready(b, unscale=self.gs[1] if self.gs is not None else None)
+
+    def finish(self):
+        """The last bias sums, the gradients x 1/S (without a sink); returns the dictionary."""
+        ops.colsum_multi(self.sums)
+        del self.sums[:]
+        if self.sink is None and self.gs is not None:
+            torch._foreach_mul_(list(self.G.values()), self.gs[1])
+        return self.G
+
+
+def _step_bwd_plan(cap, p, Pc, Ps):
+    """isc_step_bwd_plan of a reverse sweep: the weights, the split-K workspace and the prologue operands of the content
+    attention (from Pc) and of the sentiment attention (from Ps); None: that attention is not in the plan's rows."""
+    bp = _lib.StepBwdPlan()
+    E, A, H, Wd, _ = _dims(cap)
+    bp.H, bp.E, bp.A, bp.W = H, E, A, Wd
+    for field, key in (('Wih1', 'att_lstm.weight_ih'), ('Whh1', 'att_lstm.weight_hh'),
+                       ('Wih2', 'lang_lstm.weight_ih'), ('Whh2', 'lang_lstm.weight_hh'),
+                       ('W_h2att', 'attention.cont_att.h2att.weight'),
+                       ('w_alpha_c', 'attention.cont_att.att_alpha.weight'),
+                       ('W_h2word', 'attention.senti_att.h2word.weight'),
+                       ('w_alpha_s', 'attention.senti_att.word_alpha.weight'),
+                       ('W_gh', 'attention.h2att.weight'), ('W_gc', 'attention.cont2att.weight'),
+                       ('W_gs', 'attention.senti2att.weight'), ('w_gate', 'attention.att_alpha.weight')):
+        setattr(bp, field, p[key].data_ptr())
+    if Pc is not None:
+        bp.R, bp.att_p, bp.att_e = Pc.R, Pc.att_p3.data_ptr(), Pc.att_e3.data_ptr()
+    if Ps is not None:
+        bp.Mw, bp.words_p, bp.words_e = Ps.Mw, Ps.words_p3.data_ptr(), Ps.words_e3.data_ptr()
+        bp.label_w = ops.ptr(Ps.label_w)
+    skws = ops.splitk_ws(cap._dev)
+    bp.splitk_ws, bp.splitk_ws_floats = skws.data_ptr(), skws.numel()
+    return bp
+
+
+def _dlogits(lazy, d, logp, sparse, out, B, T, V, step_rows, scale):
+    """d logits of one call's B x T positions into `out`, time-major at step_rows rows per step: the softmax term from
+    the log-probs logp, or - lazy = (raw, ld_b, ld_t, part_max, part_sum) - from the raw logits and their statistics."""
+    if lazy is not None:
+        raw, ld_b, ld_t, pm, ps = lazy
+        ops.logsoftmax_bwd_raw(raw, ld_b, ld_t, B, T, V, pm, ps, step_rows, list(sparse), out, scale=scale,
+                               out_step_rows=step_rows)
+    else:
+        ops.logsoftmax_bwd_sparse(d, logp, list(sparse), out, B * T, V, remap_T=T, scale=scale, out_step_rows=step_rows)
+
+
+def _classifier_bwd(cap, g, dlogits, hs):
+    """The classifier behind d logits [n, Vp] (zero-padded to Vp = _pad32(V) columns) and its input h_lang hs [n, H]:
+    W_c's and the bias's gradients into g; returns d h [n, H]."""
+    V, (n, H) = cap.vocab_size, hs.shape
+    Vp = dlogits.shape[1]
+    Wc = g.p['classifier.weight']
+    dhd = cap._new(n, H)
+    # d h = d logits . W_c contracts over the vocabulary; the split-f16 kernels want a multiple of 32
+    Vm = V // 32 * 32
+    if Vp != V and n >= 8192:
+        # d logits is already zero-padded to Vp columns: give W_c the matching zero rows (a 20 MB copy; worth it from
+        # ~100 GFLOP on, where the large kernels run the contraction)
+        # NOT inside the weights scope: a scope keeps (pointer, planes) of every W operand it sees and the optimizer
+        # re-splits them all after its step - from the pointer.  This copy dies with the call; its planes are built in
+        # the workspace (one split launch).
+        Wc_k = cap._zeros(Vp, H)
+        Wc_k[:V].copy_(Wc)
+        ops.gemm_bwd([_nn([(dlogits, Wc_k)], dhd)], NN)
+    elif Vm != V and Vm >= 4096:
+        # fewer rows (B = 128: [2560 x 512] over K = 10 000): the first Vm vocabulary rows on the K-split skinny tile,
+        # the last V - Vm (< 32) on the fp32 tiles, accumulating
+        with _weights_scope(cap):
+            ops.gemm_bwd([_nn([(dlogits[:, :Vm], Wc[:Vm])], dhd)], NN)
+        ops.gemm_bwd([_nn([(dlogits[:, Vm:], Wc[Vm:])], dhd, True)], NN)
+    else:
+        with _weights_scope(cap):
+            ops.gemm_bwd([_nn([(dlogits, Wc)], dhd)], NN)
+    if V % 4 == 0:
+        g.tn(dlogits[:, :V], hs, 'classifier.weight')
+    else:            # vocabulary not a multiple of 4: contract on the zero-padded columns, then trim
+        dWp = cap._new(Vp, H)
+        ops.gemm_bwd([_tn([(dlogits, hs)], dWp)], TN)
+        g.put('classifier.weight', dWp[:V])
+    ops.colsum(dlogits[:, :V], g.gout('classifier.bias'))
+    return dhd
+
+
+def _lstm_dw(g, dG1, dG2, h1_prev, h1_cur, h2_prev, xt, feat, dG1_sum, fc_e, label_e):
+    """Both LSTM cells' weight and bias gradients, one contraction over all rows of the gate gradients dG1 (att-LSTM) /
+    dG2 (lang-LSTM) each - either None: that cell is left for another call.  Problems grouped by their dY operand:
+    isc_gemm_bwd splits a shared dY once and runs the group as one launch."""
+    H = h2_prev.shape[1]
+    if dG1 is not None:
+        gW1 = g.gout('att_lstm.weight_ih')
+        E = fc_e.shape[1]
+        ops.gemm_bwd([_tn([(dG1, h2_prev)], gW1[:, 0:H]), _tn([(dG1, xt)], gW1[:, H + E:]),
+                      _tn([(dG1, h1_prev)], g.gout('att_lstm.weight_hh'))], TN)
+    if dG2 is not None:
+        gW2 = g.gout('lang_lstm.weight_ih')
+        E = feat.shape[1]
+        ops.gemm_bwd([_tn([(dG2, feat)], gW2[:, 0:E]), _tn([(dG2, h1_cur)], gW2[:, E:]),
+                      _tn([(dG2, h2_prev)], g.gout('lang_lstm.weight_hh'))], TN)
+    if dG1 is not None:
+        # xt = relu(Emb[tok]) + label_e: the per-step part contracted over the rows above, the label part (and fc_e) once
+        # per caption here - dG1_sum = sum_t dG1[t]
+        once = [_tn([(dG1_sum, fc_e)], gW1[:, H:H + E])]
+        if label_e is not None:
+            once.append(_tn([(dG1_sum, label_e)], gW1[:, H + E:], True))
+        ops.gemm_bwd(once, TN)
+        g.csum(dG1, 'att_lstm.bias_ih', 'att_lstm.bias_hh')
+    if dG2 is not None:
+        g.csum(dG2, 'lang_lstm.bias_ih', 'lang_lstm.bias_hh')
+
+
+def _dx_bwd(cap, g, dG1, dG1_sum, tok, with_label):
+    """Inputs of the att-LSTM: d fc_e and d label_e (rows of dG1_sum), d xt over the rows of dG1 - and through
+    xt = relu(Emb[tok]) into the word embedding's gradient (its first accumulation).  Returns (d_fc_e, d_label_e, dEmb)."""
+    p, new = g.p, cap._new
+    E, _, H, Wd, _ = _dims(cap)
+    Wih1 = p['att_lstm.weight_ih']
+    d_fc_e = new(dG1_sum.shape[0], E)
+    d_label_e = new(dG1_sum.shape[0], Wd) if with_label else None
+    dxt = new(dG1.shape[0], Wd)
+    probs = [_nn([(dG1_sum, Wih1[:, H:H + E])], d_fc_e), _nn([(dG1, Wih1[:, H + E:])], dxt)]
+    if d_label_e is not None:
+        probs.append(_nn([(dG1_sum, Wih1[:, H + E:])], d_label_e))
+    with _weights_scope(cap):      # dX over all rows: split-f16 on planes of the W_ih slices' transposes
+        ops.gemm_bwd(probs, NN)
+    dEmb = g.gout('word_embed.0.weight')
+    # nn.Embedding(padding_idx=pad_id): the <PAD> row never gets a gradient - every accumulation into dEmb skips it
+    ops.embed_relu_bwd(p['word_embed.0.weight'], tok, dxt, dEmb, dG1.shape[0], skip_id=cap.pad_id)
+    return d_fc_e, d_label_e, dEmb
+
+
+def _content_att_grads(g, dqa, h1_cur, dwc_rows):
+    """Content attention's own parameters from the sweep's dqa [T, n, A] (h2att over all rows) and alpha partials."""
+    dqaf = dqa.view(-1, dqa.shape[2])
+    g.tn(dqaf, h1_cur, 'attention.cont_att.h2att.weight')
+    g.csum(dqaf, 'attention.cont_att.h2att.bias')
+    g.csum(dwc_rows, 'attention.cont_att.att_alpha.weight')
+    g.gout('attention.cont_att.att_alpha.bias')          # softmax is shift invariant
+
+
+def _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, label_e, lo=0, d_label_e=None):
+    """Sentiment attention's own parameters from the sweep's dqw [T, n, A] (the branch's rows: [lo, n) - the others are
+    zero) and alpha partials.  label2word(label_e) enters every step's score: d label_w = sum_t dqw[t], returned (None
+    without labels) and, given d_label_e, accumulated into it."""
+    T, n, A = dqw.shape
+    dqwf = dqw.view(T * n, A)
+    g.tn(dqwf, h1_cur, 'attention.senti_att.h2word.weight')
+    g.csum(dqwf, 'attention.senti_att.h2word.bias')
+    g.csum(dws_rows, 'attention.senti_att.word_alpha.weight')
+    g.gout('attention.senti_att.word_alpha.bias')
+    if label_e is None:
+        return None
+    d_label_w = cap._new(n * A)
+    ops.colsum(dqw.view(T, n * A), d_label_w)
+    d_label_w = d_label_w.view(n, A)[lo:]
+    g.tn(d_label_w, label_e, 'attention.senti_att.label2word.weight')
+    g.csum(d_label_w, 'attention.senti_att.label2word.bias')
+    if d_label_e is not None:
+        ops.gemm_bwd([_nn([(d_label_w, g.p['attention.senti_att.label2word.weight'])], d_label_e, True)], NN)
+    return d_label_w
+
+
+def _scan_bwd(cap, p3, e3, alpha, q, dfeat, de, w, step_rows=0, q2=None):
+    """An attention's dV = sum_t alpha_t x d feat_t and dP from every step's d e, formed once after the sweep (dfeat:
+    [T, B, D], or the rows of a [T, step_rows, D] stack).  Returns (dP, dV), shaped as the projections p3 / e3."""
+    dP, dV = cap._new(*p3.shape), cap._new(*e3.shape)
+    ops.attn_dv_from_alpha(alpha, dfeat, dV, step_rows=step_rows)
+    ops.attn_dp_from_de(p3, q, w, de, dP, q2=q2)
+    return dP, dV
+
+
+def _region_embed_bwd(cap, g, P, dP, dV):
+    """att2att -> att_embed of the regions."""
+    B, R, A = P.att_p3.shape
+    E, BR = P.att_e3.shape[2], B * R
+    att_e, att_p = P.att_e3.view(BR, E), P.att_p3.view(BR, A)
+    dzp = cap._new(BR, A)
+    ops.relu_mask_bwd(dP.view(BR, A), att_p, dzp)
+    g.tn(dzp, att_e, 'att2att.0.weight')
+    g.csum(dzp, 'att2att.0.bias')
+    dVa = dV.view(BR, E)
+    ops.gemm_bwd([_nn([(dzp, g.p['att2att.0.weight'])], dVa, True)], NN)
+    dze = cap._new(BR, E)
+    ops.relu_mask_bwd(dVa, att_e, dze, keep_mask=P.m_att, scale=P.sc)
+    g.tn(dze, P.x_att, 'att_embed.0.weight')
+    g.csum(dze, 'att_embed.0.bias')
+
+
+def _senti2att_bwd(cap, g, P, dP):
+    """senti2att of the sentiment words; returns d of its pre-activation [B*Mw, A] (for _senti_words_bwd)."""
+    B, Mw, A = P.words_p3.shape
+    dzw = cap._new(B * Mw, A)
+    ops.relu_mask_bwd(dP.view(B * Mw, A), P.words_p3.view(B * Mw, A), dzw)
+    g.tn(dzw, P.words_e3.view(B * Mw, -1), 'senti2att.0.weight')
+    g.csum(dzw, 'senti2att.0.bias')
+    return dzw
+
+
+def _senti_words_bwd(cap, g, P, dzw, dV, dEmb):
+    """The sentiment words' embedding rows: dV plus senti2att's input gradient, accumulated into dEmb."""
+    B, Mw, Wd = dV.shape
+    dVw = dV.view(B * Mw, Wd)
+    ops.gemm_bwd([_nn([(dzw, g.p['senti2att.0.weight'])], dVw, True)], NN)
+    ops.embed_relu_bwd(g.p['word_embed.0.weight'], P.sw_ids, dVw, dEmb, B * Mw, pad_first=Mw, pad_id=cap.pad_id,
+                       keep_mask=P.m_words, mask_scale=P.sc, skip_id=cap.pad_id)
+
+
+# P.fc_pre / P.cpt_pre: the tensors the `fc_feats` / `cpt_feats` attributes expose (pre-dropout; equal to the post-dropout
+# ones in sign wherever the keep-mask is 1, and their gradients ignore the mask).  fc_pre is None in seq2seq, where
+# fc_e := dropout(cpt_feats) (captioner.py:250-251).
+def _fc_embed_bwd(cap, g, P, d_fc_e, d_fc_feats):
+    """fc_embed (xe / rl): from d fc_e and the fc_feats attribute's gradient."""
+    dzf = cap._new(*d_fc_e.shape)
+    ops.relu_mask_bwd(d_fc_e, P.fc_e, dzf, keep_mask=P.m_fc, scale=P.sc)
+    if d_fc_feats is not None:
+        extra = cap._new(*d_fc_e.shape)
+        ops.relu_mask_bwd(d_fc_feats.contiguous(), P.fc_pre, extra)
+        dzf = dzf + extra
+    g.tn(dzf, P.x_fc, 'fc_embed.0.weight')
+    g.csum(dzf, 'fc_embed.0.bias')
+
+
+def _cpt_bwd(cap, P, d_fc_e, d_cpt_feats, out):
+    """d cpt (cpt2fc's output) of one call's rows into `out`: the cpt_feats attribute's gradient, and in seq2seq the
+    path through fc_e."""
+    if P.fc_pre is not None:
+        ops.relu_mask_bwd(d_cpt_feats.contiguous(), P.cpt, out)
+        return
+    ops.relu_mask_bwd(d_fc_e, P.cpt, out, keep_mask=P.m_cpt, scale=P.sc)
+    if d_cpt_feats is not None:
+        extra = cap._new(*out.shape)
+        ops.relu_mask_bwd(d_cpt_feats.contiguous(), P.cpt_pre, extra)
+        out += extra
+
+
+def _cpt2fc_bwd(cap, g, d_cpt, Ps, dEmb):
+    """cpt2fc and the concept words' mean embedding (accumulated into dEmb) over the rows of d_cpt: the rows of the
+    prologues Ps, in order."""
+    def rows(xs):
+        return xs[0] if len(xs) == 1 else torch.cat(xs)
+    p = g.p
+    g.tn(d_cpt, rows([P.cmean for P in Ps]), 'cpt2fc.0.weight')
+    g.csum(d_cpt, 'cpt2fc.0.bias')
+    dcm = cap._new(d_cpt.shape[0], p['cpt2fc.0.weight'].shape[1])
+    ops.gemm_bwd([_nn([(d_cpt, p['cpt2fc.0.weight'])], dcm)], NN)
+    C = Ps[0].cpt_ids.shape[1]
+    if any(P.cpt_ids.shape[1] != C for P in Ps):
+        raise ValueError('merged unrolls: the two calls carry different numbers of concept words')
+    ops.embed_relu_bwd(p['word_embed.0.weight'], rows([P.cpt_ids for P in Ps]).view(-1), dcm, dEmb, d_cpt.shape[0] * C,
+                       rows_per_grad=C, scale=1.0 / C, skip_id=cap.pad_id)
+
+
 # ------------------------------------------------------------------------------ backward
 def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     """Returns {param name: gradient}.  The gradient of the log-probs arrives as `dlogp` [B,T,V] (contiguous; None when
     every consumer handed its part over sparse) plus `sparse` = [(ids [B,T] int64, coef [B,T] fp32)]: coef at column ids
     of each row (XELossFn / GatherLogpFn below).  Optional gradients of the `fc_feats` (pre-dropout) and `cpt_feats`
-    attributes.
-    Gradient scale: the sweep is linear in what enters it, so everything entering is multiplied by a power of two S
-    (isc_grad_scale: the largest entering |gradient| -> 2^-4..2^-3) and the parameter gradients by 1/S at the end -
-    both exact - which keeps the f16 planes of the split-f16 contractions in their normal range."""
+    attributes.  Gradient scale and outputs: _Grads."""
     p, P, B, T = S.p, S.P, S.B, S.T
-    st = cap.settings
-    E, A, H, Wd, V = st['feat_emb_dim'], st['att_hid_dim'], st['rnn_hid_dim'], st['word_emb_dim'], cap.vocab_size
+    E, A, H, Wd, V = _dims(cap)
     new, zeros = cap._new, cap._zeros
     has_c, has_s = P.att_e3 is not None, P.words_e3 is not None
     gate = has_c and has_s
-    G = {}
     TB = T * B
-
-    def nn(segs, out, acc=False):
-        return ops.gemm_problem(segs, out, NN, accumulate=acc)
-
-    def tn(a, w, shape=None):
-        out = new(a.shape[1], w.shape[1])
-        ops.gemm_bwd([ops.gemm_problem([(a, w)], out, TN)], TN)
-        return out
-
-    pending_sums = []      # (x, outs): every bias gradient of the sweep goes out in one isc_colsum_multi at the end
-
-    def csum(x, copies=1):
-        """Column sum of x, deferred; `copies` > 1: that many identical results (tied biases) from one reduction."""
-        outs = [new(x.shape[1]) for _ in range(copies)]
-        pending_sums.append((x, outs, False))
-        return outs[0] if copies == 1 else outs
+    g = _Grads(cap, p)
 
     # ---- classifier + log-softmax: outside the recurrence, all T*B rows at once (time-major rows)
     Vp = _pad32(V)
     pk = getattr(S, 'packed', None)
     dlogits = new(TB if pk is None else pk['Np'], Vp)
-    # everything the sweep wants zeroed comes out of ONE fill (each fill is a launch of its own, ~4.5 us at any size)
-    n_lab = p['senti_label_embed.0.weight'].shape[0] if P.label_e is not None else 1
-    f32 = torch.float32
-    gs_z, dG1_sum, zero_a, zero_b, dL_z, dEmb = cap._zeros_many(((4,), f32), ((B, 4 * H), f32), ((1,), f32), ((1,), f32),
-                                                                ((n_lab, Wd), f32), ((V, Wd), f32))
-    gs = None
-    if getattr(cap, 'grad_scaling', True):
-        gs = gs_z
-        srcs = [c for _, c in sparse] + [d_fc_feats.contiguous() if d_fc_feats is not None else None,
-                                         d_cpt_feats.contiguous() if d_cpt_feats is not None else None]
-        if dlogp is not None:
-            srcs.append(dlogp.abs().amax().reshape(1))        # (a caller-defined dense loss: one extra pass)
-        ops.grad_scale(srcs, gs)
-        if d_fc_feats is not None:
-            d_fc_feats = d_fc_feats * gs[0]
-        if d_cpt_feats is not None:
-            d_cpt_feats = d_cpt_feats * gs[0]
+    gs_z, dG1_sum = g.fill((((4,), torch.float32), ((B, 4 * H), torch.float32)))
+    scale, (d_fc_feats, d_cpt_feats) = g.scale(gs_z, [c for _, c in sparse], (d_fc_feats, d_cpt_feats), [dlogp])
     if pk is not None:
         # ragged, packed classifier block (see _train_forward): d logits over the N rows inside their captions
         N = pk['N']
         sp = [(i.reshape(-1).index_select(0, pk['idx_bt']).contiguous(), c.reshape(-1).index_select(0, pk['idx_bt']).contiguous())
               for i, c in sparse]
         if sp:
-            ops.logsoftmax_bwd_raw(pk['raw'], V, 0, N, 1, V, pk['pm'], pk['ps'], N, sp, dlogits,
-                                   scale=gs[0:1] if gs is not None else None, out_step_rows=N)
+            _dlogits((pk['raw'], V, 0, pk['pm'], pk['ps']), None, None, sp, dlogits, N, 1, V, N, scale)
             if pk['Np'] > N:
                 dlogits[N:].zero_()
         else:
             dlogits.zero_()
     elif dlogp is None and not sparse:
         dlogits.zero_()
-    elif getattr(S, 'lazy', None) is not None:               # the log-probs were never formed: softmax from raw logits + stats
-        rl, ld_b, ld_t = S.lazy
-        ops.logsoftmax_bwd_raw(rl, ld_b, ld_t, B, T, V, S.pm, S.ps, B, list(sparse), dlogits,
-                               scale=gs[0:1] if gs is not None else None, out_step_rows=B)
-    else:
-        ops.logsoftmax_bwd_sparse(dlogp, S.logp, list(sparse), dlogits, B * T, V, remap_T=T,
-                                  scale=gs[0:1] if gs is not None else None)
-    Wc = p['classifier.weight']
+    else:                       # (lazy: the log-probs were never formed - softmax from raw logits + stats)
+        lazy = getattr(S, 'lazy', None)
+        _dlogits(lazy and (*lazy, S.pm, S.ps), dlogp, S.logp, sparse, dlogits, B, T, V, B, scale)
     hdrop_tb = (S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(TB, H) if pk is None else pk['hs']
-    n_rows = TB if pk is None else pk['Np']
-    dhd = new(n_rows, H)
-    # d h = d logits . W_c contracts over the vocabulary; the split-f16 kernels want a multiple of 32
-    Vm = V // 32 * 32
-    if Vp != V and n_rows >= 8192:
-        # d logits is already zero-padded to Vp columns: give W_c the matching zero rows (a 20 MB copy; worth it from
-        # ~100 GFLOP on, where the large kernels run the contraction)
-        # NOT inside the weights scope: a scope keeps (pointer, planes) of every W operand it sees and the optimizer
-        # re-splits them all after its step - from the pointer.  This copy dies with the call; its planes are built in
-        # the workspace (one split launch).
-        Wc_k = zeros(Vp, H)
-        Wc_k[:V].copy_(Wc)
-        ops.gemm_bwd([nn([(dlogits, Wc_k)], dhd)], NN)
-    elif Vm != V and Vm >= 4096:
-        # fewer rows (B = 128: [2560 x 512] over K = 10 000): the first Vm vocabulary rows on the K-split skinny tile,
-        # the last V - Vm (< 32) on the fp32 tiles, accumulating
-        with _weights_scope(cap):
-            ops.gemm_bwd([nn([(dlogits[:, :Vm], Wc[:Vm])], dhd)], NN)
-        ops.gemm_bwd([nn([(dlogits[:, Vm:], Wc[Vm:])], dhd, True)], NN)
-    else:
-        with _weights_scope(cap):
-            ops.gemm_bwd([nn([(dlogits, Wc)], dhd)], NN)
-    if V % 4 == 0:
-        dWc = new(V, H)
-        ops.gemm_bwd([ops.gemm_problem([(dlogits[:, :V], hdrop_tb)], dWc, TN)], TN)
-    else:            # vocabulary not a multiple of 4: contract on the zero-padded columns, then trim
-        dWp = new(Vp, H)
-        ops.gemm_bwd([ops.gemm_problem([(dlogits, hdrop_tb)], dWp, TN)], TN)
-        dWc = dWp[:V].contiguous()
-    G['classifier.weight'] = dWc
-    db = new(Vp)
-    ops.colsum(dlogits, db)
-    G['classifier.bias'] = db[:V].contiguous() if Vp != V else db
+    dhd = _classifier_bwd(cap, g, dlogits, hdrop_tb)
     if pk is not None:          # d h_lang back in [T,B] order, zero behind the captions' ends
         dhd = zeros(TB, H).index_copy_(0, pk['idx_tb'], dhd[:pk['N']])
     if S.hdrop is not None:     # nn.Dropout on h_lang (captioner.py:182)
@@ -351,8 +620,6 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
         ops.relu_mask_bwd(dhd, None, dhd, keep_mask=mk, scale=S.out_scale)
     dhd = dhd.view(T, B, H)
 
-    Wih1, Whh1 = p['att_lstm.weight_ih'], p['att_lstm.weight_hh']
-    Wih2, Whh2 = p['lang_lstm.weight_ih'], p['lang_lstm.weight_hh']
     # ragged unroll (see _train_forward): step t sweeps rows [0, counts[t]); everything a skipped row would have written
     # - its gradients, and the carries a row reads at the LAST step of its caption - is zero from a fill
     counts = getattr(S, 'row_counts', None)
@@ -372,50 +639,30 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     else:
         dG1, dG2 = new(T, B, 4 * H), new(T, B, 4 * H)
     # d feat of every step is kept ([T,B,E]): where it is the scan's output gradient, dV = sum_t alpha_t x dout_t is
-    # formed once after the sweep (ops.attn_dv_from_alpha) instead of a read-modify-write of [B,R,E] at every step
+    # formed once after the sweep (_scan_bwd) instead of a read-modify-write of [B,R,E] at every step
     d_feat_all, dh1 = new(T, B, E), new(B, H)
     dh2_rec, dh1_rec = new(B, H), new(B, H)
     dc1_rec, dc2_rec = [new(B, H), new(B, H)], [new(B, H), new(B, H)]
     if has_c:
         dqa, dv_all = new(T, B, A), (new(T, B, E) if gate else d_feat_all)
-        dP_att, dV_att = new_full(B, P.R, A), new_full(B, P.R, E)
-        de_c = new(T, B, P.R)           # d e of every step: dP is formed once after the sweep (ops.attn_dp_from_de)
+        de_c = new(T, B, P.R)           # d e of every step: dP is formed once after the sweep
         dwc_rows = new(B, A)
     if has_s:
         dqw, ds_all = new(T, B, A), (new(T, B, E) if gate else d_feat_all)
-        dP_w, dV_w = new_full(B, P.Mw, A), new_full(B, P.Mw, Wd)
         de_s = new(T, B, P.Mw)
         dws_rows = new(B, A)
     if gate:
         dz = new(T, B, A)
         dwg_rows, dbg_rows = new(B, A), new(B)
     # reverse sweep: one library call per time step (isc_step_bwd enqueues the ~9 kernels of the step)
-    from . import _lib
-    bp = _lib.StepBwdPlan()
-    bp.rows, bp.H, bp.E, bp.A, bp.W, bp.R, bp.Mw = B, H, E, A, Wd, P.R, P.Mw
-    for field, key in (('Wih1', 'att_lstm.weight_ih'), ('Whh1', 'att_lstm.weight_hh'),
-                       ('Wih2', 'lang_lstm.weight_ih'), ('Whh2', 'lang_lstm.weight_hh'),
-                       ('W_h2att', 'attention.cont_att.h2att.weight'),
-                       ('w_alpha_c', 'attention.cont_att.att_alpha.weight'),
-                       ('W_h2word', 'attention.senti_att.h2word.weight'),
-                       ('w_alpha_s', 'attention.senti_att.word_alpha.weight'),
-                       ('W_gh', 'attention.h2att.weight'), ('W_gc', 'attention.cont2att.weight'),
-                       ('W_gs', 'attention.senti2att.weight'), ('w_gate', 'attention.att_alpha.weight')):
-        setattr(bp, field, p[key].data_ptr())
-    ptr = ops.ptr
-    for field, t_ in (('att_p', P.att_p3), ('att_e', P.att_e3), ('words_p', P.words_p3), ('words_e', P.words_e3),
-                      ('label_w', P.label_w)):
-        setattr(bp, field, ptr(t_))
-    skws = ops.splitk_ws(cap._dev)
-    bp.splitk_ws, bp.splitk_ws_floats = skws.data_ptr(), skws.numel()
+    bp = _step_bwd_plan(cap, p, P if has_c else None, P if has_s else None)
+    bp.rows = B
     bp.dG1_sum, bp.dh1 = dG1_sum.data_ptr(), dh1.data_ptr()
     bp.dh2_rec, bp.dh1_rec = dh2_rec.data_ptr(), dh1_rec.data_ptr()
     if has_c:
-        bp.dP_att, bp.dV_att, bp.dwc_rows = None, None, dwc_rows.data_ptr()
-        bp.alpha_c_ld = S.aC.stride(0)
+        bp.dwc_rows, bp.alpha_c_ld = dwc_rows.data_ptr(), S.aC.stride(0)
     if has_s:
-        bp.dP_w, bp.dV_w, bp.dws_rows = None, None, dws_rows.data_ptr()
-        bp.alpha_s_ld = S.aS.stride(0)
+        bp.dws_rows, bp.alpha_s_ld = dws_rows.data_ptr(), S.aS.stride(0)
     if gate:
         bp.dwg_rows, bp.dbg_rows = dwg_rows.data_ptr(), dbg_rows.data_ptr()
         bp.beta_ld = S.bG.stride(0)
@@ -453,17 +700,17 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
 
     new = new_full
     if has_c:
-        ops.attn_dv_from_alpha(S.aC, dv_all, dV_att)
-        ops.attn_dp_from_de(P.att_p3, S.qa, p['attention.cont_att.att_alpha.weight'], de_c, dP_att)
+        dP_att, dV_att = _scan_bwd(cap, P.att_p3, P.att_e3, S.aC, S.qa, dv_all, de_c,
+                                   p['attention.cont_att.att_alpha.weight'])
     if has_s:
-        ops.attn_dv_from_alpha(S.aS, ds_all, dV_w)
-        ops.attn_dp_from_de(P.words_p3, S.qw, p['attention.senti_att.word_alpha.weight'], de_s, dP_w, q2=P.label_w)
+        dP_w, dV_w = _scan_bwd(cap, P.words_p3, P.words_e3, S.aS, S.qw, ds_all, de_s,
+                               p['attention.senti_att.word_alpha.weight'], q2=P.label_w)
 
     # ---- weight gradients: one contraction over all T*B rows each
     h1_prev, h1_cur = S.h1[:T].reshape(TB, H), S.h1[1:].reshape(TB, H)
     h2_prev = S.h2[:T].reshape(TB, H)
     feat_tb = (S.f if gate else (S.v if has_c else S.s)).view(TB, E)
-    xt_tb, tok_tb, lstm_rows = S.xt.view(TB, Wd), S.tok.view(-1), TB
+    xt_tb, tok_tb = S.xt.view(TB, Wd), S.tok.view(-1)
     h1_cur_l = h1_cur               # (the LSTM groups' copy: the attention contractions below stay on [T,B] rows)
     if pk is None:
         dG1f, dG2f = dG1.view(TB, 4 * H), dG2.view(TB, 4 * H)
@@ -475,142 +722,41 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
             if pk['Np'] > pk['N']:
                 out[pk['N']:].zero_()
             return out
-        dG1f, dG2f, lstm_rows = dG1, dG2, pk['Np']
+        dG1f, dG2f = dG1, dG2
         h1_prev, h1_cur_l, h2_prev, feat_tb, xt_tb = pack(h1_prev), pack(h1_cur), pack(h2_prev), pack(feat_tb), pack(xt_tb)
         tok_tb = pack(tok_tb.view(TB, 1)).view(-1)
         if pk['Np'] > pk['N']:
             tok_tb[pk['N']:].fill_(cap.pad_id)
-    gW1 = new(4 * H, H + E + Wd)
-    gW2, gwhh1, gwhh2 = new(4 * H, E + H), new(4 * H, H), new(4 * H, H)
-    # problems grouped by their dY operand: isc_gemm_bwd splits a shared dY once and runs the group as one launch
-    ops.gemm_bwd([ops.gemm_problem([(dG1f, h2_prev)], gW1[:, 0:H], TN),
-                  ops.gemm_problem([(dG1f, xt_tb)], gW1[:, H + E:], TN),
-                  ops.gemm_problem([(dG1f, h1_prev)], gwhh1, TN)], TN)
-    ops.gemm_bwd([ops.gemm_problem([(dG2f, feat_tb)], gW2[:, 0:E], TN),
-                  ops.gemm_problem([(dG2f, h1_cur_l)], gW2[:, E:], TN),
-                  ops.gemm_problem([(dG2f, h2_prev)], gwhh2, TN)], TN)
-    # xt = relu(Emb[tok]) + label_e: the per-step part contracted over T*B rows above, the label part over B here
-    once = [ops.gemm_problem([(dG1_sum, P.fc_e)], gW1[:, H:H + E], TN)]
-    if P.label_e is not None:
-        once.append(ops.gemm_problem([(dG1_sum, P.label_e)], gW1[:, H + E:], TN, accumulate=True))
-    ops.gemm_bwd(once, TN)
-    G['att_lstm.weight_ih'] = gW1
-    G['att_lstm.weight_hh'] = gwhh1
-    G['lang_lstm.weight_ih'] = gW2
-    G['lang_lstm.weight_hh'] = gwhh2
-    G['att_lstm.bias_ih'], G['att_lstm.bias_hh'] = csum(dG1f, 2)
-    G['lang_lstm.bias_ih'], G['lang_lstm.bias_hh'] = csum(dG2f, 2)
-    # inputs of the att-LSTM: fc (step-invariant), xt = relu(Emb[tok]) + label_e
-    d_fc_e = new(B, E)
-    d_label_e = new(B, Wd) if P.label_e is not None else None
-    dxt = new(lstm_rows, Wd)
-    probs = [nn([(dG1_sum, Wih1[:, H:H + E])], d_fc_e), nn([(dG1f, Wih1[:, H + E:])], dxt)]
-    if d_label_e is not None:
-        probs.append(nn([(dG1_sum, Wih1[:, H + E:])], d_label_e))
-    with _weights_scope(cap):      # dX over all T*B rows: split-f16 on planes of the W_ih slices' transposes
-        ops.gemm_bwd(probs, NN)
-    emb = p['word_embed.0.weight']
-    # nn.Embedding(padding_idx=pad_id): the <PAD> row never gets a gradient - every accumulation into dEmb skips it
-    ops.embed_relu_bwd(emb, tok_tb, dxt, dEmb, lstm_rows, skip_id=cap.pad_id)
-
+    _lstm_dw(g, dG1f, dG2f, h1_prev, h1_cur_l, h2_prev, xt_tb, feat_tb, dG1_sum, P.fc_e, P.label_e)
+    d_fc_e, d_label_e, dEmb = _dx_bwd(cap, g, dG1f, dG1_sum, tok_tb, P.label_e is not None)
     if has_c:
-        dqaf = dqa.view(TB, A)
-        G['attention.cont_att.h2att.weight'] = tn(dqaf, h1_cur)
-        G['attention.cont_att.h2att.bias'] = csum(dqaf)
-        G['attention.cont_att.att_alpha.weight'] = csum(dwc_rows).view(1, A)
-        G['attention.cont_att.att_alpha.bias'] = zero_a        # softmax is shift invariant
+        _content_att_grads(g, dqa, h1_cur, dwc_rows)
     if has_s:
-        dqwf = dqw.view(TB, A)
-        G['attention.senti_att.h2word.weight'] = tn(dqwf, h1_cur)
-        G['attention.senti_att.h2word.bias'] = csum(dqwf)
-        G['attention.senti_att.word_alpha.weight'] = csum(dws_rows).view(1, A)
-        G['attention.senti_att.word_alpha.bias'] = zero_b
-        # label2word(label_e) enters every step's score: d label_w = sum_t dqw[t]
-        d_label_w = new(B * A)
-        ops.colsum(dqw.view(T, B * A), d_label_w)
-        d_label_w = d_label_w.view(B, A)
-        G['attention.senti_att.label2word.weight'] = tn(d_label_w, P.label_e)
-        G['attention.senti_att.label2word.bias'] = csum(d_label_w)
-        ops.gemm_bwd([nn([(d_label_w, p['attention.senti_att.label2word.weight'])], d_label_e, True)], NN)
+        _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, P.label_e, d_label_e=d_label_e)
     if gate:
         dzf = dz.view(TB, A)
-        G['attention.cont2att.weight'] = tn(dzf, S.v.view(TB, E))
-        G['attention.senti2att.weight'] = tn(dzf, S.s.view(TB, E))
-        G['attention.h2att.weight'] = tn(dzf, h1_cur)
-        G['attention.cont2att.bias'], G['attention.senti2att.bias'], G['attention.h2att.bias'] = csum(dzf, 3)
-        G['attention.att_alpha.weight'] = csum(dwg_rows).view(1, A)
-        G['attention.att_alpha.bias'] = csum(dbg_rows.view(B, 1))
+        g.tn(dzf, S.v.view(TB, E), 'attention.cont2att.weight')
+        g.tn(dzf, S.s.view(TB, E), 'attention.senti2att.weight')
+        g.tn(dzf, h1_cur, 'attention.h2att.weight')
+        g.csum(dzf, 'attention.cont2att.bias', 'attention.senti2att.bias', 'attention.h2att.bias')
+        g.csum(dwg_rows, 'attention.att_alpha.weight')
+        g.csum(dbg_rows.view(B, 1), 'attention.att_alpha.bias')
 
     # ---- prologue backward
     if d_label_e is not None:
-        dL = dL_z
-        ops.embed_relu_bwd(p['senti_label_embed.0.weight'], P.label_ids, d_label_e, dL, B,
-                           keep_mask=P.m_label, mask_scale=P.sc)
-        G['senti_label_embed.0.weight'] = dL
+        ops.embed_relu_bwd(p['senti_label_embed.0.weight'], P.label_ids, d_label_e, g.gout('senti_label_embed.0.weight'),
+                           B, keep_mask=P.m_label, mask_scale=P.sc)
     if has_c:
-        BR = B * P.R
-        att_e, att_p = P.att_e3.view(BR, E), P.att_p3.view(BR, A)
-        dzp = new(BR, A)
-        ops.relu_mask_bwd(dP_att.view(BR, A), att_p, dzp)
-        G['att2att.0.weight'] = tn(dzp, att_e)
-        G['att2att.0.bias'] = csum(dzp)
-        dVa = dV_att.view(BR, E)
-        ops.gemm_bwd([nn([(dzp, p['att2att.0.weight'])], dVa, True)], NN)
-        dze = new(BR, E)
-        ops.relu_mask_bwd(dVa, att_e, dze, keep_mask=P.m_att, scale=P.sc)
-        G['att_embed.0.weight'] = tn(dze, P.x_att)
-        G['att_embed.0.bias'] = csum(dze)
+        _region_embed_bwd(cap, g, P, dP_att, dV_att)
     if has_s:
-        BM = B * P.Mw
-        w_e, w_p = P.words_e3.view(BM, Wd), P.words_p3.view(BM, A)
-        dzp = new(BM, A)
-        ops.relu_mask_bwd(dP_w.view(BM, A), w_p, dzp)
-        G['senti2att.0.weight'] = tn(dzp, w_e)
-        G['senti2att.0.bias'] = csum(dzp)
-        dVw = dV_w.view(BM, Wd)
-        ops.gemm_bwd([nn([(dzp, p['senti2att.0.weight'])], dVw, True)], NN)
-        ops.embed_relu_bwd(emb, P.sw_ids, dVw, dEmb, BM, pad_first=P.Mw, pad_id=cap.pad_id,
-                           keep_mask=P.m_words, mask_scale=P.sc, skip_id=cap.pad_id)
-    # fc_embed (xe / rl) and cpt2fc
-    d_cpt = None
-    if S.mode != 'seq2seq':
-        dzf = new(B, E)
-        ops.relu_mask_bwd(d_fc_e, P.fc_e, dzf, keep_mask=P.m_fc, scale=P.sc)
-        if d_fc_feats is not None:
-            extra = new(B, E)
-            ops.relu_mask_bwd(d_fc_feats.contiguous(), cap_pre(P, 'fc'), extra)
-            dzf = dzf + extra
-        G['fc_embed.0.weight'] = tn(dzf, P.x_fc)
-        G['fc_embed.0.bias'] = csum(dzf)
-        if d_cpt_feats is not None:
-            d_cpt = new(B, E)
-            ops.relu_mask_bwd(d_cpt_feats.contiguous(), P.cpt, d_cpt)
-    else:
-        d_cpt = new(B, E)       # seq2seq: fc_e := dropout(cpt_feats) (captioner.py:250-251)
-        ops.relu_mask_bwd(d_fc_e, P.cpt, d_cpt, keep_mask=P.m_cpt, scale=P.sc)
-        if d_cpt_feats is not None:
-            extra = new(B, E)
-            ops.relu_mask_bwd(d_cpt_feats.contiguous(), cap_pre(P, 'cpt'), extra)
-            d_cpt = d_cpt + extra
-    if d_cpt is not None:
-        G['cpt2fc.0.weight'] = tn(d_cpt, P.cmean)
-        G['cpt2fc.0.bias'] = csum(d_cpt)
-        dcm = new(B, Wd)
-        ops.gemm_bwd([nn([(d_cpt, p['cpt2fc.0.weight'])], dcm)], NN)
-        C = P.cpt_ids.shape[1]
-        ops.embed_relu_bwd(emb, P.cpt_ids.view(-1), dcm, dEmb, B * C, rows_per_grad=C, scale=1.0 / C,
-                           skip_id=cap.pad_id)
-    G['word_embed.0.weight'] = dEmb
-    ops.colsum_multi(pending_sums)
-    if gs is not None:           # undo the gradient scale: x 1/S, a power of two
-        torch._foreach_mul_(list(G.values()), gs[1])
-    return G
-
-
-def cap_pre(P, which):
-    """Pre-dropout activation (the tensor the `fc_feats` / `cpt_feats` attribute exposes); equals the
-    post-dropout one in sign wherever the keep-mask is 1, and its gradient ignores the mask."""
-    return P.fc_pre if which == 'fc' else P.cpt_pre
+        _senti_words_bwd(cap, g, P, _senti2att_bwd(cap, g, P, dP_w), dV_w, dEmb)
+    if P.fc_pre is not None:
+        _fc_embed_bwd(cap, g, P, d_fc_e, d_fc_feats)
+    if P.fc_pre is None or d_cpt_feats is not None:
+        d_cpt = new(B, E)
+        _cpt_bwd(cap, P, d_fc_e, d_cpt_feats, d_cpt)
+        _cpt2fc_bwd(cap, g, d_cpt, (P,), dEmb)
+    return g.finish()
 
 
 class DecodeFn(torch.autograd.Function):

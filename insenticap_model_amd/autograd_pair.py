@@ -23,8 +23,10 @@ branch that joins the sweep late (the shorter unroll) needs nothing special.
 """
 import torch
 
-from . import _lib, ops
-from .autograd import NN, TN, _Saved, _pad32, _weights_scope, cap_pre
+from . import ops
+from .autograd import (NN, _Grads, _Saved, _classifier_bwd, _content_att_grads, _cpt2fc_bwd, _cpt_bwd, _dims, _dlogits,
+                       _dx_bwd, _fc_embed_bwd, _lstm_dw, _nn, _pad32, _region_embed_bwd, _scan_bwd, _senti2att_bwd,
+                       _senti_att_grads, _senti_words_bwd, _step_bwd_plan, _weights_scope)
 
 
 def use_pair(cap, in_graph):
@@ -230,7 +232,8 @@ def _pair_forward(cap, xe, s2s, lazy=None):
 # ------------------------------------------------------------------------------ backward
 def _pair_backward(cap, S, d1, d2, sparse1, sparse2, d_fc_feats1, d_cpt_feats1, d_cpt_feats2):
     """{param name: gradient} of both unrolls.  d1 / d2: dense d log-prob of the two outputs (None when the criteria
-    handed theirs over sparse: sparse1 / sparse2 = [(ids, coef)]); optional gradients of the attribute tensors.
+    handed theirs over sparse: sparse1 / sparse2 = [(ids, coef)]); optional gradients of the attribute tensors.  The
+    stages around the reverse sweep are autograd._backward's, called once per branch where a branch's rows differ.
 
     With a gradient sink on the captioner (`cap._grad_sink`, dp.GradSink: the data-parallel step) every gradient is
     written straight into its view of the flat arena, the parameters are finished bucket by bucket - classifier (before
@@ -240,165 +243,59 @@ def _pair_backward(cap, S, d1, d2, sparse1, sparse2, d_fc_feats1, d_cpt_feats1, 
     B1, B2, T1, T2 = S.B1, S.B2, S.T1, S.T2
     Bt, T = B1 + B2, max(T1, T2)
     ragged = T1 != T2
-    st = cap.settings
-    E, A, H, Wd, V = st['feat_emb_dim'], st['att_hid_dim'], st['rnn_hid_dim'], st['word_emb_dim'], cap.vocab_size
+    E, A, H, Wd, V = _dims(cap)
     R, Mw = P1.R, P2.Mw
     new, zeros = cap._new, cap._zeros
     stack = zeros if ragged else new
-    G = {}
     TB = T * Bt
-    sink = getattr(cap, '_grad_sink', None)
+    g = _Grads(cap, p, getattr(cap, '_grad_sink', None))
     if (P1.label_e is None) != (P2.label_e is None):
         raise ValueError('merged unrolls: sentiment labels for both calls or for neither')
 
-    def nn(segs, out, acc=False):
-        return ops.gemm_problem(segs, out, NN, accumulate=acc)
-
-    def gout(name, *shape):
-        """The tensor parameter `name`'s gradient is computed into: its arena view under a sink, else a new tensor."""
-        t = sink.out(name) if sink is not None else new(*p[name].shape)
-        if sink is None:
-            G[name] = t                 # (parameter-shaped: autograd checks the shape of what the node returns)
-        n = 1
-        for d in shape:
-            n *= d
-        assert t.numel() == n, (name, tuple(t.shape), shape)
-        return t.view(*shape)
-
-    def tn(a, w, name):
-        out = gout(name, a.shape[1], w.shape[1])
-        ops.gemm_bwd([ops.gemm_problem([(a, w)], out, TN)], TN)
-        return out
-
-    pending_sums = []      # bias gradients of the bucket in progress: one isc_colsum_multi per bucket
-
-    def csum(x, *names):
-        """Column sum of x into the gradient(s) `names` (several: tied biases share one reduction), deferred."""
-        pending_sums.append((x, [gout(n, x.shape[1]) for n in names], False))
-
-    def zero_grad_of(name):
-        if sink is None:
-            G[name] = zeros(1)          # (under a sink the arena was zeroed before the backward)
-
-    # ---- gradient scale (autograd._backward): one power of two for everything that enters the sweep
-    # the sweep's zeroed buffers out of ONE fill (each fill is a launch of its own, ~4.5 us at any size): the gradient
-    # scale's words, running sums and recurrent gradients (the sweep always accumulates), per-row partials of the alpha
-    # weights, the h-projection gradients of each branch padded to all rows
+    # ---- gradient scale: one power of two for everything that enters the sweep
+    # the sweep's zeroed buffers out of the one fill: the gradient scale's words, running sums and recurrent gradients
+    # (the sweep always accumulates), per-row partials of the alpha weights, the h-projection gradients of each branch
+    # padded to all rows (their dW contractions run over all T*Bt rows)
+    # (rows padded to a multiple of 32 with zeros: its two dW contractions - over the B1 + B2 rows, e.g. 208 - then run on
+    # the split-f16 kernels, whose contraction length is a multiple of 32; 190 us on the fp32 tiles otherwise)
     Bp = (Bt + 31) // 32 * 32
     f32 = torch.float32
-    gs_z, dG1_sum_p, rec, dq2, dw_rows = cap._zeros_many(((4,), f32), ((Bp, 4 * H), f32), ((7, Bt, H), f32),
-                                                         ((2, T, Bt, A), f32), ((Bt, A), f32))
-    gs = None
-    if getattr(cap, 'grad_scaling', True):
-        gs = gs_z
-        srcs = [c for _, c in list(sparse1) + list(sparse2)]
-        srcs += [x.contiguous() for x in (d_fc_feats1, d_cpt_feats1, d_cpt_feats2) if x is not None]
-        dense = [d.abs().amax().reshape(1) for d in (d1, d2) if d is not None]
-        if len(srcs) + (1 if dense else 0) > _lib_scale_max():
-            dense += [x.abs().amax().reshape(1) for x in srcs[_lib_scale_max() - 1:]]
-            srcs = srcs[:_lib_scale_max() - 1]
-        if dense:
-            srcs.append(torch.cat(dense))
-        ops.grad_scale(srcs, gs)
-        d_fc_feats1 = d_fc_feats1 * gs[0] if d_fc_feats1 is not None else None
-        d_cpt_feats1 = d_cpt_feats1 * gs[0] if d_cpt_feats1 is not None else None
-        d_cpt_feats2 = d_cpt_feats2 * gs[0] if d_cpt_feats2 is not None else None
-    scale = gs[0:1] if gs is not None else None
-
-    def bucket_done(b):
-        """Every gradient of bucket b (dp.GradSink.STARTS) is enqueued: its bias sums go out, then - under a sink - the
-        bucket is unscaled in one launch and its all-reduce starts."""
-        ops.colsum_multi(pending_sums)
-        del pending_sums[:]
-        if sink is not None:
-            sink.ready(b, unscale=gs[1] if gs is not None else None)
+    gs_z, dG1_sum_p, rec, dq2, dw_rows = g.fill((((4,), f32), ((Bp, 4 * H), f32), ((7, Bt, H), f32),
+                                                 ((2, T, Bt, A), f32), ((Bt, A), f32)))
+    scale, (d_fc_feats1, d_cpt_feats1, d_cpt_feats2) = g.scale(
+        gs_z, [c for _, c in list(sparse1) + list(sparse2)], (d_fc_feats1, d_cpt_feats1, d_cpt_feats2), (d1, d2))
 
     # ---- classifier + log-softmax over all T*Bt rows (time-major)
     Vp = _pad32(V)
     idle1, idle2 = d1 is None and not sparse1, d2 is None and not sparse2
     dlogits = zeros(TB, Vp) if (ragged or idle1 or idle2) else new(TB, Vp)
-    if S.lazy is not None:                     # d1 / d2 arrived as [B,T] coefficients of the target columns (DecodePairFn)
-        raw, pm, ps = S.lazy[:3]
-        if not idle1:
-            ops.logsoftmax_bwd_raw(raw, V, Bt * V, B1, T1, V, pm, ps, Bt, list(sparse1), dlogits, scale=scale,
-                                   out_step_rows=Bt)
-        if not idle2:
-            ops.logsoftmax_bwd_raw(raw[0, B1:], V, Bt * V, B2, T2, V, pm[0, B1:], ps[0, B1:], Bt, list(sparse2),
-                                   dlogits[B1:], scale=scale, out_step_rows=Bt)
-    else:
-        if not idle1:
-            ops.logsoftmax_bwd_sparse(d1, S.logp1, list(sparse1), dlogits, B1 * T1, V, remap_T=T1, scale=scale,
-                                      out_step_rows=Bt)
-        if not idle2:
-            ops.logsoftmax_bwd_sparse(d2, S.logp2, list(sparse2), dlogits[B1:], B2 * T2, V, remap_T=T2, scale=scale,
-                                      out_step_rows=Bt)
-    Wc = p['classifier.weight']
-    hdrop_tb = (S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(TB, H)
-    dhd = new(TB, H)
-    Vm = V // 32 * 32
-    if Vp != V and TB >= 8192:
-        Wc_k = zeros(Vp, H)
-        Wc_k[:V].copy_(Wc)
-        ops.gemm_bwd([nn([(dlogits, Wc_k)], dhd)], NN)
-    elif Vm != V and Vm >= 4096:
-        with _weights_scope(cap):
-            ops.gemm_bwd([nn([(dlogits[:, :Vm], Wc[:Vm])], dhd)], NN)
-        ops.gemm_bwd([nn([(dlogits[:, Vm:], Wc[Vm:])], dhd, True)], NN)
-    else:
-        with _weights_scope(cap):
-            ops.gemm_bwd([nn([(dlogits, Wc)], dhd)], NN)
-    if V % 4 == 0:
-        dWc = gout('classifier.weight', V, H)
-        ops.gemm_bwd([ops.gemm_problem([(dlogits[:, :V], hdrop_tb)], dWc, TN)], TN)
-    else:
-        dWp = new(Vp, H)
-        ops.gemm_bwd([ops.gemm_problem([(dlogits, hdrop_tb)], dWp, TN)], TN)
-        gout('classifier.weight', V, H).copy_(dWp[:V])
-    if Vp != V:
-        db = new(Vp)
-        ops.colsum(dlogits, db)
-        gout('classifier.bias', V).copy_(db[:V])
-    else:
-        ops.colsum(dlogits, gout('classifier.bias', V))
-    bucket_done(3)                      # classifier: its exchange runs behind the whole reverse sweep
+    # (lazy: d1 / d2 arrived as [B,T] coefficients of the target columns - DecodePairFn)
+    lz = S.lazy
+    for d, sp, idle, lo, Bx, Tx, logp in ((d1, sparse1, idle1, 0, B1, T1, S.logp1),
+                                          (d2, sparse2, idle2, B1, B2, T2, S.logp2)):
+        if not idle:
+            _dlogits(lz and (lz[0][0, lo:], V, Bt * V, lz[1][0, lo:], lz[2][0, lo:]), d, logp, sp, dlogits[lo:], Bx, Tx,
+                     V, Bt, scale)
+    dhd = _classifier_bwd(cap, g, dlogits, (S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(TB, H))
+    g.bucket_done(3)                    # classifier: its exchange runs behind the whole reverse sweep
     if S.hdrop is not None:
         ops.relu_mask_bwd(dhd, None, dhd, keep_mask=S.out_masks.view(TB, H), scale=S.out_scale)
 
-    Wih1 = p['att_lstm.weight_ih']
     dG1, dG2 = stack(T, Bt, 4 * H), stack(T, Bt, 4 * H)
     d_feat_all = stack(T, Bt, E)
-    # zeroed: running sums and recurrent gradients (the sweep always accumulates), per-row partials of the alpha weights,
-    # and the h-projection gradients of each branch padded to all rows (their dW contractions run over all T*Bt rows)
-    # (rows padded to a multiple of 32 with zeros: its two dW contractions - over the B1 + B2 rows, e.g. 208 - then run on
-    # the split-f16 kernels, whose contraction length is a multiple of 32; 190 us on the fp32 tiles otherwise)
     dG1_sum = dG1_sum_p[:Bt]
     dh1 = rec[6]
     dqa, dqw = dq2.unbind(0)
     dwc_rows, dws_rows = dw_rows[:B1], dw_rows[B1:]
     de_c, de_s = new(T1, B1, R), new(T2, B2, Mw)
-    dP_att, dV_att = new(B1, R, A), new(B1, R, E)
-    dP_w, dV_w = new(B2, Mw, A), new(B2, Mw, Wd)
 
     def bwd_plan(a1, a2):
-        bp = _lib.StepBwdPlan()
-        bp.H, bp.E, bp.A, bp.W, bp.R, bp.Mw = H, E, A, Wd, R, Mw
-        for field, key in (('Wih1', 'att_lstm.weight_ih'), ('Whh1', 'att_lstm.weight_hh'),
-                           ('Wih2', 'lang_lstm.weight_ih'), ('Whh2', 'lang_lstm.weight_hh'),
-                           ('W_h2att', 'attention.cont_att.h2att.weight'),
-                           ('w_alpha_c', 'attention.cont_att.att_alpha.weight'),
-                           ('W_h2word', 'attention.senti_att.h2word.weight'),
-                           ('w_alpha_s', 'attention.senti_att.word_alpha.weight')):
-            setattr(bp, field, p[key].data_ptr())
+        bp = _step_bwd_plan(cap, p, P1 if a1 else None, P2 if a2 else None)
         if a1:
-            bp.att_p, bp.att_e = P1.att_p3.data_ptr(), P1.att_e3.data_ptr()
             bp.alpha_c_ld, bp.dwc_rows = S.aC.stride(0), dwc_rows.data_ptr()
         if a2:
-            bp.words_p, bp.words_e, bp.label_w = P2.words_p3.data_ptr(), P2.words_e3.data_ptr(), P2.label_w.data_ptr()
             bp.alpha_s_ld, bp.dws_rows = S.aS.stride(0), dws_rows.data_ptr()
         bp.pair_rows_c = B1 if (a1 and a2) else 0
-        bp.first = 0
-        skws = ops.splitk_ws(cap._dev)
-        bp.splitk_ws, bp.splitk_ws_floats = skws.data_ptr(), skws.numel()
         return bp
 
     plans = {(True, True): bwd_plan(True, True)}
@@ -435,32 +332,13 @@ def _pair_backward(cap, S, d1, d2, sparse1, sparse2, d_fc_feats1, d_cpt_feats1, 
     dG1f, dG2f = dG1.view(TB, 4 * H), dG2.view(TB, 4 * H)
     h1_prev, h1_cur = S.h1[:T].reshape(TB, H), S.h1[1:].reshape(TB, H)
     h2_prev = S.h2[:T].reshape(TB, H)
-    feat_tb = S.feat.view(TB, E)
-    dqaf, dqwf = dqa.view(TB, A), dqw.view(TB, A)
-    emb = p['word_embed.0.weight']
+    xt_tb, feat_tb = S.xt.view(TB, Wd), S.feat.view(TB, E)
 
     # ---- bucket 2: lang-LSTM and the attention's own parameters - one contraction over all T*Bt rows each
-    gW2 = gout('lang_lstm.weight_ih', 4 * H, E + H)
-    ops.gemm_bwd([ops.gemm_problem([(dG2f, feat_tb)], gW2[:, 0:E], TN),
-                  ops.gemm_problem([(dG2f, h1_cur)], gW2[:, E:], TN),
-                  ops.gemm_problem([(dG2f, h2_prev)], gout('lang_lstm.weight_hh', 4 * H, H), TN)], TN)
-    csum(dG2f, 'lang_lstm.bias_ih', 'lang_lstm.bias_hh')
-    tn(dqaf, h1_cur, 'attention.cont_att.h2att.weight')
-    csum(dqaf, 'attention.cont_att.h2att.bias')
-    csum(dwc_rows, 'attention.cont_att.att_alpha.weight')
-    zero_grad_of('attention.cont_att.att_alpha.bias')          # softmax is shift invariant
-    tn(dqwf, h1_cur, 'attention.senti_att.h2word.weight')
-    csum(dqwf, 'attention.senti_att.h2word.bias')
-    csum(dws_rows, 'attention.senti_att.word_alpha.weight')
-    zero_grad_of('attention.senti_att.word_alpha.bias')
-    d_label_w = None
-    if P2.label_w is not None:          # label2word(label_e) enters every step's score: d label_w = sum_t dqw[t]
-        d_label_w_all = new(Bt * A)
-        ops.colsum(dqw.view(T, Bt * A), d_label_w_all)
-        d_label_w = d_label_w_all.view(Bt, A)[B1:]
-        tn(d_label_w, P2.label_e, 'attention.senti_att.label2word.weight')
-        csum(d_label_w, 'attention.senti_att.label2word.bias')
-    bucket_done(2)
+    _lstm_dw(g, None, dG2f, h1_prev, h1_cur, h2_prev, xt_tb, feat_tb, None, None, None)
+    _content_att_grads(g, dqa, h1_cur, dwc_rows)
+    d_label_w = _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, P2.label_e, lo=B1)
+    g.bucket_done(2)
 
     # ---- bucket 1: att-LSTM, region embedding + projection (XE branch), sentiment-word projection (seq2seq branch)
     pad = [_const_zeros(cap, Bp - Bt, E)] if Bp > Bt else []
@@ -468,98 +346,34 @@ def _pair_backward(cap, S, d1, d2, sparse1, sparse2, d_fc_feats1, d_cpt_feats1, 
     label_e_all = None
     if P1.label_e is not None:
         label_e_all = torch.cat([P1.label_e, P2.label_e] + ([_const_zeros(cap, Bp - Bt, Wd)] if Bp > Bt else []))
-    gW1 = gout('att_lstm.weight_ih', 4 * H, H + E + Wd)
-    # (problems grouped by their dY operand: isc_gemm_bwd splits a shared dY once and runs the group as one launch)
-    ops.gemm_bwd([ops.gemm_problem([(dG1f, h2_prev)], gW1[:, 0:H], TN),
-                  ops.gemm_problem([(dG1f, S.xt.view(TB, Wd))], gW1[:, H + E:], TN),
-                  ops.gemm_problem([(dG1f, h1_prev)], gout('att_lstm.weight_hh', 4 * H, H), TN)], TN)
-    once = [ops.gemm_problem([(dG1_sum_p, fc_e_all)], gW1[:, H:H + E], TN)]
-    if label_e_all is not None:      # xt = relu(Emb[tok]) + label_e: the label part contracts over the rows, once per caption
-        once.append(ops.gemm_problem([(dG1_sum_p, label_e_all)], gW1[:, H + E:], TN, accumulate=True))
-    ops.gemm_bwd(once, TN)
-    csum(dG1f, 'att_lstm.bias_ih', 'att_lstm.bias_hh')
-    ops.attn_dv_from_alpha(S.aC, d_feat_all[:T1, :B1], dV_att, step_rows=Bt)
-    ops.attn_dp_from_de(P1.att_p3, S.qa, p['attention.cont_att.att_alpha.weight'], de_c, dP_att)
-    ops.attn_dv_from_alpha(S.aS, d_feat_all[:T2, B1:], dV_w, step_rows=Bt)
-    ops.attn_dp_from_de(P2.words_p3, S.qw, p['attention.senti_att.word_alpha.weight'], de_s, dP_w, q2=P2.label_w)
-    BR = B1 * R
-    att_e, att_p = P1.att_e3.view(BR, E), P1.att_p3.view(BR, A)
-    dzp = new(BR, A)
-    ops.relu_mask_bwd(dP_att.view(BR, A), att_p, dzp)
-    tn(dzp, att_e, 'att2att.0.weight')
-    csum(dzp, 'att2att.0.bias')
-    dVa = dV_att.view(BR, E)
-    ops.gemm_bwd([nn([(dzp, p['att2att.0.weight'])], dVa, True)], NN)
-    dze = new(BR, E)
-    ops.relu_mask_bwd(dVa, att_e, dze, keep_mask=P1.m_att, scale=P1.sc)
-    tn(dze, P1.x_att, 'att_embed.0.weight')
-    csum(dze, 'att_embed.0.bias')
-    BM = B2 * Mw
-    w_e, w_p = P2.words_e3.view(BM, Wd), P2.words_p3.view(BM, A)
-    dzw = new(BM, A)
-    ops.relu_mask_bwd(dP_w.view(BM, A), w_p, dzw)
-    tn(dzw, w_e, 'senti2att.0.weight')
-    csum(dzw, 'senti2att.0.bias')
-    bucket_done(1)
+    _lstm_dw(g, dG1f, None, h1_prev, h1_cur, h2_prev, xt_tb, feat_tb, dG1_sum_p, fc_e_all, label_e_all)
+    dP_att, dV_att = _scan_bwd(cap, P1.att_p3, P1.att_e3, S.aC, S.qa, d_feat_all[:T1, :B1], de_c,
+                               p['attention.cont_att.att_alpha.weight'], step_rows=Bt)
+    dP_w, dV_w = _scan_bwd(cap, P2.words_p3, P2.words_e3, S.aS, S.qw, d_feat_all[:T2, B1:], de_s,
+                           p['attention.senti_att.word_alpha.weight'], step_rows=Bt, q2=P2.label_w)
+    _region_embed_bwd(cap, g, P1, dP_att, dV_att)
+    dzw = _senti2att_bwd(cap, g, P2, dP_w)
+    g.bucket_done(1)
 
     # ---- bucket 0: the word / label embeddings, fc_embed, cpt2fc
-    d_fc_e = new(Bt, E)
-    d_label_e = new(Bt, Wd) if label_e_all is not None else None
-    dxt = new(TB, Wd)
-    probs = [nn([(dG1_sum, Wih1[:, H:H + E])], d_fc_e), nn([(dG1f, Wih1[:, H + E:])], dxt)]
-    if d_label_e is not None:
-        probs.append(nn([(dG1_sum, Wih1[:, H + E:])], d_label_e))
-    with _weights_scope(cap):
-        ops.gemm_bwd(probs, NN)
-    dEmb = gout('word_embed.0.weight', V, Wd)
-    if sink is None:
-        dEmb.zero_()
-    ops.embed_relu_bwd(emb, S.tok.view(-1), dxt, dEmb, TB, skip_id=cap.pad_id)
+    d_fc_e, d_label_e, dEmb = _dx_bwd(cap, g, dG1f, dG1_sum, S.tok.view(-1), label_e_all is not None)
     if d_label_w is not None:
-        ops.gemm_bwd([nn([(d_label_w, p['attention.senti_att.label2word.weight'])], d_label_e[B1:], True)], NN)
+        ops.gemm_bwd([_nn([(d_label_w, p['attention.senti_att.label2word.weight'])], d_label_e[B1:], True)], NN)
     if d_label_e is not None:
-        dL = gout('senti_label_embed.0.weight', p['senti_label_embed.0.weight'].shape[0], Wd)
-        if sink is None:
-            dL.zero_()
+        dL = g.gout('senti_label_embed.0.weight')
         for P, lo, hi in ((P1, 0, B1), (P2, B1, Bt)):
             ops.embed_relu_bwd(p['senti_label_embed.0.weight'], P.label_ids, d_label_e[lo:hi], dL, hi - lo,
                                keep_mask=P.m_label, mask_scale=P.sc)
-    dVw = dV_w.view(BM, Wd)
-    ops.gemm_bwd([nn([(dzw, p['senti2att.0.weight'])], dVw, True)], NN)
-    ops.embed_relu_bwd(emb, P2.sw_ids, dVw, dEmb, BM, pad_first=Mw, pad_id=cap.pad_id,
-                       keep_mask=P2.m_words, mask_scale=P2.sc, skip_id=cap.pad_id)
+    _senti_words_bwd(cap, g, P2, dzw, dV_w, dEmb)
     # fc_embed (XE rows) and cpt2fc (XE rows: only through the cpt_feats attribute; seq2seq rows: fc_e := dropout(cpt))
-    dzf = new(B1, E)
-    ops.relu_mask_bwd(d_fc_e[:B1], P1.fc_e, dzf, keep_mask=P1.m_fc, scale=P1.sc)
-    if d_fc_feats1 is not None:
-        extra = new(B1, E)
-        ops.relu_mask_bwd(d_fc_feats1.contiguous(), cap_pre(P1, 'fc'), extra)
-        dzf = dzf + extra
-    tn(dzf, P1.x_fc, 'fc_embed.0.weight')
-    csum(dzf, 'fc_embed.0.bias')
+    _fc_embed_bwd(cap, g, P1, d_fc_e[:B1], d_fc_feats1)
     d_cpt = zeros(Bt, E) if d_cpt_feats1 is None else new(Bt, E)
     if d_cpt_feats1 is not None:
-        ops.relu_mask_bwd(d_cpt_feats1.contiguous(), P1.cpt, d_cpt[:B1])
-    ops.relu_mask_bwd(d_fc_e[B1:], P2.cpt, d_cpt[B1:], keep_mask=P2.m_cpt, scale=P2.sc)
-    if d_cpt_feats2 is not None:
-        extra = new(B2, E)
-        ops.relu_mask_bwd(d_cpt_feats2.contiguous(), cap_pre(P2, 'cpt'), extra)
-        d_cpt[B1:] += extra
-    cmean_all = torch.cat([P1.cmean, P2.cmean])
-    tn(d_cpt, cmean_all, 'cpt2fc.0.weight')
-    csum(d_cpt, 'cpt2fc.0.bias')
-    dcm = new(Bt, Wd)
-    ops.gemm_bwd([nn([(d_cpt, p['cpt2fc.0.weight'])], dcm)], NN)
-    C = P1.cpt_ids.shape[1]
-    if P2.cpt_ids.shape[1] != C:
-        raise ValueError('merged unrolls: the two calls carry different numbers of concept words')
-    cpt_ids = torch.cat([P1.cpt_ids, P2.cpt_ids]).view(-1)
-    # (nn.Embedding(padding_idx=pad_id): the <PAD> row never gets a gradient - every accumulation into dEmb skips it)
-    ops.embed_relu_bwd(emb, cpt_ids, dcm, dEmb, Bt * C, rows_per_grad=C, scale=1.0 / C, skip_id=cap.pad_id)
-    bucket_done(0)
-    if sink is None and gs is not None:
-        torch._foreach_mul_(list(G.values()), gs[1])
-    return G
+        _cpt_bwd(cap, P1, None, d_cpt_feats1, d_cpt[:B1])
+    _cpt_bwd(cap, P2, d_fc_e[B1:], d_cpt_feats2, d_cpt[B1:])
+    _cpt2fc_bwd(cap, g, d_cpt, (P1, P2), dEmb)
+    g.bucket_done(0)
+    return g.finish()
 
 
 def _const_zeros(cap, rows, width):
@@ -570,10 +384,6 @@ def _const_zeros(cap, rows, width):
     if z is None:
         z = cache[key] = torch.zeros(rows, width, dtype=torch.float32, device=cap._dev)
     return z
-
-
-def _lib_scale_max():
-    return 4          # ISC_SCALE_SRC_MAX (include/insenticap_hip.h)
 
 
 class DecodePairFn(torch.autograd.Function):

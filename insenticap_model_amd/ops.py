@@ -917,11 +917,20 @@ def logsoftmax_bwd_raw(raw, ld_b, ld_t, B, T, V, part_max, part_sum, step_rows, 
                                              dlogits.stride(0), int(out_step_rows), stream()), 'isc_logsoftmax_bwd_raw')
 
 
-def grad_scale(sources, out2):
+def grad_scale(sources, out2, maxima=()):
     """isc_grad_scale: out[0:2] = {S, 1/S}, S the power of two that brings max |x| over `sources` into [2^-4, 2^-3);
-    `out2` is a ZEROED float32[4] (its last two words are the reduction's state, left zeroed)."""
+    `out2` is a ZEROED float32[4] (its last two words are the reduction's state, left zeroed).  `maxima`: [1] tensors
+    max |x| of further gradients, joined into one source.  Any number of sources: past the library's ISC_SCALE_SRC_MAX,
+    the surplus is reduced to its maxima and joins them."""
     assert out2.numel() >= 4
     srcs = [x for x in sources if x is not None and x.numel() > 0]
+    maxima = list(maxima)
+    cap = _lib.ISC_SCALE_SRC_MAX
+    if len(srcs) + (1 if maxima else 0) > cap:
+        maxima += [x.abs().amax().reshape(1) for x in srcs[cap - 1:]]
+        srcs = srcs[:cap - 1]
+    if maxima:
+        srcs.append(torch.cat(maxima))
     for x in srcs:
         assert x.dtype == torch.float32 and x.is_contiguous()
     n = len(srcs)

@@ -294,6 +294,22 @@ def test_grad_scale_kernel_picks_the_power_of_two():
     assert out[:2].tolist() == [2.0 ** 7, 2.0 ** -7] and out[2:].view(torch.int32).tolist() == [0, 0]
 
 
+def test_grad_scale_takes_more_sources_than_the_library():
+    """ops.grad_scale past the library's ISC_SCALE_SRC_MAX sources: the surplus is folded into one source of maxima -
+    the same {S, 1/S} as with the sources folded by hand, and as over all values in one source."""
+    g = torch.Generator().manual_seed(0)
+    scales = (1e-3, 1e-4, 1e-5, 1e-6, 2.0, 1e-7)          # the largest value sits in the surplus
+    srcs = [(torch.randn(n, generator=g) * sc).to(dev()) for n, sc in zip((7, 300, 5, 4096, 33, 2), scales)]
+    for maxima in ([], [torch.tensor([3e-2], device=dev())]):
+        out, ref, one = (torch.zeros(4, device=dev()) for _ in range(3))
+        ops.grad_scale(srcs, out, maxima)
+        ops.grad_scale(srcs[:3] + [torch.cat(maxima + [x.abs().amax().reshape(1) for x in srcs[3:]])], ref)
+        ops.grad_scale([torch.cat(srcs + maxima)], one)
+        assert out.tolist() == ref.tolist() == one.tolist()
+        top = max(float(x.abs().max()) for x in srcs + maxima)
+        assert 2.0 ** -4 <= top * out[0].item() < 2.0 ** -3 and out[2:].view(torch.int32).tolist() == [0, 0]
+
+
 def test_sparse_dlogp_handover_equals_the_dense_tensor_bit_for_bit():
     """XECriterion and the REINFORCE gather hand their gradient to the decode node as (token, weight) pairs; with the
     gradient scale off the result must equal the dense [B,T,V] route bit for bit (same kernel arithmetic), and a loss
