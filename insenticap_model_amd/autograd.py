@@ -10,6 +10,7 @@ time-stacked buffers [T(+1), B, ...], and its backward is a reverse sweep in whi
     - weights are shared across time, so nothing is lost by deferring them.
 torch is used for memory, the autograd hook-up and (train mode) random numbers only.
 """
+import itertools
 import math
 
 import torch
@@ -20,7 +21,7 @@ NN, TN = ops.NN, ops.TN
 
 
 class _Saved:
-    pass
+    xt = hdrop = keep = qa = aC = qw = aS = v = s = z = bG = None      # (what an unroll has no use for stays None)
 
 
 
@@ -36,6 +37,182 @@ def _pad32(v):
     return (v + 31) // 32 * 32
 
 
+# ------------------------------------------------------------------------------ the step loops of both forms
+# (_train_forward / _backward below and autograd_pair's merged unroll run the same loops; only the data differ)
+class _Rows:
+    """Row layout of a training unroll: [T, Bt, .] stacks; block k = (lo, B_k, T_k) owns rows [lo, lo + B_k) for steps
+    < T_k (single form: one block; merged form: XE rows, then seq2seq rows); `counts` (ragged, one block): step t runs
+    rows [0, counts[t]).  steps[t] = (r0, r1, active blocks); short: some step runs fewer than Bt rows (or ragged)."""
+
+    def __init__(self, blocks, counts=None):
+        self.blocks, self.Bt, self.T = blocks, sum(b[1] for b in blocks), max(b[2] for b in blocks)
+        self.steps = []
+        for t in range(self.T):
+            act = tuple(t < Tk for _, _, Tk in blocks)
+            on = [(lo, lo + Bk) for (lo, Bk, _), a in zip(blocks, act) if a]
+            self.steps.append((on[0][0], on[-1][1] if counts is None else counts[t], act))
+        self.short = counts is not None or any(r1 - r0 < self.Bt for r0, r1, _ in self.steps)
+
+
+def _at(x, row=None):
+    """(address of x[t] per t, bytes per row) of a [T, rows, .] view: at the step's first row r0, or at a fixed `row`."""
+    e = x.element_size()
+    b = x.data_ptr() + (row or 0) * x.stride(1) * e
+    return [b + t * x.stride(0) * e for t in range(x.shape[0])], (x.stride(1) * e if row is None else 0)
+
+
+def _steps(L, plans, common, blocks, ts, launch):
+    """Step t of `ts`: its active blocks' plan gets rows r1 - r0 and the {field: _at(..)} pointers; then launch(t, plan)."""
+    walks = {act: {**common, **{f: v for k, a in enumerate(act) if a for f, v in blocks[k].items()}} for act in plans}
+    for t in ts:
+        r0, r1, act = L.steps[t]
+        pl = plans[act]
+        pl.rows = r1 - r0
+        for field, (bases, pitch) in walks[act].items():
+            setattr(pl, field, bases[t] + r0 * pitch)
+        launch(t, pl)
+
+
+def _lds(pl, S):
+    """Leading dimensions of the attention weights and the gate's beta (a plan without that attention ignores them)."""
+    pl.alpha_c_ld, pl.alpha_s_ld, pl.beta_ld = [0 if x is None else x.stride(0) for x in (S.aC, S.aS, S.bG)]
+
+
+def _has_keep(cap, masks):
+    """Whether h_lang is dropped out: explicit mask dicts (one per block) with out<t> keys, or train mode."""
+    if any(m is not None for m in masks):
+        return any(k.startswith('out') for m in masks if m is not None for k in m)
+    return cap.training and cap.drop.p > 0.0
+
+
+def _forward_buffers(cap, S, L, Ps, keep, zero_xt, extra=()):
+    """The saved tensors (blocks from the prologues Ps): h / c [T+1, Bt, H] from a fill, the stacks (from one more fill
+    when L.short) and the tile statistics.  Returns zero tensors for the (shape, dtype) specs `extra`."""
+    E, A, H, Wd, V = _dims(cap)
+    T, Bt = L.T, L.Bt
+    S.att = {}
+    st = {'feat': (T, Bt, E), 'hdrop': (T, Bt, H) if keep else None, 'xt': (T, Bt, Wd) if zero_xt and L.short else None}
+    for k, ((lo, Bk, Tk), P) in enumerate(zip(L.blocks, Ps)):
+        if P.att_e3 is not None:
+            S.att['c'] = (k, lo)
+            st.update(qa=(Tk, Bk, A), aC=(Bk, Tk, P.R))
+        if P.words_e3 is not None:
+            S.att['s'] = (k, lo)
+            st.update(qw=(Tk, Bk, A), aS=(Bk, Tk, P.Mw))
+        if P.att_e3 is not None and P.words_e3 is not None:
+            st.update(v=(T, Bt, E), s=(T, Bt, E), z=(T, Bt, A), bG=(Bk, Tk))
+    st = {k: sh for k, sh in st.items() if sh is not None}
+    S.h1, S.c1, S.h2, S.c2 = cap._zeros(4, T + 1, Bt, H).unbind(0)
+    vals = cap._zeros_many(*[(sh, torch.float32) for sh in st.values()]) if L.short else [cap._new(*sh) for sh in st.values()]
+    S.__dict__.update(zip(st, vals))
+    out = cap._zeros_many(*extra) if extra else []        # (their own fill: they outlive S)
+    if S.xt is None:
+        S.xt = cap._new(T, Bt, Wd)
+    S.g1, S.g2 = cap._new(T, Bt, 4 * H), cap._new(T, Bt, 4 * H)      # (read back by the same step's rows only)
+    S.tok = torch.full((T, Bt), cap.pad_id, dtype=torch.int64, device=cap._dev) if any(b[2] < T for b in L.blocks) \
+        else torch.empty(T, Bt, dtype=torch.int64, device=cap._dev)
+    n_tile = (V + 127) // 128
+    S.pm, S.ps, S.pi = cap._new(T, Bt, n_tile), cap._new(T, Bt, n_tile), cap._new(T, Bt, n_tile, dtype=torch.int32)
+    return out
+
+
+def _keep_mask(cap, S, L, masks):
+    """Dropout on h_lang (captioner.py:182): ONE [T, Bt, H] keep-mask (S.keep, S.out_scale) - drawn in one launch, or
+    from explicit dicts (tests replay the reference's), which then hold out<t> for every step of their block."""
+    H, p_drop = cap.settings['rnn_hid_dim'], cap.drop.p
+    S.out_scale = 1.0 / (1.0 - p_drop) if p_drop < 1.0 else 0.0
+    if S.hdrop is None:
+        S.out_scale = 1.0
+    elif all(m is None for m in masks):
+        S.keep = torch.empty(L.T, L.Bt, H, dtype=torch.uint8, device=cap._dev).bernoulli_(1.0 - p_drop)
+    else:
+        S.keep = torch.ones(L.T, L.Bt, H, dtype=torch.uint8, device=cap._dev)
+        for (lo, Bk, Tk), m in zip(L.blocks, masks):
+            for t in range(Tk):
+                mk, S.out_scale = cap._mask_source(m)('out%d' % t, Bk, H)
+                if mk is None:
+                    raise ValueError('explicit dropout masks: out%d is missing' % t)
+                S.keep[t, lo:lo + Bk] = mk
+
+
+def _feed(cap, S, L, toks, probs, emb):
+    """Tokens of every block ([B_k, T_k] ids).  Known up front: one copy per block, one gather; returns None.  Scheduled
+    sampling (captioner.py:219-228, on for some block): step 0 fed, the uniforms of every later step in ONE launch;
+    returns what _unroll's per-step draws read: (ground-truth ids [T, Bt], uniforms, probability per block)."""
+    if not (cap.training and any(q > 0.0 for q in probs)):
+        for (lo, Bk, Tk), tk in zip(L.blocks, toks):
+            S.tok[:Tk, lo:lo + Bk].copy_(tk.t())
+        ops.embed_relu_fwd(emb, S.tok.view(-1), S.xt.view(L.T * L.Bt, -1))
+        return None
+    if len(toks) == 1 and tuple(toks[0].shape) == (L.Bt, L.T):
+        base = toks[0].t()            # (one block covering every row and step: its ids serve as they are, no copy)
+    else:
+        base = torch.full((L.T, L.Bt), cap.pad_id, dtype=torch.int64, device=cap._dev)
+        for (lo, Bk, Tk), tk in zip(L.blocks, toks):
+            base[:Tk, lo:lo + Bk].copy_(tk.t())
+    S.tok[0].copy_(base[0])
+    ops.embed_relu_fwd(emb, S.tok[0], S.xt[0])
+    return base, torch.rand(max(L.T - 1, 1), 2, L.Bt, device=cap._dev), probs
+
+
+def _unroll(cap, S, L, plans, lg, sched=None, after=None):
+    """The forward step loop of both forms: scheduled-sampling draws (sched: _feed's), isc_step_fwd, after(t).  lg: the
+    [T, Bt, V] raw logits the steps write when a draw reads them, else None (the classifier runs after the loop)."""
+    emb = S.p['word_embed.0.weight']
+    common = dict(xt=_at(S.xt), h1_prev=_at(S.h1), c1_prev=_at(S.c1), h2_prev=_at(S.h2), c2_prev=_at(S.c2),
+                  h1=_at(S.h1[1:]), c1=_at(S.c1[1:]), h2=_at(S.h2[1:]), c2=_at(S.c2[1:]), g1=_at(S.g1), g2=_at(S.g2))
+    if S.keep is not None:
+        common.update(out_mask=_at(S.keep), hdrop=_at(S.hdrop))
+    if lg is not None:
+        common.update(logits=_at(lg), pmax=_at(S.pm), psum=_at(S.ps), pidx=_at(S.pi))
+    blocks = [{} for _ in L.blocks]
+    if S.aC is not None:
+        k, lo = S.att['c']
+        blocks[k].update(qa=_at(S.qa, 0), v=_at(S.feat if S.v is None else S.v, lo), alpha_c=_at(S.aC.transpose(0, 1), 0))
+    if S.aS is not None:
+        k, lo = S.att['s']
+        blocks[k].update(qw=_at(S.qw, 0), s=_at(S.feat if S.s is None else S.s, lo), alpha_s=_at(S.aS.transpose(0, 1), 0))
+    if S.z is not None:
+        blocks[0].update(z=_at(S.z), f=_at(S.feat), beta=_at(S.bG.t()))
+    for pl in plans.values():
+        _lds(pl, S)
+        pl.out_scale, pl.ld_logits = S.out_scale, 0 if lg is None else lg.stride(1)
+
+    def launch(t, pl):
+        r0, r1, _ = L.steps[t]
+        if sched is not None and t >= 1:
+            draw(t, r0, r1)
+        ops.step_fwd(pl)
+        if after is not None:
+            after(t)
+
+    def draw(t, r0, r1):
+        base, u_all, probs = sched
+        u, spans = u_all[t - 1], []
+        for (lo, Bk, Tk), prob in zip(L.blocks, probs):         # (neighbouring blocks with one probability: one span)
+            if t < Tk:
+                if spans and spans[-1][1] == lo and spans[-1][2] == prob:
+                    spans[-1][1] = lo + Bk
+                else:
+                    spans.append([lo, lo + Bk, prob])
+        for lo, hi, prob in spans:
+            ops.sched_sample(lg[t - 1, lo:hi], S.pm[t - 1, lo:hi], S.ps[t - 1, lo:hi], S.pi[t - 1, lo:hi],
+                             u[0, lo:hi], u[1, lo:hi], prob, base[t, lo:hi], S.tok[t, lo:hi], raw=True)
+        ops.embed_relu_fwd(emb, S.tok[t, r0:r1], S.xt[t, r0:r1])
+    _steps(L, plans, common, blocks, range(L.T), launch)
+
+
+def _classify(cap, S, L):
+    """The classifier ONCE over every step's h_lang [T*Bt, H]: raw logits [T, Bt, V], statistics into S.pm / ps / pi."""
+    p, TB, V = S.p, L.T * L.Bt, cap.vocab_size
+    hs = S.hdrop if S.hdrop is not None else S.h2[1:]
+    raw = cap._new(L.T, L.Bt, V)                      # (every row is written: no fill in the ragged form)
+    n_tile = S.pm.shape[2]
+    ops.vocab_fwd(hs.reshape(TB, -1), p['classifier.weight'], p['classifier.bias'], S.pm.view(TB, n_tile),
+                  S.ps.view(TB, n_tile), S.pi.view(TB, n_tile), raw.view(TB, V))
+    return raw
+
+
 # ------------------------------------------------------------------------------ forward
 def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks, lazy=None):
     """Returns (logp [B,T,V], S). tokens_in [B,T]: ground-truth inputs (column 0 = <SOS>) - or, for the sampled
@@ -49,17 +226,12 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     the backward recomputes the softmax term from them (isc_logsoftmax_bwd_raw)."""
     p = cap._p()
     P = cap._prologue(p, mode, fc, att, cpt_words, senti_words, senti_labels, masks)
-    st = cap.settings
-    E, A, H, Wd, V = st['feat_emb_dim'], st['att_hid_dim'], st['rnn_hid_dim'], st['word_emb_dim'], cap.vocab_size
+    Wd, V = cap.settings['word_emb_dim'], cap.vocab_size
     sampling = isinstance(tokens_in, dict)
-    if sampling:
-        B, T = P.B, tokens_in['T']
-    else:
-        B, T = tokens_in.shape
-    has_c, has_s = P.att_e3 is not None, P.words_e3 is not None
+    B, T = (P.B, tokens_in['T']) if sampling else tokens_in.shape
+    sched = not sampling and cap.training and ss_prob > 0.0
     S = _Saved()
     S.p, S.P, S.mode, S.B, S.T = p, P, mode, B, T
-    new, zeros = cap._new, cap._zeros
     # Ragged unroll (Captioner.row_counts): the batch is sorted by caption length (the reference's collates,
     # dataloader.py:17,37,68,124), so the rows still inside their caption at step t are the prefix [0, counts[t]) - step t
     # runs on those rows only.  The criteria never read a position behind a caption's end (XECriterion's mask,
@@ -67,172 +239,111 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     # skipped row would have written must read as ZERO (gradients) or at least finite (activations next to a zero
     # gradient in the contractions over all T*B rows) - every buffer such a row belongs to comes out of a fill.
     counts = cap.__dict__.get('_row_counts')
-    if counts is not None and (sampling or lazy is None or (cap.training and ss_prob > 0.0) or len(counts) != T
-                               or counts[0] != B or ops.TIMER.armed):
+    if counts is not None and (sampling or lazy is None or sched or len(counts) != T or counts[0] != B):
         counts = None
     S.row_counts = counts
-    S.h1, S.c1, S.h2, S.c2 = zeros(4, T + 1, B, H).unbind(0)             # slot 0 = initial zero state (one fill)
-    S.g1, S.g2 = new(T, B, 4 * H), new(T, B, 4 * H)                      # (read back row by row, by the same step only)
-    if counts is not None:
-        new = zeros
-    S.xt, S.tok = cap._new(T, B, Wd), torch.empty(T, B, dtype=torch.int64, device=cap._dev)   # (every row written)
-    if has_c:
-        S.qa, S.v, S.aC = new(T, B, A), new(T, B, E), new(B, T, P.R)
-    if has_s:
-        S.qw, S.s, S.aS = new(T, B, A), new(T, B, E), new(B, T, P.Mw)
-    if has_c and has_s:
-        S.z, S.f, S.bG = new(T, B, A), new(T, B, E), new(B, T)
-    mask_for = cap._mask_source(masks)
-    S.out_masks, S.out_scale = [], 1.0
-    S.hdrop = None
-    n_tile = (V + 127) // 128
-    # per-step tile statistics [T, B, n_tile]: the logits become log-probs in ONE launch after the last step
-    # (isc_logsoftmax_apply_steps) - in every form of the unroll: the draws of the sampled and the scheduled-sampling
-    # forms read a step's RAW logits with its statistics (20 + 20 + 20 normalising launches per RL iteration -> 3)
-    pm_st, ps_st = cap._new(T, B, n_tile), cap._new(T, B, n_tile)
-    pi_st = cap._new(T, B, n_tile, dtype=torch.int32)
-    fed_known_ = not sampling and not (cap.training and ss_prob > 0.0)
-    out = None if (lazy is not None and fed_known_) else new(B, T, V)     # (lazy + every fed token known: raw logits only)
+    L = S.L = _Rows([(0, B, T)], counts)
+    extra = [((B, T), torch.int64), ((B, T), torch.float32), ((B, T), torch.float32), ((B, T), torch.int64),
+             ((T + 1,), torch.int32)] if sampling else []
+    extra = _forward_buffers(cap, S, L, [P], _has_keep(cap, [masks]), False, extra)
+    step_cls = sampling or sched                  # a draw reads each step's raw logits: the classifier runs per step
+    out = None if (lazy is not None and not step_cls) else cap._new(B, T, V)   # (lazy, tokens known: raw logits only)
     emb = p['word_embed.0.weight']
-    plan = cap._make_plan(p, P, B)
+    plans = {(True,): cap._make_plan(p, P, B)}
+    after = None
     if sampling:
         from ._lib import RolloutStep
-        seq = zeros(B, T, dtype=torch.int64)
-        seq_lp, seq_masks, raw = zeros(B, T), zeros(B, T), zeros(B, T, dtype=torch.int64)
+        seq, seq_lp, seq_masks, raw, alive = extra
         unfinished = torch.ones(B, dtype=torch.int32, device=cap._dev)
-        alive = zeros(T + 1, dtype=torch.int32)
         alive[0:1].fill_(B)                     # a fill kernel (a scalar assignment would be a pageable H2D copy)
         forced, sample_u = tokens_in.get('forced'), tokens_in.get('u')
         rs = RolloutStep()
-        rs.B, rs.V, rs.T, rs.n_tile, rs.W = B, V, T, n_tile, Wd
-        rs.part_max, rs.part_sum, rs.part_idx = pm_st[0].data_ptr(), ps_st[0].data_ptr(), pi_st[0].data_ptr()
-        rs.ld_logits = out.stride(0)          # (sampling: `out` always exists - every step's draw reads its raw logits)
+        rs.B, rs.V, rs.T, rs.n_tile, rs.W = B, V, T, S.pm.shape[2], Wd
+        rs.ld_logits = out.stride(0)
         rs.forced, rs.sample_u, rs.eos_id = ops.ptr(forced), ops.ptr(sample_u), cap.eos_id
         rs.seq, rs.seq_logprobs, rs.seq_masks = seq.data_ptr(), seq_lp.data_ptr(), seq_masks.data_ptr()
         rs.unfinished, rs.alive, rs.raw_tokens = unfinished.data_ptr(), alive.data_ptr(), raw.data_ptr()
         rs.emb, rs.xt_add = emb.data_ptr(), None
         S.tok[0] = cap.sos_id
         ops.embed_relu_fwd(emb, S.tok[0], S.xt[0])
-    mask_for.predraw('out', T, B, H)
-    fed_known = not sampling and not (cap.training and ss_prob > 0.0)
-    pm_all = ps_all = None
-    if fed_known:                                         # every fed token is known up front: one copy, one gather
-        S.tok.copy_(tokens_in.t())
-        ops.embed_relu_fwd(emb, S.tok.view(-1), S.xt.view(T * B, Wd))
-        # ... and nothing reads a step's logits before the unroll ends: the classifier runs ONCE over all steps'
-        # h_lang [T*B, H] afterwards (at B = 128: 20 skinny launches of 24 us -> one [2560 x V] launch), and one
-        # more launch turns its [T,B,V] logits into the [B,T,V] log-probs
-        pm_all, ps_all, pi_all = pm_st, ps_st, pi_st
-    # the weights are fixed for the whole unroll: their f16 planes are built once (few-row launches then take the
-    # one-launch skinny split-f16 kernels instead of split-K + reduce pairs)
-    # scheduled sampling: the uniforms of every step (select, draw) in ONE launch in front of the loop (was one per step)
-    u_all = torch.rand(max(T - 1, 1), 2, B, device=cap._dev) if (not sampling and not fed_known) else None
+
+        def after(t):                                 # draw on the raw logits (normalised after the loop)
+            rs.t, rs.logits = t, out[:, t].data_ptr()
+            rs.part_max, rs.part_sum, rs.part_idx = S.pm[t].data_ptr(), S.ps[t].data_ptr(), S.pi[t].data_ptr()
+            rs.xt_next = S.xt[t + 1].data_ptr() if t + 1 < T else None
+            ops.rollout_finalize(rs)
+            if t + 1 < T:
+                S.tok[t + 1].copy_(seq[:, t])         # it * unfinished, written by this finalize
+    _keep_mask(cap, S, L, [masks])
+    ss = None if sampling else _feed(cap, S, L, [tokens_in], [ss_prob], emb)
     with _weights_scope(cap):
-        for t in range(T):
-            if sampling:
-                if t >= 1:
-                    S.tok[t].copy_(seq[:, t - 1])             # it * unfinished, written by the previous finalize
-            elif not fed_known:
-                if t >= 1:                                    # scheduled sampling, captioner.py:219-228:
-                    u = u_all[t - 1]                          # select + draw on the device, no host test
-                    ops.sched_sample(out[:, t - 1], pm_st[t - 1], ps_st[t - 1], pi_st[t - 1], u[0], u[1], ss_prob,
-                                     tokens_in[:, t], S.tok[t], raw=True)
-                else:
-                    S.tok[t] = tokens_in[:, t]
-                ops.embed_relu_fwd(emb, S.tok[t], S.xt[t])        # plain relu(Emb[tok]); label term is in P.pre1
-            om, osc = mask_for('out%d' % t, B, H)
-            save = {'g1': S.g1[t], 'g2': S.g2[t]}
-            if om is not None:
-                if S.hdrop is None:
-                    S.hdrop = new(T, B, H)
-                save['hdrop'] = S.hdrop[t]
-                S.out_scale = osc
-            S.out_masks.append(om)
-            ws = {'_plan': plan} if pm_all is not None else {'pmax': pm_st[t], 'psum': ps_st[t], 'pidx': pi_st[t],
-                                                              '_plan': plan}
-            if has_c:
-                ws['qa'], ws['v'] = S.qa[t], S.v[t]
-            if has_s:
-                ws['qw'], ws['s'] = S.qw[t], S.s[t]
-            if has_c and has_s:
-                ws['z'], ws['f'] = S.z[t], S.f[t]
-            logits = out[:, t] if pm_all is None else None
-            if counts is not None:
-                plan.rows = counts[t]
-            cap._step(p, P, ws, S.xt[t], (S.h1[t], S.h2[t]), (S.c1[t], S.c2[t]),
-                      (S.h1[t + 1], S.h2[t + 1]), (S.c1[t + 1], S.c2[t + 1]),
-                      S.aC[:, t] if has_c else None, S.aS[:, t] if has_s else None,
-                      S.bG[:, t:t + 1] if (has_c and has_s) else None, logits, om, osc, save=save,
-                      normalize=False)
-            if sampling:                                      # draw on the raw logits (normalised after the loop)
-                rs.t, rs.logits = t, logits.data_ptr()
-                rs.part_max, rs.part_sum, rs.part_idx = pm_st[t].data_ptr(), ps_st[t].data_ptr(), pi_st[t].data_ptr()
-                rs.xt_next = S.xt[t + 1].data_ptr() if t + 1 < T else None
-                ops.rollout_finalize(rs)
-        S.lazy = None
-        S.packed = None
-        if pm_all is not None and counts is not None and lazy is not None and sum(counts) < T * B:
-            # ragged: the classifier and everything behind it see the N = sum(counts) rows inside their captions only -
-            # h_lang gathered into packed time-major order (row n = (t, b), b < counts[t]), the statistics, raw logits,
-            # log p(target) and - in the backward - d logits, d h and the classifier's gradients over N rows
-            # (the row indices are built on the device from the T counts: a host-built index would travel through a
-            # freshly pinned buffer every iteration; N is known here, so nonzero needs no read-back)
-            N = int(sum(counts))
-            cnt = ops.to_device(torch.tensor(counts, dtype=torch.int64), cap._dev)
-            live = torch.arange(B, device=cap._dev).unsqueeze(0) < cnt.unsqueeze(1)              # [T,B]
-            i_tb = torch.nonzero_static(live.reshape(-1), size=N).reshape(-1)                    # t*B + b, time-major
-            idx = torch.stack([i_tb, (i_tb % B) * T + i_tb // B])
-            # (N rounded up to whole tiles / k-blocks of the split-f16 kernels - the row count is the contraction length of
-            # the classifier's dW; the pad rows are zero in h_lang and in d logits)
-            Np = (N + 255) // 256 * 256
-            hs = zeros(Np, H)
-            torch.index_select((S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(T * B, H), 0, idx[0], out=hs[:N])
-            pm_p, ps_p = cap._new(Np, n_tile), cap._new(Np, n_tile)
-            pi_p = cap._new(Np, n_tile, dtype=torch.int32)
-            rawl = cap._new(Np, V)
-            ops.vocab_fwd(hs, p['classifier.weight'], p['classifier.bias'], pm_p, ps_p, pi_p, rawl)
-            ids_p = lazy.reshape(-1).index_select(0, idx[1]).contiguous()
-            tlp_p = cap._new(N)
-            ops.gather_logp_raw(rawl, V, 0, N, 1, V, pm_p, ps_p, N, ids_p, tlp_p)
-            tlp = zeros(B * T).index_copy_(0, idx[1], tlp_p).view(B, T)
-            S.packed = dict(N=N, Np=Np, idx_tb=idx[0], idx_bt=idx[1], hs=hs, raw=rawl, pm=pm_p, ps=ps_p, tlp=tlp)
-            del rawl
-        elif pm_all is not None:
-            hs = S.hdrop if S.hdrop is not None else S.h2[1:]
-            rawl = cap._new(T, B, V)                           # (every row is written: no fill in the ragged form)
-            ops.vocab_fwd(hs.reshape(T * B, H), p['classifier.weight'], p['classifier.bias'], pm_all.view(T * B, n_tile),
-                          ps_all.view(T * B, n_tile), pi_all.view(T * B, n_tile), rawl.view(T * B, V))
+        _unroll(cap, S, L, plans, out.transpose(0, 1) if step_cls else None, ss, after)
+        S.lazy = S.packed = None
+        if not step_cls and counts is not None and sum(counts) < T * B:
+            S.packed = _packed_classifier(cap, S, counts, lazy)
+        elif not step_cls:
+            rawl = _classify(cap, S, L)
             if lazy is not None:
                 S.lazy = (rawl, V, B * V)                     # raw logits time-major: row (b,t) at b*V + t*B*V
             else:
-                ops.logsoftmax_apply_steps(out, pm_all, ps_all, src_tbv=rawl)
+                ops.logsoftmax_apply_steps(out, S.pm, S.ps, src_tbv=rawl)
             del rawl
         elif lazy is not None:
             S.lazy = (out, out.stride(0), out.stride(1))      # raw logits [B,T,V]: row (b,t) at b*T*V + t*V
         else:
-            ops.logsoftmax_apply_steps(out, pm_st, ps_st)     # in place: [B,T,V] raw logits -> log-probs
+            ops.logsoftmax_apply_steps(out, S.pm, S.ps)       # in place: [B,T,V] raw logits -> log-probs
     if sampling:
         S.sample = (seq, seq_masks, raw, alive)
-    cap._set_weights(S.aC if has_c else None, S.aS if has_s else None,
-                     S.bG if (has_c and has_s) else None, T)
+    cap._set_weights(S.aC, S.aS, S.bG, T)
+    S.pi = None                             # (the tile statistics: only the lazy forms' backward reads them)
+    if S.lazy is None:
+        S.pm = S.ps = None
     if S.packed is not None:
         S.logp, S.lazy_ids, S.lazy_live = None, lazy.contiguous(), None
         return S.packed.pop('tlp'), S
     if S.lazy is not None:
-        S.pm, S.ps = pm_st, ps_st
         S.lazy_live = None
         if sampling:      # log p(drawn token) * live (captioner.py:336; zero after the reference's early break)
             S.lazy_ids = raw
             S.lazy_live = (alive[:T] > 0).to(torch.float32)
         else:
             S.lazy_ids = lazy.contiguous()
-        tlp = new(B, T)
+        tlp = cap._new(B, T)
         rl, ld_b, ld_t = S.lazy
-        ops.gather_logp_raw(rl, ld_b, ld_t, B, T, V, pm_st, ps_st, B, S.lazy_ids, tlp, live=S.lazy_live)
+        ops.gather_logp_raw(rl, ld_b, ld_t, B, T, V, S.pm, S.ps, B, S.lazy_ids, tlp, live=S.lazy_live)
         S.logp = None
         return tlp, S
     S.logp = out
     return out, S
+
+
+def _packed_classifier(cap, S, counts, lazy):
+    """Ragged: the classifier and everything behind it see the N = sum(counts) rows inside their captions only - h_lang
+    gathered into packed time-major order (row n = (t, b), b < counts[t]), the statistics, raw logits, log p(target) and
+    - in the backward - d logits, d h and the classifier's gradients over N rows (the row indices are built on the device
+    from the T counts: a host-built index would travel through a freshly pinned buffer every iteration; N is known here,
+    so nonzero needs no read-back)."""
+    p, B, T, H, V = S.p, S.B, S.T, cap.settings['rnn_hid_dim'], cap.vocab_size
+    N = int(sum(counts))
+    cnt = ops.to_device(torch.tensor(counts, dtype=torch.int64), cap._dev)
+    live = torch.arange(B, device=cap._dev).unsqueeze(0) < cnt.unsqueeze(1)              # [T,B]
+    i_tb = torch.nonzero_static(live.reshape(-1), size=N).reshape(-1)                    # t*B + b, time-major
+    idx = torch.stack([i_tb, (i_tb % B) * T + i_tb // B])
+    # (N rounded up to whole tiles / k-blocks of the split-f16 kernels - the row count is the contraction length of
+    # the classifier's dW; the pad rows are zero in h_lang and in d logits)
+    Np = (N + 255) // 256 * 256
+    hs = cap._zeros(Np, H)
+    torch.index_select((S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(T * B, H), 0, idx[0], out=hs[:N])
+    n_tile = S.pm.shape[2]
+    pm_p, ps_p = cap._new(Np, n_tile), cap._new(Np, n_tile)
+    pi_p = cap._new(Np, n_tile, dtype=torch.int32)
+    rawl = cap._new(Np, V)
+    ops.vocab_fwd(hs, p['classifier.weight'], p['classifier.bias'], pm_p, ps_p, pi_p, rawl)
+    ids_p = lazy.reshape(-1).index_select(0, idx[1]).contiguous()
+    tlp_p = cap._new(N)
+    ops.gather_logp_raw(rawl, V, 0, N, 1, V, pm_p, ps_p, N, ids_p, tlp_p)
+    tlp = cap._zeros(B * T).index_copy_(0, idx[1], tlp_p).view(B, T)
+    return dict(N=N, Np=Np, idx_tb=idx[0], idx_bt=idx[1], hs=hs, raw=rawl, pm=pm_p, ps=ps_p, tlp=tlp)
 
 
 # ------------------------------------------------------------------------------ backward: stages of both forms
@@ -575,14 +686,92 @@ def _cpt2fc_bwd(cap, g, d_cpt, Ps, dEmb):
                        rows_per_grad=C, scale=1.0 / C, skip_id=cap.pad_id)
 
 
+def _sweep_buffers(cap, g, S, L, zero_rec, sum_rows, packed_rows=0):
+    """The reverse sweep's buffers; from g's ONE fill: gs_z, dG1_sum [sum_rows, 4H], what the sweep accumulates into when
+    zero_rec, every gradient stack when L.short - but packed dG1 / dG2 [packed_rows, 4H] (_sweep zeroes their pad)."""
+    E, A, H, _, _ = _dims(cap)
+    T, Bt = L.T, L.Bt
+    rec, big = {'rec': (7, Bt, H)}, {'d_feat': (T, Bt, E)}
+    for q, de, dw, x in (('dqa', 'de_c', 'dwc_rows', S.aC), ('dqw', 'de_s', 'dws_rows', S.aS)):
+        if x is not None:
+            rec.update({q: (T, Bt, A), dw: (x.shape[0], A)})
+            big[de] = (x.shape[1], x.shape[0], x.shape[2])
+    if S.z is not None:
+        rec.update(dwg_rows=(Bt, A), dbg_rows=(Bt, 1))
+        big.update(dv=(T, Bt, E), ds=(T, Bt, E), dz=(T, Bt, A))
+    dG = (packed_rows or T * Bt, 4 * H)
+    zeroed = dict(gs_z=(4,), dG1_sum=(sum_rows, 4 * H), **(rec if zero_rec else {}), **(big if L.short else {}))
+    if L.short and not packed_rows:
+        zeroed.update(dG1=dG, dG2=dG)
+    D = _Saved()
+    D.__dict__.update(zip(zeroed, g.fill([(sh, torch.float32) for sh in zeroed.values()])))
+    D.__dict__.update({k: cap._new(*sh) for k, sh in dict(rec, **big, dG1=dG, dG2=dG).items() if k not in zeroed})
+    return D
+
+
+def _sweep(cap, S, L, plans, D, dhd, first, packed=False):
+    """The reverse step loop of both forms, t = T-1 down; `first`: no incoming recurrent gradients at T-1 (else the
+    filled buffers are accumulated into).  packed: step t's dG1 / dG2 rows follow the earlier steps' rows directly.
+    Returns h1_prev, h1_cur, h2_prev, xt, feat as [T*Bt, .] rows."""
+    T, Bt, rec = L.T, L.Bt, D.rec
+    dG_rows = list(itertools.accumulate((r1 - r0 for r0, r1, _ in L.steps), initial=0)) if packed else None
+
+    def rows(x):                          # [Bt, .] buffers: the step's rows, whichever the step
+        return _at(x.unsqueeze(0).expand(T, *x.shape))
+
+    def alt(i, step):                     # cell-state gradients: two buffers, swapped every step
+        return [rec[i + ((t + step) & 1)].data_ptr() for t in range(T)], rec.stride(1) * 4
+    common = dict(g1=_at(S.g1), c1_prev=_at(S.c1), c1=_at(S.c1[1:]), g2=_at(S.g2), c2_prev=_at(S.c2), c2=_at(S.c2[1:]),
+                  dhd=_at(dhd), d_feat=_at(D.d_feat), dG1_sum=rows(D.dG1_sum[:Bt]), dh1=rows(rec[6]),
+                  dh2_rec=rows(rec[0]), dh1_rec=rows(rec[1]), dc1_in=alt(2, 1), dc1_out=alt(2, 0), dc2_in=alt(4, 1),
+                  dc2_out=alt(4, 0))
+    for name in ('dG1', 'dG2'):
+        x = getattr(D, name)
+        if dG_rows is None:
+            common[name] = _at(x.view(T, Bt, -1))
+        else:                             # (packed: the pad rows behind the last step's block are zero)
+            x[dG_rows[-1]:].zero_()
+            common[name] = [x[o].data_ptr() for o in dG_rows[:T]], 0
+    blocks = [{} for _ in L.blocks]
+    if S.aC is not None:
+        k, lo = S.att['c']
+        blocks[k].update(qa=_at(S.qa, 0), v=_at(S.feat if S.v is None else S.v, lo), alpha_c=_at(S.aC.transpose(0, 1), 0),
+                         dqa=_at(D.dqa, lo), de_c=_at(D.de_c, 0))
+    if S.aS is not None:
+        k, lo = S.att['s']
+        blocks[k].update(qw=_at(S.qw, 0), s=_at(S.feat if S.s is None else S.s, lo), alpha_s=_at(S.aS.transpose(0, 1), 0),
+                         dqw=_at(D.dqw, lo), de_s=_at(D.de_s, 0))
+    if S.z is not None:
+        blocks[0].update(dv=_at(D.dv), ds=_at(D.ds), z=_at(S.z), beta=_at(S.bG.t()), dz=_at(D.dz))
+    for bp in plans.values():
+        _lds(bp, S)
+        for name in ('dwc_rows', 'dws_rows', 'dwg_rows', 'dbg_rows'):
+            setattr(bp, name, ops.ptr(getattr(D, name, None)))
+
+    def launch(t, bp):
+        bp.first, bp.last = int(first and t == T - 1), int(t == 0)
+        ops.step_bwd(bp)
+    # the weights do not change during the sweep: few-row launches take the one-launch skinny split-f16 kernel on
+    # planes of W^T built once here (isc_gemm_bwd, NN layout), instead of fp32 split-K slabs + a reduce kernel per GEMM
+    with _weights_scope(cap):
+        _steps(L, plans, common, blocks, range(T - 1, -1, -1), launch)
+    return [x.reshape(T * Bt, -1) for x in (S.h1[:T], S.h1[1:], S.h2[:T], S.xt, S.feat)]
+
+
+def _dropout_bwd(S, dhd):
+    """nn.Dropout on h_lang (captioner.py:182): d h_lang [T*Bt, H] through the keep-mask, in place."""
+    if S.keep is not None:
+        ops.relu_mask_bwd(dhd, None, dhd, keep_mask=S.keep.view(dhd.shape), scale=S.out_scale)
+
+
 # ------------------------------------------------------------------------------ backward
 def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     """Returns {param name: gradient}.  The gradient of the log-probs arrives as `dlogp` [B,T,V] (contiguous; None when
     every consumer handed its part over sparse) plus `sparse` = [(ids [B,T] int64, coef [B,T] fp32)]: coef at column ids
     of each row (XELossFn / GatherLogpFn below).  Optional gradients of the `fc_feats` (pre-dropout) and `cpt_feats`
     attributes.  Gradient scale and outputs: _Grads."""
-    p, P, B, T = S.p, S.P, S.B, S.T
-    E, A, H, Wd, V = _dims(cap)
+    p, P, B, T, L = S.p, S.P, S.B, S.T, S.L
+    E, A, H, _, V = _dims(cap)
     new, zeros = cap._new, cap._zeros
     has_c, has_s = P.att_e3 is not None, P.words_e3 is not None
     gate = has_c and has_s
@@ -593,8 +782,13 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     Vp = _pad32(V)
     pk = getattr(S, 'packed', None)
     dlogits = new(TB if pk is None else pk['Np'], Vp)
-    gs_z, dG1_sum = g.fill((((4,), torch.float32), ((B, 4 * H), torch.float32)))
-    scale, (d_fc_feats, d_cpt_feats) = g.scale(gs_z, [c for _, c in sparse], (d_fc_feats, d_cpt_feats), [dlogp])
+    # ragged unroll (see _train_forward): step t sweeps rows [0, counts[t]); everything a skipped row would have written
+    # - its gradients, and the carries a row reads at the LAST step of its caption - is zero from the fill, and the sweep
+    # has no "first" step (a row's own last step is wherever its caption ends).  Packed: step t's gate gradients at rows
+    # [offs[t], offs[t] + counts[t]) - the contractions over all rows behind the sweep (both LSTM cells' dW groups, dxt,
+    # the bias sums) see N rows, no gather
+    D = _sweep_buffers(cap, g, S, L, L.short, B, 0 if pk is None else pk['Np'])
+    scale, (d_fc_feats, d_cpt_feats) = g.scale(D.gs_z, [c for _, c in sparse], (d_fc_feats, d_cpt_feats), [dlogp])
     if pk is not None:
         # ragged, packed classifier block (see _train_forward): d logits over the N rows inside their captions
         N = pk['N']
@@ -615,106 +809,23 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     dhd = _classifier_bwd(cap, g, dlogits, hdrop_tb)
     if pk is not None:          # d h_lang back in [T,B] order, zero behind the captions' ends
         dhd = zeros(TB, H).index_copy_(0, pk['idx_tb'], dhd[:pk['N']])
-    if S.hdrop is not None:     # nn.Dropout on h_lang (captioner.py:182)
-        mk = torch.stack(S.out_masks).reshape(TB, H)
-        ops.relu_mask_bwd(dhd, None, dhd, keep_mask=mk, scale=S.out_scale)
-    dhd = dhd.view(T, B, H)
-
-    # ragged unroll (see _train_forward): step t sweeps rows [0, counts[t]); everything a skipped row would have written
-    # - its gradients, and the carries a row reads at the LAST step of its caption - is zero from a fill
-    counts = getattr(S, 'row_counts', None)
-    new_full = new
-    if counts is not None:
-        new = zeros
-    if pk is not None:
-        # packed: step t's gate gradients at rows [offs[t], offs[t] + counts[t]) - the sweep takes per-step pointers, so the
-        # contractions over all rows behind it (both LSTM cells' dW groups, dxt, the bias sums) see N rows, no gather
-        Np, offs = pk['Np'], [0]
-        for m in counts:
-            offs.append(offs[-1] + m)
-        dG1, dG2 = new_full(Np, 4 * H), new_full(Np, 4 * H)
-        if Np > pk['N']:
-            dG1[pk['N']:].zero_()
-            dG2[pk['N']:].zero_()
-    else:
-        dG1, dG2 = new(T, B, 4 * H), new(T, B, 4 * H)
-    # d feat of every step is kept ([T,B,E]): where it is the scan's output gradient, dV = sum_t alpha_t x dout_t is
-    # formed once after the sweep (_scan_bwd) instead of a read-modify-write of [B,R,E] at every step
-    d_feat_all, dh1 = new(T, B, E), new(B, H)
-    dh2_rec, dh1_rec = new(B, H), new(B, H)
-    dc1_rec, dc2_rec = [new(B, H), new(B, H)], [new(B, H), new(B, H)]
+    _dropout_bwd(S, dhd)
+    h1_prev, h1_cur, h2_prev, xt_tb, feat_tb = _sweep(
+        cap, S, L, {(True,): _step_bwd_plan(cap, p, P if has_c else None, P if has_s else None)}, D, dhd.view(T, B, H),
+        not L.short, pk is not None)
+    dG1_sum = D.dG1_sum
     if has_c:
-        dqa, dv_all = new(T, B, A), (new(T, B, E) if gate else d_feat_all)
-        de_c = new(T, B, P.R)           # d e of every step: dP is formed once after the sweep
-        dwc_rows = new(B, A)
-    if has_s:
-        dqw, ds_all = new(T, B, A), (new(T, B, E) if gate else d_feat_all)
-        de_s = new(T, B, P.Mw)
-        dws_rows = new(B, A)
-    if gate:
-        dz = new(T, B, A)
-        dwg_rows, dbg_rows = new(B, A), new(B)
-    # reverse sweep: one library call per time step (isc_step_bwd enqueues the ~9 kernels of the step)
-    bp = _step_bwd_plan(cap, p, P if has_c else None, P if has_s else None)
-    bp.rows = B
-    bp.dG1_sum, bp.dh1 = dG1_sum.data_ptr(), dh1.data_ptr()
-    bp.dh2_rec, bp.dh1_rec = dh2_rec.data_ptr(), dh1_rec.data_ptr()
-    if has_c:
-        bp.dwc_rows, bp.alpha_c_ld = dwc_rows.data_ptr(), S.aC.stride(0)
-    if has_s:
-        bp.dws_rows, bp.alpha_s_ld = dws_rows.data_ptr(), S.aS.stride(0)
-    if gate:
-        bp.dwg_rows, bp.dbg_rows = dwg_rows.data_ptr(), dbg_rows.data_ptr()
-        bp.beta_ld = S.bG.stride(0)
-    # the weights do not change during the sweep: few-row launches take the one-launch skinny split-f16 kernel on
-    # planes of W^T built once here (isc_gemm_bwd, NN layout), instead of fp32 split-K slabs + a reduce kernel per GEMM
-    with _weights_scope(cap):
-        for t in range(T - 1, -1, -1):
-            cur, nxt = t & 1, (t + 1) & 1
-            bp.first, bp.last = int(t == T - 1), int(t == 0)
-            if counts is not None:
-                # (no "first" step: a row's own last step is wherever its caption ends - carries and time-accumulated
-                # buffers start from the fill instead)
-                bp.rows, bp.first = counts[t], 0
-            bp.g1, bp.c1_prev, bp.c1 = S.g1[t].data_ptr(), S.c1[t].data_ptr(), S.c1[t + 1].data_ptr()
-            bp.g2, bp.c2_prev, bp.c2 = S.g2[t].data_ptr(), S.c2[t].data_ptr(), S.c2[t + 1].data_ptr()
-            bp.dhd = dhd[t].data_ptr()
-            bp.dG1, bp.dG2 = (dG1[t].data_ptr(), dG2[t].data_ptr()) if pk is None else \
-                (dG1[offs[t]:].data_ptr(), dG2[offs[t]:].data_ptr())
-            bp.d_feat = d_feat_all[t].data_ptr()
-            if gate:
-                bp.dv, bp.ds = dv_all[t].data_ptr(), ds_all[t].data_ptr()
-            bp.dc1_in, bp.dc1_out = dc1_rec[nxt].data_ptr(), dc1_rec[cur].data_ptr()
-            bp.dc2_in, bp.dc2_out = dc2_rec[nxt].data_ptr(), dc2_rec[cur].data_ptr()
-            if has_c:
-                bp.qa, bp.v, bp.alpha_c, bp.dqa = S.qa[t].data_ptr(), S.v[t].data_ptr(), S.aC[:, t].data_ptr(), \
-                    dqa[t].data_ptr()
-                bp.de_c = de_c[t].data_ptr()
-            if has_s:
-                bp.qw, bp.s, bp.alpha_s, bp.dqw = S.qw[t].data_ptr(), S.s[t].data_ptr(), S.aS[:, t].data_ptr(), \
-                    dqw[t].data_ptr()
-                bp.de_s = de_s[t].data_ptr()
-            if gate:
-                bp.z, bp.beta, bp.dz = S.z[t].data_ptr(), S.bG[:, t:t + 1].data_ptr(), dz[t].data_ptr()
-            ops.step_bwd(bp)
-
-    new = new_full
-    if has_c:
-        dP_att, dV_att = _scan_bwd(cap, P.att_p3, P.att_e3, S.aC, S.qa, dv_all, de_c,
+        dP_att, dV_att = _scan_bwd(cap, P.att_p3, P.att_e3, S.aC, S.qa, D.dv if gate else D.d_feat, D.de_c,
                                    p['attention.cont_att.att_alpha.weight'])
     if has_s:
-        dP_w, dV_w = _scan_bwd(cap, P.words_p3, P.words_e3, S.aS, S.qw, ds_all, de_s,
+        dP_w, dV_w = _scan_bwd(cap, P.words_p3, P.words_e3, S.aS, S.qw, D.ds if gate else D.d_feat, D.de_s,
                                p['attention.senti_att.word_alpha.weight'], q2=P.label_w)
 
     # ---- weight gradients: one contraction over all T*B rows each
-    h1_prev, h1_cur = S.h1[:T].reshape(TB, H), S.h1[1:].reshape(TB, H)
-    h2_prev = S.h2[:T].reshape(TB, H)
-    feat_tb = (S.f if gate else (S.v if has_c else S.s)).view(TB, E)
-    xt_tb, tok_tb = S.xt.view(TB, Wd), S.tok.view(-1)
+    tok_tb = S.tok.view(-1)
     h1_cur_l = h1_cur               # (the LSTM groups' copy: the attention contractions below stay on [T,B] rows)
-    if pk is None:
-        dG1f, dG2f = dG1.view(TB, 4 * H), dG2.view(TB, 4 * H)
-    else:
+    dG1f, dG2f = D.dG1, D.dG2       # ([T*B or the packed rows, 4H])
+    if pk is not None:
         # packed gate gradients: their partners gathered to the same rows (pad rows zero / <PAD>)
         def pack(x):
             out = new(pk['Np'], x.shape[1], dtype=x.dtype)
@@ -722,7 +833,6 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
             if pk['Np'] > pk['N']:
                 out[pk['N']:].zero_()
             return out
-        dG1f, dG2f = dG1, dG2
         h1_prev, h1_cur_l, h2_prev, feat_tb, xt_tb = pack(h1_prev), pack(h1_cur), pack(h2_prev), pack(feat_tb), pack(xt_tb)
         tok_tb = pack(tok_tb.view(TB, 1)).view(-1)
         if pk['Np'] > pk['N']:
@@ -730,17 +840,17 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     _lstm_dw(g, dG1f, dG2f, h1_prev, h1_cur_l, h2_prev, xt_tb, feat_tb, dG1_sum, P.fc_e, P.label_e)
     d_fc_e, d_label_e, dEmb = _dx_bwd(cap, g, dG1f, dG1_sum, tok_tb, P.label_e is not None)
     if has_c:
-        _content_att_grads(g, dqa, h1_cur, dwc_rows)
+        _content_att_grads(g, D.dqa, h1_cur, D.dwc_rows)
     if has_s:
-        _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, P.label_e, d_label_e=d_label_e)
+        _senti_att_grads(cap, g, D.dqw, h1_cur, D.dws_rows, P.label_e, d_label_e=d_label_e)
     if gate:
-        dzf = dz.view(TB, A)
+        dzf = D.dz.view(TB, A)
         g.tn(dzf, S.v.view(TB, E), 'attention.cont2att.weight')
         g.tn(dzf, S.s.view(TB, E), 'attention.senti2att.weight')
         g.tn(dzf, h1_cur, 'attention.h2att.weight')
         g.csum(dzf, 'attention.cont2att.bias', 'attention.senti2att.bias', 'attention.h2att.bias')
-        g.csum(dwg_rows, 'attention.att_alpha.weight')
-        g.csum(dbg_rows.view(B, 1), 'attention.att_alpha.bias')
+        g.csum(D.dwg_rows, 'attention.att_alpha.weight')
+        g.csum(D.dbg_rows, 'attention.att_alpha.bias')
 
     # ---- prologue backward
     if d_label_e is not None:
