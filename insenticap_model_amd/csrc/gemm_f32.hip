@@ -1412,6 +1412,7 @@ __device__ __forceinline__ void h3_frag_from_f32(const char *row, int oct, int s
 #define H3_STAMP 0
 #endif
 #if H3_STAMP
+#define H3_STAMP_AT(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 __device__ unsigned long long g_h3_stamp[16];
 extern "C" int isc_debug_h3_stamps(unsigned long long *out16_host, int reset) {
     if (out16_host && hipMemcpyFromSymbol(out16_host, HIP_SYMBOL(g_h3_stamp), sizeof(g_h3_stamp)) != hipSuccess) return 1;
@@ -1421,46 +1422,98 @@ extern "C" int isc_debug_h3_stamps(unsigned long long *out16_host, int reset) {
     }
     return ISC_OK;
 }
+#else
+#define H3_STAMP_AT(v)
 #endif
 
+// Geometry of a large split-f16 tile kernel: WM x WN waves of 32 x (32 TN) accumulators each, NBUF LDS buffers in a
+// ring with NBUF - 1 chunks of DMA in flight; KSLICE: the launch may split K over workgroups (raw partial tiles to
+// slabs).  Everything else follows from these.
+template <int WM_, int WN_, int TN_, int NBUF_, bool KSLICE_>
+struct H3Geom {
+    static constexpr int WM = WM_, WN = WN_, TN = TN_, NBUF = NBUF_, AHEAD = NBUF_ - 1;
+    static constexpr bool KSLICE = KSLICE_;
+    static constexpr int NB = 2 * TN;                            // 16-column blocks of a wave
+    static constexpr int BM = 32 * WM, BN = 16 * NB * WN;
+    static constexpr int PA = BM * 128, PB = BN * 128;           // bytes per A / W image (row = 128 B: 32 hi | 32 lo halfs)
+    static constexpr int ST = PA + PB;                           // bytes per buffer
+    static constexpr int LDS_BYTES = NBUF * ST;
+    static constexpr int NW = WM * WN, THREADS = 64 * NW;
+    static constexpr int APW = BM / 8 / NW, BPW = BN / 8 / NW;   // 8-row staging pieces of A / of W a wave issues
+    static constexpr int DMAS = APW + BPW;                       // LDS-DMA instructions per wave and stage
+    static_assert(TN == 2 || TN == 4, "two or four groups of column blocks per chunk");
+    static_assert(APW * 8 * NW == BM && BPW * 8 * NW == BN && NBUF >= 2 && AHEAD * DMAS < 64, "pieces, ring, vmcnt range");
+};
+// 128 x 128, 4 x 1 waves, two buffers = 64 KB, two workgroups per CU (see above)
+using H3Tile128 = H3Geom<4, 1, 4, 2, true>;
+// 256 x 128 with EIGHT waves and three 48 KB buffers: one workgroup per CU keeps two chunks of DMA in flight (96 KB
+// against the 64 KB of two 128-row workgroups with one chunk each) - these launches are bound by the DMA round trip,
+// not by the matrix pipe: [4096 x 9984 x 512] 178 -> 137 us, [4096 x 2048 x 1536] 97 -> 76 us (tools/h3_gemm_lab.hip).
+// Used when the launch has >= 224 such tiles.
+using H3Tile256 = H3Geom<8, 1, 4, 3, false>;
+// 64 x 128 (2 x 2 waves, 32 x 64 accumulators each; linear epilogue): launches whose 128-row tiling would leave CUs
+// idle - the per-step projections with N = 512 at 4096 rows are 256 tiles of 64 x 128.  Per chunk: A planes 2 x 4 KB,
+// W planes 2 x 8 KB; four buffers = 96 KB, one workgroup per CU, so the DMA round trip has to be covered by the
+// workgroup's own prefetch depth, not by a neighbour.  (Round 3: six buffers = five chunks in flight measured the same as
+// four / three - gate sum [4096 x 512 x 1024] 31.9 us either way - so the round trip is covered; what these N = 512
+// launches pay is the ISSUE of their LDS-DMA pieces: six per wave and chunk against 24 MFMAs, where the 256-row kernel
+// has 48.)
+using H3Tile64 = H3Geom<2, 2, 2, 4, false>;
+
+// s_waitcnt vmcnt that leaves the youngest `in_flight` (<= MAXF) stages of DMAS instructions outstanding; the
+// immediates are compile-time
+template <int MAXF, int DMAS>
+__device__ __forceinline__ void h3_wait_stages(int in_flight) {
+    if constexpr (MAXF == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (in_flight >= MAXF) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(MAXF * DMAS) : "memory");
+    else h3_wait_stages<MAXF - 1, DMAS>(in_flight);
+}
+
+using I0 = std::integral_constant<int, 0>;
+using I1 = std::integral_constant<int, 1>;
+using I2 = std::integral_constant<int, 2>;
+using I3 = std::integral_constant<int, 3>;
+
+// The body of gemm_h3_kernel / gemm_h3x_kernel / gemm_h3m_kernel (geometry G).
 // AF32: some activation segment comes as fp32 rows (split after the fragment read); false = every segment has planes,
 // and the per-buffer test is compiled out of the fragment loads (it cost the all-planes decode loop ~5-10 %).
-template <int EPI, bool AF32>
-__global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
-    ISC_GATE_RETURN(L);
-#if H3_STAMP
-    const unsigned long long stamp0 = __builtin_amdgcn_s_memtime();
-#endif
-    constexpr int BM = 128, BN = 128, TN = 4;
-    constexpr int PA = 128 * 128, PB = 128 * 128;       // bytes per A / W image (row = 128 B: 32 hi | 32 lo halfs)
-    constexpr int ST = PA + PB;                         // bytes per buffer
+template <class G, int EPI, bool AF32>
+__device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
+    H3_STAMP_AT(stamp0);
+    constexpr int NB = G::NB, NQ = NB / 2;              // NQ groups of two column blocks per chunk
+    constexpr int PA = G::PA, ST = G::ST, APW = G::APW, BPW = G::BPW, NBUF = G::NBUF, AHEAD = G::AHEAD;
+    static_assert(EPI == EPI_LINEAR || G::WN == 1, "the LSTM and vocabulary epilogues take the tile's whole rows");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char *lds = reinterpret_cast<char *>(smem);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wm = tid >> 6;
+    const int w = tid >> 6, wm = w / G::WN, wn = w % G::WN;
     int pi, tm, tn, ks, ksplit;
     map_tile(L, pi, tm, tn, ks, ksplit);
     const DevProb &P = L.p[pi];
     const int M = P.M, N = P.N, Kp = P.Kp;
-    const int row0 = tm * BM, col0 = tn * BN;
+    const int row0 = tm * G::BM, col0 = tn * G::BN;
 
     // staging in pieces of 8 rows x 128 B = whole lines of the interleaved plane layout (a row's 32 hi + 32 lo halfs
-    // of a k-block): wave w issues A pieces 4w .. 4w+3 and W pieces 4w .. 4w+3; piece ii = image rows 8*ii .. +8,
-    // 8 lanes per row.  (Pieces of 16 rows x 64 B - hi and lo fetched by different instructions - touched every line
-    // twice and ran 9-14 % slower: tools/h3_gemm_lab.hip, r02.)  Image position p of row r holds chunk p ^ ((r>>1)&7).
-    // W planes are K-packed [N, Kp]; A planes come by K-segment (P.ap: the split kernel's packed planes as one
-    // segment, or the producers' per-tensor planes), switched at chunk boundaries.
-    const _Float16 *src[8];
-    int arow[4], aq[4];
+    // of a k-block): wave w issues A pieces APW w .. + APW and W pieces BPW w .. + BPW; piece ii = image rows
+    // 8*ii .. +8, 8 lanes per row.  (Pieces of 16 rows x 64 B - hi and lo fetched by different instructions - touched
+    // every line twice and ran 9-14 % slower: tools/h3_gemm_lab.hip, r02.)  Image position p of row r holds chunk
+    // p ^ ((r>>1)&7).  W planes are K-packed [N, Kp]; A planes come by K-segment (P.ap: the split kernel's packed planes
+    // as one segment, or the producers' per-tensor planes), switched at chunk boundaries.
+    const _Float16 *src[APW + BPW];
+    int arow[APW], aq[APW];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int t = 32 * wm + 8 * i + (lane >> 3);
-        const int q = (lane & 7) ^ ((t >> 1) & 7);
+    for (int i = 0; i < APW; ++i) {
+        const int t = 8 * APW * w + 8 * i + (lane >> 3);
         int ar = row0 + t;
         arow[i] = ar < M ? ar : M - 1;
-        aq[i] = q * 8;
+        aq[i] = ((lane & 7) ^ ((t >> 1) & 7)) * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < BPW; ++i) {
+        const int t = 8 * BPW * w + 8 * i + (lane >> 3);
+        const int q = (lane & 7) ^ ((t >> 1) & 7);
         long long wr;
         if (EPI == EPI_LSTM) {
             wr = (long long)(t >> 5) * P.H + tn * 32 + h3_lstm_wrow_in_gate(t);     // (gate, unit): see epi_lstm_frag16
@@ -1468,7 +1521,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
             const int c = col0 + t;
             wr = c < N ? c : N - 1;
         }
-        src[4 + i] = P.Wh + wr * 2 * Kp + q * 8;
+        src[APW + i] = P.Wh + wr * 2 * Kp + q * 8;
     }
     int cs = 0, ck = 0, segK = 0;
     bool seg_f32 = false;                // the segment has no planes: its fp32 rows are staged (128 B per row and chunk,
@@ -1478,52 +1531,53 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
         segK = a.K;
         seg_f32 = AF32 && a.hi == nullptr;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < APW; ++i)
             src[i] = seg_f32 ? reinterpret_cast<const _Float16 *>(P.seg[si].A + (long long)arow[i] * P.seg[si].lda) + aq[i]
                              : a.hi + (long long)arow[i] * a.ld + aq[i];
     };
-    // this workgroup's share of the k-blocks (ksplit > 1, linear epilogue only: raw partial tiles go to slabs)
-    const int nchunks_all = Kp / 32;
-    const int c_lo = ksplit > 1 ? (int)((long long)nchunks_all * ks / ksplit) : 0;
-    const int c_hi = ksplit > 1 ? (int)((long long)nchunks_all * (ks + 1) / ksplit) : nchunks_all;
-    {
+    int nchunks = Kp / 32;
+    if constexpr (G::KSLICE) {
+        // this workgroup's share of the k-blocks (ksplit > 1, linear epilogue only: raw partial tiles go to slabs)
+        const int c_lo = ksplit > 1 ? (int)((long long)nchunks * ks / ksplit) : 0;
+        const int c_hi = ksplit > 1 ? (int)((long long)nchunks * (ks + 1) / ksplit) : nchunks;
         int k0 = c_lo * 32;
         while (cs + 1 < P.nap && k0 >= P.ap[cs].K) { k0 -= P.ap[cs].K; ++cs; }
         set_aseg(cs);
         if (c_lo > 0) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                src[i] += (long long)(k0 >> 5) * 64;
-                src[4 + i] += (long long)c_lo * 64;
-            }
+            for (int i = 0; i < APW; ++i) src[i] += (long long)(k0 >> 5) * 64;
+#pragma unroll
+            for (int i = 0; i < BPW; ++i) src[APW + i] += (long long)c_lo * 64;
             ck = k0;
         }
+        nchunks = c_hi - c_lo;
+    } else {
+        set_aseg(0);
     }
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds + wm * 4096);
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
+    const unsigned wv = __builtin_amdgcn_readfirstlane((unsigned)w);
+    auto dma1 = [&](unsigned dst, const _Float16 *&p) __attribute__((always_inline)) {
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(dst), "v"(p) : "memory");
+        p += 64;                                          // next 32-k block: 32 hi + 32 lo halfs further
+    };
     auto stage = [&](int buf) __attribute__((always_inline)) {
+        const unsigned b = lds0 + buf * ST;
         f32_bufs = (f32_bufs & ~(1u << buf)) | ((seg_f32 ? 1u : 0u) << buf);
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
+        for (int i = 0; i < APW; ++i) dma1(b + (APW * wv + i) * 1024, src[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                             :: "s"(lds0 + buf * ST + p * PA + i * 1024), "v"(src[4 * p + i]) : "memory");
-                src[4 * p + i] += 64;                     // next 32-k block: 32 hi + 32 lo halfs further
-            }
+        for (int i = 0; i < BPW; ++i) dma1(b + PA + (BPW * wv + i) * 1024, src[APW + i]);
         ck += 32;
         if (ck >= segK) {
             ck = 0;
             if (++cs < P.nap) set_aseg(cs);
         }
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
 
     // v_mfma_f32_16x16x32_f16 (round 3; the 32x32x16 form of rounds 1-2 ran 7-16 % slower on the same tile, staging and
     // LDS image - tools/h3_mfma16_lab.hip): the wave's 32 x 16 NB tile = 2 row blocks x NB column blocks, ONE MFMA per
     // block, product term and 32-k chunk.  Fragment of lane l: row (l & 15) of the block, k-octet (l >> 4) = 16-byte
     // chunk (l >> 4) of the row image's hi half, chunk 4 + (l >> 4) of its lo half (positions XOR-swizzled as staged).
-    constexpr int NB = 2 * TN, NQ = NB / 2;             // NQ groups of two column blocks per chunk
     f32x4 acc0[2][NB], acc1[2][NB];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1554,7 +1608,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
         const char *base = lds + buf * ST + PA;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int rb = ((Q * 2 + j) * 16 + fr) * 128;
+            const int rb = (wn * 16 * NB + (Q * 2 + j) * 16 + fr) * 128;
             bh[SL][j] = *reinterpret_cast<const h8 *>(base + rb + ph);
             bl[SL][j] = *reinterpret_cast<const h8 *>(base + rb + pl);
         }
@@ -1572,8 +1626,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
     };
     // one chunk's MFMAs with the W fragments of group q + 1 read under the MFMAs of group q; `between` runs in front of
     // the last group (the barrier, then the next chunk's A fragments into the other A set and its group-0 W fragments)
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
     auto chunk_mma = [&](int cur, auto setc, auto between) __attribute__((always_inline)) {
         if constexpr (NQ == 4) {
             lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
@@ -1582,458 +1634,26 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
             between();
             mma(setc, I3{}, I1{});
         } else {
-            static_assert(NQ == 2, "two or four groups of column blocks per chunk");
             lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
             between();
             mma(setc, I1{}, I1{});
         }
     };
-    const int nchunks = c_hi - c_lo;
-#if H3_STAMP
-    const unsigned long long stamp1 = __builtin_amdgcn_s_memtime();
-#endif
-    stage(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // NBUF buffers, AHEAD chunks in flight: the wait in front of a barrier leaves the younger stages outstanding
+    auto wait_for = [&](int in_flight) __attribute__((always_inline)) { h3_wait_stages<AHEAD - 1, G::DMAS>(in_flight); };
+    H3_STAMP_AT(stamp1);
+#pragma unroll
+    for (int q = 0; q < AHEAD; ++q)
+        if (q == 0 || q < nchunks) stage(q);
+    wait_for((nchunks < AHEAD ? nchunks : AHEAD) - 1);
     __syncthreads();
     lfragA(0, I0{});
     lfragB(0, I0{}, I0{});
     // per chunk: the second half's W fragments are read under the first half's MFMAs, the next chunk's A fragments
     // (into the other A set) and first-half W fragments under the second half's
-    auto chunk = [&](int c, auto setc, auto nsetc) __attribute__((always_inline)) {
-        const int cur = c & 1, nxt = cur ^ 1;
-        const bool has1 = c + 1 < nchunks;
-        if (has1) stage(nxt);                 // buffer nxt was last read in front of the previous barrier
-        chunk_mma(cur, setc, [&]() __attribute__((always_inline)) {
-            if (has1) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                lfragA(nxt, nsetc);
-                lfragB(nxt, I0{}, I0{});
-            }
-        });
-    };
-    for (int c = 0; c < nchunks; c += 2) {
-        chunk(c, I0{}, I1{});
-        if (c + 1 < nchunks) chunk(c + 1, I1{}, I0{});
-    }
-#if H3_STAMP
-    const unsigned long long stamp2 = __builtin_amdgcn_s_memtime();
-#endif
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], 1.f / 2048.f, acc0[i][j][r]);
-
-    if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag16<NB>(P, acc0, wm * 32, lane, row0, col0, tn);
-    } else if constexpr (EPI == EPI_LSTM) {
-        epi_lstm_frag16(P, acc0, wm * 32, lane, row0, tn);
-    } else {
-        if (ksplit > 1) epi_slab_frag16<NB, AF32>(P, acc0, wm * 32, lane, row0, col0, ks);
-        else epi_linear_frag16<NB, AF32>(P, acc0, wm * 32, 0, lane, row0, col0);
-    }
-#if H3_STAMP
-    if (EPI == EPI_VOCAB) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the epilogue's stores have left
-        const unsigned long long stamp3 = __builtin_amdgcn_s_memtime();
-        if (lane == 0) {
-            atomicAdd(&g_h3_stamp[0], 1ull);
-            atomicAdd(&g_h3_stamp[1], stamp1 - stamp0);
-            atomicAdd(&g_h3_stamp[2], stamp2 - stamp1);
-            atomicAdd(&g_h3_stamp[3], stamp3 - stamp2);
-        }
-    }
-#endif
-}
-
-// H3 on a 256 x 128 tile with EIGHT waves (32 x 128 accumulators, the same fragment code) and three 48 KB buffers:
-// one workgroup per CU keeps two chunks of DMA in flight (96 KB against the 64 KB of two 128-row workgroups with one
-// chunk each) - these launches are bound by the DMA round trip, not by the matrix pipe: [4096 x 9984 x 512] 178 -> 137 us,
-// [4096 x 2048 x 1536] 97 -> 76 us (tools/h3_gemm_lab.hip).  Used when the launch has >= 224 such tiles.
-template <int EPI, bool AF32>
-__global__ __launch_bounds__(512) void gemm_h3x_kernel(const DevLaunch L) {
-    ISC_GATE_RETURN(L);
-#if H3_STAMP
-    const unsigned long long stamp0 = __builtin_amdgcn_s_memtime();
-#endif
-    constexpr int BM = 256, BN = 128, TN = 4;
-    constexpr int PA = 256 * 128, PB = 128 * 128;       // bytes per A / W image (row = 128 B: 32 hi | 32 lo halfs)
-    constexpr int ST = PA + PB;                         // bytes per buffer (48 KB)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    char *lds = reinterpret_cast<char *>(smem);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wm = tid >> 6;
-    int pi, tm, tn, ks, ksplit;
-    map_tile(L, pi, tm, tn, ks, ksplit);
-    const DevProb &P = L.p[pi];
-    const int M = P.M, N = P.N, Kp = P.Kp;
-    const int row0 = tm * BM, col0 = tn * BN;
-
-    // staging pieces of 8 rows x 128 B (whole lines, see gemm_h3_kernel): A image 32 pieces (four per wave), W image 16
-    // (two per wave).  A by K-segment.
-    const _Float16 *src[6];
-    int arow[4], aq[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int t = 32 * wm + 8 * i + (lane >> 3);
-        int ar = row0 + t;
-        arow[i] = ar < M ? ar : M - 1;
-        aq[i] = ((lane & 7) ^ ((t >> 1) & 7)) * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int t = 16 * wm + 8 * i + (lane >> 3);
-        const int q = (lane & 7) ^ ((t >> 1) & 7);
-        long long wr;
-        if (EPI == EPI_LSTM) {
-            wr = (long long)(t >> 5) * P.H + tn * 32 + h3_lstm_wrow_in_gate(t);     // (gate, unit): see epi_lstm_frag16
-        } else {
-            const int c = col0 + t;
-            wr = c < N ? c : N - 1;
-        }
-        src[4 + i] = P.Wh + wr * 2 * Kp + q * 8;
-    }
-    int cs = 0, ck = 0, segK = 0;
-    bool seg_f32 = false;                // the segment has no planes: its fp32 rows are staged (128 B per row and chunk,
-    unsigned f32_bufs = 0;               // like a plane row) and split after the fragment read; bit b: buffer b holds fp32
-    auto set_aseg = [&](int si) __attribute__((always_inline)) {
-        const DevASeg a = P.ap[si];
-        segK = a.K;
-        seg_f32 = AF32 && a.hi == nullptr;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            src[i] = seg_f32 ? reinterpret_cast<const _Float16 *>(P.seg[si].A + (long long)arow[i] * P.seg[si].lda) + aq[i]
-                             : a.hi + (long long)arow[i] * a.ld + aq[i];
-    };
-    set_aseg(0);
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
-    const unsigned wv = __builtin_amdgcn_readfirstlane((unsigned)wm);
-    auto dma1 = [&](unsigned dst, const _Float16 *&p) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(dst), "v"(p) : "memory");
-        p += 64;
-    };
-    auto stage = [&](int buf) __attribute__((always_inline)) {
-        const unsigned b = lds0 + buf * ST;
-        f32_bufs = (f32_bufs & ~(1u << buf)) | ((seg_f32 ? 1u : 0u) << buf);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma1(b + (4 * wv + i) * 1024, src[i]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) dma1(b + PA + (2 * wv + i) * 1024, src[4 + i]);
-        ck += 32;
-        if (ck >= segK) {
-            ck = 0;
-            if (++cs < P.nap) set_aseg(cs);
-        }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-
-    // v_mfma_f32_16x16x32_f16 (round 3; the 32x32x16 form of rounds 1-2 ran 7-16 % slower on the same tile, staging and
-    // LDS image - tools/h3_mfma16_lab.hip): the wave's 32 x 16 NB tile = 2 row blocks x NB column blocks, ONE MFMA per
-    // block, product term and 32-k chunk.  Fragment of lane l: row (l & 15) of the block, k-octet (l >> 4) = 16-byte
-    // chunk (l >> 4) of the row image's hi half, chunk 4 + (l >> 4) of its lo half (positions XOR-swizzled as staged).
-    constexpr int NB = 2 * TN, NQ = NB / 2;             // NQ groups of two column blocks per chunk
-    f32x4 acc0[2][NB], acc1[2][NB];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { acc0[i][j][r] = 0.f; acc1[i][j][r] = 0.f; }
-
-    const int fr = lane & 15, fq = lane >> 4, fsw = (fr >> 1) & 7;
-    const int ph = (fq ^ fsw) * 16, pl = ((4 + fq) ^ fsw) * 16;
-    h8 ah[2][2], al[2][2], bh[2][2], bl[2][2];          // A: [set][row block]; W: [slot][column block of the group]
-    auto lfragA = [&](int buf, auto setc) __attribute__((always_inline)) {
-        constexpr int S = decltype(setc)::value;
-        const char *base = lds + buf * ST;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int ra = (wm * 32 + i * 16 + fr) * 128;
-            if (AF32 && ((f32_bufs >> buf) & 1u)) {
-                h3_frag_from_f32(base + ra, fq, fsw, ah[S][i], al[S][i]);
-            } else {
-                ah[S][i] = *reinterpret_cast<const h8 *>(base + ra + ph);
-                al[S][i] = *reinterpret_cast<const h8 *>(base + ra + pl);
-            }
-        }
-    };
-    auto lfragB = [&](int buf, auto grpc, auto slotc) __attribute__((always_inline)) {
-        constexpr int Q = decltype(grpc)::value, SL = decltype(slotc)::value;
-        const char *base = lds + buf * ST + PA;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int rb = ((Q * 2 + j) * 16 + fr) * 128;
-            bh[SL][j] = *reinterpret_cast<const h8 *>(base + rb + ph);
-            bl[SL][j] = *reinterpret_cast<const h8 *>(base + rb + pl);
-        }
-    };
-    auto mma = [&](auto setc, auto grpc, auto slotc) __attribute__((always_inline)) {
-        constexpr int S = decltype(setc)::value, Q = decltype(grpc)::value, SL = decltype(slotc)::value;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc0[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bh[SL][j], acc0[i][Q * 2 + j], 0, 0, 0);
-                acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bl[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
-                acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[S][i], bh[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
-            }
-    };
-    // one chunk's MFMAs with the W fragments of group q + 1 read under the MFMAs of group q; `between` runs in front of
-    // the last group (the barrier, then the next chunk's A fragments into the other A set and its group-0 W fragments)
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    auto chunk_mma = [&](int cur, auto setc, auto between) __attribute__((always_inline)) {
-        if constexpr (NQ == 4) {
-            lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
-            lfragB(cur, I2{}, I0{}); mma(setc, I1{}, I1{});
-            lfragB(cur, I3{}, I1{}); mma(setc, I2{}, I0{});
-            between();
-            mma(setc, I3{}, I1{});
-        } else {
-            static_assert(NQ == 2, "two or four groups of column blocks per chunk");
-            lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
-            between();
-            mma(setc, I1{}, I1{});
-        }
-    };
-    // three buffers, two chunks in flight (6 DMAs per wave and chunk): vmcnt(6) leaves the younger chunk outstanding
-    const int nchunks = Kp / 32;
-#if H3_STAMP
-    const unsigned long long stamp1 = __builtin_amdgcn_s_memtime();
-#endif
-    stage(0);
-    if (nchunks > 1) stage(1);
-    if (nchunks > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    lfragA(0, I0{});
-    lfragB(0, I0{}, I0{});
-    int cur = 0;
-    auto chunk = [&](int c, auto setc, auto nsetc) __attribute__((always_inline)) {
-        const int nxt = cur == 2 ? 0 : cur + 1, nn = nxt == 2 ? 0 : nxt + 1;
-        if (c + 2 < nchunks) stage(nn);           // buffer nn was last read in front of the previous barrier
-        chunk_mma(cur, setc, [&]() __attribute__((always_inline)) {
-            if (c + 1 < nchunks) {
-                if (c + 2 < nchunks) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                lfragA(nxt, nsetc);
-                lfragB(nxt, I0{}, I0{});
-            }
-        });
-        cur = nxt;
-    };
-    for (int c = 0; c < nchunks; c += 2) {
-        chunk(c, I0{}, I1{});
-        if (c + 1 < nchunks) chunk(c + 1, I1{}, I0{});
-    }
-#if H3_STAMP
-    const unsigned long long stamp2 = __builtin_amdgcn_s_memtime();
-#endif
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], 1.f / 2048.f, acc0[i][j][r]);
-
-    if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag16<NB>(P, acc0, wm * 32, lane, row0, col0, tn);
-    } else if constexpr (EPI == EPI_LSTM) {
-        epi_lstm_frag16(P, acc0, wm * 32, lane, row0, tn);
-    } else {
-        epi_linear_frag16<NB, AF32>(P, acc0, wm * 32, 0, lane, row0, col0);
-    }
-#if H3_STAMP
-    if (EPI != EPI_VOCAB) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the epilogue's stores have left
-        const unsigned long long stamp3 = __builtin_amdgcn_s_memtime();
-        const int slot = EPI == EPI_LSTM ? (Kp == 1024 ? 1 : Kp == 1536 ? 2 : -1) : 3;
-        if (lane == 0 && slot >= 0) {
-            atomicAdd(&g_h3_stamp[4 * slot + 0], 1ull);
-            atomicAdd(&g_h3_stamp[4 * slot + 1], stamp1 - stamp0);
-            atomicAdd(&g_h3_stamp[4 * slot + 2], stamp2 - stamp1);
-            atomicAdd(&g_h3_stamp[4 * slot + 3], stamp3 - stamp2);
-        }
-    }
-#endif
-}
-
-#define H3M_NBUF 4
-// H3 on the 64 x 128 geometry (2 x 2 waves, 32 x 64 accumulators each; linear epilogue): launches whose 128-row
-// tiling would leave CUs idle - the per-step projections with N = 512 at 4096 rows are 256 tiles of 64 x 128.
-// Per chunk: A planes 2 x 4 KB, W planes 2 x 8 KB; four buffers = 96 KB, one workgroup per CU.
-template <bool AF32>
-__global__ __launch_bounds__(256) void gemm_h3m_kernel(const DevLaunch L) {
-    ISC_GATE_RETURN(L);
-    rows_kernarg_warm<ROWS_KERNARG_LINES(DevLaunch)>();      // (one batch of scalar loads for the launch descriptor: common.h)
-    constexpr int TN = 2;
-    constexpr int PA = 64 * 128, PB = 128 * 128;        // bytes per A / W image (row = 128 B: 32 hi | 32 lo halfs)
-    constexpr int ST = PA + PB;                         // bytes per buffer
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    char *lds = reinterpret_cast<char *>(smem);
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6, wm = w >> 1, wn = w & 1;
-    int pi, tm, tn, ks, ksplit;
-    map_tile(L, pi, tm, tn, ks, ksplit);
-    const DevProb &P = L.p[pi];
-    const int M = P.M, N = P.N, Kp = P.Kp;
-    const int row0 = tm * 64, col0 = tn * 128;
-
-    // staging pieces of 8 rows x 128 B (whole lines, see gemm_h3_kernel): A image two pieces per wave (by K-segment),
-    // W image four
-    const _Float16 *src[6];
-    int arow[2], aq[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int t = 16 * w + 8 * i + (lane >> 3);
-        int ar = row0 + t;
-        arow[i] = ar < M ? ar : M - 1;
-        aq[i] = ((lane & 7) ^ ((t >> 1) & 7)) * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int t = 32 * w + 8 * i + (lane >> 3);
-        const int q = (lane & 7) ^ ((t >> 1) & 7);
-        int c = col0 + t;
-        c = c < N ? c : N - 1;
-        src[2 + i] = P.Wh + (long long)c * 2 * Kp + q * 8;
-    }
-    int cs = 0, ck = 0, segK = 0;
-    bool seg_f32 = false;                // see gemm_h3_kernel
-    unsigned f32_bufs = 0;
-    auto set_aseg = [&](int si) __attribute__((always_inline)) {
-        const DevASeg a = P.ap[si];
-        segK = a.K;
-        seg_f32 = AF32 && a.hi == nullptr;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            src[i] = seg_f32 ? reinterpret_cast<const _Float16 *>(P.seg[si].A + (long long)arow[i] * P.seg[si].lda) + aq[i]
-                             : a.hi + (long long)arow[i] * a.ld + aq[i];
-    };
-    set_aseg(0);
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
-    const unsigned wv = __builtin_amdgcn_readfirstlane((unsigned)w);
-    auto dma1 = [&](unsigned dst, const _Float16 *&p) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(dst), "v"(p) : "memory");
-        p += 64;
-    };
-    auto stage = [&](int buf) __attribute__((always_inline)) {
-        const unsigned b = lds0 + buf * ST;
-        f32_bufs = (f32_bufs & ~(1u << buf)) | ((seg_f32 ? 1u : 0u) << buf);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) dma1(b + (2 * wv + i) * 1024, src[i]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma1(b + PA + (4 * wv + i) * 1024, src[2 + i]);
-        ck += 32;
-        if (ck >= segK) {
-            ck = 0;
-            if (++cs < P.nap) set_aseg(cs);
-        }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-
-    // v_mfma_f32_16x16x32_f16 (round 3; the 32x32x16 form of rounds 1-2 ran 7-16 % slower on the same tile, staging and
-    // LDS image - tools/h3_mfma16_lab.hip): the wave's 32 x 16 NB tile = 2 row blocks x NB column blocks, ONE MFMA per
-    // block, product term and 32-k chunk.  Fragment of lane l: row (l & 15) of the block, k-octet (l >> 4) = 16-byte
-    // chunk (l >> 4) of the row image's hi half, chunk 4 + (l >> 4) of its lo half (positions XOR-swizzled as staged).
-    constexpr int NB = 2 * TN, NQ = NB / 2;             // NQ groups of two column blocks per chunk
-    f32x4 acc0[2][NB], acc1[2][NB];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { acc0[i][j][r] = 0.f; acc1[i][j][r] = 0.f; }
-
-    const int fr = lane & 15, fq = lane >> 4, fsw = (fr >> 1) & 7;
-    const int ph = (fq ^ fsw) * 16, pl = ((4 + fq) ^ fsw) * 16;
-    h8 ah[2][2], al[2][2], bh[2][2], bl[2][2];          // A: [set][row block]; W: [slot][column block of the group]
-    auto lfragA = [&](int buf, auto setc) __attribute__((always_inline)) {
-        constexpr int S = decltype(setc)::value;
-        const char *base = lds + buf * ST;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int ra = (wm * 32 + i * 16 + fr) * 128;
-            if (AF32 && ((f32_bufs >> buf) & 1u)) {
-                h3_frag_from_f32(base + ra, fq, fsw, ah[S][i], al[S][i]);
-            } else {
-                ah[S][i] = *reinterpret_cast<const h8 *>(base + ra + ph);
-                al[S][i] = *reinterpret_cast<const h8 *>(base + ra + pl);
-            }
-        }
-    };
-    auto lfragB = [&](int buf, auto grpc, auto slotc) __attribute__((always_inline)) {
-        constexpr int Q = decltype(grpc)::value, SL = decltype(slotc)::value;
-        const char *base = lds + buf * ST + PA;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int rb = (wn * 64 + (Q * 2 + j) * 16 + fr) * 128;
-            bh[SL][j] = *reinterpret_cast<const h8 *>(base + rb + ph);
-            bl[SL][j] = *reinterpret_cast<const h8 *>(base + rb + pl);
-        }
-    };
-    auto mma = [&](auto setc, auto grpc, auto slotc) __attribute__((always_inline)) {
-        constexpr int S = decltype(setc)::value, Q = decltype(grpc)::value, SL = decltype(slotc)::value;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc0[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bh[SL][j], acc0[i][Q * 2 + j], 0, 0, 0);
-                acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bl[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
-                acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[S][i], bh[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
-            }
-    };
-    // one chunk's MFMAs with the W fragments of group q + 1 read under the MFMAs of group q; `between` runs in front of
-    // the last group (the barrier, then the next chunk's A fragments into the other A set and its group-0 W fragments)
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    auto chunk_mma = [&](int cur, auto setc, auto between) __attribute__((always_inline)) {
-        if constexpr (NQ == 4) {
-            lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
-            lfragB(cur, I2{}, I0{}); mma(setc, I1{}, I1{});
-            lfragB(cur, I3{}, I1{}); mma(setc, I2{}, I0{});
-            between();
-            mma(setc, I3{}, I1{});
-        } else {
-            static_assert(NQ == 2, "two or four groups of column blocks per chunk");
-            lfragB(cur, I1{}, I1{}); mma(setc, I0{}, I0{});
-            between();
-            mma(setc, I1{}, I1{});
-        }
-    };
-    // H3M_NBUF buffers, H3M_NBUF - 1 chunks in flight: these launches run one workgroup per CU, so the DMA round trip
-    // has to be covered by the workgroup's own prefetch depth, not by a neighbour.  (Round 3: six buffers = five chunks
-    // in flight measured the same as four / three - gate sum [4096 x 512 x 1024] 31.9 us either way - so the round trip
-    // is covered; what these N = 512 launches pay is the ISSUE of their LDS-DMA pieces: six per wave and chunk against
-    // 24 MFMAs, where the 256-row kernel has 48.)
-    const int nchunks = Kp / 32;
-    constexpr int NBUF = H3M_NBUF, AHEAD = NBUF - 1;
-    auto wait_for = [&](int in_flight) __attribute__((always_inline)) {   // stages that may still be outstanding (6 DMAs each)
-        if (in_flight >= 4) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-        else if (in_flight == 3) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-        else if (in_flight == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (in_flight == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    static_assert(AHEAD <= 5 && AHEAD >= 2, "wait_for covers up to 4 younger stages");
-#pragma unroll
-    for (int q = 0; q < AHEAD; ++q)
-        if (q < nchunks) stage(q);
-    wait_for((nchunks < AHEAD ? nchunks : AHEAD) - 1);
-    __syncthreads();
-    lfragA(0, I0{});
-    lfragB(0, I0{}, I0{});
-    int cur = 0;                                       // ring position of chunk c
-    auto chunk = [&](int c, auto setc, auto nsetc) __attribute__((always_inline)) {
+    int ring = 0;                                      // ring position of chunk c; with two buffers it is the chunk's
+    auto chunk = [&](int c, auto setc, auto nsetc) __attribute__((always_inline)) {    // parity = its A set: compile-time
+        const int cur = NBUF == 2 ? decltype(setc)::value : ring;
         const int nxt = cur + 1 == NBUF ? 0 : cur + 1;
         int far = cur + AHEAD;                         // where chunk c + AHEAD goes: the buffer chunk c - 1 left,
         if (far >= NBUF) far -= NBUF;                  // last read in front of the previous barrier
@@ -2047,19 +1667,63 @@ __global__ __launch_bounds__(256) void gemm_h3m_kernel(const DevLaunch L) {
                 lfragB(nxt, I0{}, I0{});
             }
         });
-        cur = nxt;
+        ring = nxt;
     };
     for (int c = 0; c < nchunks; c += 2) {
         chunk(c, I0{}, I1{});
         if (c + 1 < nchunks) chunk(c + 1, I1{}, I0{});
     }
+    H3_STAMP_AT(stamp2);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], 1.f / 2048.f, acc0[i][j][r]);
-    epi_linear_frag16<NB, AF32>(P, acc0, wm * 32, wn * 64, lane, row0, col0);
+
+    if constexpr (EPI == EPI_VOCAB) {
+        epi_vocab_frag16<NB>(P, acc0, wm * 32, lane, row0, col0, tn);
+    } else if constexpr (EPI == EPI_LSTM) {
+        epi_lstm_frag16(P, acc0, wm * 32, lane, row0, tn);
+    } else {
+        if (G::KSLICE && ksplit > 1) epi_slab_frag16<NB, AF32>(P, acc0, wm * 32, lane, row0, col0, ks);
+        else epi_linear_frag16<NB, AF32>(P, acc0, wm * 32, wn * 16 * NB, lane, row0, col0);
+    }
+#if H3_STAMP
+    // slot 0: the 128-row vocabulary form; slots 1 - 3: the 256-row LSTM (K = 1024, K = 1536) and linear forms
+    const int slot = G::BM == 128 && EPI == EPI_VOCAB ? 0
+                   : G::BM == 256 && EPI == EPI_LSTM ? (Kp == 1024 ? 1 : Kp == 1536 ? 2 : -1)
+                   : G::BM == 256 && EPI == EPI_LINEAR ? 3 : -1;
+    if (slot >= 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the epilogue's stores have left
+        H3_STAMP_AT(stamp3);
+        if (lane == 0) {
+            atomicAdd(&g_h3_stamp[4 * slot + 0], 1ull);
+            atomicAdd(&g_h3_stamp[4 * slot + 1], stamp1 - stamp0);
+            atomicAdd(&g_h3_stamp[4 * slot + 2], stamp2 - stamp1);
+            atomicAdd(&g_h3_stamp[4 * slot + 3], stamp3 - stamp2);
+        }
+    }
+#endif
+}
+
+template <int EPI, bool AF32>
+__global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    h3_tile_body<H3Tile128, EPI, AF32>(L);
+}
+
+template <int EPI, bool AF32>
+__global__ __launch_bounds__(512) void gemm_h3x_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    h3_tile_body<H3Tile256, EPI, AF32>(L);
+}
+
+template <bool AF32>
+__global__ __launch_bounds__(256) void gemm_h3m_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    rows_kernarg_warm<ROWS_KERNARG_LINES(DevLaunch)>();      // (one batch of scalar loads for the launch descriptor: common.h)
+    h3_tile_body<H3Tile64, EPI_LINEAR, AF32>(L);
 }
 
 // Operand split in front of gemm_h3_kernel: gathers the K-segments of one operand into the two packed f16 planes
@@ -3363,11 +3027,33 @@ static bool h3_any_f32(const DevLaunch &L) {
     return false;
 }
 
-template <int EPI>
-static int launch_h3(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = 65536;                                          // two workgroups per CU
-    if (h3_any_f32(L)) hipLaunchKernelGGL((gemm_h3_kernel<EPI, true>), dim3(L.total_tiles), dim3(256), lds, st, L);
-    else hipLaunchKernelGGL((gemm_h3_kernel<EPI, false>), dim3(L.total_tiles), dim3(256), lds, st, L);
+template <class G, int EPI, bool AF32>
+static constexpr auto h3_tile_kernel() {
+    if constexpr (std::is_same_v<G, H3Tile128>) return &gemm_h3_kernel<EPI, AF32>;
+    else if constexpr (std::is_same_v<G, H3Tile256>) return &gemm_h3x_kernel<EPI, AF32>;
+    else return &gemm_h3m_kernel<AF32>;
+}
+
+// One launch of a large split-f16 tile kernel of geometry G (the tiling of L is the caller's).
+template <class G, int EPI>
+static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
+    static_assert(EPI == EPI_LINEAR || !std::is_same_v<G, H3Tile64>, "the 64-row kernel has the linear epilogue only");
+    constexpr size_t lds = G::LDS_BYTES;
+    constexpr auto planes = h3_tile_kernel<G, EPI, false>(), f32_rows = h3_tile_kernel<G, EPI, true>();
+    if constexpr (lds > 65536) {                                           // one workgroup per CU
+        static std::atomic<bool> attr_set{false};
+        if (!attr_set.load()) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(planes),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(f32_rows),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return (int)e;
+            attr_set.store(true);
+        }
+    }
+    const auto kernel = h3_any_f32(L) ? f32_rows : planes;
+    hipLaunchKernelGGL(kernel, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -3516,25 +3202,6 @@ static const H3WEntry *h3w_find(const H3WScope *sc, const DevProb &p, int transp
     return nullptr;
 }
 
-template <int EPI>
-static int launch_h3x(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = 3 * (2 * 256 * 64 + 2 * 128 * 64);             // 147456: one workgroup per CU
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3x_kernel<EPI, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3x_kernel<EPI, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set.store(true);
-    }
-    if (h3_any_f32(L)) hipLaunchKernelGGL((gemm_h3x_kernel<EPI, true>), dim3(L.total_tiles), dim3(512), lds, st, L);
-    else hipLaunchKernelGGL((gemm_h3x_kernel<EPI, false>), dim3(L.total_tiles), dim3(512), lds, st, L);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
-}
-
 // 256-row tiles when they fill the chip, else the 128-row kernel.  The vocabulary projection stays on the 128-row
 // kernel: its epilogue (per-row softmax statistics, ~3k VALU instructions per wave) is as long as its 16-chunk main
 // loop, and only a second, out-of-phase workgroup on the CU overlaps the two (174 us on the 256-row tile vs 162 us;
@@ -3547,28 +3214,10 @@ static int launch_h3_big(DevLaunch &L, hipStream_t st) {
     if (EPI != EPI_VOCAB && t256 >= 224) {        // (round 3: 160 - the three h-projections on this kernel - measured the same)
         ++g_h3x_launches;
         finish_tiling(L, 3);
-        return launch_h3x<EPI>(L, st);
+        return launch_h3_tile<H3Tile256, EPI>(L, st);
     }
     finish_tiling(L, 4);
-    return launch_h3<EPI>(L, st);
-}
-
-static int launch_h3m(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = H3M_NBUF * (2 * 64 * 64 + 2 * 128 * 64);      // 4 x 24 KB = 98304: one workgroup per CU
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3m_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3m_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set.store(true);
-    }
-    if (h3_any_f32(L)) hipLaunchKernelGGL(gemm_h3m_kernel<true>, dim3(L.total_tiles), dim3(256), lds, st, L);
-    else hipLaunchKernelGGL(gemm_h3m_kernel<false>, dim3(L.total_tiles), dim3(256), lds, st, L);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
+    return launch_h3_tile<H3Tile128, EPI>(L, st);
 }
 
 // Operand-split jobs of one launch: add() lays the planes of an operand out in the workspace and queues its job.
@@ -3679,7 +3328,7 @@ static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, 
     if (rc) return 1;
     if (half_tile) {
         finish_tiling(L, 1);
-        rc = launch_h3m(L, st);
+        rc = launch_h3_tile<H3Tile64, EPI_LINEAR>(L, st);
     } else {
         // a long contraction on few 128 x 128 tiles (one problem, linear epilogue): S slices of K so that the launch fills
         // the chip's 512 workgroup slots, raw partial tiles to slabs behind the planes in the workspace, then the reduce
@@ -4045,7 +3694,7 @@ static unsigned try_h3_tn(DevLaunch &L, float *ws, long long ws_floats, hipStrea
                 rc = launch_h3_big<EPI_LINEAR>(L1, st);
             } else if (tiles >= H3_MIN_TILES / 2) {
                 finish_tiling(L1, 1);
-                rc = launch_h3m(L1, st);
+                rc = launch_h3_tile<H3Tile64, EPI_LINEAR>(L1, st);
             } else {
                 int T = h3s_pick_tile<EPI_LINEAR>(L1, mode == 2 ? 1 : mode), start = 0;
                 if (!T) T = 2;
