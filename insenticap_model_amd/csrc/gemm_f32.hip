@@ -13,23 +13,46 @@
 // activation buffer and no packed weight copy is ever materialised - every segment reads the
 // caller's tensors where they live.  Up to 3 independent problems share one launch.
 //
-// Tiling for gfx950: 256-thread workgroup = 4 wavefronts of 64; each wave owns a
-// 32 x (32*TN) accumulator built from 32x32x2 fp32 MFMAs (exact fp32 FMA chains, so the
-// result matches an fp32 CPU GEMM to rounding-order noise - bf16/TF32-like paths would
-// break the 1e-4 log-prob parity bound).  Two tile shapes:
-//   L: 128 x 128 (4 waves stacked in M, TN=4)  - batch-sized problems
-//   S:  32 x 128 (4 waves side by side in N)   - small-M problems (beam rows, B<=128)
-// K is consumed in 32-wide chunks, global -> registers -> LDS (double buffered, rows padded
-// to 36 floats so that the ds_read_b128 fragment reads are bank-conflict free), one
-// barrier per chunk.  The finished tile is staged through LDS once so that every epilogue
-// sees (row, col) coordinates and writes full, coalesced rows.
+// The fp32 engine, 256-thread workgroups = 4 wavefronts of 64; each wave owns 32 x 32 accumulator fragments built from
+// 32x32x2 fp32 MFMAs (exact fp32 FMA chains, so the result matches an fp32 CPU GEMM to rounding-order noise -
+// bf16/TF32-like paths would break the 1e-4 log-prob parity bound).  K is consumed in 32-wide chunks, one barrier per
+// chunk, by two families of tile kernels:
+//   * gemm_kernel, register-staged, every layout (NT / NN / TN): global -> registers -> LDS (double buffered, rows
+//     padded to 36 floats so that the ds_read_b128 fragment reads are bank-conflict free); the finished tile is staged
+//     through LDS once so that every epilogue sees (row, col) coordinates and writes full, coalesced rows.
+//       L: 128 x 128 (4 waves stacked in M, TN=4)  - batch-sized problems
+//       M:  64 x 128 (2 x 2 waves, TN=2)
+//       S:  32 x 128 (4 waves side by side in N)   - small-M problems (beam rows, B<=128)
+//   * the LDS-DMA tiles, NT layout only: global -> LDS by global_load_lds_dwordx4 into XOR-swizzled buffers, epilogues
+//     straight from the accumulator registers.  One body (f32_dma_tile_body) under three geometries (F32Geom):
+//       XL: 256 x 128 (gemm_xl_kernel, 3-deep ring),  LD: 128 x 128 (gemm_ld_kernel),  MD: 64 x 128 (gemm_md_kernel,
+//       linear epilogue only).
+// Small-M problems also have deterministic split-K (splitk_*_kernel) and a GEMV form (gemv_rows_kernel) further down.
 #include <atomic>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// compile-time indices for the kernels' unrolled pipelines (LDS buffers, fragment sets, DMA pieces)
+using I0 = std::integral_constant<int, 0>;
+using I1 = std::integral_constant<int, 1>;
+using I2 = std::integral_constant<int, 2>;
+using I3 = std::integral_constant<int, 3>;
+// f(integral_constant<int, 0>{}) ... f(integral_constant<int, N - 1>{}): a loop whose index stays a constant expression.
+// Not a `#pragma unroll` loop: where the compiler declines to unroll one (it did around the six-case linear epilogue of
+// gemm_xl_kernel<0>), a register array indexed by the loop variable - the accumulators - goes to scratch.
+template <class F, int... Is>
+__device__ __forceinline__ void static_for_seq(F &&f, std::integer_sequence<int, Is...>) {
+    (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
 
 #define BK 32
 #define LDT 36  // padded LDS row (floats): 36*r mod 64 is a distinct multiple of 4 for 16 rows
@@ -651,10 +674,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const DevLaunch L) {
         int mine = nchunks - c_lo;
         nchunks = mine < 0 ? 0 : (mine < cps ? mine : cps);
     }
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
     // One chunk: LDS[CUR] holds it and fragment set 0 its first k-block; the register stage holds
     // chunk c+1 (if any).  Exactly one barrier per chunk, placed in front of the last k-block's MFMAs.
     auto chunk_body = [&](auto curc, auto nxtc, auto fastc, bool has1, bool has2) __attribute__((always_inline)) {
@@ -746,83 +765,127 @@ __global__ __launch_bounds__(256) void gemm_kernel(const DevLaunch L) {
     else if (EPI == EPI_LSTM) epi_lstm_tile<BM, BN>(P, Cs, row0, tn, tid);
 }
 
-// ---------------------------------------------------------------- XL tile: 256 x 128, one workgroup per CU
-// For batch-sized NT problems.  4 waves stacked in M, each owning a 64 x 128 accumulator (2 x 4 MFMA
-// fragments, 128 AGPRs): twice the MFMAs per staged byte of the 128 x 128 tile.  Operand chunks go
-// (M0 carries the LDS destination of an LDS-DMA; it is written in the same asm statement that uses it, with the one
-// wait state the ISA asks for between an SALU write of M0 and a memory instruction with the LDS modifier: hipcc's hazard
-// recogniser does not look inside inline asm.)
-// global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass) into a
-// 3-deep ring (144 KB), so the DMA of chunk c+2 is in flight while chunk c is contracted and only a
-// counted vmcnt (never 0 in steady state) precedes the one barrier per chunk.  The 12 DMA
-// instructions of a chunk are issued one by one in the shadow of 8-MFMA groups.  An LDS-DMA writes
-// lane-linear (wave-uniform base + 16 B * lane), which rules out padded rows: the tile image is
-// [rows][8 slots of 16 B] with slot = k-quad ^ ((row >> 1) & 7), applied to the per-lane SOURCE address
-// when staging and to the ds_read_b128 address when reading fragments (conflict-free for the
-// instruction's four 16-lane groups).  The DMA is issued from inline asm (M0 = LDS address): the
-// compiler would otherwise drain every DMA (vmcnt(0)) in front of the next ds_read.
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_xl_kernel(const DevLaunch L) {
-    ISC_GATE_RETURN(L);
-    constexpr int BM = 256, BN = 128, TN = 4;
-    constexpr int TSA = BM * BK, TSB = BN * BK;         // floats per ring slot
+// ---------------------------------------------------------------- LDS-DMA tiles (NT layout): XL 256 x 128, LD 128 x 128, MD 64 x 128
+// Geometry of an fp32 LDS-DMA tile kernel: WM x WN waves, each owning FM x TN accumulator fragments of 32 x 32; NBUF LDS
+// buffers in a ring with NBUF - 1 chunks of DMA in flight; PER staging pieces of the chunk NBUF - 1 ahead are issued
+// after each MFMA group (one MFMA per accumulator fragment) of k-blocks 0 - 2.  Everything else follows from these.
+template <int WM_, int WN_, int FM_, int TN_, int NBUF_, int PER_>
+struct F32Geom {
+    static constexpr int WM = WM_, WN = WN_, FM = FM_, TN = TN_, NBUF = NBUF_, PER = PER_, AHEAD = NBUF_ - 1;
+    static constexpr int BM = 32 * FM * WM, BN = 32 * TN * WN;
+    static constexpr int TSA = BM * BK, TSB = BN * BK;           // floats per A / W buffer
+    static constexpr int LDS_BYTES = NBUF * (TSA + TSB) * (int)sizeof(float);
+    static constexpr int NW = WM * WN, THREADS = 64 * NW;
+    static constexpr int APW = BM / 8 / NW, BPW = BN / 8 / NW;   // 8-row staging pieces of A / of W a wave issues
+    static constexpr int DMAS = APW + BPW;                       // LDS-DMA instructions per wave and chunk
+    static constexpr int WAIT = (NBUF - 2) * DMAS;               // the steady-state vmcnt in front of the barrier: the
+                                                                 // largest immediate dma_wait_stages<AHEAD - 1, DMAS> emits
+    static_assert(THREADS == 256 && NBUF >= 2, "four waves, at least a double buffer");
+    static_assert(APW * 8 * NW == BM && BPW * 8 * NW == BN, "the staging pieces divide evenly over the waves");
+    static_assert(APW % 2 == 0 && BPW % 2 == 0, "piece parity = bit 2 of the swizzle's (row >> 1) & 7");
+    static_assert(DMAS % PER == 0 && DMAS <= PER * 12, "a chunk's pieces fit behind the MFMA groups of k-blocks 0 - 2");
+    static_assert(WAIT < 64, "vmcnt range");
+};
+// XL, for batch-sized problems: each wave owns a 64 x 128 accumulator (2 x 4 fragments, 128 AGPRs) - twice the MFMAs
+// per staged byte of the 128 x 128 tile.  144 KB of LDS = one workgroup per CU, which has to cover its own DMA round
+// trips: a 3-deep ring keeps chunk c+2 in flight while chunk c is contracted, so only a counted vmcnt (never 0 in
+// steady state) precedes the barrier, and the 12 pieces of a chunk go out one by one in the shadow of 8-MFMA groups.
+using F32TileXL = F32Geom<4, 1, 2, 4, 3, 1>;
+// LD: the L tile's geometry (4 waves stacked in M, 32 x 128 accumulator each) without its register stage and ds_write
+// pass (~9 % of the register-staged loop).  64 KB of LDS keep two workgroups on a CU, so an epilogue-heavy kernel -
+// the vocabulary projection: 16 chunks of MFMAs, then per-row softmax statistics - still has a neighbour to hide its
+// epilogue behind, which the XL tile does not.  Chunk c+1's eight pieces per wave are issued inside k-block 0 of
+// chunk c and retired with vmcnt(0).
+using F32TileLD = F32Geom<4, 1, 1, 4, 2, 2>;
+// MD: the LD scheme on the M geometry (2 x 2 waves, 32 x 64 accumulator each; linear epilogue) for the per-step
+// projections with N = 512: their 64-row tiles are what balances 4096 x 512 outputs over 256 CUs, and at one to three
+// workgroups per CU the register-staged form of that tile leaves the matrix pipe idle over its chunk-boundary round
+// trips.
+using F32TileMD = F32Geom<2, 2, 1, 2, 2, 2>;
+
+// s_waitcnt vmcnt that leaves the youngest `in_flight` (at most MAXF) stages of DMAS instructions outstanding; the
+// immediates are compile-time
+template <int MAXF, int DMAS>
+__device__ __forceinline__ void dma_wait_stages(int in_flight) {
+    if constexpr (MAXF == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if (in_flight >= MAXF) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(MAXF * DMAS) : "memory");
+    else dma_wait_stages<MAXF - 1, DMAS>(in_flight);
+}
+
+// The body of gemm_xl_kernel / gemm_ld_kernel / gemm_md_kernel (geometry G).
+// Operand chunks go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass).  M0 carries
+// the LDS destination of an LDS-DMA; it is written in the same asm statement that uses it, with the one wait state the
+// ISA asks for between an SALU write of M0 and a memory instruction with the LDS modifier: hipcc's hazard recogniser
+// does not look inside inline asm.  An LDS-DMA writes lane-linear (wave-uniform base + 16 B * lane), which rules out
+// padded rows: the tile image is [rows][8 slots of 16 B] with slot = k-quad ^ ((row >> 1) & 7), applied to the
+// per-lane SOURCE address when staging and to the ds_read_b128 address when reading fragments (conflict-free for the
+// instruction's four 16-lane groups).  The DMA is issued from inline asm: the compiler would otherwise drain every
+// DMA (vmcnt(0)) in front of the next ds_read.  Ring positions are compile-time (the chunk loop is unrolled NBUF
+// times), so every LDS offset is an immediate.
+template <class G, int EPI>
+__device__ __forceinline__ void f32_dma_tile_body(const DevLaunch &L) {
+    constexpr int FM = G::FM, TN = G::TN, TSA = G::TSA, TSB = G::TSB, APW = G::APW, BPW = G::BPW, DMAS = G::DMAS;
+    constexpr int NBUF = G::NBUF, AHEAD = G::AHEAD;
+    static_assert(EPI == EPI_LINEAR || G::WN == 1, "the LSTM and vocabulary epilogues take the tile's whole rows");
+    static_assert(EPI != EPI_LSTM || BPW == 4, "LSTM weight rows: wave w stages the 32 units of gate w");
+    static_assert(BK == 32, "chunk body written for 4 k-blocks of 8");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *As = smem;                     // [3][TSA]
-    float *Bs = smem + 3 * TSA;           // [3][TSB]
+    float *As = smem;                     // [NBUF][TSA]
+    float *Bs = smem + NBUF * TSA;        // [NBUF][TSB]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wm = tid >> 6;
+    const int w = tid >> 6, wm = w / G::WN, wn = w % G::WN;
     int pi, tm, tn, ks, ksplit;
     map_tile(L, pi, tm, tn, ks, ksplit);
     const DevProb &P = L.p[pi];
     const int M = P.M, N = P.N;
-    const int row0 = tm * BM, col0 = tn * BN;
+    const int row0 = tm * G::BM, col0 = tn * G::BN;
 
-    // staging pieces (8 rows x 128 B each): A piece i of wave w = tile rows 64w + 8i .. +8, B piece i =
-    // tile columns 32w + 8i .. +8; lane -> (row = lane>>3, slot = lane&7).  Rows past the edge re-read
-    // the last valid row (their results are never stored).
-    int arow[8];
-    long long wrow[4];
+    // staging pieces (8 rows x 128 B each): A piece i of wave w = tile rows 8 (APW w + i) .. +8, W piece i = tile
+    // columns 8 (BPW w + i) .. +8; lane -> (row = lane>>3, slot = lane&7).  Rows past the edge re-read the last valid
+    // row (their results are never stored).
+    int arow[APW];
+    long long wrow[BPW];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int r = row0 + 64 * wm + 8 * i + (lane >> 3);
+    for (int i = 0; i < APW; ++i) {
+        const int r = row0 + 8 * APW * w + 8 * i + (lane >> 3);
         arow[i] = r < M ? r : M - 1;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < BPW; ++i) {
         if (EPI == EPI_LSTM) {
-            wrow[i] = (long long)wm * P.H + tn * 32 + 8 * i + (lane >> 3);   // gate wm, unit tn*32 + ..
+            wrow[i] = (long long)w * P.H + tn * 32 + 8 * i + (lane >> 3);     // gate w, unit tn*32 + ..
         } else {
-            const int c = col0 + 32 * wm + 8 * i + (lane >> 3);
+            const int c = col0 + 8 * BPW * w + 8 * i + (lane >> 3);
             wrow[i] = c < N ? c : N - 1;
         }
     }
     const int lq = lane & 7, lh = lane >> 4;   // (tile row >> 1) & 7 == (4*(i&1) + lh) for both operands
-    const float *pa[8], *pb[4];
+    const float *pa[APW], *pb[BPW];
     int cs = 0, ck = 0, segK = 0;
     auto set_seg = [&](int si) __attribute__((always_inline)) {
         const DevSeg sg = P.seg[si];
         segK = sg.K;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pa[i] = sg.A + (long long)arow[i] * sg.lda + (lq ^ (4 * (i & 1) + lh)) * 4;
+        for (int i = 0; i < APW; ++i) pa[i] = sg.A + (long long)arow[i] * sg.lda + (lq ^ (4 * (i & 1) + lh)) * 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pb[i] = sg.W + wrow[i] * sg.ldw + (lq ^ (4 * (i & 1) + lh)) * 4;
+        for (int i = 0; i < BPW; ++i) pb[i] = sg.W + wrow[i] * sg.ldw + (lq ^ (4 * (i & 1) + lh)) * 4;
     };
-    const unsigned a_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)As + wm * 64 * BK * 4);
-    const unsigned b_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)Bs + wm * 32 * BK * 4);
+    const unsigned a_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)As + w * APW * 8 * BK * 4);
+    const unsigned b_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)Bs + w * BPW * 8 * BK * 4);
     auto dma = [&](auto bufc, auto idxc) __attribute__((always_inline)) {
         constexpr int BUF = decltype(bufc)::value, IDX = decltype(idxc)::value;
-        if constexpr (IDX < 8) {
+        if constexpr (IDX < APW) {
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
                          :: "s"(a_lds0 + (BUF * TSA + 8 * IDX * BK) * 4), "v"(pa[IDX]) : "memory");
             pa[IDX] += BK;
         } else {
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "s"(b_lds0 + (BUF * TSB + 8 * (IDX - 8) * BK) * 4), "v"(pb[IDX - 8]) : "memory");
-            pb[IDX - 8] += BK;
+                         :: "s"(b_lds0 + (BUF * TSB + 8 * (IDX - APW) * BK) * 4), "v"(pb[IDX - APW]) : "memory");
+            pb[IDX - APW] += BK;
         }
-        if constexpr (IDX == 11) {         // the chunk is fully issued: move the loader on
+        if constexpr (IDX == DMAS - 1) {   // the chunk is fully issued: move the loader on
             ck += BK;
             if (ck >= segK) {
                 ck = 0;
@@ -830,44 +893,32 @@ __global__ __launch_bounds__(256) void gemm_xl_kernel(const DevLaunch L) {
             }
         }
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    auto dma_all = [&](auto bufc) __attribute__((always_inline)) {
-        dma(bufc, I0{}); dma(bufc, I1{}); dma(bufc, I2{}); dma(bufc, I3{});
-        dma(bufc, std::integral_constant<int, 4>{}); dma(bufc, std::integral_constant<int, 5>{});
-        dma(bufc, std::integral_constant<int, 6>{}); dma(bufc, std::integral_constant<int, 7>{});
-        dma(bufc, std::integral_constant<int, 8>{}); dma(bufc, std::integral_constant<int, 9>{});
-        dma(bufc, std::integral_constant<int, 10>{}); dma(bufc, std::integral_constant<int, 11>{});
-    };
 
-    f32x16 acc[2][TN];
+    f32x16 acc[FM][TN];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    static_assert(BK == 32, "chunk body written for 4 k-blocks of 8");
     const int frow = lane & 31, khalf = lane >> 5;
     const int fsw = (frow >> 1) & 7;       // identical for rows frow + 32*j
-    float4 fa[2][2], fb[2][TN];
+    float4 fa[2][FM], fb[2][TN];
     auto lfrag = [&](auto bufc, auto kbc, auto setc) __attribute__((always_inline)) {
         constexpr int BUF = decltype(bufc)::value, kb = decltype(kbc)::value, ST = decltype(setc)::value;
         const int slot = ((2 * kb + khalf) ^ fsw) * 4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-            fa[ST][i] = *reinterpret_cast<const float4 *>(As + BUF * TSA + (wm * 64 + i * 32 + frow) * BK + slot);
+        for (int i = 0; i < FM; ++i)
+            fa[ST][i] = *reinterpret_cast<const float4 *>(As + BUF * TSA + (wm * 32 * FM + i * 32 + frow) * BK + slot);
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-            fb[ST][j] = *reinterpret_cast<const float4 *>(Bs + BUF * TSB + (j * 32 + frow) * BK + slot);
+            fb[ST][j] = *reinterpret_cast<const float4 *>(Bs + BUF * TSB + ((wn * TN + j) * 32 + frow) * BK + slot);
     };
     auto mma_e = [&](auto setc, auto ec) __attribute__((always_inline)) {
         constexpr int ST = decltype(setc)::value, e = decltype(ec)::value;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < FM; ++i) {
             const float a[4] = {fa[ST][i].x, fa[ST][i].y, fa[ST][i].z, fa[ST][i].w};
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
@@ -876,212 +927,81 @@ __global__ __launch_bounds__(256) void gemm_xl_kernel(const DevLaunch L) {
             }
         }
     };
-    // one k-block (32 MFMAs) with up to 4 DMA pieces of chunk c+2 issued between its 8-MFMA groups
-    auto mma_dma = [&](auto setc, auto bufc, auto basec, bool on) __attribute__((always_inline)) {
-        constexpr int B0 = decltype(basec)::value;
-        mma_e(setc, I0{}); if (on) dma(bufc, std::integral_constant<int, B0 + 0>{});
-        mma_e(setc, I1{}); if (on) dma(bufc, std::integral_constant<int, B0 + 1>{});
-        mma_e(setc, I2{}); if (on) dma(bufc, std::integral_constant<int, B0 + 2>{});
-        mma_e(setc, I3{}); if (on) dma(bufc, std::integral_constant<int, B0 + 3>{});
+    // k-block kb of a chunk from fragment set kb & 1: four MFMA groups, group g = 4 kb + e followed by pieces
+    // PER g .. + PER of the chunk AHEAD further on (when there is one) until that chunk is fully issued
+    auto mma_dma = [&](auto kbc, auto farc, bool on) __attribute__((always_inline)) {
+        constexpr int kb = decltype(kbc)::value;
+        static_for<4>([&](auto ec) __attribute__((always_inline)) {
+            mma_e(std::integral_constant<int, (kb & 1)>{}, ec);
+            constexpr int P0 = G::PER * (4 * kb + decltype(ec)::value);
+            if constexpr (P0 < DMAS) {
+                if (on) static_for<G::PER>([&](auto pc) __attribute__((always_inline)) {
+                    dma(farc, std::integral_constant<int, P0 + decltype(pc)::value>{});
+                });
+            }
+        });
     };
     int nchunks = 0;
     for (int s = 0; s < P.nseg; ++s) nchunks += P.seg[s].K / BK;
-    // chunk c lives in ring slot c % 3.  Slot (c+2) % 3 was last read in chunk c-1, whose reads all
-    // retired (lgkmcnt(0)) in front of that chunk's barrier - so its DMA may start right away.
-    auto chunk_body = [&](auto curc, auto nxtc, auto nnc, bool has1, bool has2) __attribute__((always_inline)) {
+    // Chunk c lives in buffer c % NBUF.  Buffer (c + AHEAD) % NBUF was last read in chunk c-1, whose reads all retired
+    // (lgkmcnt(0)) in front of that chunk's barrier - so its DMA may start right away.
+    auto chunk_body = [&](auto curc, int c) __attribute__((always_inline)) {
+        constexpr int CUR = decltype(curc)::value;
+        using Nxt = std::integral_constant<int, (CUR + 1) % NBUF>;
+        using Far = std::integral_constant<int, (CUR + AHEAD) % NBUF>;
+        const bool has1 = c + 1 < nchunks, far = c + AHEAD < nchunks;
         lfrag(curc, I1{}, I1{});
-        mma_dma(I0{}, nnc, I0{}, has2);
+        mma_dma(I0{}, Far{}, far);
         lfrag(curc, I2{}, I0{});
-        mma_dma(I1{}, nnc, std::integral_constant<int, 4>{}, has2);
+        mma_dma(I1{}, Far{}, far);
         lfrag(curc, I3{}, I1{});
-        mma_dma(I0{}, nnc, std::integral_constant<int, 8>{}, has2);
+        mma_dma(I2{}, Far{}, far);
         if (has1) {
-            // chunk c+1 (issued one chunk ago) must have landed; chunk c+2's 12 pieces stay in flight
-            if (has2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // chunk c+1 must have landed; the chunks issued after it (what is left of them near the end) stay in flight
+            dma_wait_stages<AHEAD - 1, DMAS>(nchunks - c - 2);
             __syncthreads();
-            lfrag(nxtc, I0{}, I0{});
+            lfrag(Nxt{}, I0{}, I0{});
         }
-        mma_e(I1{}, I0{}); mma_e(I1{}, I1{}); mma_e(I1{}, I2{}); mma_e(I1{}, I3{});
+        mma_dma(I3{}, Far{}, false);
     };
     set_seg(0);
-    dma_all(I0{});
-    if (nchunks > 1) {
-        dma_all(I1{});
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    static_for<AHEAD>([&](auto qc) __attribute__((always_inline)) {
+        if (decltype(qc)::value == 0 || decltype(qc)::value < nchunks)
+            static_for<DMAS>([&](auto ic) __attribute__((always_inline)) { dma(qc, ic); });
+    });
+    dma_wait_stages<AHEAD - 1, DMAS>(nchunks - 1);
     __syncthreads();
     lfrag(I0{}, I0{}, I0{});
-    for (int c = 0; c < nchunks; c += 3) {
-        chunk_body(I0{}, I1{}, I2{}, c + 1 < nchunks, c + 2 < nchunks);
-        if (c + 1 < nchunks) chunk_body(I1{}, I2{}, I0{}, c + 2 < nchunks, c + 3 < nchunks);
-        if (c + 2 < nchunks) chunk_body(I2{}, I0{}, I1{}, c + 3 < nchunks, c + 4 < nchunks);
-    }
+    for (int c = 0; c < nchunks; c += NBUF)
+        static_for<NBUF>([&](auto bc) __attribute__((always_inline)) {
+            constexpr int B = decltype(bc)::value;
+            if (B == 0 || c + B < nchunks) chunk_body(bc, c + B);
+        });
 
-    if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag<TN, 1, BM>(P, acc[0], wm * 64, 0, 0, lane, row0, col0, tn, smem);
-        epi_vocab_frag<TN, 1, BM>(P, acc[1], wm * 64 + 32, 0, 0, lane, row0, col0, tn, smem);
-    } else if constexpr (EPI == EPI_LSTM) {
-        epi_lstm_frag(P, acc[0], wm * 64, lane, row0, tn);
-        epi_lstm_frag(P, acc[1], wm * 64 + 32, lane, row0, tn);
-    } else {
-        epi_linear_frag<4>(P, acc[0], wm * 64, 0, lane, row0, col0);
-        epi_linear_frag<4>(P, acc[1], wm * 64 + 32, 0, lane, row0, col0);
-    }
+    static_for<FM>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        const int frow0 = wm * 32 * FM + 32 * i;
+        if constexpr (EPI == EPI_VOCAB) epi_vocab_frag<TN, 1, G::BM>(P, acc[i], frow0, 0, 0, lane, row0, col0, tn, smem);
+        else if constexpr (EPI == EPI_LSTM) epi_lstm_frag(P, acc[i], frow0, lane, row0, tn);
+        else epi_linear_frag<TN>(P, acc[i], frow0, wn * 32 * TN, lane, row0, col0);
+    });
 }
 
-// ---------------------------------------------------------------- LD tile: 128 x 128 by LDS-DMA, two workgroups per CU
-// The L tile's geometry (4 waves stacked in M, 32 x 128 accumulator each) fed like the XL tile: operands by
-// global_load_lds_dwordx4 into two XOR-swizzled 32 KB buffers, no register stage and no ds_write pass (the
-// register-staged loop spends ~9 % of its time moving the staged chunk VGPR -> LDS).  64 KB of LDS keep two
-// workgroups on a CU, so an epilogue-heavy kernel - the vocabulary projection: 16 chunks of MFMAs, then per-row
-// softmax statistics - still has a neighbour to hide its epilogue behind, which the XL tile does not.
-// Chunk c+1's eight DMAs per wave are issued inside k-block 0 of chunk c (its buffer was last read before the
-// previous barrier) and retired with vmcnt(0) in front of the one barrier per chunk.
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_xl_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    f32_dma_tile_body<F32TileXL, EPI>(L);
+}
+
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_ld_kernel(const DevLaunch L) {
     ISC_GATE_RETURN(L);
-    constexpr int BM = 128, BN = 128, TN = 4;
-    constexpr int TS = 128 * BK;                        // floats per operand buffer
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *As = smem;                     // [2][TS]
-    float *Bs = smem + 2 * TS;            // [2][TS]
+    f32_dma_tile_body<F32TileLD, EPI>(L);
+}
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wm = tid >> 6;
-    int pi, tm, tn, ks, ksplit;
-    map_tile(L, pi, tm, tn, ks, ksplit);
-    const DevProb &P = L.p[pi];
-    const int M = P.M, N = P.N;
-    const int row0 = tm * BM, col0 = tn * BN;
-
-    // staging pieces (8 rows x 128 B): piece i of wave w = tile rows / columns 32w + 8i .. +8
-    int arow[4];
-    long long wrow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = row0 + 32 * wm + 8 * i + (lane >> 3);
-        arow[i] = r < M ? r : M - 1;
-        if (EPI == EPI_LSTM) {
-            wrow[i] = (long long)wm * P.H + tn * 32 + 8 * i + (lane >> 3);
-        } else {
-            const int c = col0 + 32 * wm + 8 * i + (lane >> 3);
-            wrow[i] = c < N ? c : N - 1;
-        }
-    }
-    const int lq = lane & 7, lh = lane >> 4;
-    const float *pa[4], *pb[4];
-    int cs = 0, ck = 0, segK = 0;
-    auto set_seg = [&](int si) __attribute__((always_inline)) {
-        const DevSeg sg = P.seg[si];
-        segK = sg.K;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            pa[i] = sg.A + (long long)arow[i] * sg.lda + (lq ^ (4 * (i & 1) + lh)) * 4;
-            pb[i] = sg.W + wrow[i] * sg.ldw + (lq ^ (4 * (i & 1) + lh)) * 4;
-        }
-    };
-    const unsigned a_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)As + wm * 32 * BK * 4);
-    const unsigned b_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)Bs + wm * 32 * BK * 4);
-    auto dma = [&](auto bufc, auto idxc) __attribute__((always_inline)) {
-        constexpr int BUF = decltype(bufc)::value, IDX = decltype(idxc)::value;
-        if constexpr (IDX < 4) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "s"(a_lds0 + (BUF * TS + 8 * IDX * BK) * 4), "v"(pa[IDX]) : "memory");
-            pa[IDX] += BK;
-        } else {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "s"(b_lds0 + (BUF * TS + 8 * (IDX - 4) * BK) * 4), "v"(pb[IDX - 4]) : "memory");
-            pb[IDX - 4] += BK;
-        }
-        if constexpr (IDX == 7) {
-            ck += BK;
-            if (ck >= segK) {
-                ck = 0;
-                if (++cs < P.nseg) set_seg(cs);
-            }
-        }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
-    using I5 = std::integral_constant<int, 5>;
-    using I6 = std::integral_constant<int, 6>;
-    using I7 = std::integral_constant<int, 7>;
-
-    f32x16 acc[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-    static_assert(BK == 32, "chunk body written for 4 k-blocks of 8");
-    const int frow = lane & 31, khalf = lane >> 5;
-    const int fsw = (frow >> 1) & 7;
-    float4 fa[2], fb[2][TN];
-    auto lfrag = [&](auto bufc, auto kbc, auto setc) __attribute__((always_inline)) {
-        constexpr int BUF = decltype(bufc)::value, kb = decltype(kbc)::value, ST = decltype(setc)::value;
-        const int slot = ((2 * kb + khalf) ^ fsw) * 4;
-        fa[ST] = *reinterpret_cast<const float4 *>(As + BUF * TS + (wm * 32 + frow) * BK + slot);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-            fb[ST][j] = *reinterpret_cast<const float4 *>(Bs + BUF * TS + (j * 32 + frow) * BK + slot);
-    };
-    auto mma_e = [&](auto setc, auto ec) __attribute__((always_inline)) {
-        constexpr int ST = decltype(setc)::value, e = decltype(ec)::value;
-        const float a[4] = {fa[ST].x, fa[ST].y, fa[ST].z, fa[ST].w};
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float b[4] = {fb[ST][j].x, fb[ST][j].y, fb[ST][j].z, fb[ST][j].w};
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc[j], 0, 0, 0);
-        }
-    };
-    auto mma = [&](auto setc) __attribute__((always_inline)) {
-        mma_e(setc, I0{}); mma_e(setc, I1{}); mma_e(setc, I2{}); mma_e(setc, I3{});
-    };
-    int nchunks = 0;
-    for (int s = 0; s < P.nseg; ++s) nchunks += P.seg[s].K / BK;
-    auto chunk_body = [&](auto curc, auto nxtc, bool has1) __attribute__((always_inline)) {
-        lfrag(curc, I1{}, I1{});
-        // k-block 0: 4 MFMAs, then two DMA pieces of the next chunk, four times over
-        mma_e(I0{}, I0{}); if (has1) { dma(nxtc, I0{}); dma(nxtc, I1{}); }
-        mma_e(I0{}, I1{}); if (has1) { dma(nxtc, I2{}); dma(nxtc, I3{}); }
-        mma_e(I0{}, I2{}); if (has1) { dma(nxtc, I4{}); dma(nxtc, I5{}); }
-        mma_e(I0{}, I3{}); if (has1) { dma(nxtc, I6{}); dma(nxtc, I7{}); }
-        lfrag(curc, I2{}, I0{});
-        mma(I1{});
-        lfrag(curc, I3{}, I1{});
-        mma(I0{});
-        if (has1) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            lfrag(nxtc, I0{}, I0{});
-        }
-        mma(I1{});
-    };
-    set_seg(0);
-    dma(I0{}, I0{}); dma(I0{}, I1{}); dma(I0{}, I2{}); dma(I0{}, I3{});
-    dma(I0{}, I4{}); dma(I0{}, I5{}); dma(I0{}, I6{}); dma(I0{}, I7{});
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    lfrag(I0{}, I0{}, I0{});
-    for (int c = 0; c < nchunks; c += 2) {
-        chunk_body(I0{}, I1{}, c + 1 < nchunks);
-        if (c + 1 < nchunks) chunk_body(I1{}, I0{}, c + 2 < nchunks);
-    }
-
-    if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag<TN, 1, BM>(P, acc, wm * 32, 0, 0, lane, row0, col0, tn, smem);
-    } else if constexpr (EPI == EPI_LSTM) {
-        epi_lstm_frag(P, acc, wm * 32, lane, row0, tn);
-    } else {
-        epi_linear_frag<4>(P, acc, wm * 32, 0, lane, row0, col0);
-    }
+__global__ __launch_bounds__(256) void gemm_md_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    f32_dma_tile_body<F32TileMD, EPI_LINEAR>(L);
 }
 
 // ---- epilogues for the C/D layout of v_mfma_f32_16x16x32_f16 (the split-f16 tile kernels, round 3) ----------------
@@ -1460,20 +1380,6 @@ using H3Tile256 = H3Geom<8, 1, 4, 3, false>;
 // has 48.)
 using H3Tile64 = H3Geom<2, 2, 2, 4, false>;
 
-// s_waitcnt vmcnt that leaves the youngest `in_flight` (<= MAXF) stages of DMAS instructions outstanding; the
-// immediates are compile-time
-template <int MAXF, int DMAS>
-__device__ __forceinline__ void h3_wait_stages(int in_flight) {
-    if constexpr (MAXF == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (in_flight >= MAXF) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(MAXF * DMAS) : "memory");
-    else h3_wait_stages<MAXF - 1, DMAS>(in_flight);
-}
-
-using I0 = std::integral_constant<int, 0>;
-using I1 = std::integral_constant<int, 1>;
-using I2 = std::integral_constant<int, 2>;
-using I3 = std::integral_constant<int, 3>;
-
 // The body of gemm_h3_kernel / gemm_h3x_kernel / gemm_h3m_kernel (geometry G).
 // AF32: some activation segment comes as fp32 rows (split after the fragment read); false = every segment has planes,
 // and the per-buffer test is compiled out of the fragment loads (it cost the all-planes decode loop ~5-10 %).
@@ -1640,7 +1546,7 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
         }
     };
     // NBUF buffers, AHEAD chunks in flight: the wait in front of a barrier leaves the younger stages outstanding
-    auto wait_for = [&](int in_flight) __attribute__((always_inline)) { h3_wait_stages<AHEAD - 1, G::DMAS>(in_flight); };
+    auto wait_for = [&](int in_flight) __attribute__((always_inline)) { dma_wait_stages<AHEAD - 1, G::DMAS>(in_flight); };
     H3_STAMP_AT(stamp1);
 #pragma unroll
     for (int q = 0; q < AHEAD; ++q)
@@ -1809,137 +1715,6 @@ __global__ __launch_bounds__(256) void h3_split_kernel(const SplitLaunch S) {
     *reinterpret_cast<h8 *>(J.hi + o) = hi;
     *reinterpret_cast<h8 *>(J.lo + o) = lo;
 }
-
-// ---------------------------------------------------------------- MD tile: 64 x 128 by LDS-DMA (linear epilogue)
-// The LD scheme on the M geometry (2 x 2 waves, 32 x 64 accumulator each) for the per-step projections with
-// N = 512: their 64-row tiles are what balances 4096 x 512 outputs over 256 CUs, and at one to three workgroups
-// per CU the register-staged form of that tile leaves the matrix pipe idle over its chunk-boundary round trips.
-__global__ __launch_bounds__(256) void gemm_md_kernel(const DevLaunch L) {
-    ISC_GATE_RETURN(L);
-    constexpr int TN = 2;
-    constexpr int TSA = 64 * BK, TSB = 128 * BK;      // floats per operand buffer
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *As = smem;                     // [2][TSA]
-    float *Bs = smem + 2 * TSA;           // [2][TSB]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = tid >> 6, wm = w >> 1, wn = w & 1;
-    int pi, tm, tn, ks, ksplit;
-    map_tile(L, pi, tm, tn, ks, ksplit);
-    const DevProb &P = L.p[pi];
-    const int M = P.M, N = P.N;
-    const int row0 = tm * 64, col0 = tn * 128;
-
-    // staging pieces (8 rows x 128 B): A pieces 2w, 2w+1 = tile rows 16w + 8i; B pieces 4w .. 4w+3 = columns 32w + 8i
-    int arow[2];
-    long long wrow[4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int r = row0 + 16 * w + 8 * i + (lane >> 3);
-        arow[i] = r < M ? r : M - 1;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = col0 + 32 * w + 8 * i + (lane >> 3);
-        wrow[i] = c < N ? c : N - 1;
-    }
-    const int lq = lane & 7, lh = lane >> 4;
-    const float *pa[2], *pb[4];
-    int cs = 0, ck = 0, segK = 0;
-    auto set_seg = [&](int si) __attribute__((always_inline)) {
-        const DevSeg sg = P.seg[si];
-        segK = sg.K;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) pa[i] = sg.A + (long long)arow[i] * sg.lda + (lq ^ (4 * (i & 1) + lh)) * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pb[i] = sg.W + wrow[i] * sg.ldw + (lq ^ (4 * (i & 1) + lh)) * 4;
-    };
-    const unsigned a_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)As + w * 16 * BK * 4);
-    const unsigned b_lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)Bs + w * 32 * BK * 4);
-    auto dma = [&](auto bufc, auto idxc) __attribute__((always_inline)) {
-        constexpr int BUF = decltype(bufc)::value, IDX = decltype(idxc)::value;
-        if constexpr (IDX < 2) {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "s"(a_lds0 + (BUF * TSA + 8 * IDX * BK) * 4), "v"(pa[IDX]) : "memory");
-            pa[IDX] += BK;
-        } else {
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-                         :: "s"(b_lds0 + (BUF * TSB + 8 * (IDX - 2) * BK) * 4), "v"(pb[IDX - 2]) : "memory");
-            pb[IDX - 2] += BK;
-        }
-        if constexpr (IDX == 5) {
-            ck += BK;
-            if (ck >= segK) {
-                ck = 0;
-                if (++cs < P.nseg) set_seg(cs);
-            }
-        }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
-    using I5 = std::integral_constant<int, 5>;
-
-    f32x16 acc[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    const int frow = lane & 31, khalf = lane >> 5;
-    const int fsw = (frow >> 1) & 7;
-    float4 fa[2], fb[2][TN];
-    auto lfrag = [&](auto bufc, auto kbc, auto setc) __attribute__((always_inline)) {
-        constexpr int BUF = decltype(bufc)::value, kb = decltype(kbc)::value, ST = decltype(setc)::value;
-        const int slot = ((2 * kb + khalf) ^ fsw) * 4;
-        fa[ST] = *reinterpret_cast<const float4 *>(As + BUF * TSA + (wm * 32 + frow) * BK + slot);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-            fb[ST][j] = *reinterpret_cast<const float4 *>(Bs + BUF * TSB + ((wn * TN + j) * 32 + frow) * BK + slot);
-    };
-    auto mma_e = [&](auto setc, auto ec) __attribute__((always_inline)) {
-        constexpr int ST = decltype(setc)::value, e = decltype(ec)::value;
-        const float a[4] = {fa[ST].x, fa[ST].y, fa[ST].z, fa[ST].w};
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float b[4] = {fb[ST][j].x, fb[ST][j].y, fb[ST][j].z, fb[ST][j].w};
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc[j], 0, 0, 0);
-        }
-    };
-    auto mma = [&](auto setc) __attribute__((always_inline)) {
-        mma_e(setc, I0{}); mma_e(setc, I1{}); mma_e(setc, I2{}); mma_e(setc, I3{});
-    };
-    int nchunks = 0;
-    for (int s = 0; s < P.nseg; ++s) nchunks += P.seg[s].K / BK;
-    auto chunk_body = [&](auto curc, auto nxtc, bool has1) __attribute__((always_inline)) {
-        lfrag(curc, I1{}, I1{});
-        mma_e(I0{}, I0{}); if (has1) { dma(nxtc, I0{}); dma(nxtc, I1{}); }
-        mma_e(I0{}, I1{}); if (has1) { dma(nxtc, I2{}); dma(nxtc, I3{}); }
-        mma_e(I0{}, I2{}); if (has1) { dma(nxtc, I4{}); dma(nxtc, I5{}); }
-        mma_e(I0{}, I3{});
-        lfrag(curc, I2{}, I0{});
-        mma(I1{});
-        lfrag(curc, I3{}, I1{});
-        mma(I0{});
-        if (has1) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            lfrag(nxtc, I0{}, I0{});
-        }
-        mma(I1{});
-    };
-    set_seg(0);
-    dma(I0{}, I0{}); dma(I0{}, I1{}); dma(I0{}, I2{}); dma(I0{}, I3{}); dma(I0{}, I4{}); dma(I0{}, I5{});
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    lfrag(I0{}, I0{}, I0{});
-    for (int c = 0; c < nchunks; c += 2) {
-        chunk_body(I0{}, I1{}, c + 1 < nchunks);
-        if (c + 1 < nchunks) chunk_body(I1{}, I0{}, c + 2 < nchunks);
-    }
-    epi_linear_frag<TN>(P, acc, wm * 32, wn * 64, lane, row0, col0);
-}
-
 
 // ---------------------------------------------------------------- H3S: skinny split-f16 tiles for few-row launches
 // (H3S_LAB_MODE = 1 / 2 / 3 builds time-only variants of the kernel below - DMA only / + fragment reads / MFMAs without
@@ -2811,39 +2586,36 @@ static int launch_cfg(const DevLaunch &L, hipStream_t st) {
     return ISC_OK;
 }
 
-template <int EPI>
-static int launch_xl(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = (size_t)3 * (256 + 128) * BK * sizeof(float);   // 147456 >= Cs 256 x 132 floats
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_xl_kernel<EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set.store(true);
+template <class G, int EPI>
+static constexpr auto f32_dma_kernel() {
+    if constexpr (std::is_same_v<G, F32TileXL>) return &gemm_xl_kernel<EPI>;
+    else if constexpr (std::is_same_v<G, F32TileLD>) return &gemm_ld_kernel<EPI>;
+    else return &gemm_md_kernel;
+}
+
+// One launch of an fp32 LDS-DMA tile kernel of geometry G (the tiling of L is the caller's).
+template <class G, int EPI>
+static int launch_f32_dma(const DevLaunch &L, hipStream_t st) {
+    static_assert(EPI == EPI_LINEAR || !std::is_same_v<G, F32TileMD>, "the 64-row kernel has the linear epilogue only");
+    constexpr size_t lds = G::LDS_BYTES;       // XL 147456: one workgroup per CU; LD 65536: two; MD 49152: three
+    constexpr auto kernel = f32_dma_kernel<G, EPI>();
+    if constexpr (lds > 65536) {
+        static std::atomic<bool> attr_set{false};  // idempotent: a race only repeats the same call
+        if (!attr_set.load()) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return (int)e;
+            attr_set.store(true);
+        }
     }
-    hipLaunchKernelGGL((gemm_xl_kernel<EPI>), dim3(L.total_tiles), dim3(256), lds, st, L);
+    hipLaunchKernelGGL(kernel, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
 
-template <int EPI>
-static int launch_ld(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = (size_t)4 * 128 * BK * sizeof(float);           // 65536: two workgroups per CU
-    hipLaunchKernelGGL((gemm_ld_kernel<EPI>), dim3(L.total_tiles), dim3(256), lds, st, L);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
-}
-
-// Tile shapes: 0 = L 128x128 (4 waves stacked in M), 1 = M 64x128 (2x2 waves), 2 = S 32x128 (4 waves in N),
-// 3 = XL 256x128 (LDS-DMA ring, NT layout only), 4 = LD 128x128 by LDS-DMA (NT layout only)
-static const int kTileBM[5] = {128, 64, 32, 256, 128};
-
-static int launch_md(const DevLaunch &L, hipStream_t st) {
-    constexpr size_t lds = (size_t)2 * (64 + 128) * BK * sizeof(float);    // 49152: three workgroups per CU
-    hipLaunchKernelGGL(gemm_md_kernel, dim3(L.total_tiles), dim3(256), lds, st, L);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
-}
+// Tile shapes: 0 = L 128x128 (4 waves stacked in M), 1 = M 64x128 (2x2 waves; MD by LDS-DMA for plain linear NT launches),
+// 2 = S 32x128 (4 waves in N), 3 = XL 256x128 (LDS-DMA ring, NT layout only), 4 = LD 128x128 by LDS-DMA (NT layout only)
+static const int kTileBM[5] = {128, F32TileMD::BM, 32, F32TileXL::BM, F32TileLD::BM};
 
 static std::atomic<int> g_md_enabled{1};   // isc_set_tile_override(102 / 103): MD path off / on (A/B measurements)
 
@@ -2853,12 +2625,12 @@ static int launch_any(const DevLaunch &L, int tile, hipStream_t st) {
         if (tile == 1 && g_md_enabled.load()) {
             bool plain = true;
             for (int i = 0; i < L.nprob; ++i) plain = plain && L.p[i].ksplit <= 1;
-            if (plain) return launch_md(L, st);
+            if (plain) return launch_f32_dma<F32TileMD, EPI_LINEAR>(L, st);
         }
     }
     if constexpr (!AKM && !BKM) {
-        if (tile == 3) return launch_xl<EPI>(L, st);
-        if (tile == 4) return launch_ld<EPI>(L, st);
+        if (tile == 3) return launch_f32_dma<F32TileXL, EPI>(L, st);
+        if (tile == 4) return launch_f32_dma<F32TileLD, EPI>(L, st);
     }
     if (tile == 0) return launch_cfg<4, 1, 4, EPI, AKM, BKM>(L, st);
     if (tile == 1) return launch_cfg<2, 2, 2, EPI, AKM, BKM>(L, st);

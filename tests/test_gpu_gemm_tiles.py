@@ -1,6 +1,6 @@
-"""Every GEMM tile shape (128x128, 64x128, 32x128 register-staged; 256x128 and 128x128 by LDS-DMA) behind the same
-entry points: each must match an fp64 reference and - because every shape accumulates an output element
-over k in the same order - must agree bit for bit with the others."""
+"""Every GEMM tile shape (128x128, 64x128, 32x128 register-staged; 256x128, 128x128 and - what tile 1 runs for plain
+linear NT launches - 64x128 by LDS-DMA) behind the same entry points: each must match an fp64 reference and - because
+every shape accumulates an output element over k in the same order - must agree bit for bit with the others."""
 import numpy as np
 import pytest
 import torch
