@@ -308,6 +308,23 @@ typedef struct {
 int isc_rollout_finalize(const isc_rollout_step *s_host, void *stream);
 long long isc_rollout_finalize_launches(void);   /* launches so far (tests: isc_rows_ext.fin_prev saves them) */
 
+/* Controlled sampling of the sampled roll-out: temperature, top-k, nucleus (top-p).  Per row, tokens are ranked by raw
+ * logit (largest first, ties to the smaller id), mass w_i = exp((x_i - x_max) / temperature); top-k keeps the first k
+ * ranks (0 or >= V: off); top-p, applied to the survivors with summed mass W_k, keeps rank j iff the mass of the ranks
+ * in front of it is < top_p * W_k (rank 0 always; >= 1: off); the draw is the inverse CDF over the kept set in
+ * vocabulary order against sample_u * (kept mass).  seq_logprobs stays the MODEL's log_softmax(x)[token];
+ * sampling_logprobs (optional, [B,T]) receives log(w_token / kept mass).  Everything else - seq, seq_masks, <EOS>, the
+ * `alive` counters, raw_tokens, xt_next - as isc_rollout_finalize with sample_u (required here, as are the logits;
+ * `forced` must be null).  One launch, no host read; integer (fixed-point) mass sums: bit-repeatable.
+ * temperature must be finite and > 0, top_k >= 0, top_p > 0: otherwise ISC_E_SHAPE before any launch. */
+typedef struct {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float *sampling_logprobs;
+} isc_sample_filter;
+int isc_rollout_finalize_filtered(const isc_rollout_step *s_host, const isc_sample_filter *f_host, void *stream);
+
 /* Scheduled sampling of the teacher-forced unrolls (captioner.py:219-228): out_ids[b] = u_select[b] < ss_prob
  * ? a draw from exp(logp[b,:]) (inverse CDF with uniform u_draw[b], vocabulary order) : base_ids[b*stride].
  * logp = the previous step's normalised output, part_* = that step's tile statistics from isc_vocab_fwd. */

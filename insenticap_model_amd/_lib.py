@@ -139,6 +139,12 @@ class RolloutStep(C.Structure):
                 ('emb', C.c_void_p), ('xt_add', C.c_void_p), ('xt_next', C.c_void_p)]
 
 
+class SampleFilter(C.Structure):
+    """isc_sample_filter: temperature / top-k / top-p of isc_rollout_finalize_filtered."""
+    _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('top_p', C.c_float),
+                ('sampling_logprobs', C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -202,6 +208,7 @@ SIGNATURES = {
                                             C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     'isc_rollout_finalize': (C.c_int, [C.POINTER(RolloutStep), C.c_void_p]),
     'isc_rollout_finalize_launches': (C.c_longlong, []),
+    'isc_rollout_finalize_filtered': (C.c_int, [C.POINTER(RolloutStep), C.POINTER(SampleFilter), C.c_void_p]),
     'isc_beam_merge': (C.c_int, [C.POINTER(BeamMergeArgs), C.c_void_p]),
     'isc_beam_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'isc_beam_topk': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

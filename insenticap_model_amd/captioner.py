@@ -796,9 +796,34 @@ class Captioner(nn.Module):
         return pred, pred2
 
     def forward_rl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, sample_max,
-                   _replay=None, _masks=None):
+                   _replay=None, _masks=None, temperature=1.0, top_k=0, top_p=1.0, generator=None,
+                   return_sampling_logprobs=False, _uniforms=None):
         """Greedy (`sample_max=1`) or sampled roll-out (captioner.py:290-349) with the whole T-step loop
-        enqueued without a host sync; `_replay` [B,T] forces the raw draws (parity tests)."""
+        enqueued without a host sync; `_replay` [B,T] forces the raw draws (parity tests).
+        Sampled roll-outs (`sample_max=0`) take the sampling controls `temperature` (> 0), `top_k` (0: off) and `top_p`
+        (nucleus; >= 1: off) - decided per row on the device (isc_rollout_finalize_filtered), still without a host sync -
+        and `generator` for the uniforms; `_uniforms` [B,T] float32 replaces the drawn uniforms (tests, the counterpart of
+        `_replay`).  `seq_logprobs` stays the MODEL's log-probability of the drawn token; `return_sampling_logprobs=True`
+        appends a fourth tensor, the log-probability under the distribution that was sampled.  With the default controls
+        the call is today's plain multinomial roll-out, bit for bit.  Inference only for now."""
+        temperature, top_k, top_p = ops.check_sample_filter(temperature, top_k, top_p)
+        filtered = temperature != 1.0 or 0 < top_k < self.vocab_size or top_p < 1.0
+        if sample_max and (filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
+            raise ValueError('temperature / top_k / top_p / generator / return_sampling_logprobs / _uniforms apply to '
+                             'sampled roll-outs only (sample_max=0)')
+        if _replay is not None and (filtered or return_sampling_logprobs or _uniforms is not None):
+            raise ValueError('_replay forces the tokens: it excludes the sampling controls')
+        if filtered and self._needs_grad():
+            raise ValueError('filtered sampling (temperature / top_k / top_p) is inference-only for now: call it under '
+                             'torch.no_grad() (the backward through 1 / temperature is not built)')
+        if not sample_max and not self._needs_grad() and _replay is None and (
+                filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
+            filt = self._sample_filter(temperature, top_k, top_p, generator, _uniforms, return_sampling_logprobs)
+            out = self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0, None,
+                                _masks, filt)
+            return out[:3] + ((filt['slp'],) if return_sampling_logprobs else ())
+        if return_sampling_logprobs or _uniforms is not None or generator is not None:
+            raise ValueError('generator / return_sampling_logprobs / _uniforms are not available with gradients enabled')
         if not sample_max and self._needs_grad():
             from .autograd import rollout_with_grad
             return rollout_with_grad(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels,
@@ -812,6 +837,14 @@ class Captioner(nn.Module):
             return self._graphed_rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len)
         return self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len,
                              sample_max, _replay, _masks)[:3]
+
+    def _sample_filter(self, temperature=1.0, top_k=0, top_p=1.0, generator=None, uniforms=None, want_slp=False):
+        """The sampling controls of one sampled roll-out as `_rollout` takes them (`filt`); after the call `filt['slp']`
+        holds the sampling log-probabilities when `want_slp`."""
+        temperature, top_k, top_p = ops.check_sample_filter(temperature, top_k, top_p)
+        return dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator, uniforms=uniforms,
+                    want_slp=bool(want_slp),
+                    filtered=temperature != 1.0 or 0 < top_k < self.vocab_size or top_p < 1.0)
 
     # ------------------------------------------------------------------ hipGraph replay of the greedy roll-out
     def enable_rollout_graphs(self, on=True, max_graphs=4):
@@ -948,18 +981,18 @@ class Captioner(nn.Module):
         return gb
 
     def _rollout(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                 masks):
+                 masks, filt=None):
         self._p()                                  # raises on CPU parameters before anything touches the device
         if not self._features_in_domain(fc_feats, att_feats):
             # features beyond the split-f16 domain: the reference decodes whatever its encoder produced
             # (captioner.py:198-214, 294-315) - so does this call, on the exact-fp32 engine
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                          replay, masks)
+                                          replay, masks, filt)
         # frozen weights for prologue + loop: split them once per call - or, with unchanged weights, once per run of calls
         with ops.h3_weights_scope(self._dev, key=self._weights_key()):
             return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                      replay, masks)
+                                      replay, masks, filt)
 
     # ------------------------------------------------------------------ operand domain of the split-f16 engine
     SPLIT_F16_MAX = 65504.0
@@ -1025,7 +1058,7 @@ class Captioner(nn.Module):
                           'features to keep the fast engine.' % what)
 
     def _rollout_impl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                      masks):
+                      masks, filt=None):
         p = self._p()
         arm = ops.TIMER.arm_step          # bench.py: time the kernels of ONE step (-1: the prologue)
         ops.TIMER.armed, ops.TIMER.phase = (arm == -1), 'prologue'
@@ -1081,8 +1114,20 @@ class Captioner(nn.Module):
         if not sample_max:
             if replay is not None:
                 forced = self._ids(replay)
+            elif filt is not None and filt['uniforms'] is not None:
+                sample_u = filt['uniforms']
+                if (not torch.is_tensor(sample_u) or sample_u.dtype != torch.float32 or tuple(sample_u.shape) != (B, T)):
+                    raise ValueError('_uniforms must be a float32 tensor of shape [B, T] = [%d, %d]' % (B, T))
+                sample_u = sample_u.to(self._dev).contiguous()
+            elif filt is not None and filt['generator'] is not None:
+                sample_u = torch.rand(B, T, device=self._dev, generator=filt['generator'])
             else:
                 sample_u = torch.rand(B, T, device=self._dev)
+        # temperature / top-k / top-p: the filtered finalize takes the plain one's place (same launch count per step)
+        filtered = filt is not None and filt['filtered']
+        slp = None
+        if filt is not None and filt['want_slp'] and filtered:
+            slp = self._zeros(B, T)
         mask_for = self._mask_source(masks)
         rs = RolloutStep()
         rs.B, rs.V, rs.T, rs.n_tile, rs.W = B, V, T, ws['pmax'].shape[1], Wd
@@ -1118,8 +1163,14 @@ class Captioner(nn.Module):
                 rs.t = t
                 rs.unfinished = unf[t].data_ptr() if fuse else unfinished.data_ptr()
                 rs.xt_next = None if use_tab else xt[nxt].data_ptr()
-                ops.rollout_finalize(rs)
+                if filtered:
+                    ops.rollout_finalize_filtered(rs, filt['temperature'], filt['top_k'], filt['top_p'], slp)
+                else:
+                    ops.rollout_finalize(rs)
         ops.TIMER.armed = False
+        if filt is not None and filt['want_slp']:
+            # (default controls: the sampled distribution IS the model's)
+            filt['slp'] = slp if filtered else seq_logprobs.clone()
         # no host read: the executed-step count stays on the device (`alive`) until someone needs it
         self._set_weights(aC, aS, bG, alive)
         return seq, seq_logprobs, seq_masks, raw, alive
@@ -1175,6 +1226,35 @@ class Captioner(nn.Module):
                 return on_exact_engine()
             ops.check_numerics('Captioner.sample')
         return out
+
+    @torch.no_grad()
+    def sample_captions(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, n=1, max_seq_len=16,
+                        temperature=1.0, top_k=0, top_p=1.0, generator=None, _uniforms=None):
+        """`n` sampled captions per image under the sampling controls of `forward_rl` (temperature / top_k / top_p):
+        every image's inputs are repeated `n` times on the device (rows i*n ... i*n + n - 1 belong to image i) and ONE
+        sampled roll-out draws all I*n captions.  Returns (captions[I][n], id_sequences[I][n]); the strings are built as
+        `sample_batch` builds them (words up to <EOS>, <EOS> itself left out of the string and kept in the ids).
+        `_uniforms` [I*n, max_seq_len]: test hook, as in `forward_rl`."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('n must be >= 1, got %r' % (n,))
+        ops.check_sample_filter(temperature, top_k, top_p)
+        if self.training:
+            self.eval()
+
+        def rep(x):
+            return None if x is None else x.repeat_interleave(n, dim=0)
+        seq, _, masks = self.forward_rl(rep(fc_feats), rep(att_feats), rep(cpt_words), rep(senti_words),
+                                        rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
+                                        top_p=top_p, generator=generator, _uniforms=_uniforms)
+        seq_h, len_h = seq.cpu().tolist(), masks.sum(1).long().cpu().tolist()      # the call's one host read
+        i2w, eos = self.idx2word, self.eos_id
+        captions, ids = [], []
+        for i in range(len(seq_h) // n):
+            rows = [seq_h[i * n + j][:len_h[i * n + j]] for j in range(n)]
+            captions.append([' '.join(i2w[w] for w in words if w != eos) for words in rows])
+            ids.append(rows)
+        return captions, ids
 
     def get_optim_criterion(self, lr, weight_decay=0):
         from .optim import FusedClampAdam   # a torch.optim.Adam subclass: same state_dict layout

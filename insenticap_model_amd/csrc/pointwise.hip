@@ -427,6 +427,310 @@ extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
     return ISC_OK;
 }
 
+// ------------------------------------------------------------------ filtered sampling: temperature, top-k, top-p
+// The sampled roll-out's finalize with a per-row decision, on the device, of WHICH tokens may be drawn.  Ranking is by raw
+// logit (largest first, ties to the smaller id): one 64-bit key K = (descending image of x : id), all distinct, ascending
+// K = rank order.  The kept set is a rank prefix, i.e. {K <= K*}; K* is found by SELECTION, never by sorting the row:
+//   1. a 256-bucket histogram (integer counts, integer masses) over buckets LINEAR in (max - x) - monotone in x, so a
+//      bucket is a rank interval - and a scan over the buckets find the bucket that holds the boundary;
+//   2. that bucket's few elements are ranked against each other (all pairs) - or, when it holds more than 256 (rows of
+//      tied logits), by a radix descent over the bits of K, eight levels of 256 buckets.
+// Top-k selects by count; top-p then selects by mass among the survivors, against top_p * (their summed mass).
+// Masses are FIXED POINT: w = exp((x - max) / T) in (0, 1] scaled to 2^32 in a 64-bit sum.  Integer adds commute, so the
+// LDS atomics of the histograms and every reduction give the same bits on every run; an element's rounding error is
+// 2^-33 of the row's largest mass (V = 20000: <= 2.3e-6 of the total if every error had one sign, ~1e-8 as they fall).
+// The draw is the inverse CDF over the kept set in vocabulary order, against u * (kept mass), in the same integers.
+// One 256-thread workgroup per row, the row staged in LDS once (V <= ISC_FLT_STAGE_MAX; longer rows are re-read from
+// L2); a workgroup walks rows blockIdx.x, + gridDim.x, ... so that `alive` sees one atomic per workgroup.
+typedef unsigned long long isc_u64;
+#define ISC_FLT_STAGE_MAX 12288
+#define ISC_FLT_MAX_GRID 768            // 3 workgroups of ~47 KB LDS per CU
+#define ISC_FLT_MASS_SPAN 23.0f         // exp(-23) * 2^32 < 1/2: beyond (max - x) / T = 23 a mass rounds to zero
+
+struct DevFilter {
+    float c_exp;       // log2(e) / temperature
+    float tau;
+    int top_k;         // 0: off
+    float top_p;       // >= 1: off
+    float *slp;        // optional [B,T]: log-probability under the sampled distribution
+    int staged;        // row in LDS
+};
+
+__device__ __forceinline__ isc_u64 flt_key(float x, int i) {
+    unsigned b = __float_as_uint(x);
+    if (b == 0x80000000u) b = 0u;                                     // -0 ranks with +0
+    const unsigned dk = (b & 0x80000000u) ? b : (~b & 0x7fffffffu);   // larger x -> smaller dk
+    return ((isc_u64)dk << 32) | (unsigned)i;
+}
+
+__device__ __forceinline__ unsigned flt_mass(float x, float gmax, float c_exp) {
+    const float e = __builtin_amdgcn_exp2f(fminf((x - gmax) * c_exp, 0.f)) * 4294967296.0f;
+    return (unsigned)__builtin_rintf(fminf(e, 4294967040.0f));       // NaN -> 0
+}
+
+__device__ __forceinline__ int flt_bucket(float x, float gmax, float cb) {
+    return (int)fminf(fmaxf((gmax - x) * cb, 0.f), 255.f);           // NaN -> 0
+}
+
+// exclusive prefix of (c, m) over the 256 threads of the workgroup, in thread order
+__device__ __forceinline__ void flt_scan(unsigned &c, isc_u64 &m, unsigned *s32, isc_u64 *s64, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned ci = c;
+    isc_u64 mi = m;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned nc = __shfl_up(ci, o, 64);
+        const isc_u64 nm = __shfl_up(mi, o, 64);
+        if (lane >= o) { ci += nc; mi += nm; }
+    }
+    __syncthreads();                      // (the scratch words may still be read from the previous use)
+    if (lane == 63) { s32[wave] = ci; s64[wave] = mi; }
+    __syncthreads();
+    unsigned bc = 0;
+    isc_u64 bm = 0;
+    for (int w = 0; w < wave; ++w) { bc += s32[w]; bm += s64[w]; }
+    c = bc + ci - c;
+    m = bm + mi - m;
+}
+
+__global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const DevRollout R, const DevFilter F) {
+    extern __shared__ float flt_row[];
+    __shared__ isc_u64 h_mass[256], c_key[256], c_mass[256], s64[4], sh64[4];
+    __shared__ unsigned h_cnt[256], s32[4];
+    __shared__ int shi[4];
+    __shared__ float shf[4];
+    if (R.alive[R.t] == 0) return;          // block-uniform
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = R.V;
+    int alive = 0;
+    for (int b = blockIdx.x; b < R.B; b += gridDim.x) {
+        const float *xg = R.logits + (long long)b * R.ld_logits;
+        const float *xs = F.staged ? flt_row : xg;
+        const int unf = R.unfinished[b];    // (thread 0 rewrites it behind the barriers below)
+        float gmax, S;
+        int gidx;
+        fold_row_stats(R.part_max + (long long)b * R.n_tile, R.part_sum + (long long)b * R.n_tile,
+                       R.part_idx + (long long)b * R.n_tile, R.n_tile, lane, gmax, gidx, S);
+        // ---- pass 1: stage the row, its minimum, its total mass
+        isc_u64 wsum = 0;
+        float mn = INFINITY;
+        if (F.staged && !(R.ld_logits & 3) && !(V & 3) && !((uintptr_t)R.logits & 15)) {
+            for (int i = tid * 4; i < V; i += 1024) {
+                const float4 v = *reinterpret_cast<const float4 *>(xg + i);
+                *reinterpret_cast<float4 *>(flt_row + i) = v;
+                mn = fminf(fminf(mn, fminf(v.x, v.y)), fminf(v.z, v.w));
+                wsum += (isc_u64)flt_mass(v.x, gmax, F.c_exp) + flt_mass(v.y, gmax, F.c_exp);
+                wsum += (isc_u64)flt_mass(v.z, gmax, F.c_exp) + flt_mass(v.w, gmax, F.c_exp);
+            }
+        } else {
+            for (int i = tid; i < V; i += 256) {
+                const float x = xg[i];
+                if (F.staged) flt_row[i] = x;
+                mn = fminf(mn, x);
+                wsum += flt_mass(x, gmax, F.c_exp);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            wsum += __shfl_xor(wsum, o, 64);
+            mn = fminf(mn, __shfl_xor(mn, o, 64));
+        }
+        if (lane == 0) { s64[wave] = wsum; shf[wave] = mn; }
+        __syncthreads();
+        isc_u64 Wk = s64[0] + s64[1] + s64[2] + s64[3];            // mass of the survivors so far: every token
+        const float xmin = fminf(fminf(shf[0], shf[1]), fminf(shf[2], shf[3]));
+        unsigned Nk = (unsigned)V;
+        isc_u64 Kstar = ~0ull;                                      // kept = {K <= Kstar}: every token
+        // ---- selection: pass 0 by count (top-k), pass 1 by mass (top-p) among pass 0's survivors
+        for (int mode = 0; mode < 2; ++mode) {
+            if (mode == 0 ? !(F.top_k > 0 && F.top_k < V) : !(F.top_p < 1.0f)) continue;      // uniform
+            const isc_u64 Klim = Kstar, Wtot = Wk;
+            const unsigned Ntot = Nk, klim = (unsigned)F.top_k;
+            isc_u64 Mlim = (isc_u64)((double)F.top_p * (double)Wtot);
+            if (Mlim < 1) Mlim = 1;                                 // rank 0 is always kept
+            const float span = gmax - xmin;
+            const float rr = mode == 0 ? span : fminf(span, ISC_FLT_MASS_SPAN * F.tau);
+            const float cb = rr > 1e-30f ? 256.0f / rr : 0.f;
+#define FLT_COND(C, M) (mode == 0 ? (C) < klim : (M) < Mlim)
+            __syncthreads();
+            h_cnt[tid] = 0; h_mass[tid] = 0;
+            if (tid == 0) { shi[0] = -1; shi[1] = 0; shi[2] = 0; sh64[0] = 0; sh64[1] = 0; }
+            __syncthreads();
+            // bucket 255 takes everything beyond the span (by mass: the zero-mass tail): it gets no atomics, its count and
+            // mass are what the others leave of the totals
+            for (int i = tid; i < V; i += 256) {
+                const float x = xs[i];
+                if (flt_key(x, i) > Klim) continue;
+                const int bk = flt_bucket(x, gmax, cb);
+                if (bk < 255) {
+                    atomicAdd(&h_cnt[bk], 1u);
+                    atomicAdd(&h_mass[bk], (isc_u64)flt_mass(x, gmax, F.c_exp));
+                }
+            }
+            __syncthreads();
+            unsigned n = tid < 255 ? h_cnt[tid] : 0u, C = n;
+            isc_u64 m = tid < 255 ? h_mass[tid] : 0ull, M = m;
+            flt_scan(C, M, s32, s64, tid);
+            if (tid == 255) { n = Ntot - C; m = Wtot - M; }
+            if (n > 0 && FLT_COND(C, M)) atomicMax(&shi[0], tid);
+            __syncthreads();
+            const int bstar = shi[0];
+            if (bstar < 0) continue;                                // (no survivor at all: a row of NaN keys) uniform
+            __syncthreads();
+            if (tid == bstar) { s32[0] = C; s32[1] = n; s64[0] = M; }
+            __syncthreads();
+            unsigned Cb = s32[0];
+            const unsigned nstar = s32[1];
+            isc_u64 Mb = s64[0];
+            if (nstar <= 256) {
+                // the boundary bucket's elements, ranked against each other
+                for (int i = tid; i < V; i += 256) {
+                    const float x = xs[i];
+                    const isc_u64 K = flt_key(x, i);
+                    if (K <= Klim && flt_bucket(x, gmax, cb) == bstar) {
+                        const int slot = atomicAdd(&shi[1], 1);
+                        if (slot < 256) { c_key[slot] = K; c_mass[slot] = flt_mass(x, gmax, F.c_exp); }
+                    }
+                }
+                __syncthreads();
+                if (tid < (int)nstar) {
+                    const isc_u64 myK = c_key[tid], myM = c_mass[tid];
+                    unsigned cnt = Cb;
+                    isc_u64 ms = Mb;
+                    for (int j = 0; j < (int)nstar; ++j) {
+                        const isc_u64 kj = c_key[j], mj = c_mass[j];
+                        if (kj < myK) { ++cnt; ms += mj; }
+                    }
+                    if (FLT_COND(cnt, ms)) {
+                        atomicMax(&sh64[0], myK);
+                        atomicAdd(&sh64[1], myM);
+                        atomicAdd(&shi[2], 1);
+                    }
+                }
+                __syncthreads();
+                Kstar = sh64[0]; Wk = Mb + sh64[1]; Nk = Cb + (unsigned)shi[2];
+            } else {
+                // many elements in one bucket (tied logits): radix descent over the bits of K, most significant first
+                isc_u64 prefix = 0, lastm = 0;
+                for (int shift = 56; shift >= 0; shift -= 8) {
+                    __syncthreads();
+                    h_cnt[tid] = 0; h_mass[tid] = 0;
+                    if (tid == 0) shi[0] = -1;
+                    __syncthreads();
+                    for (int i = tid; i < V; i += 256) {
+                        const float x = xs[i];
+                        const isc_u64 K = flt_key(x, i);
+                        if (K <= Klim && flt_bucket(x, gmax, cb) == bstar && (shift == 56 || (K >> (shift + 8)) == prefix)) {
+                            const int d = (int)((K >> shift) & 255);
+                            atomicAdd(&h_cnt[d], 1u);
+                            atomicAdd(&h_mass[d], (isc_u64)flt_mass(x, gmax, F.c_exp));
+                        }
+                    }
+                    __syncthreads();
+                    const unsigned nd = h_cnt[tid];
+                    const isc_u64 md = h_mass[tid];
+                    unsigned Cd = nd;
+                    isc_u64 Md = md;
+                    flt_scan(Cd, Md, s32, s64, tid);
+                    if (nd > 0 && FLT_COND(Cb + Cd, Mb + Md)) atomicMax(&shi[0], tid);
+                    __syncthreads();
+                    const int dstar = shi[0] < 0 ? 0 : shi[0];
+                    if (tid == dstar) { s32[0] = Cd; s64[0] = Md; s64[1] = md; }
+                    __syncthreads();
+                    Cb += s32[0]; Mb += s64[0]; lastm = s64[1];
+                    prefix = (prefix << 8) | (unsigned)dstar;
+                }
+                Kstar = prefix; Wk = Mb + lastm; Nk = Cb + 1;
+            }
+#undef FLT_COND
+        }
+        // ---- draw: inverse CDF over the kept set in vocabulary order; thread t owns ids [t * chunk, (t + 1) * chunk)
+        // (chunk odd: the threads' LDS reads fall on different banks)
+        const int chunk = ((V + 255) >> 8) | 1;
+        const int i0 = tid * chunk < V ? tid * chunk : V, i1 = i0 + chunk < V ? i0 + chunk : V;
+        isc_u64 own = 0;
+        for (int i = i0; i < i1; ++i) {
+            const float x = xs[i];
+            if (flt_key(x, i) <= Kstar) own += flt_mass(x, gmax, F.c_exp);
+        }
+        unsigned c0 = 0;
+        isc_u64 ex = own;
+        __syncthreads();
+        if (tid == 0) shi[3] = -1;
+        flt_scan(c0, ex, s32, s64, tid);
+        const isc_u64 target = (isc_u64)((double)R.sample_u[(long long)b * R.T + R.t] * (double)Wk);
+        if (own > 0 && ex <= target && target < ex + own) {          // exactly one thread (the masses sum to Wk > target)
+            isc_u64 run = ex;
+            int pick = i1 - 1;
+            for (int i = i0; i < i1; ++i) {
+                const float x = xs[i];
+                if (flt_key(x, i) <= Kstar) run += flt_mass(x, gmax, F.c_exp);
+                if (run > target) { pick = i; break; }
+            }
+            shi[3] = pick;
+        }
+        __syncthreads();
+        const int pk = shi[3];
+        const long long it = pk < 0 ? gidx : pk;                    // (a row without any mass: non-finite, flagged)
+        // ---- the step's outputs, as rollout_finalize_row writes them
+        const long long itm = unf ? it : 0;
+        const int u2 = unf && (itm != R.eos_id);
+        if (tid == 0) {
+            const float xi = xs[it];
+            const long long o = (long long)b * R.T + R.t;
+            R.seq_masks[o] = (float)unf;
+            R.seq[o] = itm;
+            R.seq_logprobs[o] = (xi - gmax) - logf(S);               // the MODEL's log-probability of the token
+            if (F.slp)
+                F.slp[o] = (float)(((double)xi - (double)gmax) / (double)F.tau - log((double)Wk * (1.0 / 4294967296.0)));
+            if (R.raw_tokens) R.raw_tokens[o] = it;
+            R.unfinished[b] = u2;
+            alive += u2;
+        }
+        if (R.xt_next) {
+            const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
+            const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
+            float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
+            for (int i = tid; i < (R.W >> 2); i += 256) {
+                float4 v = src[i];
+                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
+                dst[i] = v;
+            }
+        }
+        __syncthreads();                    // the row in LDS and the scratch words are the next row's
+    }
+    if (tid == 0 && alive) atomicAdd(&R.alive[R.t + 1], alive);
+}
+
+extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, void *stream) {
+    if (!s || !f) return ISC_E_NULL;
+    if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
+        !s->unfinished || !s->alive || !s->emb || !s->logits || !s->sample_u)
+        return ISC_E_NULL;
+    if (!(f->temperature > 0.f) || !(f->temperature <= 3.0e38f) || f->top_k < 0 || !(f->top_p > 0.f)) return ISC_E_SHAPE;
+    if (s->B <= 0 || s->V <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3) || s->n_tile <= 0 ||
+        s->ld_logits < s->V || s->forced)
+        return ISC_E_SHAPE;
+    DevRollout R;
+    R.B = s->B; R.V = s->V; R.T = s->T; R.t = s->t; R.n_tile = s->n_tile; R.W = s->W;
+    R.part_max = s->part_max; R.part_sum = s->part_sum; R.part_idx = s->part_idx;
+    R.logits = s->logits; R.ld_logits = s->ld_logits; R.forced = nullptr; R.sample_u = s->sample_u;
+    R.eos_id = s->eos_id; R.seq = s->seq; R.seq_logprobs = s->seq_logprobs; R.seq_masks = s->seq_masks;
+    R.unfinished = s->unfinished; R.alive = s->alive; R.raw_tokens = s->raw_tokens;
+    R.emb = s->emb; R.xt_add = s->xt_add; R.xt_next = s->xt_next;
+    R.rows_per_wave = 1;
+    DevFilter F;
+    F.c_exp = (float)(1.4426950408889634 / (double)f->temperature);
+    F.tau = f->temperature; F.top_k = f->top_k; F.top_p = f->top_p; F.slp = f->sampling_logprobs;
+    F.staged = s->V <= ISC_FLT_STAGE_MAX;
+    const int grid = s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID;
+    hipLaunchKernelGGL(rollout_finalize_filtered_kernel, dim3(grid), dim3(256),
+                       F.staged ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0, (hipStream_t)stream, R, F);
+    ISC_LAUNCH_CHECK();
+    ++g_finalize_launches;
+    return ISC_OK;
+}
+
 // ------------------------------------------------------------------ scheduled sampling (captioner.py:219-228)
 // out[b] = (u_select[b] < ss_prob) ? draw from exp(logp[b, :]) with uniform u_draw[b] : base[b].
 // One launch and no host decision in place of rand / `if mask.sum() == 0` / multinomial / index_copy_:

@@ -766,6 +766,30 @@ def rollout_finalize(step):
     TIMER.end(e0, 'rollout_finalize[%d]' % step.B, 0.0, 4.0 * step.B * (3 * step.n_tile + 2 * step.W))
 
 
+def check_sample_filter(temperature, top_k, top_p):
+    """The domain of the sampling controls (isc_sample_filter): ValueError before anything touches the device."""
+    import math
+    t, p = float(temperature), float(top_p)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError('temperature must be finite and > 0, got %r' % (temperature,))
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError('top_k must be an integer >= 0 (0: off), got %r' % (top_k,))
+    if not p > 0.0:
+        raise ValueError('top_p must be > 0 (>= 1: off), got %r' % (top_p,))
+    return t, int(top_k), p
+
+
+def rollout_finalize_filtered(step, temperature=1.0, top_k=0, top_p=1.0, sampling_logprobs=None):
+    """isc_rollout_finalize_filtered: the sampled roll-out's finalize with temperature / top-k / top-p (one launch)."""
+    f = _lib.SampleFilter()
+    f.temperature, f.top_k, f.top_p = check_sample_filter(temperature, top_k, top_p)
+    f.sampling_logprobs = ptr(sampling_logprobs)
+    lib = _lib.load()
+    e0 = TIMER.begin()
+    check(lib.isc_rollout_finalize_filtered(C.byref(step), C.byref(f), stream()), 'isc_rollout_finalize_filtered')
+    TIMER.end(e0, 'rollout_finalize_filtered[%d]' % step.B, 0.0, 4.0 * step.B * (step.V + 2 * step.n_tile + 2 * step.W))
+
+
 def sched_sample(logp, part_max, part_sum, part_idx, u_select, u_draw, ss_prob, base_ids, out_ids, raw=False):
     """out_ids[b] = u_select[b] < ss_prob ? draw from exp(logp[b]) : base_ids[b]  (base_ids may be a strided column).
     raw: `logp` holds the row's raw logits (isc_sched_sample_raw)."""
@@ -812,7 +836,7 @@ def xe_loss_fwd(logp, target, lengths_i32, out2):
 
 
 __all__ = [n for n in dir() if n.endswith('_fwd') or n.endswith('_problem')] + [
-    'RolloutStep', 'rollout_finalize', 'beam_topk', 'logsoftmax_apply', 'require_device']
+    'RolloutStep', 'rollout_finalize', 'rollout_finalize_filtered', 'beam_topk', 'logsoftmax_apply', 'require_device']
 
 
 # ---------------------------------------------------------------------------- backward
