@@ -539,10 +539,8 @@ __global__ __launch_bounds__(256) void gate_mix_kernel(const float *z, const flo
         const float f = beta * v[o] + (1.0f - beta) * s[o];
         out[o] = f;
         if (out_hi) {
-            const _Float16 fh = (_Float16)f;
-            const long long po = (long long)b * 2 * D + (d >> 5) * 64 + (d & 31);
-            out_hi[po] = fh;
-            out_lo[po] = (_Float16)((f - (float)fh) * 2048.f);
+            const long long po = plane_index(b, d, D);
+            isc_split_f16(f, out_hi[po], out_lo[po]);
         }
     }
 }

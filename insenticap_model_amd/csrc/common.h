@@ -93,21 +93,62 @@ static __device__ long long *g_rows_stamp;
 // Returns 1 when it took the launch (*rc = its status), 0 when the shape is not its own.
 int rows_scan_gate_try(const isc_scan_gate_args *a, int rows, hipStream_t st, int *rc);
 
-// f16 planes of four consecutive outputs d .. d+3 of row `row` of a [rows, D] tensor (split-f16 GEMM operands:
-// hi = f16(x), lo = f16((x - hi) * 2048); interleaved layout of gemm_f32.hip: per row and 32-wide block 32 hi then
-// 32 lo values, lo pointer = hi pointer + 32)
-__device__ __forceinline__ void store_planes4(_Float16 *hi, _Float16 *lo, long long row, int d, int D, const float4 &x) {
-    const long long o = row * 2 * D + (d >> 5) * 64 + (d & 31);
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    const float v[4] = {x.x, x.y, x.z, x.w};
-    h4 a, b;
+// ---- the split-f16 number format (operands of the f16 matrix cores: gemm_f32.hip) -------------------------------
+//     x = hi + lo * 2^-11,   hi = f16(x),   lo = f16((x - hi) * 2^11)        (the subtraction is exact in fp32)
+constexpr float ISC_SPLIT_LO_SCALE = 2048.f;
+constexpr float ISC_SPLIT_LO_WEIGHT = 1.f / 2048.f;      // weight of the hi * lo cross terms in a contraction
+__device__ __forceinline__ void isc_split_f16(float x, _Float16 &hi, _Float16 &lo) {
+    const _Float16 h = (_Float16)x;
+    hi = h;
+    lo = (_Float16)((x - (float)h) * ISC_SPLIT_LO_SCALE);
+}
+// Plane layout: one buffer per [rows, K] tensor, K % 32 == 0; per row and per 32-deep k-block the 32 hi values are
+// followed by the 32 lo values, so the 64 bytes of hi and the 64 bytes of lo that one chunk consumes form one 128-byte
+// line:  hi(row, k) at base[row * 2K + (k >> 5) * 64 + (k & 31)],  lo = the same + 32.  The `lo` pointers carried
+// around are `hi + 32`.
+__host__ __device__ __forceinline__ long long plane_index(long long row, int k, int K) {
+    return row * 2 * K + (k >> 5) * 64 + (k & 31);
+}
+// planes of NV consecutive values x[0 .. NV) of one row, starting at element k (NV divides 32: they share a k-block)
+template <int NV>
+__device__ __forceinline__ void store_planes(_Float16 *hi, _Float16 *lo, long long row, int k, int K, const float (&x)[NV]) {
+    typedef _Float16 hv __attribute__((ext_vector_type(NV)));
+    hv a, b;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        a[e] = (_Float16)v[e];
-        b[e] = (_Float16)((v[e] - (float)a[e]) * 2048.f);
+    for (int e = 0; e < NV; ++e) {
+        _Float16 h, l;
+        isc_split_f16(x[e], h, l);
+        a[e] = h;
+        b[e] = l;
     }
-    *reinterpret_cast<h4 *>(hi + o) = a;
-    *reinterpret_cast<h4 *>(lo + o) = b;
+    const long long o = plane_index(row, k, K);
+    *reinterpret_cast<hv *>(hi + o) = a;
+    *reinterpret_cast<hv *>(lo + o) = b;
+}
+__device__ __forceinline__ void store_planes4(_Float16 *hi, _Float16 *lo, long long row, int d, int D, const float4 &x) {
+    const float v[4] = {x.x, x.y, x.z, x.w};
+    store_planes<4>(hi, lo, row, d, D, v);
+}
+
+// ---- the LSTM cell (gate order i, f, g, o), the one definition every kernel's epilogue calls ---------------------
+// Gate pre-activation: the contraction's sum, then  += (b_ih + b_hh);  += pre;  += table row  - in this order (the
+// merged training paths and the graph-versus-eager tests compare kernels bit for bit).
+// (a term whose flag is off is never read: the callers leave it unloaded)
+__device__ __forceinline__ float isc_lstm_gate_sum(float g, bool has_b, const float &b, bool has_pre, const float &pre,
+                                                   bool has_tab, const float &tab) {
+    if (has_b) g += b;
+    if (has_pre) g += pre;
+    if (has_tab) g += tab;
+    return g;
+}
+// g[4]: pre-activations in, activations (what gates_out saves) out; c2, h2: the new state
+__device__ __forceinline__ void isc_lstm_cell(float (&g)[4], float c_prev, float &c2, float &h2) {
+    g[0] = isc_sigmoid(g[0]);
+    g[1] = isc_sigmoid(g[1]);
+    g[2] = isc_tanh(g[2]);
+    g[3] = isc_sigmoid(g[3]);
+    c2 = g[1] * c_prev + g[0] * g[2];
+    h2 = g[3] * isc_tanh(c2);
 }
 
 // Kernel arguments are read by scalar loads where they are first used; every first touch of a 64-byte line of the

@@ -28,6 +28,11 @@
 //       XL: 256 x 128 (gemm_xl_kernel, 3-deep ring),  LD: 128 x 128 (gemm_ld_kernel),  MD: 64 x 128 (gemm_md_kernel,
 //       linear epilogue only).
 // Small-M problems also have deterministic split-K (splitk_*_kernel) and a GEMV form (gemv_rows_kernel) further down.
+//
+// Epilogues, one definition each: epi_linear_finish (a float4 group or one element of a reduced tile), epi_linear_frag /
+// epi_vocab_frag (straight from accumulator registers, over the fragment layouts Frag32 / Frag16), wave_vocab_tile128
+// (one row's 128-column tile on one wave), lstm_cells around isc_lstm_cell (epi_lstm_frag16 keeps a copy of its own).  The
+// split-f16 number format, its plane layout and the cell's arithmetic are in common.h.
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -66,13 +71,6 @@ struct DevSeg {
     const _Float16 *A_hi, *A_lo;      // caller-provided planes of A ([M,K] contiguous) or null
 };
 
-// Plane layout (split-f16 operands): one buffer per [rows, K] tensor, K % 32 == 0; per row and per 32-deep k-block
-// the 32 hi values are followed by the 32 lo values, so the 64 bytes of hi and the 64 bytes of lo that one chunk
-// consumes form one 128-byte line:  hi(row, k) at base[row * 2K + (k >> 5) * 64 + (k & 31)],  lo = the same + 32.
-// The `lo` pointers carried around are `hi + 32`.
-__host__ __device__ __forceinline__ long long plane_index(long long row, int k, int K) {
-    return row * 2 * K + (k >> 5) * 64 + (k & 31);
-}
 struct DevASeg {                      // one K-segment of the split-f16 A operand
     const _Float16 *hi, *lo;
     int ld, K;                        // ld = row stride in halfs = 2 * K of the tensor the planes belong to
@@ -165,81 +163,107 @@ __device__ __forceinline__ void map_tile(const DevLaunch &L, int &pi, int &tm, i
 }
 
 // ---- epilogues, shared by the tile shapes ---------------------------------------------------------
-// Vocabulary epilogue of one 32 x (32*TN) accumulator fragment, straight from the registers (no LDS
-// round trip).  C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5), so
-// one register index r is one output row per half-wave and the row's 32*TN columns of this wave sit
-// on the 32 lanes of that half.  Per row: max / arg-max / sum exp(x - max) by 5-step butterflies
-// inside the half-wave (4 DPP steps inside the 16-lane rows + one swizzle across them).  frow0 = tile-relative first row of the
-// fragment, fcol0 = tile-relative first column.  WN == 1 writes the tile statistics directly,
-// otherwise they go to smx/ssm/six[wn][BM] for the cross-wave combine.
-template <int TN, int WN, int BM>
-__device__ __forceinline__ void epi_vocab_frag(const DevProb &P, f32x16 (&acc)[TN], int frow0, int fcol0, int wn,
-                                               int lane, int row0, int col0, int tn, float *smem) {
-    const int M = P.M, N = P.N;
-    float bv[TN];
-    bool cok[TN];
+// Where the accumulators of a wave's 32-row fragment sit, for the two MFMA shapes in use.  A lane holds NR rows x NC
+// column blocks of CW columns; element (e, j) is tile row frow0 + row(e, lane), tile column fcol0 + CW j + col(lane).
+// The lanes that share a row (equal row(e, .)) reduce over it with row_sum / row_argmax.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// v_mfma_f32_32x32x*: f32x16 acc[NC]; one register index is one output row per half-wave, and the row's 32 NC columns
+// sit on the 32 lanes of that half - reductions are 4 DPP steps inside the 16-lane rows + one swizzle across them.
+struct Frag32 {
+    static constexpr int CW = 32, NR = 16;
+    static __device__ __forceinline__ int col(int lane) { return lane & 31; }
+    static __device__ __forceinline__ int row(int e, int lane) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
+    template <int NC>
+    static __device__ __forceinline__ float get(const f32x16 (&acc)[NC], int e, int j) { return acc[j][e]; }
+    template <int NC>
+    static __device__ __forceinline__ void set(f32x16 (&acc)[NC], int e, int j, float v) { acc[j][e] = v; }
+    static __device__ __forceinline__ float row_sum(float v) { return half_sum(v); }
+    static __device__ __forceinline__ void row_argmax(float &v, int &i) { half_argmax(v, i); }
+};
+// v_mfma_f32_16x16x32_f16 (the large split-f16 tiles): f32x4 acc[2][NC], 2 row blocks x NC column blocks of 16 x 16; a
+// row's 16 NC columns sit on the 16 lanes of ONE DPP row - reductions are four DPP steps, no swizzle.
+struct Frag16 {
+    static constexpr int CW = 16, NR = 8;
+    static __device__ __forceinline__ int col(int lane) { return lane & 15; }
+    static __device__ __forceinline__ int row(int e, int lane) { return (e >> 2) * 16 + 4 * (lane >> 4) + (e & 3); }
+    template <int NC>
+    static __device__ __forceinline__ float get(const f32x4 (&acc)[2][NC], int e, int j) { return acc[e >> 2][j][e & 3]; }
+    template <int NC>
+    static __device__ __forceinline__ void set(f32x4 (&acc)[2][NC], int e, int j, float v) { acc[e >> 2][j][e & 3] = v; }
+    static __device__ __forceinline__ float row_sum(float v) { return row16_sum(v); }
+    static __device__ __forceinline__ void row_argmax(float &v, int &i) { row16_argmax(v, i); }
+};
+
+// Vocabulary epilogue of one fragment (layout F, NC column blocks), straight from the registers (no LDS round trip).
+// Per row: max / arg-max / sum exp(x - max) over the wave's CW * NC columns.  frow0 = tile-relative first row of the
+// fragment, fcol0 = tile-relative first column.  WN == 1 (the wave spans the 128-column tile) writes the tile
+// statistics directly, otherwise they go to smx/ssm/six[wn][BM] for the cross-wave combine.
+template <class F, int NC, int WN, int BM, class Acc>
+__device__ __forceinline__ void epi_vocab_frag(const DevProb &P, Acc &acc, int frow0, int fcol0, int wn, int lane,
+                                               int row0, int col0, int tn, float *smem) {
+    constexpr int NR = F::NR;
+    const int M = P.M, N = P.N, gn0 = col0 + fcol0 + F::col(lane);
+    float bv[NC];
+    bool cok[NC];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int gn = col0 + fcol0 + j * 32 + (lane & 31);
-        cok[j] = gn < N;
-        bv[j] = cok[j] ? P.bias0[gn] : 0.f;
+    for (int j = 0; j < NC; ++j) {
+        cok[j] = gn0 + j * F::CW < N;
+        bv[j] = cok[j] ? P.bias0[gn0 + j * F::CW] : 0.f;
     }
-    float *smx = smem;                    // [WN][BM] cross-wave combine (WN > 1 only)
-    float *ssm = smem + WN * BM;
-    int *six = reinterpret_cast<int *>(smem + 2 * WN * BM);
-    // Phased over the fragment's 16 rows, every phase straight-line code: the 16 dependent reduction
-    // chains interleave instead of running one after the other between per-row branches.
-    float mx[16], sm[16];
-    int ix[16];
+    // Phased over the fragment's rows, every phase straight-line code: the dependent reduction chains of the rows
+    // interleave instead of running one after the other between per-row branches.
+    float mx[NR], sm[NR];
+    int ix[NR];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        mx[r] = -INFINITY;
-        ix[r] = 0x7fffffff;
+    for (int e = 0; e < NR; ++e) {
+        mx[e] = -INFINITY;
+        ix[e] = 0x7fffffff;
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            acc[j][r] = cok[j] ? acc[j][r] + bv[j] : -INFINITY;      // acc now holds the logits
-            const int gn = col0 + fcol0 + j * 32 + (lane & 31);
-            if (acc[j][r] > mx[r]) { mx[r] = acc[j][r]; ix[r] = gn; }   // j ascending => smaller column wins ties
+        for (int j = 0; j < NC; ++j) {
+            const float x = cok[j] ? F::get(acc, e, j) + bv[j] : -INFINITY;
+            F::set(acc, e, j, x);                                            // acc now holds the logits
+            if (x > mx[e]) { mx[e] = x; ix[e] = gn0 + j * F::CW; }           // j ascending => smaller column wins ties
         }
     }
     if (P.C) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int gm = row0 + frow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        for (int e = 0; e < NR; ++e) {
+            const int gm = row0 + frow0 + F::row(e, lane);
             if (gm < M) {
-                float *crow = P.C + (long long)gm * P.ld_logits + col0 + fcol0 + (lane & 31);
+                float *crow = P.C + (long long)gm * P.ld_logits + gn0;
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    if (cok[j]) crow[j * 32] = acc[j][r];
+                for (int j = 0; j < NC; ++j)
+                    if (cok[j]) crow[j * F::CW] = F::get(acc, e, j);
             }
         }
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) half_argmax(mx[r], ix[r]);
+    for (int e = 0; e < NR; ++e) F::row_argmax(mx[e], ix[e]);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        sm[r] = 0.f;
+    for (int e = 0; e < NR; ++e) {
+        sm[e] = 0.f;
 #pragma unroll
-        for (int j = 0; j < TN; ++j) sm[r] += cok[j] ? __expf(acc[j][r] - mx[r]) : 0.f;   // padded columns add 0
+        for (int j = 0; j < NC; ++j) sm[e] += cok[j] ? __expf(F::get(acc, e, j) - mx[e]) : 0.f;   // padded columns add 0
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sm[r] = half_sum(sm[r]);
-    if ((lane & 31) == 0) {
+    for (int e = 0; e < NR; ++e) sm[e] = F::row_sum(sm[e]);
+    if (F::col(lane) == 0) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = frow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const int gm = row0 + row;
+        for (int e = 0; e < NR; ++e) {
+            const int row = frow0 + F::row(e, lane);
             if constexpr (WN == 1) {
-                if (gm < M) {
-                    const long long o = (long long)gm * P.ntile_total + tn;
-                    P.pmax[o] = mx[r];
-                    P.psum[o] = sm[r];
-                    P.pidx[o] = ix[r];
+                if (row0 + row < M) {
+                    const long long o = (long long)(row0 + row) * P.ntile_total + tn;
+                    P.pmax[o] = mx[e];
+                    P.psum[o] = sm[e];
+                    P.pidx[o] = ix[e];
                 }
             } else {
-                smx[wn * BM + row] = mx[r];
-                ssm[wn * BM + row] = sm[r];
-                six[wn * BM + row] = ix[r];
+                float *smx = smem, *ssm = smem + WN * BM;                     // [WN][BM] each
+                int *six = reinterpret_cast<int *>(smem + 2 * WN * BM);
+                smx[wn * BM + row] = mx[e];
+                ssm[wn * BM + row] = sm[e];
+                six[wn * BM + row] = ix[e];
             }
         }
     }
@@ -252,10 +276,48 @@ __device__ __forceinline__ void epi_stage_frag(float *Cs, int LDC, f32x16 (&acc)
     for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = frow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const int col = fcol0 + j * 32 + (lane & 31);
+            const int row = frow0 + Frag32::row(r, lane);
+            const int col = fcol0 + j * 32 + Frag32::col(lane);
             Cs[row * LDC + col] = acc[j][r];
         }
+}
+
+// The linear epilogue of NE (4 or 1) consecutive outputs (gm, gn .. gn + NE - 1) whose contraction sums are o[]: three
+// biases, accumulate, ReLU, pre-mask copy, keep-mask, store - one float4 per group where the row stride and the matrix
+// border allow.  The one definition behind the staged tiles, the skinny tiles, the split-K reduction and the GEMV tail.
+template <int NE>
+__device__ __forceinline__ void epi_linear_finish(const DevProb &P, int gm, int gn, float (&o)[NE]) {
+    static_assert(NE == 4 || NE == 1, "a float4 group or one element");
+    const int N = P.N;
+    float pre[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int n = gn + e;
+        pre[e] = 0.f;
+        if (n < N) {
+            if (P.bias0) o[e] += P.bias0[n];
+            if (P.bias1) o[e] += P.bias1[n];
+            if (P.bias2) o[e] += P.bias2[n];
+            if (P.accumulate) o[e] += P.C[(long long)gm * P.ldc + n];
+            if (P.relu) o[e] = isc_relu(o[e]);
+            pre[e] = o[e];
+            if (P.mask) o[e] = o[e] * (float)P.mask[(long long)gm * N + n] * P.mask_scale;
+        }
+    }
+    float *dst = P.C + (long long)gm * P.ldc + gn;
+    if constexpr (NE == 4) {
+        if ((P.ldc & 3) == 0 && gn + 3 < N) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+            if (P.C_pre)
+                *reinterpret_cast<float4 *>(P.C_pre + (long long)gm * P.ldc + gn) =
+                    make_float4(pre[0], pre[1], pre[2], pre[3]);
+            return;
+        }
+    }
+    for (int e = 0; e < NE && gn + e < N; ++e) {
+        dst[e] = o[e];
+        if (P.C_pre) P.C_pre[(long long)gm * P.ldc + gn + e] = pre[e];
+    }
 }
 
 template <int BM, int BN>
@@ -274,46 +336,20 @@ __device__ __forceinline__ void epi_linear_tile(const DevProb &P, const float *C
         }
         return;
     }
-    const bool vec = (P.ldc & 3) == 0;
     for (int idx = tid; idx < BM * (BN / 4); idx += 256) {
         const int row = idx / (BN / 4), c4 = (idx % (BN / 4)) * 4;
         const int gm = row0 + row, gn = col0 + c4;
         if (gm >= M || gn >= N) continue;
-        float4 v = *reinterpret_cast<const float4 *>(Cs + row * LDC + c4);
-        float o[4] = {v.x, v.y, v.z, v.w}, pre[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int n = gn + e;
-            if (n < N) {
-                if (P.bias0) o[e] += P.bias0[n];
-                if (P.bias1) o[e] += P.bias1[n];
-                if (P.bias2) o[e] += P.bias2[n];
-                if (P.accumulate) o[e] += P.C[(long long)gm * P.ldc + n];
-                if (P.relu) o[e] = isc_relu(o[e]);
-                pre[e] = o[e];
-                if (P.mask) o[e] = o[e] * (float)P.mask[(long long)gm * N + n] * P.mask_scale;
-            }
-        }
-        float *dst = P.C + (long long)gm * P.ldc + gn;
-        if (vec && gn + 3 < N) {
-            *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-            if (P.C_pre)
-                *reinterpret_cast<float4 *>(P.C_pre + (long long)gm * P.ldc + gn) =
-                    make_float4(pre[0], pre[1], pre[2], pre[3]);
-        } else {
-            for (int e = 0; e < 4 && gn + e < N; ++e) {
-                dst[e] = o[e];
-                if (P.C_pre) P.C_pre[(long long)gm * P.ldc + gn + e] = pre[e];
-            }
-        }
+        const float4 v = *reinterpret_cast<const float4 *>(Cs + row * LDC + c4);
+        float o[4] = {v.x, v.y, v.z, v.w};
+        epi_linear_finish<4>(P, gm, gn, o);
     }
 }
 
-// LSTM cell update from the four gate pre-activations of NE (row, unit) elements, gate order i, f, g, o.
+// LSTM cell update (isc_lstm_cell, common.h) from the four gate pre-activations of NE (row, unit) elements.
 // The epilogue's global operands - hoisted `pre` term, embedding-table row (behind its token id),
 // c_prev - are fetched for all NE elements BEFORE any arithmetic: issued element by element inside the
 // compute loop they formed NE serial dependent round trips (att-LSTM at B=4096: +24 us per launch).
-// Per element:  g += (b_ih + b_hh);  g += pre;  g += table row   (same order in every kernel).
 template <int NE>
 __device__ __forceinline__ void lstm_cells(const DevProb &P, const int (&gm)[NE], int unit, const bool (&ok)[NE],
                                            float (&g)[NE][4]) {
@@ -346,28 +382,22 @@ __device__ __forceinline__ void lstm_cells(const DevProb &P, const int (&gm)[NE]
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (has_b) g[e][k] += b[k];
-            if (has_pre) g[e][k] += q[e][k];
-            if (has_tab) g[e][k] += t[e][k];
-        }
-        const float gi = isc_sigmoid(g[e][0]), gf = isc_sigmoid(g[e][1]), gg = isc_tanh(g[e][2]), go = isc_sigmoid(g[e][3]);
-        const float c2 = gf * cp[e] + gi * gg;
-        const float h2 = go * isc_tanh(c2);
+        for (int k = 0; k < 4; ++k) g[e][k] = isc_lstm_gate_sum(g[e][k], has_b, b[k], has_pre, q[e][k], has_tab, t[e][k]);
+        float c2, h2;
+        isc_lstm_cell(g[e], cp[e], c2, h2);
         if (ok[e]) {
             const long long o = (long long)gm[e] * H + unit;
             P.c_out[o] = c2;
             P.h_out[o] = h2;
             if (P.h_hi) {
-                const _Float16 hh = (_Float16)h2;
                 const long long po = plane_index(gm[e], unit, H);
-                P.h_hi[po] = hh;
-                P.h_lo[po] = (_Float16)((h2 - (float)hh) * 2048.f);
+                isc_split_f16(h2, P.h_hi[po], P.h_lo[po]);
             }
             if (P.hmask) P.hdrop[o] = h2 * (float)P.hmask[o] * P.mask_scale;
             if (P.gates_out) {
                 float *go_ = P.gates_out + (long long)gm[e] * 4 * H + unit;
-                go_[0] = gi; go_[H] = gf; go_[2 * H] = gg; go_[3 * H] = go;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) go_[k * H] = g[e][k];
             }
         }
     }
@@ -407,7 +437,7 @@ __device__ __forceinline__ void epi_lstm_frag(const DevProb &P, f32x16 (&acc)[4]
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int r = half * 8 + e;
-            gm[e] = row0 + frow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            gm[e] = row0 + frow0 + Frag32::row(r, lane);
             ok[e] = gm[e] < P.M;
 #pragma unroll
             for (int k = 0; k < 4; ++k) g[e][k] = acc[k][r];
@@ -416,61 +446,72 @@ __device__ __forceinline__ void epi_lstm_frag(const DevProb &P, f32x16 (&acc)[4]
     }
 }
 
-// Linear epilogue of TN sub-tiles of 32 columns starting at tile column fcol0.  EDGE: the fragment touches the
-// matrix border (per-element predicates); FEAT: accumulate / pre-activation copy / keep-mask in play.  Interior
-// fragments run without per-element branches whatever the features.
-template <int TN, bool EDGE, bool FEAT, bool RELU>
-__device__ __forceinline__ void epi_linear_frag_impl(const DevProb &P, f32x16 (&acc)[TN], int frow0, int fcol0, int lane,
+// Numerics status (isc_status): word 1 = a split-f16 linear launch that staged CALLER data as fp32 rows (the raw region
+// features of the prologue, training-mode activations) produced a non-finite pre-activation - an operand at or beyond the
+// f16 range (|x| >= 65520: its hi plane is inf), or a NaN / inf fed in.
+ISC_STATUS_DECL(gemm)
+
+// Linear epilogue of one fragment (layout F, NC column blocks starting at tile column fcol0), straight from the
+// registers.  EDGE: the fragment touches the matrix border (per-element predicates); FEAT: accumulate / pre-activation
+// copy / keep-mask in play; CHECK: flag non-finite pre-activations.  Interior fragments run without per-element
+// branches whatever the features.
+template <class F, int NC, bool EDGE, bool FEAT, bool RELU, bool CHECK, class Acc>
+__device__ __forceinline__ void epi_linear_frag_impl(const DevProb &P, const Acc &acc, int frow0, int fcol0, int lane,
                                                      int row0, int col0) {
-    const int M = P.M, N = P.N;
-    float b0[TN], b1[TN], b2[TN];
-    bool cok[TN];
+    const int M = P.M, N = P.N, gn0 = col0 + fcol0 + F::col(lane);
+    float b0[NC], b1[NC], b2[NC];
+    bool cok[NC];
     const bool h0 = P.bias0 != nullptr, h1 = P.bias1 != nullptr, h2 = P.bias2 != nullptr;
     const bool f_acc = FEAT && P.accumulate, f_pre = FEAT && P.C_pre != nullptr, f_mask = FEAT && P.mask != nullptr;
+    [[maybe_unused]] bool bad = false;
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int gn = col0 + fcol0 + j * 32 + (lane & 31);
+    for (int j = 0; j < NC; ++j) {
+        const int gn = gn0 + j * F::CW;
         cok[j] = !EDGE || gn < N;
         b0[j] = (h0 && cok[j]) ? P.bias0[gn] : 0.f;
         b1[j] = (h1 && cok[j]) ? P.bias1[gn] : 0.f;
         b2[j] = (h2 && cok[j]) ? P.bias2[gn] : 0.f;
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int gm = row0 + frow0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    for (int e = 0; e < F::NR; ++e) {
+        const int gm = row0 + frow0 + F::row(e, lane);
         if (EDGE && gm >= M) continue;
-        float *crow = P.C + (long long)gm * P.ldc + col0 + fcol0 + (lane & 31);
-        float prev[TN];
-        if (f_acc) {                                   // all TN loads of the row before any arithmetic
+        float *crow = P.C + (long long)gm * P.ldc + gn0;
+        float prev[NC];
+        if (f_acc) {                                   // all NC loads of the row before any arithmetic
 #pragma unroll
-            for (int j = 0; j < TN; ++j) prev[j] = (!EDGE || cok[j]) ? crow[j * 32] : 0.f;
+            for (int j = 0; j < NC; ++j) prev[j] = (!EDGE || cok[j]) ? crow[j * F::CW] : 0.f;
         }
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
+        for (int j = 0; j < NC; ++j) {
             if (EDGE && !cok[j]) continue;
-            float o = acc[j][r];
+            float o = F::get(acc, e, j);
             if (h0) o += b0[j];
             if (h1) o += b1[j];
             if (h2) o += b2[j];
             if (f_acc) o += prev[j];
+            if constexpr (CHECK) bad |= !(fabsf(o) <= 3.0e38f);
             if (RELU) o = isc_relu(o);
             if constexpr (FEAT) {
-                const int gn = col0 + fcol0 + j * 32 + (lane & 31);
+                const int gn = gn0 + j * F::CW;
                 if (f_pre) P.C_pre[(long long)gm * P.ldc + gn] = o;
                 if (f_mask) o = o * (float)P.mask[(long long)gm * N + gn] * P.mask_scale;
             }
-            crow[j * 32] = o;
+            crow[j * F::CW] = o;
         }
+    }
+    if constexpr (CHECK) {
+        if (__any(bad) && lane == 0) isc_flag_gemm(ISC_STATUS_WORD_LINEAR);
     }
 }
 
-template <int TN>
-__device__ __forceinline__ void epi_linear_frag(const DevProb &P, f32x16 (&acc)[TN], int frow0, int fcol0, int lane,
+template <class F, int NC, bool CHECK, class Acc>
+__device__ __forceinline__ void epi_linear_frag(const DevProb &P, const Acc &acc, int frow0, int fcol0, int lane,
                                                 int row0, int col0) {
     const bool feat = P.accumulate || P.C_pre || P.mask;
-    const bool edge = !(row0 + frow0 + 32 <= P.M && col0 + fcol0 + 32 * TN <= P.N);
+    const bool edge = !(row0 + frow0 + 32 <= P.M && col0 + fcol0 + F::CW * NC <= P.N);
     const bool relu = P.relu != 0;
-#define ISC_EPI_CASE(E, F, R) epi_linear_frag_impl<TN, E, F, R>(P, acc, frow0, fcol0, lane, row0, col0)
+#define ISC_EPI_CASE(E, FT, R) epi_linear_frag_impl<F, NC, E, FT, R, CHECK>(P, acc, frow0, fcol0, lane, row0, col0)
     if (edge) {
         if (relu) ISC_EPI_CASE(true, true, true); else ISC_EPI_CASE(true, true, false);
     } else if (feat) {
@@ -727,7 +768,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const DevLaunch L) {
     else k_loop(std::false_type{});
 
     if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag<TN, WN, BM>(P, acc, wm * 32, wn * TN * 32, wn, lane, row0, col0, tn, smem);
+        epi_vocab_frag<Frag32, TN, WN, BM>(P, acc, wm * 32, wn * TN * 32, wn, lane, row0, col0, tn, smem);
         if constexpr (WN > 1) {
             float *smx = smem;
             float *ssm = smem + WN * BM;
@@ -981,9 +1022,9 @@ __device__ __forceinline__ void f32_dma_tile_body(const DevLaunch &L) {
     static_for<FM>([&](auto ic) __attribute__((always_inline)) {
         constexpr int i = decltype(ic)::value;
         const int frow0 = wm * 32 * FM + 32 * i;
-        if constexpr (EPI == EPI_VOCAB) epi_vocab_frag<TN, 1, G::BM>(P, acc[i], frow0, 0, 0, lane, row0, col0, tn, smem);
+        if constexpr (EPI == EPI_VOCAB) epi_vocab_frag<Frag32, TN, 1, G::BM>(P, acc[i], frow0, 0, 0, lane, row0, col0, tn, smem);
         else if constexpr (EPI == EPI_LSTM) epi_lstm_frag(P, acc[i], frow0, lane, row0, tn);
-        else epi_linear_frag<TN>(P, acc[i], frow0, wn * 32 * TN, lane, row0, col0);
+        else epi_linear_frag<Frag32, TN, false>(P, acc[i], frow0, wn * 32 * TN, lane, row0, col0);
     });
 }
 
@@ -1004,83 +1045,7 @@ __global__ __launch_bounds__(256) void gemm_md_kernel(const DevLaunch L) {
     f32_dma_tile_body<F32TileMD, EPI_LINEAR>(L);
 }
 
-// ---- epilogues for the C/D layout of v_mfma_f32_16x16x32_f16 (the split-f16 tile kernels, round 3) ----------------
-// A wave's tile = 2 row blocks x NB column blocks of 16 x 16; acc[i][j] is an f32x4 whose element r on lane l is tile
-// row frow0 + 16 i + 4 (l >> 4) + r, tile column fcol0 + 16 j + (l & 15): a lane holds 8 rows x NB columns, and a row's
-// 16 NB columns sit on the 16 lanes of ONE DPP row - per-row reductions are four DPP steps, no swizzle.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Vocabulary statistics (max, arg-max, sum exp(x - max)) of the wave's 32 rows over its 16 NB columns (= the whole
-// 128-column tile: the kernels that use this have one wave across N), straight from the registers.
-template <int NB>
-__device__ __forceinline__ void epi_vocab_frag16(const DevProb &P, f32x4 (&acc)[2][NB], int frow0, int lane, int row0,
-                                                 int col0, int tn) {
-    const int M = P.M, N = P.N;
-    float bv[NB];
-    bool cok[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int gn = col0 + j * 16 + (lane & 15);
-        cok[j] = gn < N;
-        bv[j] = cok[j] ? P.bias0[gn] : 0.f;
-    }
-    float mx[8], sm[8];
-    int ix[8];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = i * 4 + r;
-            mx[e] = -INFINITY;
-            ix[e] = 0x7fffffff;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                acc[i][j][r] = cok[j] ? acc[i][j][r] + bv[j] : -INFINITY;      // acc now holds the logits
-                const int gn = col0 + j * 16 + (lane & 15);
-                if (acc[i][j][r] > mx[e]) { mx[e] = acc[i][j][r]; ix[e] = gn; }   // j ascending => smaller column wins ties
-            }
-        }
-    if (P.C) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gm = row0 + frow0 + i * 16 + 4 * (lane >> 4) + r;
-                if (gm < M) {
-                    float *crow = P.C + (long long)gm * P.ld_logits + col0 + (lane & 15);
-#pragma unroll
-                    for (int j = 0; j < NB; ++j)
-                        if (cok[j]) crow[j * 16] = acc[i][j][r];
-                }
-            }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) row16_argmax(mx[e], ix[e]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = i * 4 + r;
-            sm[e] = 0.f;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) sm[e] += cok[j] ? __expf(acc[i][j][r] - mx[e]) : 0.f;   // padded columns add 0
-        }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sm[e] = row16_sum(sm[e]);
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int gm = row0 + frow0 + (e >> 2) * 16 + 4 * (lane >> 4) + (e & 3);
-            if (gm < M) {
-                const long long o = (long long)gm * P.ntile_total + tn;
-                P.pmax[o] = mx[e];
-                P.psum[o] = sm[e];
-                P.pidx[o] = ix[e];
-            }
-        }
-    }
-}
-
+// ---- epilogues of the split-f16 tile kernels (accumulator layout Frag16) ------------------------------------------
 // LSTM cells from a 32 x 128 gate-interleaved tile.  The kernels stage W so that tile column t = 32 gate + 16 hf + l
 // holds (gate, unit 2 l + hf) of the tile's 32 units (h3_lstm_wrow): column block j = gate j >> 1, hf = j & 1, and lane l
 // owns all four gates of the ADJACENT units 2 (l & 15), 2 (l & 15) + 1 for its 8 rows.  Every global operand of the
@@ -1088,6 +1053,10 @@ __device__ __forceinline__ void epi_vocab_frag16(const DevProb &P, f32x4 (&acc)[
 // float2 per lane and 16 lanes x 8 B = a full 128-byte segment per row - with one unit per lane (64-byte segments,
 // twice the instructions) the att-LSTM's epilogue, which streams 16 KB per caption of `pre` and table rows, cost the
 // kernel 14 us at B = 4096.  All loads of a row batch are issued before any arithmetic (see lstm_cells).
+// This epilogue spells the cell's arithmetic out instead of calling isc_lstm_gate_sum / isc_lstm_cell: behind the
+// calls the compiler moves a row's arithmetic under the row's store predicate, every row then waits for the stores of
+// the row before it (gemm_h3x_kernel<lstm>: 136 -> 143 waits), and the 16384-row LSTM launches ran 0.6-0.8 % slower.
+// The bit-identity tests across tile kernels hold the two spellings together.
 __device__ __forceinline__ int h3_lstm_wrow_in_gate(int t) { return 2 * (t & 15) + ((t >> 4) & 1); }
 
 __device__ __forceinline__ void epi_lstm_frag16(const DevProb &P, f32x4 (&acc)[2][8], int frow0, int lane, int row0,
@@ -1146,7 +1115,7 @@ __device__ __forceinline__ void epi_lstm_frag16(const DevProb &P, f32x4 (&acc)[2
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     g[k] = acc[i][2 * k + hf][r];
-                    // g += (b_ih + b_hh);  g += pre;  g += table row   (same order in every kernel: lstm_cells)
+                    // the order of isc_lstm_gate_sum (common.h); written out, as is the cell below: see above
                     if (has_b) g[k] += hf ? b[k].y : b[k].x;
                     if (has_pre) g[k] += hf ? q[r][k].y : q[r][k].x;
                     if (has_tab) g[k] += hf ? t[r][k].y : t[r][k].x;
@@ -1162,10 +1131,12 @@ __device__ __forceinline__ void epi_lstm_frag16(const DevProb &P, f32x4 (&acc)[2
                 *reinterpret_cast<float2 *>(P.h_out + o) = make_float2(h2[0], h2[1]);
                 if (P.h_hi) {
                     typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-                    const _Float16 a0 = (_Float16)h2[0], a1 = (_Float16)h2[1];
+                    _Float16 a0, a1, l0, l1;
+                    isc_split_f16(h2[0], a0, l0);
+                    isc_split_f16(h2[1], a1, l1);
                     const long long po = plane_index(gm[r], u0, H);          // u0 even: the pair stays in its 32-block
                     h2v hi = {a0, a1};
-                    h2v lo = {(_Float16)((h2[0] - (float)a0) * 2048.f), (_Float16)((h2[1] - (float)a1) * 2048.f)};
+                    h2v lo = {l0, l1};
                     *reinterpret_cast<h2v *>(P.h_hi + po) = hi;
                     *reinterpret_cast<h2v *>(P.h_lo + po) = lo;
                 }
@@ -1185,81 +1156,6 @@ __device__ __forceinline__ void epi_lstm_frag16(const DevProb &P, f32x4 (&acc)[2
     }
 }
 
-// Numerics status (isc_status): word 1 = a split-f16 linear launch that staged CALLER data as fp32 rows (the raw region
-// features of the prologue, training-mode activations) produced a non-finite pre-activation - an operand at or beyond the
-// f16 range (|x| >= 65520: its hi plane is inf), or a NaN / inf fed in.
-ISC_STATUS_DECL(gemm)
-
-// Linear epilogue (same feature set and template split as epi_linear_frag).  CHECK: flag non-finite pre-activations.
-template <int NB, bool EDGE, bool FEAT, bool RELU, bool CHECK>
-__device__ __forceinline__ void epi_linear_frag16_impl(const DevProb &P, f32x4 (&acc)[2][NB], int frow0, int fcol0,
-                                                       int lane, int row0, int col0) {
-    const int M = P.M, N = P.N;
-    float b0[NB], b1[NB], b2[NB];
-    bool cok[NB];
-    const bool h0 = P.bias0 != nullptr, h1 = P.bias1 != nullptr, h2 = P.bias2 != nullptr;
-    const bool f_acc = FEAT && P.accumulate, f_pre = FEAT && P.C_pre != nullptr, f_mask = FEAT && P.mask != nullptr;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int gn = col0 + fcol0 + j * 16 + (lane & 15);
-        cok[j] = !EDGE || gn < N;
-        b0[j] = (h0 && cok[j]) ? P.bias0[gn] : 0.f;
-        b1[j] = (h1 && cok[j]) ? P.bias1[gn] : 0.f;
-        b2[j] = (h2 && cok[j]) ? P.bias2[gn] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gm = row0 + frow0 + i * 16 + 4 * (lane >> 4) + r;
-            if (EDGE && gm >= M) continue;
-            float *crow = P.C + (long long)gm * P.ldc + col0 + fcol0 + (lane & 15);
-            float prev[NB];
-            if (f_acc) {                                   // all loads of the row before any arithmetic
-#pragma unroll
-                for (int j = 0; j < NB; ++j) prev[j] = (!EDGE || cok[j]) ? crow[j * 16] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                if (EDGE && !cok[j]) continue;
-                float o = acc[i][j][r];
-                if (h0) o += b0[j];
-                if (h1) o += b1[j];
-                if (h2) o += b2[j];
-                if (f_acc) o += prev[j];
-                if constexpr (CHECK) bad |= !(fabsf(o) <= 3.0e38f);
-                if (RELU) o = isc_relu(o);
-                if constexpr (FEAT) {
-                    const int gn = col0 + fcol0 + j * 16 + (lane & 15);
-                    if (f_pre) P.C_pre[(long long)gm * P.ldc + gn] = o;
-                    if (f_mask) o = o * (float)P.mask[(long long)gm * N + gn] * P.mask_scale;
-                }
-                crow[j * 16] = o;
-            }
-        }
-    if constexpr (CHECK) {
-        if (__any(bad) && lane == 0) isc_flag_gemm(ISC_STATUS_WORD_LINEAR);
-    }
-}
-
-template <int NB, bool CHECK>
-__device__ __forceinline__ void epi_linear_frag16(const DevProb &P, f32x4 (&acc)[2][NB], int frow0, int fcol0, int lane,
-                                                  int row0, int col0) {
-    const bool feat = P.accumulate || P.C_pre || P.mask;
-    const bool edge = !(row0 + frow0 + 32 <= P.M && col0 + fcol0 + 16 * NB <= P.N);
-    const bool relu = P.relu != 0;
-#define ISC_EPI_CASE(E, F, R) epi_linear_frag16_impl<NB, E, F, R, CHECK>(P, acc, frow0, fcol0, lane, row0, col0)
-    if (edge) {
-        if (relu) ISC_EPI_CASE(true, true, true); else ISC_EPI_CASE(true, true, false);
-    } else if (feat) {
-        if (relu) ISC_EPI_CASE(false, true, true); else ISC_EPI_CASE(false, true, false);
-    } else {
-        if (relu) ISC_EPI_CASE(false, false, true); else ISC_EPI_CASE(false, false, false);
-    }
-#undef ISC_EPI_CASE
-}
-
 // K-split form of the large split-f16 linear tile: workgroup (tile, ks) contracts its share of the k-blocks and stores the
 // RAW partial tile to slab[ks] ([M, N] row-major); splitk_linear_kernel sums the slabs in fixed order and applies the
 // epilogue.  For long contractions on few tiles - the classifier's dX over T x (B1 + B2) = 4160 rows is 132 tiles of
@@ -1270,27 +1166,26 @@ __device__ __forceinline__ void epi_slab_frag16(const DevProb &P, f32x4 (&acc)[2
     float *base = P.slab + (long long)ks * P.slab_stride;
     bool bad = false;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int e = 0; e < Frag16::NR; ++e) {
+        const int gm = row0 + frow0 + Frag16::row(e, lane);
+        if (gm >= P.M) continue;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gm = row0 + frow0 + i * 16 + 4 * (lane >> 4) + r;
-            if (gm >= P.M) continue;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const int gn = col0 + j * 16 + (lane & 15);
-                if (gn >= P.N) continue;
-                const float o = acc[i][j][r];
-                if constexpr (CHECK) bad |= !(fabsf(o) <= 3.0e38f);
-                base[(long long)gm * P.N + gn] = o;
-            }
+        for (int j = 0; j < NB; ++j) {
+            const int gn = col0 + j * Frag16::CW + Frag16::col(lane);
+            if (gn >= P.N) continue;
+            const float o = Frag16::get(acc, e, j);
+            if constexpr (CHECK) bad |= !(fabsf(o) <= 3.0e38f);
+            base[(long long)gm * P.N + gn] = o;
         }
+    }
     if constexpr (CHECK) {
         if (__any(bad) && lane == 0) isc_flag_gemm(ISC_STATUS_WORD_LINEAR);
     }
 }
 
 // ---------------------------------------------------------------- H3 tile: 128 x 128 on the f16 matrix cores
-// fp32 operands, fp32 results, f16 MFMA rate.  Every operand value is split once into two f16 planes,
+// fp32 operands, fp32 results, f16 MFMA rate.  Every operand value is split once into two f16 planes (isc_split_f16,
+// common.h),
 //     x = hi + lo * 2^-11,   hi = f16(x),   lo = f16((x - hi) * 2^11)
 // which keeps >= 22 significant bits of x for |x| >= 2^-14 and an absolute error <= 2^-35 below (the subtraction is
 // exact in fp32; tests/test_h3_math.py),
@@ -1317,9 +1212,10 @@ __device__ __forceinline__ void h3_frag_from_f32(const char *row, int oct, int s
     const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
+        _Float16 h, l;
+        isc_split_f16(x[e], h, l);
         hi[e] = h;
-        lo[e] = (_Float16)((x[e] - (float)h) * 2048.f);
+        lo[e] = l;
     }
 }
 
@@ -1585,15 +1481,15 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], 1.f / 2048.f, acc0[i][j][r]);
+            for (int r = 0; r < 4; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], ISC_SPLIT_LO_WEIGHT, acc0[i][j][r]);
 
     if constexpr (EPI == EPI_VOCAB) {
-        epi_vocab_frag16<NB>(P, acc0, wm * 32, lane, row0, col0, tn);
+        epi_vocab_frag<Frag16, NB, 1, G::BM>(P, acc0, wm * 32, 0, 0, lane, row0, col0, tn, nullptr);
     } else if constexpr (EPI == EPI_LSTM) {
         epi_lstm_frag16(P, acc0, wm * 32, lane, row0, tn);
     } else {
         if (G::KSLICE && ksplit > 1) epi_slab_frag16<NB, AF32>(P, acc0, wm * 32, lane, row0, col0, ks);
-        else epi_linear_frag16<NB, AF32>(P, acc0, wm * 32, wn * 16 * NB, lane, row0, col0);
+        else epi_linear_frag<Frag16, NB, AF32>(P, acc0, wm * 32, wn * 16 * NB, lane, row0, col0);
     }
 #if H3_STAMP
     // slot 0: the 128-row vocabulary form; slots 1 - 3: the 256-row LSTM (K = 1024, K = 1536) and linear forms
@@ -1679,24 +1575,16 @@ __global__ __launch_bounds__(256) void h3_split_kernel(const SplitLaunch S) {
         // thread -> (n = tid / 4, 8 consecutive k = 8 * (tid % 4)): four threads write one row's 64 B of hi and 64 B of lo
         const int n = threadIdx.x >> 2, q = (threadIdx.x & 3) * 8;
         if (n0 + n < J.rows) {
-            h8 hi, lo;
+            float x[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float x = t[q + e][n];
-                const _Float16 h = (_Float16)x;
-                hi[e] = h;
-                lo[e] = (_Float16)((x - (float)h) * 2048.f);
-            }
-            const long long o = plane_index(n0 + n, kq + q, J.Kp);
-            *reinterpret_cast<h8 *>(J.hi + o) = hi;
-            *reinterpret_cast<h8 *>(J.lo + o) = lo;
+            for (int e = 0; e < 8; ++e) x[e] = t[q + e][n];
+            store_planes<8>(J.hi, J.lo, n0 + n, kq + q, J.Kp, x);
         }
         return;
     }
     if (idx >= (long long)J.rows * k8n) return;
     const int row = (int)(idx / k8n);
     int k = (int)(idx - (long long)row * k8n) * 8;
-    const long long o = plane_index(row, k, J.Kp);        // 8 consecutive k never leave their 32-block
     const float *sp = J.src[0];
     int ld = J.ld[0], k0 = 0;
 #pragma unroll
@@ -1705,15 +1593,7 @@ __global__ __launch_bounds__(256) void h3_split_kernel(const SplitLaunch S) {
     const float *p = sp + (long long)row * ld + (k - k0);
     const float4 v0 = *reinterpret_cast<const float4 *>(p), v1 = *reinterpret_cast<const float4 *>(p + 4);
     const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    h8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)((x[e] - (float)h) * 2048.f);
-    }
-    *reinterpret_cast<h8 *>(J.hi + o) = hi;
-    *reinterpret_cast<h8 *>(J.lo + o) = lo;
+    store_planes<8>(J.hi, J.lo, row, k, J.Kp, x);        // 8 consecutive k never leave their 32-block
 }
 
 // ---------------------------------------------------------------- H3S: skinny split-f16 tiles for few-row launches
@@ -1741,7 +1621,25 @@ __device__ __forceinline__ void h3s_dma(unsigned lds_addr, const char *src) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_addr), "v"(src) : "memory");
 }
 
-// The 128-column statistics of a BM-row vocabulary tile from its four 32-column waves' (epi_vocab_frag<1, 4, BM>).
+// The MFMA operand fragments of one 32-deep k-block (two 16-deep steps) from 4 KB images: ia / iw = this lane's row
+// (lane & 31) of the A / W image, fh = lane >> 5, fsw = the row's chunk swizzle.  A W image always holds planes; an A
+// image holds planes or, with af32, fp32 rows that are split here.
+__device__ __forceinline__ void h3s_read_frags(const char *ia, const char *iw, bool af32, int fh, int fsw, h8 (&a1)[2],
+                                               h8 (&a2)[2], h8 (&b1)[2], h8 (&b2)[2]) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        if (af32) {
+            h3_frag_from_f32(ia, 2 * kk + fh, fsw, a1[kk], a2[kk]);
+        } else {
+            a1[kk] = *reinterpret_cast<const h8 *>(ia + (((2 * kk + fh) ^ fsw) * 16));
+            a2[kk] = *reinterpret_cast<const h8 *>(ia + (((4 + 2 * kk + fh) ^ fsw) * 16));
+        }
+        b1[kk] = *reinterpret_cast<const h8 *>(iw + (((2 * kk + fh) ^ fsw) * 16));
+        b2[kk] = *reinterpret_cast<const h8 *>(iw + (((4 + 2 * kk + fh) ^ fsw) * 16));
+    }
+}
+
+// The 128-column statistics of a BM-row vocabulary tile from its four 32-column waves' (epi_vocab_frag<Frag32, 1, 4, BM>).
 template <int BM>
 __device__ __forceinline__ void h3s_vocab_combine(const DevProb &P, const float *smem, int tid, int row0, int tn) {
     const float *smx = smem;
@@ -1904,29 +1802,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
         if (false)
 #endif
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const char *ia = img + t * 4096;
-                if (af32) {
-                    const float4 v0 = *reinterpret_cast<const float4 *>(ia + (((4 * kk + 2 * fh) ^ fsw) * 16));
-                    const float4 v1 = *reinterpret_cast<const float4 *>(ia + (((4 * kk + 2 * fh + 1) ^ fsw) * 16));
-                    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const _Float16 h = (_Float16)x[e];
-                        a1[t][kk][e] = h;
-                        a2[t][kk][e] = (_Float16)((x[e] - (float)h) * 2048.f);
-                    }
-                } else {
-                    a1[t][kk] = *reinterpret_cast<const h8 *>(ia + (((2 * kk + fh) ^ fsw) * 16));
-                    a2[t][kk] = *reinterpret_cast<const h8 *>(ia + (((4 + 2 * kk + fh) ^ fsw) * 16));
-                }
-                const char *iw = img + IMG + t * 4096;
-                b1[t][kk] = *reinterpret_cast<const h8 *>(iw + (((2 * kk + fh) ^ fsw) * 16));
-                b2[t][kk] = *reinterpret_cast<const h8 *>(iw + (((4 + 2 * kk + fh) ^ fsw) * 16));
-            }
-        }
+        for (int t = 0; t < T; ++t)
+            h3s_read_frags(img + t * 4096, img + IMG + t * 4096, af32, fh, fsw, a1[t], a2[t], b1[t], b2[t]);
         if (EARLY) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the fragments are in registers: the slot is free
             if (i + R < n) issue(i + R);
@@ -1952,7 +1829,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
 #pragma unroll
         for (int j = 0; j < T; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], 1.f / 2048.f, acc0[i][j][r]);
+            for (int r = 0; r < 16; ++r) acc0[i][j][r] = fmaf(acc1[i][j][r], ISC_SPLIT_LO_WEIGHT, acc0[i][j][r]);
     __syncthreads();                                     // every wave is done with its ring: LDS is free
 
     if constexpr (EPI == EPI_VOCAB) {
@@ -1970,12 +1847,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
             __syncthreads();                             // the exchange area is the statistics' combine area next
         }
         f32x16 accv[1] = {acc0[0][0]};
-        if (NW == 4 || wave < 4) epi_vocab_frag<1, 4, BM>(P, accv, 0, wave * 32, wave, lane, row0, col0, tn, smem);
+        if (NW == 4 || wave < 4) epi_vocab_frag<Frag32, 1, 4, BM>(P, accv, 0, wave * 32, wave, lane, row0, col0, tn, smem);
         __syncthreads();
         h3s_vocab_combine<BM>(P, smem, tid, row0, tn);
         return;
     } else {
-        // partial tile of this wave -> LDS (C/D layout: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5))
+        // partial tile of this wave -> LDS
         float *mine = smem + wave * (BM * LDR);
 #pragma unroll
         for (int i = 0; i < T; ++i)
@@ -1983,7 +1860,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
             for (int j = 0; j < T; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    mine[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = acc0[i][j][r];
+                    mine[(i * 32 + Frag32::row(r, lane)) * LDR + j * 32 + fr] = acc0[i][j][r];
         __syncthreads();
         if (NW > 4 && tid >= 256) return;                // the epilogue maps 256 threads onto the tile
         auto red = [&](int row, int col) __attribute__((always_inline)) {
@@ -1999,7 +1876,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
                 const int row = grp / (BN / 4), c4 = (grp % (BN / 4)) * 4;
                 const int gm = row0 + row, gn = col0 + c4;
                 if (gm >= M || gn >= N) continue;
-                float o[4], pre[4];
+                float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = red(row, c4 + e);
                 if (ksplit > 1) {                                    // raw partial sums (N % 4 == 0 on this route)
@@ -2007,32 +1884,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_h3s_kernel(const DevLaunch L) {
                         make_float4(o[0], o[1], o[2], o[3]);
                     continue;
                 }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int nn = gn + e;
-                    pre[e] = 0.f;
-                    if (nn < N) {
-                        if (P.bias0) o[e] += P.bias0[nn];
-                        if (P.bias1) o[e] += P.bias1[nn];
-                        if (P.bias2) o[e] += P.bias2[nn];
-                        if (P.accumulate) o[e] += P.C[(long long)gm * P.ldc + nn];
-                        if (P.relu) o[e] = isc_relu(o[e]);
-                        pre[e] = o[e];
-                        if (P.mask) o[e] = o[e] * (float)P.mask[(long long)gm * N + nn] * P.mask_scale;
-                    }
-                }
-                float *dst = P.C + (long long)gm * P.ldc + gn;
-                if ((P.ldc & 3) == 0 && gn + 3 < N) {
-                    *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                    if (P.C_pre)
-                        *reinterpret_cast<float4 *>(P.C_pre + (long long)gm * P.ldc + gn) =
-                            make_float4(pre[0], pre[1], pre[2], pre[3]);
-                } else {
-                    for (int e = 0; e < 4 && gn + e < N; ++e) {
-                        dst[e] = o[e];
-                        if (P.C_pre) P.C_pre[(long long)gm * P.ldc + gn + e] = pre[e];
-                    }
-                }
+                epi_linear_finish<4>(P, gm, gn, o);
             }
         } else {
             constexpr int UN = 8 * T, NR = T * T;                    // units of the tile; rows per thread
@@ -2130,25 +1982,7 @@ __global__ __launch_bounds__(256) void gemm_h3v_kernel(const DevLaunch L) {
         const char *ia = lds + st * H3V_STAGE_BYTES + fr * 128;
         const char *iw = ia + 4096 + wave * 4096;
         h8 a1[2], a2[2], b1[2], b2[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            if (af32) {
-                const float4 v0 = *reinterpret_cast<const float4 *>(ia + (((4 * kk + 2 * fh) ^ fsw) * 16));
-                const float4 v1 = *reinterpret_cast<const float4 *>(ia + (((4 * kk + 2 * fh + 1) ^ fsw) * 16));
-                const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const _Float16 h = (_Float16)x[e];
-                    a1[kk][e] = h;
-                    a2[kk][e] = (_Float16)((x[e] - (float)h) * 2048.f);
-                }
-            } else {
-                a1[kk] = *reinterpret_cast<const h8 *>(ia + (((2 * kk + fh) ^ fsw) * 16));
-                a2[kk] = *reinterpret_cast<const h8 *>(ia + (((4 + 2 * kk + fh) ^ fsw) * 16));
-            }
-            b1[kk] = *reinterpret_cast<const h8 *>(iw + (((2 * kk + fh) ^ fsw) * 16));
-            b2[kk] = *reinterpret_cast<const h8 *>(iw + (((4 + 2 * kk + fh) ^ fsw) * 16));
-        }
+        h3s_read_frags(ia, iw, af32, fh, fsw, a1, a2, b1, b2);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[kk], b1[kk], acc0, 0, 0, 0);
@@ -2158,10 +1992,10 @@ __global__ __launch_bounds__(256) void gemm_h3v_kernel(const DevLaunch L) {
         st = st == H3V_STAGES - 1 ? 0 : st + 1;
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc0[r] = fmaf(acc1[r], 1.f / 2048.f, acc0[r]);
+    for (int r = 0; r < 16; ++r) acc0[r] = fmaf(acc1[r], ISC_SPLIT_LO_WEIGHT, acc0[r]);
     __syncthreads();                                     // every wave is done with the stages: LDS is free
     f32x16 accv[1] = {acc0};
-    epi_vocab_frag<1, 4, BM>(P, accv, 0, wave * 32, wave, lane, row0, col0, tn, smem);
+    epi_vocab_frag<Frag32, 1, 4, BM>(P, accv, 0, wave * 32, wave, lane, row0, col0, tn, smem);
     __syncthreads();
     h3s_vocab_combine<BM>(P, smem, tid, row0, tn);
 }
@@ -2187,32 +2021,13 @@ __global__ __launch_bounds__(256) void splitk_linear_kernel(const DevLaunch L) {
     float4 v = part[0];
 #pragma unroll
     for (int s = 1; s < 16; ++s) { v.x += part[s].x; v.y += part[s].y; v.z += part[s].z; v.w += part[s].w; }
-    float o[4] = {v.x, v.y, v.z, v.w}, pre[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int n = gn + e;
-        if (P.bias0) o[e] += P.bias0[n];
-        if (P.bias1) o[e] += P.bias1[n];
-        if (P.bias2) o[e] += P.bias2[n];
-        if (P.accumulate) o[e] += P.C[(long long)gm * P.ldc + n];
-        if (P.relu) o[e] = isc_relu(o[e]);
-        pre[e] = o[e];
-        if (P.mask) o[e] = o[e] * (float)P.mask[(long long)gm * N + n] * P.mask_scale;
-    }
-    float *dst = P.C + (long long)gm * P.ldc + gn;
-    if ((P.ldc & 3) == 0) {
-        *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-        if (P.C_pre)
-            *reinterpret_cast<float4 *>(P.C_pre + (long long)gm * P.ldc + gn) = make_float4(pre[0], pre[1], pre[2], pre[3]);
-    } else {
-        for (int e = 0; e < 4; ++e) {
-            dst[e] = o[e];
-            if (P.C_pre) P.C_pre[(long long)gm * P.ldc + gn + e] = pre[e];
-        }
-    }
+    float o[4] = {v.x, v.y, v.z, v.w};
+    epi_linear_finish<4>(P, gm, gn, o);                 // (N % 4 == 0 on this route: no column past the border)
 }
 
-__global__ __launch_bounds__(256) void splitk_lstm_kernel(const DevLaunch L) {
+// (64 slab values in flight leave 16 registers of the 6-waves-per-SIMD budget, which the allocator meets or misses by
+// two registers from build to build: the budget is stated)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void splitk_lstm_kernel(const DevLaunch L) {
     ISC_GATE_RETURN(L);
     const DevProb &P = L.p[0];
     const int H = P.H;
@@ -2229,32 +2044,45 @@ __global__ __launch_bounds__(256) void splitk_lstm_kernel(const DevLaunch L) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) part[k][s] = s < S ? sl[(long long)s * P.slab_stride] : 0.f;
     }
-    float g[4];
+    const int gma[1] = {gm};
+    const bool ok[1] = {true};
+    float g[1][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float a = part[k][0];
 #pragma unroll
         for (int s = 1; s < 16; ++s) a += part[k][s];      // fixed order; the unused slots add 0
-        if (P.bias0) a += P.bias0[k * H + unit] + P.bias1[k * H + unit];
-        if (P.pre) a += P.pre[(long long)gm * 4 * H + k * H + unit];
-        if (P.tab) a += P.tab[P.tab_ids[(long long)gm * P.tab_ids_stride] * 4 * H + k * H + unit];
-        g[k] = a;
+        g[0][k] = a;
     }
-    const float gi = isc_sigmoid(g[0]), gf = isc_sigmoid(g[1]), gg = isc_tanh(g[2]), go = isc_sigmoid(g[3]);
-    const float c2 = gf * P.c_prev[i] + gi * gg;
-    const float h2 = go * isc_tanh(c2);
-    P.c_out[i] = c2;
-    P.h_out[i] = h2;
-    if (P.h_hi) {
-        const _Float16 hh = (_Float16)h2;
-        const long long po = plane_index(gm, unit, H);
-        P.h_hi[po] = hh;
-        P.h_lo[po] = (_Float16)((h2 - (float)hh) * 2048.f);
+    // the sums are formed here: left to sink below the cell's loads, the 64 slab values would stay live across them
+    asm volatile("" : "+v"(g[0][0]), "+v"(g[0][1]), "+v"(g[0][2]), "+v"(g[0][3]));
+    lstm_cells<1>(P, gma, unit, ok, g);
+}
+
+// The statistics of one row's 128-column tile tn on one wave: lane l holds the contraction sums v[h] of columns
+// 128 tn + l + 64 h.  Adds the bias, optionally writes the logits, and emits the tile's (max, arg-max, sum exp) the
+// tile kernels' epilogue would have produced.
+__device__ __forceinline__ void wave_vocab_tile128(const DevProb &P, int gm, int tn, const float (&v)[2], int lane) {
+    float x[2];
+    int col[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        col[h] = tn * 128 + lane + 64 * h;
+        const bool ok = col[h] < P.N;
+        x[h] = ok ? v[h] + P.bias0[col[h]] : -INFINITY;
+        if (ok && P.C) P.C[(long long)gm * P.ld_logits + col[h]] = x[h];
     }
-    if (P.hmask) P.hdrop[i] = h2 * (float)P.hmask[i] * P.mask_scale;
-    if (P.gates_out) {
-        float *q = P.gates_out + (long long)gm * 4 * H + unit;
-        q[0] = gi; q[H] = gf; q[2 * H] = gg; q[3 * H] = go;
+    float mx = x[0];
+    int ix = col[0];
+    if (x[1] > mx) { mx = x[1]; ix = col[1]; }             // equal: the lower column (h = 0) stays
+    wave_argmax(mx, ix);
+    float sm = (x[0] > -INFINITY ? __expf(x[0] - mx) : 0.f) + (x[1] > -INFINITY ? __expf(x[1] - mx) : 0.f);
+    sm = wave_sum(sm);
+    if (lane == 0) {
+        const long long o = (long long)gm * P.ntile_total + tn;
+        P.pmax[o] = mx;
+        P.psum[o] = sm;
+        P.pidx[o] = ix;
     }
 }
 
@@ -2270,34 +2098,21 @@ __global__ __launch_bounds__(256) void splitk_vocab_kernel(const DevLaunch L) {
     if (w >= (long long)P.M * n_tile) return;
     const int gm = (int)(w / n_tile), tn = (int)(w % n_tile);
     const int N = P.N, S = P.ksplit;
-    float x[2];
-    int col[2];
+    float v[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        col[h] = tn * 128 + lane + 64 * h;
-        const bool ok = col[h] < N;
-        const float *sl = P.slab + (long long)gm * N + (ok ? col[h] : 0);
+        const int col = tn * 128 + lane + 64 * h;
+        const bool ok = col < N;
+        const float *sl = P.slab + (long long)gm * N + (ok ? col : 0);
         float part[16];
 #pragma unroll
         for (int s = 0; s < 16; ++s) part[s] = (ok && s < S) ? sl[(long long)s * P.slab_stride] : 0.f;
         float a = part[0];
 #pragma unroll
         for (int s = 1; s < 16; ++s) a += part[s];
-        x[h] = ok ? a + P.bias0[col[h]] : -INFINITY;
-        if (ok && P.C) P.C[(long long)gm * P.ld_logits + col[h]] = x[h];
+        v[h] = a;
     }
-    float mx = x[0];
-    int ix = col[0];
-    if (x[1] > mx) { mx = x[1]; ix = col[1]; }             // equal: the lower column (h = 0) stays
-    wave_argmax(mx, ix);
-    float sm = (x[0] > -INFINITY ? __expf(x[0] - mx) : 0.f) + (x[1] > -INFINITY ? __expf(x[1] - mx) : 0.f);
-    sm = wave_sum(sm);
-    if (lane == 0) {
-        const long long o = (long long)gm * n_tile + tn;
-        P.pmax[o] = mx;
-        P.psum[o] = sm;
-        P.pidx[o] = ix;
-    }
+    wave_vocab_tile128(P, gm, tn, v, lane);
 }
 
 // ---------------------------------------------------------------- few rows: fused GEMV kernels (exact fp32)
@@ -2466,29 +2281,9 @@ __global__ __launch_bounds__(64 * NW) void gemv_rows_kernel(const DevLaunch L) {
             red[(lane & 7) * 128 + wave * 16 + rnd * 8 + (lane >> 3)] = acc[0];
         }
         __syncthreads();
-        const int n_tile = P.ntile_total;
         for (int m = wave; m < M; m += NW) {
-            float x[2];
-            int col[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                col[h] = col0 + lane + 64 * h;
-                const bool ok = col[h] < N;
-                x[h] = ok ? red[m * 128 + lane + 64 * h] + P.bias0[col[h]] : -INFINITY;
-                if (ok && P.C) P.C[(long long)m * P.ld_logits + col[h]] = x[h];
-            }
-            float mx = x[0];
-            int ix = col[0];
-            if (x[1] > mx) { mx = x[1]; ix = col[1]; }             // equal: the lower column stays
-            wave_argmax(mx, ix);
-            float sm = (x[0] > -INFINITY ? __expf(x[0] - mx) : 0.f) + (x[1] > -INFINITY ? __expf(x[1] - mx) : 0.f);
-            sm = wave_sum(sm);
-            if (lane == 0) {
-                const long long o = (long long)m * n_tile + tile;
-                P.pmax[o] = mx;
-                P.psum[o] = sm;
-                P.pidx[o] = ix;
-            }
+            const float v[2] = {red[m * 128 + lane], red[m * 128 + lane + 64]};
+            wave_vocab_tile128(P, m, tile, v, lane);
         }
     } else {
         const int KS = P.ksplit;                         // 1, 2 or 4 (try_gemv)
@@ -2529,16 +2324,9 @@ __global__ __launch_bounds__(64 * NW) void gemv_rows_kernel(const DevLaunch L) {
             } else {
                 const int m = lane >> 2, e = lane & 3, n = quad * 4 + e;
                 if (lane < 4 * MR && m < M && n < N) {
-                    float o = rq[e * MR + m];
-                    for (int j = 1; j < KS; ++j) o += rq[j * 32 + e * MR + m];
-                    if (P.bias0) o += P.bias0[n];
-                    if (P.bias1) o += P.bias1[n];
-                    if (P.bias2) o += P.bias2[n];
-                    if (P.accumulate) o += P.C[(long long)m * P.ldc + n];
-                    if (P.relu) o = isc_relu(o);
-                    if (P.C_pre) P.C_pre[(long long)m * P.ldc + n] = o;
-                    if (P.mask) o = o * (float)P.mask[(long long)m * N + n] * P.mask_scale;
-                    P.C[(long long)m * P.ldc + n] = o;
+                    float o[1] = {rq[e * MR + m]};
+                    for (int j = 1; j < KS; ++j) o[0] += rq[j * 32 + e * MR + m];
+                    epi_linear_finish<1>(P, m, n, o);
                 }
             }
         }

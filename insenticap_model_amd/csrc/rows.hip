@@ -431,15 +431,10 @@ __global__ __launch_bounds__(768) void rows_lstm_kernel(const RLstmArgs a) {
         float v = pr[0];
 #pragma unroll
         for (int sw = 1; sw < 8; ++sw) v += sw < S ? pr[sw] : 0.f;
-        // g += (b_ih + b_hh);  g += pre;  g += table row   (the order of lstm_cells, gemm_f32.hip)
-        if (a.b_ih) v += b[k];
-        if (a.pre) v += q[k];
-        if (a.tab) v += tb[k];
-        gt[k] = v;
+        gt[k] = isc_lstm_gate_sum(v, a.b_ih != nullptr, b[k], a.pre != nullptr, q[k], a.tab != nullptr, tb[k]);
     }
-    const float gi = isc_sigmoid(gt[0]), gf = isc_sigmoid(gt[1]), gg = isc_tanh(gt[2]), go = isc_sigmoid(gt[3]);
-    const float c2 = gf * cp + gi * gg;
-    const float h2 = go * isc_tanh(c2);
+    float c2, h2;
+    isc_lstm_cell(gt, cp, c2, h2);
     a.c_out[(long long)m * H + unit] = c2;
     a.h_out[(long long)m * H + unit] = h2;
     RSTAMP(6);

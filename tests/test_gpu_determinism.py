@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _split_f16 import planes as _planes
 from conftest import case_setup
 from insenticap_model_amd import Captioner, ops, synth
 
@@ -87,6 +88,113 @@ def test_splitk_route_matches_single_pass(M, N, K):
     ob = torch.empty(4096, N, device=dev())
     ops.linear_fwd([ops.linear_problem([(big, w)], ob, b)])
     np.testing.assert_allclose(ob[:M].cpu().numpy(), outs[0].cpu().numpy(), atol=1e-5, rtol=1e-5)
+
+
+@pytest.fixture
+def fp32_splitk_route():
+    """Exact-fp32 engine (no split-f16 kernels); with more than 8 rows (no few-row kernel) and the workspace ops attaches,
+    a launch of few tiles then takes plan_splitk: raw slabs from the 32 x 128 tile, then a splitk_*_kernel."""
+    prev = ops.set_h3_mode(0)
+    yield
+    ops.set_h3_mode(prev)
+
+
+def _rand(g, *shape, scale=1.0):
+    return (torch.rand(*shape, generator=g) * 2 - 1) * scale
+
+
+def test_splitk_linear_reduce_every_feature(fp32_splitk_route):
+    """splitk_linear_kernel (2 slabs) with bias, ReLU, accumulate, keep-mask and the pre-mask copy, against fp64."""
+    M, N, K1, K2 = 40, 200, 256, 64
+    g = torch.Generator().manual_seed(M * 31 + N)
+    x1, w1, b = _rand(g, M, K1), _rand(g, N, K1, scale=K1 ** -0.5), _rand(g, N)
+    x2, w2 = _rand(g, M, K2), _rand(g, N, K2, scale=K2 ** -0.5)
+    keep = (torch.rand(M, N, generator=g) > 0.5).to(torch.uint8)
+    prior = _rand(g, M, N)
+    ref_pre = torch.relu(x1.double() @ w1.double().t() + x2.double() @ w2.double().t() + b.double() + prior.double())
+    ref_out = ref_pre * keep.double() * 2.0
+    segs = [(x1.to(dev()), w1.to(dev())), (x2.to(dev()), w2.to(dev()))]
+    db, dkeep = b.to(dev()), keep.to(dev())
+    outs = []
+    for rep in range(2):
+        out = prior.clone().to(dev())
+        pre = torch.full((M, N), float('nan'), device=dev())
+        ops.linear_fwd([ops.linear_problem(segs, out, db, relu=True, keep_mask=dkeep, mask_scale=2.0, out_pre=pre,
+                                           accumulate=True)])
+        torch.cuda.synchronize()
+        np.testing.assert_allclose(out.cpu().numpy(), ref_out.float().numpy(), atol=3e-5, rtol=1e-5)
+        np.testing.assert_allclose(pre.cpu().numpy(), ref_pre.float().numpy(), atol=3e-5, rtol=1e-5)
+        assert torch.equal(out, pre * dkeep.float() * 2.0)         # exact, whatever the route
+        outs.append((out.cpu(), pre.cpu()))
+    assert all(torch.equal(a, b) for a, b in zip(*outs))           # fixed-order slab reduction
+
+
+def test_splitk_lstm_reduce_every_feature(fp32_splitk_route):
+    """splitk_lstm_kernel (3 slabs) with the hoisted term, the token table, planes of h, saved gates and the dropout
+    output, against fp64."""
+    M, H = 40, 64
+    g = torch.Generator().manual_seed(M + H)
+    ks = (320, 64)
+    xs = [_rand(g, M, k) for k in ks]
+    ws = [_rand(g, 4 * H, k, scale=(3 * k) ** -0.5) for k in ks]
+    b_ih, b_hh, c0, pre = _rand(g, 4 * H), _rand(g, 4 * H), _rand(g, M, H), _rand(g, M, 4 * H, scale=0.3)
+    tab, ids = _rand(g, 50, 4 * H, scale=0.3), torch.randint(0, 50, (M,), generator=g)
+    keep = (torch.rand(M, H, generator=g) > 0.5).to(torch.uint8)
+    z = (sum(x.double() @ w.double().t() for x, w in zip(xs, ws)) + b_ih.double() + b_hh.double() + pre.double() +
+         tab.double()[ids])
+    i, f, gg, o = z.split(H, dim=1)
+    c_ref = torch.sigmoid(f) * c0.double() + torch.sigmoid(i) * torch.tanh(gg)
+    h_ref = torch.sigmoid(o) * torch.tanh(c_ref)
+    act = torch.cat([torch.sigmoid(i), torch.sigmoid(f), torch.tanh(gg), torch.sigmoid(o)], dim=1)
+    dsegs = [(x.to(dev()), w.to(dev())) for x, w in zip(xs, ws)]
+    d = [v.to(dev()) for v in (b_ih, b_hh, c0, pre, tab, ids, keep)]
+    outs = []
+    for rep in range(2):
+        h, c = torch.empty(M, H, device=dev()), torch.empty(M, H, device=dev())
+        gates, hdrop = torch.empty(M, 4 * H, device=dev()), torch.empty(M, H, device=dev())
+        hp = torch.empty(2, M, H, dtype=torch.float16, device=dev())
+        ops.lstm_fwd(dsegs, d[0], d[1], d[2], h, c, gates_out=gates, pre=d[3], tab=d[4], tab_ids=d[5], h_planes=hp,
+                     h_keep_mask=d[6], mask_scale=2.0, hdrop_out=hdrop)
+        torch.cuda.synchronize()
+        np.testing.assert_allclose(h.cpu().numpy(), h_ref.float().numpy(), atol=2e-5)
+        np.testing.assert_allclose(c.cpu().numpy(), c_ref.float().numpy(), atol=2e-5)
+        np.testing.assert_allclose(gates.cpu().numpy(), act.float().numpy(), atol=2e-5)
+        assert torch.equal(hdrop, h * d[6].float() * 2.0)          # exact, whatever the route
+        assert torch.equal(hp, _planes(h))                         # the epilogue's planes == re-splitting h
+        outs.append([v.cpu() for v in (h, c, gates, hdrop, hp)])
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+
+
+@pytest.mark.parametrize('logits', [True, False])
+def test_splitk_vocab_reduce(fp32_splitk_route, logits):
+    """splitk_vocab_kernel (2 slabs; the last 128-column tile is ragged) against fp64, with and without logits."""
+    M, V, K = 40, 1000, 320
+    g = torch.Generator().manual_seed(V + M)
+    h, W, bias = _rand(g, M, K), _rand(g, V, K, scale=4 * K ** -0.5), _rand(g, V)
+    logits_ref = h.double() @ W.double().t() + bias.double()
+    lse_ref = torch.logsumexp(logits_ref, 1)
+    nt = (V + 127) // 128
+    dh, dW, dbias = h.to(dev()), W.to(dev()), bias.to(dev())
+    outs = []
+    for rep in range(2):
+        pm, ps = torch.empty(M, nt, device=dev()), torch.empty(M, nt, device=dev())
+        pi = torch.empty(M, nt, device=dev(), dtype=torch.int32)
+        lg = torch.empty(M, V, device=dev()) if logits else None
+        ops.vocab_fwd(dh, dW, dbias, pm, ps, pi, lg)
+        torch.cuda.synchronize()
+        mx = pm.max(1).values
+        lse = mx + torch.log((ps * torch.exp(pm - mx[:, None])).sum(1))
+        np.testing.assert_allclose(lse.cpu().numpy(), lse_ref.float().numpy(), atol=3e-5, rtol=1e-5)
+        arg = pi.gather(1, pm.argmax(1)[:, None]).squeeze(1).long().cpu()
+        ref_arg = logits_ref.argmax(1)
+        for r in (arg != ref_arg).nonzero().flatten().tolist():
+            top2 = logits_ref[r].topk(2).values
+            assert (top2[0] - top2[1]).item() < 1e-5, (r, top2)
+        if logits:
+            np.testing.assert_allclose(lg.cpu().numpy(), logits_ref.float().numpy(), atol=3e-5, rtol=1e-5)
+            assert torch.equal(arg, lg.argmax(1).cpu())
+        outs.append([v.cpu() for v in (pm, ps, pi) + ((lg,) if logits else ())])
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
 
 
 def test_step_plan_equals_per_kernel_path():

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _split_f16 import planes as _planes
 from insenticap_model_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -82,23 +83,31 @@ def test_lstm_all_tiles(M, H):
     xs = [_rand(g, M, k) for k in ks]
     ws = [_rand(g, 4 * H, k, scale=(3 * k) ** -0.5) for k in ks]
     b_ih, b_hh, pre, c0 = _rand(g, 4 * H), _rand(g, 4 * H), _rand(g, M, 4 * H, scale=0.3), _rand(g, M, H)
-    z = sum(x.double() @ w.double().t() for x, w in zip(xs, ws)) + b_ih.double() + b_hh.double() + pre.double()
+    tab, ids = _rand(g, 50, 4 * H, scale=0.3), torch.randint(0, 50, (M,), generator=g)
+    keep = (torch.rand(M, H, generator=g) > 0.5).to(torch.uint8)
+    z = (sum(x.double() @ w.double().t() for x, w in zip(xs, ws)) + b_ih.double() + b_hh.double() + pre.double() +
+         tab.double()[ids])
     i, f, gg, o = z.split(H, dim=1)
     c_ref = torch.sigmoid(f) * c0.double() + torch.sigmoid(i) * torch.tanh(gg)
     h_ref = torch.sigmoid(o) * torch.tanh(c_ref)
     gates_ref = torch.cat([torch.sigmoid(i), torch.sigmoid(f), torch.tanh(gg), torch.sigmoid(o)], 1)
     dsegs = [(x.to(dev()), w.to(dev())) for x, w in zip(xs, ws)]
-    dargs = [v.to(dev()) for v in (b_ih, b_hh, c0, pre)]
+    dargs = [v.to(dev()) for v in (b_ih, b_hh, c0, pre, tab, ids, keep)]
     base = None
     for t in TILES:
         ops.set_tile_override(t)
         h, c = torch.empty(M, H, device=dev()), torch.empty(M, H, device=dev())
         gates = torch.empty(M, 4 * H, device=dev())
-        ops.lstm_fwd(dsegs, dargs[0], dargs[1], dargs[2], h, c, gates_out=gates, pre=dargs[3])
+        hdrop = torch.empty(M, H, device=dev())
+        hp = torch.empty(2, M, H, dtype=torch.float16, device=dev())
+        ops.lstm_fwd(dsegs, dargs[0], dargs[1], dargs[2], h, c, gates_out=gates, pre=dargs[3], tab=dargs[4],
+                     tab_ids=dargs[5], h_planes=hp, h_keep_mask=dargs[6], mask_scale=2.0, hdrop_out=hdrop)
         torch.cuda.synchronize()
         np.testing.assert_allclose(h.cpu().numpy(), h_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
         np.testing.assert_allclose(c.cpu().numpy(), c_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
         np.testing.assert_allclose(gates.cpu().numpy(), gates_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
+        assert torch.equal(hdrop, h * dargs[6].float() * 2.0), 'tile %d' % t        # exact, whatever the route
+        assert torch.equal(hp, _planes(h)), 'tile %d' % t                           # the planes == re-splitting h
         if base is None:
             base = (h.cpu(), c.cpu())
         else:

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _split_f16 import planes as _planes
 from insenticap_model_amd import Captioner, ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -29,13 +30,6 @@ def _rand(g, *shape, scale=1.0):
 
 def _n():
     return ops._lib.load().isc_gemv_launches()
-
-
-def _planes(x):
-    M, K = x.shape
-    hi = x.to(torch.float16)
-    lo = ((x - hi.float()) * 2048.0).to(torch.float16)
-    return torch.stack([hi.view(M, K // 32, 32), lo.view(M, K // 32, 32)], dim=2).reshape(2, M, K).contiguous()
 
 
 @pytest.mark.parametrize('M', [1, 2, 3, 4, 5, 6, 7, 8])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _split_f16 import planes as _planes
 from insenticap_model_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -26,15 +27,6 @@ def dev():
 
 def _rand(g, *shape, scale=1.0):
     return (torch.rand(*shape, generator=g) * 2 - 1) * scale
-
-
-def _planes(x):
-    """[2, M, K] f16 buffer in the library's interleaved layout (isc_seg.A_hi): per row and 32-k block 32 hi then 32 lo."""
-    M, K = x.shape
-    hi = x.to(torch.float16)
-    lo = ((x - hi.float()) * 2048.0).to(torch.float16)
-    buf = torch.stack([hi.view(M, K // 32, 32), lo.view(M, K // 32, 32)], dim=2)       # [M, K/32, 2, 32]
-    return buf.reshape(2, M, K).contiguous()
 
 
 def _launches():
