@@ -103,7 +103,14 @@ int isc_h3_weights_refresh(void *stream);
 typedef struct {
     const float *A; /* [M, K] activations, leading dim lda */
     const float *W; /* [N, K] weight slice (row-major, K contiguous), leading dim ldw */
-    int32_t lda, ldw, K, _pad;
+    int32_t lda, ldw, K;
+    /* 0: A is fp32 (above).  1: A points at _Float16 rows [M, K] with lda in HALFS - isc_linear_fwd only, and only
+     * where the launch takes the large split-f16 kernels, which read such rows natively (an f16 value is its own hi
+     * plane and has lo == 0, so the result equals the fp32 path's on the up-cast values bit for bit).  Needs
+     * K % 32 == 0, lda % 8 == 0 and a 16-byte aligned A.  isc_linear_f16_native tells beforehand whether a launch will
+     * be read natively; every entry point that cannot read halfs returns ISC_E_SHAPE for a_f16 = 1 and launches
+     * nothing - convert with isc_f16_to_f32 first. */
+    int32_t a_f16;
     /* Optional (forward entry points, split-f16 path): the f16 planes of A as a producer wrote them
      * (isc_lstm_problem.h_hi / h_lo ...): hi = f16(x), lo = f16((x - hi) * 2048), in ONE buffer of 2*M*K halfs with the
      * two planes interleaved per 32-wide k-block (so that a chunk consumes whole 128-byte lines):
@@ -139,6 +146,18 @@ typedef struct {
 } isc_linear_problem;
 
 int isc_linear_fwd(const isc_linear_problem *probs_host, int n_prob, void *stream);
+/* 1 when isc_linear_fwd, called now with these problems on `stream`, reads their isc_seg.a_f16 = 1 segments natively
+ * (the large split-f16 kernels take the launch and every such segment meets the alignment rules), else 0: the caller
+ * then converts those segments (isc_f16_to_f32) and clears the flag.  The answer comes from the dispatch of
+ * isc_linear_fwd itself, run without launching.  isc_h3_f16a_launches: launches that read at least one f16 segment
+ * natively (test hook). */
+int isc_linear_f16_native(const isc_linear_problem *probs_host, int n_prob, void *stream);
+long long isc_h3_f16a_launches(void);
+/* dst[r, c] = (float)src[r, c] for _Float16 src [rows, cols] (leading dims ld_src in halfs, ld_dst in floats; exact).
+ * isc_f16_convert_launches: how often it ran (test hook: the native f16 path must not move it). */
+int isc_f16_to_f32(const void *src, int64_t ld_src, float *dst, int64_t ld_dst, int64_t rows, int64_t cols,
+                   void *stream);
+long long isc_f16_convert_launches(void);
 
 /* Backward-pass contractions of the same layers (what autograd derives for nn.Linear /
  * nn.LSTMCell / the classifier in train_xe.py:190, decoder.py:165), on the same MFMA kernel:

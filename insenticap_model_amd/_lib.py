@@ -16,8 +16,9 @@ c_f32p = C.c_void_p  # device pointers travel as integers
 
 
 class Seg(C.Structure):
+    """isc_seg.  a_f16 = 1: A points at float16 rows, lda in halfs (isc_linear_fwd on the large split-f16 kernels only)."""
     _fields_ = [('A', C.c_void_p), ('W', C.c_void_p), ('lda', C.c_int32), ('ldw', C.c_int32),
-                ('K', C.c_int32), ('_pad', C.c_int32), ('A_hi', C.c_void_p), ('A_lo', C.c_void_p)]
+                ('K', C.c_int32), ('a_f16', C.c_int32), ('A_hi', C.c_void_p), ('A_lo', C.c_void_p)]
 
 
 class LinearProblem(C.Structure):
@@ -163,6 +164,10 @@ SIGNATURES = {
     'isc_h3_weights_resume': (C.c_int, [C.c_void_p, C.c_void_p]),
     'isc_h3_weights_refresh': (C.c_int, [C.c_void_p]),
     'isc_linear_fwd': (C.c_int, [C.POINTER(LinearProblem), C.c_int, C.c_void_p]),
+    'isc_linear_f16_native': (C.c_int, [C.POINTER(LinearProblem), C.c_int, C.c_void_p]),
+    'isc_h3_f16a_launches': (C.c_longlong, []),
+    'isc_f16_to_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    'isc_f16_convert_launches': (C.c_longlong, []),
     'isc_gemm_bwd': (C.c_int, [C.POINTER(LinearProblem), C.c_int, C.c_int, C.c_void_p]),
     'isc_lstm_fwd': (C.c_int, [C.POINTER(LstmProblem), C.c_void_p]),
     'isc_step_fwd': (C.c_int, [C.POINTER(StepPlan), C.c_void_p]),

@@ -909,6 +909,9 @@ class DecodeFn(torch.autograd.Function):
 
 
 def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_labels, ss_prob, masks, targets=None):
+    # a backward will run: float16 features become fp32 once, here - forward and backward read that copy (the dW
+    # contractions and the exact engine read fp32), so losses and gradients are those of feats.float()
+    fc, att = (None if x is None else cap._f32(x) for x in (fc, att))
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
     ids = cap._ids(captions)
@@ -931,6 +934,7 @@ def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, rep
     """Sampled roll-out with REINFORCE gradients (captioner.py:290-349, sample_max=0, train mode): one unroll
     that samples each next token on the device and keeps the activations for the backward pass; the returned
     log-probs are log p(drawn token), zero after the reference's early `break`."""
+    fc, att = cap._f32(fc), cap._f32(att)          # (as xe_with_grad: fp32 once, in front of the prologue)
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
     B = fc.shape[0]

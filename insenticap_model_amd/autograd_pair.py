@@ -265,6 +265,7 @@ def pair_with_grad(cap, fc, att, cpt_words, captions, senti_labels, ss_prob, s_c
     """forward_xe + forward_seq2seq of one iteration through one step chain.  Returns (logp_xe, logp_s2s, cpt_feats of
     the seq2seq call); captioner.fc_feats / .cpt_feats are left as the XE call leaves them (what the domain-align loss
     reads, train_xe.py:163)."""
+    fc, att = cap._f32(fc), cap._f32(att)          # (as autograd.xe_with_grad: fp32 once, in front of the prologue)
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
     ids1, ids2 = cap._ids(captions), cap._ids(s_captions)

@@ -13,6 +13,8 @@ step over I*beam rows + one device top-k per time step and ONE host read of the 
 scores are Python floats (fp64 sums of fp32 log-probs, :404-406) and the per-step selection is
 a stable descending sort over candidates in insertion order (:409), which fixes tie order.
 """
+import weakref
+
 import numpy as np
 import torch
 
@@ -197,7 +199,7 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
         return None
     if not (fc_feats.is_cuda and att_feats.is_cuda):
         return None
-    ins = [cap._f32(fc_feats), cap._f32(att_feats), senti_words, senti_labels]
+    ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
     key = _graph_key(cap, ins, beam, decoding_constraint, T)
     entry = cache.get(key)
     if not isinstance(entry, tuple):
@@ -213,7 +215,7 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
     into one graph and every further CHUNK steps into another (one pool, buffers shared): a search costs one input copy,
     <= ceil(T / CHUNK) graph launches with one counter read between them, and the read-back."""
     dev = cap._dev
-    ins = [cap._f32(fc_feats), cap._f32(att_feats), senti_words, senti_labels]
+    ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
     key = _graph_key(cap, ins, beam, decoding_constraint, T)
     cache = cap._beam_graphs
     entry = cache.get(key)
@@ -238,6 +240,9 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
         stream = cap.__dict__.get('_beam_stream')        # one capture stream per captioner, held for itself
         if stream is None or stream.device != dev:
             stream = cap.__dict__['_beam_stream'] = ops.private_stream(dev)
+            # (given back with the captioner, as its roll-out stream is: the pool has 32 per device)
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            weakref.finalize(cap, ops.release_stream_state, idx, stream.cuda_stream)
         pool = torch.cuda.graph_pool_handle()
         graphs = []
         # (few-row searches are ONE graph: its last node copies the results into this pinned buffer)

@@ -173,6 +173,14 @@ class Captioner(nn.Module):
         ops.require_device(x)
         return x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
 
+    def _feat(self, x):
+        """Image features as the prologue reads them: float16 stays float16 while no backward will run (the att_embed /
+        fc_embed GEMMs read it as it is - no fp32 image of the batch); anything else, and every training call, is fp32."""
+        if x.dtype == torch.float16 and not self._needs_grad():
+            ops.require_device(x)
+            return x.contiguous()
+        return self._f32(x)
+
     def _ids(self, x):
         ops.require_device(x)
         return x.long().contiguous()
@@ -229,9 +237,9 @@ class Captioner(nn.Module):
         mask_for = self._mask_source(masks)
         first = []   # small independent problems that share one launch
         if mode != 'seq2seq':
-            fc = self._f32(fc)
+            fc = self._feat(fc)
             B = fc.shape[0]
-            att = self._f32(att).reshape(B, -1, att.shape[-1])
+            att = self._feat(att).reshape(B, -1, att.shape[-1])
             R = att.shape[1]
             P.B, P.R = B, R
             m, sc = mask_for('fc', B, E)
@@ -871,7 +879,7 @@ class Captioner(nn.Module):
         return st
 
     def _graphed_rollout(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T):
-        ins = [self._f32(fc_feats), self._f32(att_feats), cpt_words, senti_words, senti_labels]
+        ins = [self._feat(fc_feats), self._feat(att_feats), cpt_words, senti_words, senti_labels]
         # keyed on the weights' VALUES (every parameter's storage and version, the fused optimizer's epoch): a graph
         # holds no weight-split launches - the planes its warm-up run left on the roll-out stream are valid exactly
         # as long as this key is.  After a weight change the first call runs eagerly there (rebuilding the planes),

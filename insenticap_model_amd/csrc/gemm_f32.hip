@@ -67,7 +67,7 @@ enum { EPI_LINEAR = 0, EPI_LSTM = 1, EPI_VOCAB = 2 };
 struct DevSeg {
     const float *A;
     const float *W;
-    int lda, ldw, K, pad;
+    int lda, ldw, K, a_f16;           // a_f16: A points at _Float16 rows, lda in halfs (isc_seg.a_f16)
     const _Float16 *A_hi, *A_lo;      // caller-provided planes of A ([M,K] contiguous) or null
 };
 
@@ -1279,8 +1279,14 @@ using H3Tile64 = H3Geom<2, 2, 2, 4, false>;
 // The body of gemm_h3_kernel / gemm_h3x_kernel / gemm_h3m_kernel (geometry G).
 // AF32: some activation segment comes as fp32 rows (split after the fragment read); false = every segment has planes,
 // and the per-buffer test is compiled out of the fragment loads (it cost the all-planes decode loop ~5-10 %).
-template <class G, int EPI, bool AF32>
+// AF16 (with AF32; linear epilogue): some activation segment comes as _Float16 rows (DevSeg.a_f16).  Such a value is its
+// own hi and its lo is zero, so the row is staged as it is - one 128-byte line holds 64 k = TWO chunks - into every
+// chunk's buffer (the second touch of a line hits L2; with two buffers the image of chunk c is gone before chunk c + 1
+// runs), the fragment's hi is read from the half of the image row the chunk's parity names, and the al * bh MFMA, which
+// would add exact zeros, is not issued: the result is the fp32-row form's on the up-cast values, bit for bit.
+template <class G, int EPI, bool AF32, bool AF16 = false>
 __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
+    static_assert(!AF16 || (AF32 && EPI == EPI_LINEAR), "f16 rows come next to fp32 rows, in isc_linear_fwd only");
     H3_STAMP_AT(stamp0);
     constexpr int NB = G::NB, NQ = NB / 2;              // NQ groups of two column blocks per chunk
     constexpr int PA = G::PA, ST = G::ST, APW = G::APW, BPW = G::BPW, NBUF = G::NBUF, AHEAD = G::AHEAD;
@@ -1328,10 +1334,22 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
     int cs = 0, ck = 0, segK = 0;
     bool seg_f32 = false;                // the segment has no planes: its fp32 rows are staged (128 B per row and chunk,
     unsigned f32_bufs = 0;               // like a plane row) and split after the fragment read; bit b: buffer b holds fp32
+    bool seg_f16 = false;                // AF16: the segment's rows are f16; bit b of f16_bufs: buffer b holds such a line,
+    unsigned f16_bufs = 0, odd_bufs = 0; // bit b of odd_bufs: its chunk is the line's second half
     auto set_aseg = [&](int si) __attribute__((always_inline)) {
         const DevASeg a = P.ap[si];
         segK = a.K;
         seg_f32 = AF32 && a.hi == nullptr;
+        if constexpr (AF16) {
+            seg_f16 = seg_f32 && P.seg[si].a_f16 != 0;
+            seg_f32 = seg_f32 && !seg_f16;
+            if (seg_f16) {
+#pragma unroll
+                for (int i = 0; i < APW; ++i)
+                    src[i] = reinterpret_cast<const _Float16 *>(P.seg[si].A) + (long long)arow[i] * P.seg[si].lda + aq[i];
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < APW; ++i)
             src[i] = seg_f32 ? reinterpret_cast<const _Float16 *>(P.seg[si].A + (long long)arow[i] * P.seg[si].lda) + aq[i]
@@ -1365,8 +1383,28 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
     auto stage = [&](int buf) __attribute__((always_inline)) {
         const unsigned b = lds0 + buf * ST;
         f32_bufs = (f32_bufs & ~(1u << buf)) | ((seg_f32 ? 1u : 0u) << buf);
+        bool a_staged = false;
+        if constexpr (AF16) {
+            const bool odd = (ck & 32) != 0;                  // (chunk parity restarts with the segment: ck does)
+            f16_bufs = (f16_bufs & ~(1u << buf)) | ((seg_f16 ? 1u : 0u) << buf);
+            odd_bufs = (odd_bufs & ~(1u << buf)) | ((seg_f16 && odd ? 1u : 0u) << buf);
+            if (seg_f16) {
+                // a segment of an odd number of chunks ends on half a line: the lanes of its second half re-read the
+                // first (nobody reads that part of the image) instead of running past the row's K halfs
+                const bool tail = !odd && ck + 32 >= segK;
 #pragma unroll
-        for (int i = 0; i < APW; ++i) dma1(b + (APW * wv + i) * 1024, src[i]);
+                for (int i = 0; i < APW; ++i) {
+                    const _Float16 *p = src[i] - (tail && aq[i] >= 32 ? 32 : 0);
+                    dma1(b + (APW * wv + i) * 1024, p);
+                    if (odd) src[i] += 64;                    // the next line after the pair
+                }
+                a_staged = true;
+            }
+        }
+        if (!a_staged) {
+#pragma unroll
+            for (int i = 0; i < APW; ++i) dma1(b + (APW * wv + i) * 1024, src[i]);
+        }
 #pragma unroll
         for (int i = 0; i < BPW; ++i) dma1(b + PA + (BPW * wv + i) * 1024, src[APW + i]);
         ck += 32;
@@ -1391,9 +1429,22 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
     const int fr = lane & 15, fq = lane >> 4, fsw = (fr >> 1) & 7;
     const int ph = (fq ^ fsw) * 16, pl = ((4 + fq) ^ fsw) * 16;
     h8 ah[2][2], al[2][2], bh[2][2], bl[2][2];          // A: [set][row block]; W: [slot][column block of the group]
+    bool a16[2] = {false, false};                       // AF16: A set s holds an f16 chunk (hi only)
     auto lfragA = [&](int buf, auto setc) __attribute__((always_inline)) {
         constexpr int S = decltype(setc)::value;
         const char *base = lds + buf * ST;
+        if constexpr (AF16) {
+            a16[S] = ((f16_bufs >> buf) & 1u) != 0;
+            if (a16[S]) {
+                const int po = (((int)((odd_bufs >> buf) & 1u) * 4 + fq) ^ fsw) * 16;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    ah[S][i] = *reinterpret_cast<const h8 *>(base + (wm * 32 + i * 16 + fr) * 128 + po);
+                    al[S][i] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int ra = (wm * 32 + i * 16 + fr) * 128;
@@ -1423,7 +1474,10 @@ __device__ __forceinline__ void h3_tile_body(const DevLaunch &L) {
             for (int i = 0; i < 2; ++i) {
                 acc0[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bh[SL][j], acc0[i][Q * 2 + j], 0, 0, 0);
                 acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[S][i], bl[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
-                acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[S][i], bh[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
+                // (an f16 chunk has lo == 0: the third term would add exact zeros.  Guarding the one MFMA keeps the
+                // accumulators in registers; two copies of the loop nest, or of the chunk, spilled 190-580 B per lane)
+                if (!(AF16 && a16[S]))
+                    acc1[i][Q * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[S][i], bh[SL][j], acc1[i][Q * 2 + j], 0, 0, 0);
             }
     };
     // one chunk's MFMAs with the W fragments of group q + 1 read under the MFMAs of group q; `between` runs in front of
@@ -1526,6 +1580,13 @@ __global__ __launch_bounds__(256) void gemm_h3m_kernel(const DevLaunch L) {
     ISC_GATE_RETURN(L);
     rows_kernarg_warm<ROWS_KERNARG_LINES(DevLaunch)>();      // (one batch of scalar loads for the launch descriptor: common.h)
     h3_tile_body<H3Tile64, EPI_LINEAR, AF32>(L);
+}
+
+// The three geometries with f16 activation rows read natively (linear epilogue: isc_linear_fwd with isc_seg.a_f16).
+template <class G>
+__global__ __launch_bounds__(G::THREADS, G::LDS_BYTES <= 65536 ? 2 : 1) void gemm_h3_f16a_kernel(const DevLaunch L) {
+    ISC_GATE_RETURN(L);
+    h3_tile_body<G, EPI_LINEAR, true, true>(L);
 }
 
 // Operand split in front of gemm_h3_kernel: gathers the K-segments of one operand into the two packed f16 planes
@@ -2349,10 +2410,18 @@ static void copy_segs(DevProb &d, const isc_seg *seg, int nseg) {
     d.nseg = nseg;
     for (int s = 0; s < nseg; ++s) {
         d.seg[s].A = seg[s].A; d.seg[s].W = seg[s].W;
-        d.seg[s].lda = seg[s].lda; d.seg[s].ldw = seg[s].ldw; d.seg[s].K = seg[s].K; d.seg[s].pad = 0;
+        d.seg[s].lda = seg[s].lda; d.seg[s].ldw = seg[s].ldw; d.seg[s].K = seg[s].K; d.seg[s].a_f16 = seg[s].a_f16;
         d.seg[s].A_hi = static_cast<const _Float16 *>(seg[s].A_hi);
         d.seg[s].A_lo = static_cast<const _Float16 *>(seg[s].A_lo);
     }
+}
+
+// isc_seg.a_f16: A holds _Float16 rows.  Only isc_linear_fwd on the large split-f16 kernels reads them; every other entry
+// point answers ISC_E_SHAPE in front of any launch (a kernel must never read halfs as floats).
+static bool segs_any_f16(const isc_seg *seg, int nseg) {
+    for (int s = 0; s < nseg && s < ISC_MAX_SEG; ++s)
+        if (seg[s].a_f16) return true;
+    return false;
 }
 
 template <int WM, int WN, int TN, int EPI, bool AKM, bool BKM>
@@ -2505,8 +2574,9 @@ static void finish_tiling(DevLaunch &L, int tile) {
 // ---- split-f16 path (gemm_h3_kernel) ----
 // isc_set_h3_mode: 0 = off, 1 = auto, 2 = large kernels whenever the shapes allow, 3 / 4 = skinny kernel (32 / 64 tiles)
 static std::atomic<int> g_h3_mode{1};
-static std::atomic<long long> g_h3_launches{0}, g_h3x_launches{0};
+static std::atomic<long long> g_h3_launches{0}, g_h3x_launches{0}, g_h3_f16a_launches{0};
 extern "C" long long isc_h3_launches(void) { return g_h3_launches.load(); }
+extern "C" long long isc_h3_f16a_launches(void) { return g_h3_f16a_launches.load(); }
 extern "C" long long isc_h3x_launches(void) { return g_h3x_launches.load(); }
 extern "C" int isc_set_h3_mode(int mode) {
     if (mode >= 0 && mode <= 4) return g_h3_mode.exchange(mode);
@@ -2521,8 +2591,10 @@ extern "C" int isc_set_gemv_rows(int rows) {           // 0 = off; returns the p
 extern "C" long long isc_gemv_launches(void) { return g_gemv_launches.load(); }
 
 // Takes the launch when every problem has <= g_gemv_rows rows and fits the LDS image.  Returns 1 when it went out.
+// (`plan` - here and in try_h3s / try_h3: decide only; returns 1 where the launch would have gone out, launches nothing
+// and leaves the weights scope as it is - isc_linear_f16_native)
 template <int EPI>
-static int try_gemv(DevLaunch &L, hipStream_t st, int &rc) {
+static int try_gemv(DevLaunch &L, hipStream_t st, int &rc, bool plan = false) {
     constexpr int NW = EPI == EPI_VOCAB ? 8 : 4;
     const int rows = g_gemv_rows.load(), mode = g_h3_mode.load();
     if (rows <= 0 || mode > 1 || g_tile_override.load() >= 0) return 0;
@@ -2540,6 +2612,7 @@ static int try_gemv(DevLaunch &L, hipStream_t st, int &rc) {
         if (EPI == EPI_LSTM && (p.H <= 0 || p.N != 4 * p.H)) return 0;
         kmax = K > kmax ? K : kmax;
     }
+    if (plan) return 1;
     for (int i = 0; i < L.nprob; ++i) {
         DevProb &p = L.p[i];
         int nchunk = 0;
@@ -2587,6 +2660,13 @@ static bool h3_any_f32(const DevLaunch &L) {
     return false;
 }
 
+static bool h3_any_f16(const DevLaunch &L) {              // an f16 segment read natively (caller's planes go first)
+    for (int i = 0; i < L.nprob; ++i)
+        for (int s = 0; s < L.p[i].nseg; ++s)
+            if (L.p[i].seg[s].a_f16 && !(L.p[i].seg[s].A_hi && L.p[i].seg[s].A_lo)) return true;
+    return false;
+}
+
 template <class G, int EPI, bool AF32>
 static constexpr auto h3_tile_kernel() {
     if constexpr (std::is_same_v<G, H3Tile128>) return &gemm_h3_kernel<EPI, AF32>;
@@ -2610,6 +2690,26 @@ static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return (int)e;
             attr_set.store(true);
+        }
+    }
+    if (h3_any_f16(L)) {
+        if constexpr (EPI == EPI_LINEAR) {
+            constexpr auto f16_rows = &gemm_h3_f16a_kernel<G>;
+            if constexpr (lds > 65536) {
+                static std::atomic<bool> attr16_set{false};
+                if (!attr16_set.load()) {
+                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(f16_rows),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    if (e != hipSuccess) return (int)e;
+                    attr16_set.store(true);
+                }
+            }
+            hipLaunchKernelGGL(f16_rows, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
+            ISC_LAUNCH_CHECK();
+            ++g_h3_f16a_launches;
+            return ISC_OK;
+        } else {
+            return ISC_E_SHAPE;
         }
     }
     const auto kernel = h3_any_f32(L) ? f32_rows : planes;
@@ -2845,7 +2945,8 @@ struct H3Planner {
 // Plans the planes of every problem inside the caller's workspace, launches the operand split and the GEMM.
 // Returns 1 when the launch went out on this path (rc = its status), 0 when the path does not apply.
 template <int EPI>
-static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0) {
+static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0,
+                  bool plan = false) {
     const int h3_mode = g_h3_mode.load();
     if (h3_mode == 0 || g_tile_override.load() >= 0 || !ws || ((uintptr_t)ws & 255)) return 0;
     long long tiles = 0, need = 0;
@@ -2877,6 +2978,7 @@ static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, 
         for (int i = 0; i < L.nprob; ++i) jobs += 1;
         if (jobs > H3_MAX_JOBS) return 0;
     }
+    if (plan) return 1;
     H3Planner pl(ws, scope);
     for (int i = 0; i < L.nprob; ++i) {
         DevProb &p = L.p[i];
@@ -2895,7 +2997,9 @@ static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, 
         int S = 1;
         // (backward dX contractions only - `transposed` - unless forced: a forward launch keeps ONE summation order at every
         // batch size, so that a ReLU's sign at a pre-activation of ~0 does not depend on how many rows share the launch)
-        if (EPI == EPI_LINEAR && L.nprob == 1 && (L.p[0].N & 3) == 0 && (g_h3_ksplit.load() == 2 || (transposed && g_h3_ksplit.load()))) {
+        // (f16 rows are read in one slice of K: the line pairs of a slice would have to start on an even chunk)
+        if (EPI == EPI_LINEAR && L.nprob == 1 && (L.p[0].N & 3) == 0 && !h3_any_f16(L) &&
+            (g_h3_ksplit.load() == 2 || (transposed && g_h3_ksplit.load()))) {
             DevProb &p = L.p[0];
             const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128);
             const int nblk = p.Kp / 32;
@@ -3065,7 +3169,8 @@ static int launch_h3s_t(const DevLaunch &L, int T, hipStream_t st) {
 // more rows than H3S_MAX_ROWS, or a launch the large split-f16 kernels do better (h3s_pick_tile).
 // Modes 3 / 4 force the 32 x 32 / 64 x 64 tile (tests): without a scope the weight planes then go to the workspace.
 template <int EPI>
-static int try_h3s(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0) {
+static int try_h3s(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0,
+                   bool plan = false) {
     const int mode = g_h3_mode.load();
     if ((mode != 1 && mode != 3 && mode != 4) || g_tile_override.load() >= 0) return 0;
     H3WScope *sc = h3w_scope_of(st);
@@ -3086,6 +3191,7 @@ static int try_h3s(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st,
     if (!T) return 0;                                     // the large kernels' launch
     if (!ws || ((uintptr_t)ws & 255) || need > ws_floats) return 0;   // planes that do not fit the scope go here
     if (L.nprob > H3_MAX_JOBS) return 0;
+    if (plan) return 1;
     int S = 1;
     if constexpr (EPI == EPI_LINEAR) S = h3s_pick_ksplit(L, T, ws_floats - need - 64);
     float *slab = ws + ((ws_floats - 64) & ~63LL);        // slabs from the end of the workspace, planes from its start
@@ -3314,7 +3420,9 @@ static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st) {
     return ISC_OK;
 }
 
-extern "C" int isc_linear_fwd(const isc_linear_problem *pr, int n_prob, void *stream) {
+// isc_linear_fwd.  plan: the dispatch without a launch - returns 1 when the large split-f16 kernels would take these
+// problems (the one path that reads isc_seg.a_f16 segments), 0 when another path would, < 0 for a bad argument.
+static int linear_fwd_run(const isc_linear_problem *pr, int n_prob, void *stream, bool plan) {
     if (!pr) return ISC_E_NULL;
     if (n_prob < 1 || n_prob > 3) return ISC_E_SHAPE;
     DevLaunch L = {};
@@ -3335,10 +3443,12 @@ extern "C" int isc_linear_fwd(const isc_linear_problem *pr, int n_prob, void *st
         d.ldc = q.ldc; d.C = q.C; d.C_pre = q.C_pre; d.accumulate = q.accumulate;
     }
     int rc = ISC_OK;
-    if (try_gemv<EPI_LINEAR>(L, (hipStream_t)stream, rc)) return rc;
-    if (try_h3s<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
+    if (try_gemv<EPI_LINEAR>(L, (hipStream_t)stream, rc, plan)) return plan ? 0 : rc;
+    if (try_h3s<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc, 0, plan)) return plan ? 0 : rc;
     const int S = plan_splitk(L, pr[0].splitk_ws, pr[0].splitk_ws_floats);
-    if (S == 1 && try_h3<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
+    if (S == 1 && try_h3<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc, 0, plan))
+        return plan ? 1 : rc;
+    if (plan) return 0;
     const int tile = S > 1 ? 2 : pick_tile(L, true);
     finish_tiling(L, tile);
     rc = launch_any<EPI_LINEAR, false, false>(L, tile, (hipStream_t)stream);
@@ -3346,10 +3456,36 @@ extern "C" int isc_linear_fwd(const isc_linear_problem *pr, int n_prob, void *st
     return launch_splitk_linear_reduce(L, (hipStream_t)stream);
 }
 
+// What the native form asks of an f16 segment (K % 32 == 0 is check_segs')
+static bool f16_segs_aligned(const isc_linear_problem *pr, int n_prob) {
+    for (int i = 0; i < n_prob; ++i)
+        for (int s = 0; s < pr[i].nseg && s < ISC_MAX_SEG; ++s)
+            if (pr[i].seg[s].a_f16 && ((pr[i].seg[s].lda & 7) || !isc_aligned16(pr[i].seg[s].A))) return false;
+    return true;
+}
+
+extern "C" int isc_linear_f16_native(const isc_linear_problem *pr, int n_prob, void *stream) {
+    if (!pr || n_prob < 1 || n_prob > 3 || !f16_segs_aligned(pr, n_prob)) return 0;
+    return linear_fwd_run(pr, n_prob, stream, true) == 1 ? 1 : 0;
+}
+
+extern "C" int isc_linear_fwd(const isc_linear_problem *pr, int n_prob, void *stream) {
+    bool any16 = false;
+    for (int i = 0; pr && i < n_prob && i < 3; ++i) any16 = any16 || segs_any_f16(pr[i].seg, pr[i].nseg);
+    if (any16) {                       // f16 rows: the large split-f16 kernels or nothing
+        if (!f16_segs_aligned(pr, n_prob)) return ISC_E_ALIGN;
+        const int native = linear_fwd_run(pr, n_prob, stream, true);
+        if (native != 1) return native < 0 ? native : ISC_E_SHAPE;
+    }
+    return linear_fwd_run(pr, n_prob, stream, false);
+}
+
 // Backward-pass contractions on the same kernel (include/insenticap_hip.h: isc_gemm_bwd).
 extern "C" int isc_gemm_bwd(const isc_linear_problem *pr, int n_prob, int layout, void *stream) {
     if (!pr) return ISC_E_NULL;
     if (n_prob < 1 || n_prob > 3 || (layout != ISC_LAYOUT_NN && layout != ISC_LAYOUT_TN)) return ISC_E_SHAPE;
+    for (int i = 0; i < n_prob; ++i)
+        if (segs_any_f16(pr[i].seg, pr[i].nseg)) return ISC_E_SHAPE;          // fp32 operands only
     // dW = sum over segments of A_s^T W_s where some segments have a row count the split-f16 kernels cannot take (K % 32
     // != 0: the once-per-caption block of the att-LSTM's dW has B rows, 80 in the seq2seq unroll) and others are large:
     // two launches - the K % 32 == 0 segments first (split-f16), the rest accumulating on the fp32 tiles - instead of
@@ -3437,6 +3573,7 @@ extern "C" int isc_lstm_fwd(const isc_lstm_problem *q, void *stream) {
     if (!q) return ISC_E_NULL;
     int rc = check_segs(q->seg, q->nseg);
     if (rc) return rc;
+    if (segs_any_f16(q->seg, q->nseg)) return ISC_E_SHAPE;                    // fp32 activations only
     if (!q->c_prev || !q->h_out || !q->c_out) return ISC_E_NULL;
     if ((!q->b_ih || !q->b_hh) && !q->pre) return ISC_E_NULL;       // biases may only be folded into `pre`
     if ((q->b_ih == nullptr) != (q->b_hh == nullptr)) return ISC_E_NULL;

@@ -855,6 +855,46 @@ extern "C" int isc_copy_multi(void *const *dst, const void *const *src, const in
     return ISC_OK;
 }
 
+// ------------------------------------------------------------------ f16 -> fp32 rows
+// What a consumer that cannot read f16 features gets (isc_seg.a_f16): one thread per 8 consecutive columns of a row
+// (one 16-byte load, two 16-byte stores) when pointers and leading dimensions allow, else one thread per element.
+static std::atomic<long long> g_f16_convert_launches{0};
+extern "C" long long isc_f16_convert_launches(void) { return g_f16_convert_launches.load(); }
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void f16_to_f32_kernel(const _Float16 *src, long long ld_src, float *dst, long long ld_dst,
+                                                         long long rows, long long cols) {
+    typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+    const long long per_row = VEC ? cols >> 3 : cols;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * per_row) return;
+    const long long r = i / per_row, c = i - r * per_row;
+    if (VEC) {
+        const h8v v = *reinterpret_cast<const h8v *>(src + r * ld_src + c * 8);
+        float *o = dst + r * ld_dst + c * 8;
+        *reinterpret_cast<float4 *>(o) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+        *reinterpret_cast<float4 *>(o + 4) = make_float4((float)v[4], (float)v[5], (float)v[6], (float)v[7]);
+    } else {
+        dst[r * ld_dst + c] = (float)src[r * ld_src + c];
+    }
+}
+
+extern "C" int isc_f16_to_f32(const void *src, int64_t ld_src, float *dst, int64_t ld_dst, int64_t rows, int64_t cols,
+                              void *stream) {
+    if (!src || !dst) return ISC_E_NULL;
+    if (rows <= 0 || cols <= 0 || ld_src < cols || ld_dst < cols) return ISC_E_SHAPE;
+    const bool vec = (cols & 7) == 0 && (ld_src & 7) == 0 && (ld_dst & 3) == 0 && isc_aligned16(src) && isc_aligned16(dst);
+    const long long n = rows * (vec ? cols >> 3 : cols);
+    if (n > (1LL << 31) * 255) return ISC_E_SHAPE;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const _Float16 *s = static_cast<const _Float16 *>(src);
+    if (vec) hipLaunchKernelGGL(f16_to_f32_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, s, ld_src, dst, ld_dst, rows, cols);
+    else hipLaunchKernelGGL(f16_to_f32_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, s, ld_src, dst, ld_dst, rows, cols);
+    ISC_LAUNCH_CHECK();
+    ++g_f16_convert_launches;
+    return ISC_OK;
+}
+
 // ------------------------------------------------------------------ log-softmax apply
 __global__ __launch_bounds__(256) void logsoftmax_apply_kernel(float *logits, long long ld, int M, int V,
                                                                const float *pmax, const float *psum,

@@ -45,7 +45,34 @@ def _caps(caps, max_seq_len, pad_index, caption_width=None):
 def _feats(xs):
     if len(xs) and hasattr(xs[0], 'row') and hasattr(xs[0], 'tensor'):     # rows of a DeviceFeatureStore: gathered on the device
         return RowGather(xs[0].tensor, torch.from_numpy(np.asarray([x.row for x in xs], dtype=np.int64)))
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(xs, dtype=np.float32)))
+    # float16 items (a store written with dtype=float16) stay float16; a mixed or any other batch is fp32, as ever
+    f16 = len(xs) > 0 and all(getattr(x, 'dtype', None) == np.float16 for x in xs)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(xs, dtype=np.float16 if f16 else np.float32)))
+
+
+def _feature_dtype(dtype):
+    """np.float32 / np.float16 for the `dtype=` of the stores (numpy or torch spelling)."""
+    if dtype in (torch.float16, torch.float32):
+        return np.float16 if dtype == torch.float16 else np.float32
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float16), np.dtype(np.float32)):
+        raise ValueError('feature stores hold float32 or float16, not %s' % (dt,))
+    return dt.type
+
+
+def _as_feature(array, dtype):
+    """`array` as `dtype` (np.float32 / np.float16).  A finite value that float16 would round to +-inf raises: the
+    split-f16 engine's domain ends at 65504 and an inf must never be STORED silently."""
+    if dtype == np.float32 or getattr(array, 'dtype', None) == np.float16:
+        return np.asarray(array, dtype=dtype)
+    src = np.asarray(array)
+    with np.errstate(over='ignore'):
+        out = src.astype(np.float16)
+    bad = np.isinf(out) & np.isfinite(src)
+    if bad.any():
+        raise ValueError('float16 features: max |x| = %g of the values beyond 65504 would be stored as inf - scale the '
+                         'features or keep float32' % float(np.abs(src[bad]).max()))
+    return out
 
 
 class RowGather:
@@ -141,7 +168,7 @@ def create_collate_fn(name, pad_index=0, max_seq_len=17, num_concepts=5, num_sen
 
 
 class FeatureStore:
-    """fn -> fp32 feature array, backed by ONE `.npy` file opened as a memory map plus `<path>.index.json`
+    """fn -> fp32 (or, written with dtype=np.float16, float16) feature array, backed by ONE `.npy` file opened as a memory map plus `<path>.index.json`
     ({fn: row}).  Stands where the reference passes an h5 file name (`fc_feats` / `att_feats` arguments of its
     Dataset classes, dataloader.py:164-178): `store[fn]` returns what `h5py.File(path)[fn][:]` returned there.
     A plain dict {fn: ndarray} is accepted by the datasets as well."""
@@ -154,9 +181,10 @@ class FeatureStore:
             self.index = json.load(f)
 
     @staticmethod
-    def write(path, fns, array):
+    def write(path, fns, array, dtype=np.float32):
+        """dtype=np.float16 halves the file (and every copy behind it); a value it cannot hold raises ValueError."""
         import json
-        array = np.ascontiguousarray(array, dtype=np.float32)
+        array = np.ascontiguousarray(_as_feature(array, _feature_dtype(dtype)))
         assert len(fns) == array.shape[0] and len(set(fns)) == len(fns)
         np.save(path, array)
         if not path.endswith('.npy'):
@@ -166,16 +194,17 @@ class FeatureStore:
         return path
 
     @classmethod
-    def from_h5(cls, h5_path, npy_path, fns=None):
+    def from_h5(cls, h5_path, npy_path, fns=None, dtype=np.float32):
         """One-off conversion of a reference feature file (an h5 dataset per image, dataloader.py:171-178) into the
         memory-mapped `.npy` + index pair; returns the opened store.  Needs h5py (H5FeatureStore says so)."""
         src = H5FeatureStore(h5_path)
         fns = list(fns if fns is not None else src.keys())
         first = src[fns[0]]
         path = npy_path if npy_path.endswith('.npy') else npy_path + '.npy'
-        out = np.lib.format.open_memmap(path, mode='w+', dtype=np.float32, shape=(len(fns),) + first.shape)
+        dtype = _feature_dtype(dtype)
+        out = np.lib.format.open_memmap(path, mode='w+', dtype=dtype, shape=(len(fns),) + first.shape)
         for i, fn in enumerate(fns):            # row by row: the set does not have to fit in host memory
-            out[i] = src[fn]
+            out[i] = _as_feature(src[fn], dtype)
         out.flush()
         del out
         import json
@@ -246,7 +275,8 @@ class _Row:
 
 
 class DeviceFeatureStore:
-    """All features of a dataset RESIDENT ON THE DEVICE: fn -> row of one [N, ...] fp32 tensor in HBM.  The reference reads
+    """All features of a dataset RESIDENT ON THE DEVICE: fn -> row of one [N, ...] fp32 tensor in HBM (`dtype=torch.float16`:
+    a float16 tensor, half the bytes; inference reads it as it is, training converts a batch to fp32 in front of its prologue).  The reference reads
     an image's features from an h5 file per item (dataloader.py:164-178) and a 512-image RL batch of 6 x 6 x 2048 regions is
     151 MB to read, stack, pin and copy - 55-76 ms on the host per iteration, against 22.5 ms for the iteration itself
     (tools/rl_loop_probe.py).  An MI355X has 288 GB: the 113 k training images of COCO are 34 GB at 6 x 6 regions (160 GB
@@ -263,24 +293,26 @@ class DeviceFeatureStore:
         self.index, self.tensor = index, tensor
 
     @classmethod
-    def from_arrays(cls, fns, array, device, chunk_rows=4096):
+    def from_arrays(cls, fns, array, device, chunk_rows=4096, dtype=torch.float32):
         assert len(fns) == len(array) and len(set(fns)) == len(fns)
         device = torch.device(device)
-        first = np.asarray(array[0], dtype=np.float32)
-        out = torch.empty((len(fns),) + first.shape, dtype=torch.float32, device=device)
-        pin = torch.empty((min(chunk_rows, len(fns)),) + first.shape, dtype=torch.float32).pin_memory()
+        np_dtype = _feature_dtype(dtype)
+        t_dtype = torch.float16 if np_dtype == np.float16 else torch.float32
+        first = np.asarray(array[0])
+        out = torch.empty((len(fns),) + first.shape, dtype=t_dtype, device=device)
+        pin = torch.empty((min(chunk_rows, len(fns)),) + first.shape, dtype=t_dtype).pin_memory()
         for lo in range(0, len(fns), chunk_rows):                 # through one kept pinned chunk: no 34 GB host copy
             hi = min(lo + chunk_rows, len(fns))
-            np.stack([np.asarray(array[i], dtype=np.float32) for i in range(lo, hi)], out=pin.numpy()[:hi - lo])
+            np.stack([_as_feature(array[i], np_dtype) for i in range(lo, hi)], out=pin.numpy()[:hi - lo])
             out[lo:hi].copy_(pin[:hi - lo], non_blocking=True)
             torch.cuda.current_stream(device).synchronize()       # (the chunk buffer is reused)
         return cls({fn: i for i, fn in enumerate(fns)}, out)
 
     @classmethod
-    def from_store(cls, store, device, fns=None):
+    def from_store(cls, store, device, fns=None, dtype=torch.float32):
         store = _store(store)
         fns = list(fns if fns is not None else store.keys())
-        return cls.from_arrays(fns, [store[fn] for fn in fns], device)
+        return cls.from_arrays(fns, [store[fn] for fn in fns], device, dtype=dtype)
 
     def __getitem__(self, fn):
         return _Row(self.tensor, self.index[fn])

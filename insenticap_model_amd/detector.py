@@ -22,6 +22,11 @@ from .ops import OutOfDomain
 from .rewards import RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward
 
 
+def _helper_input(feats):
+    """The stock-torch helper nets (fp32 parameters) read fp32: float16 features get an fp32 view at their call site."""
+    return feats if feats.dtype == torch.float32 else feats.float()
+
+
 class Detector(nn.Module):
     MAX_BATCHES_PER_CALL = 500      # decoder.py:65
 
@@ -320,7 +325,7 @@ class Detector(nn.Module):
 
     def _image_sentiments(self, fns, att_feats):
         if not self.cache_image_sentiments:
-            return self.senti_detector.sample(att_feats, self.senti_threshold)[0].detach()
+            return self.senti_detector.sample(_helper_input(att_feats), self.senti_threshold)[0].detach()
         key = (self.senti_threshold, tuple(att_feats.shape[1:]), att_feats.dtype) + \
             tuple((q.data_ptr(), q._version) for q in self.senti_detector.parameters())
         if key != self._senti_cache_key:                 # weights reloaded / threshold changed
@@ -328,7 +333,7 @@ class Detector(nn.Module):
         cache = self._senti_cache
         if all(fn in cache for fn in fns):
             return ops.upload([cache[fn] for fn in fns], torch.int64, att_feats.device)
-        labels = self.senti_detector.sample(att_feats, self.senti_threshold)[0].detach()
+        labels = self.senti_detector.sample(_helper_input(att_feats), self.senti_threshold)[0].detach()
         for fn, lab in zip(fns, labels.tolist()):
             cache[fn] = lab
         return labels
@@ -339,7 +344,7 @@ class Detector(nn.Module):
         att_feats = att_feats.unsqueeze(0)
         # the label stays on the device until the search is queued: the category name (a host read) is looked up behind the
         # search's own read-back instead of draining the device between the two (tools/eval_loop_probe.py)
-        senti_label, _, _ = self.senti_detector.sample_device(att_feats, self.senti_threshold)
+        senti_label, _, _ = self.senti_detector.sample_device(_helper_input(att_feats), self.senti_threshold)
         captions, _ = self.captioner.sample(fc_feats, att_feats, sentis_tensor, senti_label, beam_size,
                                             decoding_constraint, self.max_seq_len)
         return captions, self.senti_detector.names(senti_label)

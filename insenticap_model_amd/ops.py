@@ -270,10 +270,11 @@ def _fill_segs(dst, segs):
         A, W = sg[0], sg[1]
         assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
         assert A.shape[1] == W.shape[1], (A.shape, W.shape)
-        assert A.dtype == torch.float32 and W.dtype == torch.float32
+        assert A.dtype in (torch.float32, torch.float16) and W.dtype == torch.float32
         s = dst[i]
         s.A, s.W = A.data_ptr(), W.data_ptr()
         s.lda, s.ldw, s.K = A.stride(0), W.stride(0), A.shape[1]
+        s.a_f16 = int(A.dtype == torch.float16)      # float16 rows (isc_seg.a_f16): linear_problem / linear_fwd only
         planes = sg[2] if len(sg) > 2 else None      # optional [2, M, K] f16 planes of A (isc_seg.A_hi / A_lo)
         if planes is not None:
             assert planes.dtype == torch.float16 and planes.is_contiguous() and planes.shape == (2,) + tuple(A.shape)
@@ -437,6 +438,7 @@ def linear_problem(segs, out, bias0=None, bias1=None, bias2=None, relu=False, ke
     """out[M,N] = act(sum_s A_s W_s^T + bias0 + bias1) [* keep_mask * mask_scale]."""
     p = LinearProblem()
     _fill_segs(p.seg, segs)
+    p.f16_segs = [(i, sg[0]) for i, sg in enumerate(segs) if sg[0].dtype == torch.float16]
     p.nseg = len(segs)
     p.M, p.N = out.shape
     assert segs[0][0].shape[0] == p.M and segs[0][1].shape[0] == p.N
@@ -454,10 +456,40 @@ def linear_problem(segs, out, bias0=None, bias1=None, bias2=None, relu=False, ke
     return p
 
 
+def f16_to_f32(x, out=None):
+    """fp32 copy of a float16 matrix [rows, cols] (unit column stride) by the library's kernel (isc_f16_to_f32)."""
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel():
+        check(_lib.load().isc_f16_to_f32(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0],
+                                         x.shape[1], stream()), 'isc_f16_to_f32')
+    return out
+
+
+def f16_convert_launches():
+    return _lib.load().isc_f16_convert_launches()
+
+
+def h3_f16a_launches():
+    return _lib.load().isc_h3_f16a_launches()
+
+
 def linear_fwd(problems):
     lib = _lib.load()
     _attach_ws(problems[0], torch.cuda.current_device())
     arr = (LinearProblem * len(problems))(*problems)
+    if any(getattr(q, 'f16_segs', None) for q in problems) and \
+            not lib.isc_linear_f16_native(arr, len(problems), stream()):
+        # float16 activations on a launch the large split-f16 kernels will not take (few rows, exact engine, a K or a
+        # stride they cannot stage ...): an fp32 copy for this launch - explicit, counted (isc_f16_convert_launches)
+        for q in problems:
+            for i, A in getattr(q, 'f16_segs', None) or ():
+                A32 = f16_to_f32(A)
+                q.keep = getattr(q, 'keep', []) + [A32]          # (lives as long as the problem)
+                q.seg[i].A, q.seg[i].lda, q.seg[i].a_f16 = A32.data_ptr(), A32.stride(0), 0
+            q.f16_segs = []
+        arr = (LinearProblem * len(problems))(*problems)
     e0 = TIMER.begin()
     check(lib.isc_linear_fwd(arr, len(problems), stream()), 'isc_linear_fwd')
     if e0 is not None:
@@ -1165,7 +1197,7 @@ def private_stream(device):
     """A torch.cuda.Stream that no other owner inside this package holds (and that is not the caller's current stream).
     torch hands out the 32 pool streams of a device round robin, so the 33rd Stream() IS the first again - and
     everything kept per stream here (split-K workspace, weight planes, weights-scope slot) would be shared with it.
-    Owners: train_graph.XETrainGraph (two), a captioner's roll-out stream, the eager training step's side stream."""
+    Owners: train_graph.XETrainGraph (two), a captioner's roll-out and beam-search streams, the eager training step's side stream."""
     device = torch.device(device)
     idx = device.index if device.index is not None else torch.cuda.current_device()
     cur = torch.cuda.current_stream(idx).cuda_stream
