@@ -197,6 +197,10 @@ typedef struct {
     int64_t tab_ids_stride;
     float *splitk_ws;           /* optional split-K workspace, see isc_linear_problem */
     int64_t splitk_ws_floats;
+    /* pre_div > 1: `pre` holds one row per IMAGE of M / pre_div images ([M / pre_div, 4H]) and row m adds
+     * pre[m / pre_div] - the captions drawn for one image share its fc / label term (isc_step_plan.row_div).
+     * M % pre_div == 0; 0 or 1 = one row of `pre` per row. */
+    int32_t pre_div, _pad2;
 } isc_lstm_problem;
 
 int isc_lstm_fwd(const isc_lstm_problem *prob_host, void *stream);
@@ -254,6 +258,12 @@ typedef struct {
      * (cache-resident) replace the per-caption [B,M,.] copies that were streamed from HBM every step. */
     const int64_t *row_ids;
     int64_t row_ids_ld;
+    /* row_div > 1: the rows come in groups of row_div that attend to the SAME features - P, V, q2 and row_ids hold one
+     * entry per group (`rows / row_div` of them: the n captions drawn for one image share its regions) and row b reads
+     * entry b / row_div; q, out, alpha_out and the planes stay per row.  One workgroup then serves up to 8 rows of a
+     * group from ONE pass over the group's P and V rows (attn_scan_group_kernel), with per row the arithmetic - and the
+     * bits - of the plain launch on the expanded tensors.  rows % row_div == 0; 0 or 1 = the plain launch. */
+    int32_t row_div, _pad;
 } isc_scan_problem;
 
 int isc_attn_scan_fwd(const isc_scan_problem *probs_host, int n_prob, int B, void *stream);
@@ -480,6 +490,14 @@ typedef struct {
      * and the classifier then run once over all rows, the two h-projections as two problems of one launch and the two
      * scans as the two problems of one isc_attn_scan_fwd launch.  fp32 rows only (no state planes).  0 = off. */
     int32_t pair_rows_c, _pad2;
+    /* row_div > 1: `rows` = images x row_div decode rows, row r belongs to image r / row_div (the captions drawn per
+     * image by a sampled roll-out), and the step-invariant tensors of an image - pre1, att_p, att_e, label_w, words_ids
+     * (per-row words_p / words_e as well) - hold one entry per IMAGE, as documented for isc_rows_ext.row_div.
+     * isc_step_fwd hands it to the att-LSTM (isc_lstm_problem.pre_div) and to both scans (isc_scan_problem.row_div);
+     * everything else of the step is per row as always.  rows % row_div == 0; not with pair_rows_c and not with the
+     * fused gate scan (gate_Gc / gate_Gs) of the general kernels.  isc_rows_step_fwd ignores it: the few-row step
+     * takes isc_rows_ext.row_div.  0 or 1 = off. */
+    int32_t row_div, _pad3;
 } isc_step_plan;
 
 int isc_step_fwd(const isc_step_plan *plan_host, void *stream);

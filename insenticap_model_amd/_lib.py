@@ -37,7 +37,8 @@ class LstmProblem(C.Structure):
                 ('hdrop_out', C.c_void_p), ('h_hi', C.c_void_p), ('h_lo', C.c_void_p),
                 ('pre', C.c_void_p), ('tab', C.c_void_p),
                 ('tab_ids', C.c_void_p), ('tab_ids_stride', C.c_int64),
-                ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)]
+                ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64),
+                ('pre_div', C.c_int32), ('_pad2', C.c_int32)]
 
 
 class ScanProblem(C.Structure):
@@ -45,7 +46,7 @@ class ScanProblem(C.Structure):
                 ('w', C.c_void_p), ('w_bias', C.c_void_p), ('R', C.c_int32), ('A', C.c_int32),
                 ('D', C.c_int32), ('rows', C.c_int32), ('out', C.c_void_p), ('alpha_out', C.c_void_p),
                 ('alpha_ld', C.c_int64), ('out_hi', C.c_void_p), ('out_lo', C.c_void_p),
-                ('row_ids', C.c_void_p), ('row_ids_ld', C.c_int64)]
+                ('row_ids', C.c_void_p), ('row_ids_ld', C.c_int64), ('row_div', C.c_int32), ('_pad', C.c_int32)]
 
 
 class ScanBwdProblem(C.Structure):
@@ -82,7 +83,7 @@ class StepPlan(C.Structure):
                  ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)] +
                 _f('h1_prev_hi h1_prev_lo h2_prev_hi h2_prev_lo h1_hi h1_lo h2_hi h2_lo '
                    'v_hi v_lo s_hi s_lo f_hi f_lo words_ids', C.c_void_p) + [('words_ids_ld', C.c_int64)] +
-                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c _pad2', C.c_int32))
+                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c _pad2 row_div _pad3', C.c_int32))
 
 
 class StepBwdPlan(C.Structure):

@@ -55,6 +55,7 @@ class _Pro:
     label_e = None   # [B,W]   sentiment-label embedding (added to every xt)
     label_w = None   # [B,A]   label2word(label_e): step-invariant term of the senti attention
     pre1 = None      # [B,4H]  fc_e W_fc^T + label_e W_x^T + b_ih + b_hh: step-invariant att-LSTM input
+    row_div = 1      # decode rows per image (forward_rl captions_per_image): everything above is per IMAGE
     tab = None       # [V,4H]  relu(Emb) W_x^T (inference only): replaces the word-embedding K-segment
     gate_Gc = None   # [B*R,A] att_e through cont2att.weight (few-row inference: isc_attn_scan_gate_fwd)
     gate_Gs = None   # [B*M,A] / [V,A] words_e through senti2att.weight
@@ -472,6 +473,7 @@ class Captioner(nn.Module):
             pl.words_ids, pl.words_ids_ld = P.words_ids.data_ptr(), P.words_ids.stride(0)
         ws = ops.splitk_ws(self._dev)
         pl.splitk_ws, pl.splitk_ws_floats = ws.data_ptr(), ws.numel()
+        pl.row_div = P.row_div if P.row_div > 1 else 0       # rows = images x row_div: P holds one entry per image
         return pl
 
     def _step(self, p, P, ws, xt, h_cur, c_cur, h_nxt, c_nxt, alpha_c=None, alpha_s=None, beta=None,
@@ -557,7 +559,8 @@ class Captioner(nn.Module):
         if P.tab is None:
             segs.insert(1, (xt, Wih[:, H + E:]))
         ops.lstm_fwd(segs, None, None, c_cur[0], h_nxt[0], c_nxt[0], gates_out=save.get('g1'),
-                     pre=P.pre1, tab=P.tab, tab_ids=tok if P.tab is not None else None, h_planes=pn(0))
+                     pre=P.pre1, tab=P.tab, tab_ids=tok if P.tab is not None else None, h_planes=pn(0),
+                     pre_div=P.row_div)
         h1 = h_nxt[0]
         has_cont, has_senti = P.att_e3 is not None, P.words_e3 is not None
         probs, scans = [], []
@@ -567,14 +570,15 @@ class Captioner(nn.Module):
             scans.append(ops.scan_problem(P.att_p3, P.att_e3, ws['qa'],
                                           p['attention.cont_att.att_alpha.weight'],
                                           p['attention.cont_att.att_alpha.bias'], ws['v'], alpha_c,
-                                          out_planes=wp('v')))
+                                          out_planes=wp('v'), row_div=P.row_div))
         if has_senti:
             probs.append(ops.linear_problem([(h1, p['attention.senti_att.h2word.weight'], pn(0))], ws['qw'],
                                             p['attention.senti_att.h2word.bias']))
             scans.append(ops.scan_problem(P.words_p3, P.words_e3, ws['qw'],
                                           p['attention.senti_att.word_alpha.weight'],
                                           p['attention.senti_att.word_alpha.bias'], ws['s'], alpha_s,
-                                          q2=P.label_w, out_planes=wp('s'), row_ids=P.words_ids))
+                                          q2=P.label_w, out_planes=wp('s'), row_ids=P.words_ids,
+                                          row_div=P.row_div))
         gate = has_cont and has_senti
         if gate:   # the h2att(h1) term of the gate rides in the same launch as the two projections
             probs.append(ops.linear_problem([(h1, p['attention.h2att.weight'], pn(0))], ws['z'],
@@ -805,7 +809,7 @@ class Captioner(nn.Module):
 
     def forward_rl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, sample_max,
                    _replay=None, _masks=None, temperature=1.0, top_k=0, top_p=1.0, generator=None,
-                   return_sampling_logprobs=False, _uniforms=None):
+                   return_sampling_logprobs=False, _uniforms=None, captions_per_image=1):
         """Greedy (`sample_max=1`) or sampled roll-out (captioner.py:290-349) with the whole T-step loop
         enqueued without a host sync; `_replay` [B,T] forces the raw draws (parity tests).
         Sampled roll-outs (`sample_max=0`) take the sampling controls `temperature` (> 0), `top_k` (0: off) and `top_p`
@@ -813,7 +817,15 @@ class Captioner(nn.Module):
         and `generator` for the uniforms; `_uniforms` [B,T] float32 replaces the drawn uniforms (tests, the counterpart of
         `_replay`).  `seq_logprobs` stays the MODEL's log-probability of the drawn token; `return_sampling_logprobs=True`
         appends a fourth tensor, the log-probability under the distribution that was sampled.  With the default controls
-        the call is today's plain multinomial roll-out, bit for bit.  Inference only for now."""
+        the call is today's plain multinomial roll-out, bit for bit.  Inference only for now.
+        `captions_per_image=n` > 1 draws n captions per image without repeating the image: the five inputs hold one
+        entry per image, [I, ...]; everything step-invariant (embedded regions, their projection, the att-LSTM's hoisted
+        term) is computed and kept once per image, and the decode runs on I*n rows that share it (the scan loads a
+        region row once for an image's rows).  `_uniforms`, `_replay`, the returned tensors, the sampling log-probs and
+        the attention-weight attributes are [I*n, ...], row i*n + j = draw j of image i - the layout of the same call on
+        inputs repeated with `repeat_interleave(n, 0)`; `fc_feats` / `cpt_feats` stay [I, ...].  Sampled roll-outs only
+        (n equal greedy captions would be a mistake), inference only (no gradients, eval mode, no `_masks`)."""
+        n_cap = self._check_captions_per_image(captions_per_image, sample_max, _masks)
         temperature, top_k, top_p = ops.check_sample_filter(temperature, top_k, top_p)
         filtered = temperature != 1.0 or 0 < top_k < self.vocab_size or top_p < 1.0
         if sample_max and (filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
@@ -828,7 +840,7 @@ class Captioner(nn.Module):
                 filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
             filt = self._sample_filter(temperature, top_k, top_p, generator, _uniforms, return_sampling_logprobs)
             out = self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0, None,
-                                _masks, filt)
+                                _masks, filt, group=n_cap)
             return out[:3] + ((filt['slp'],) if return_sampling_logprobs else ())
         if return_sampling_logprobs or _uniforms is not None or generator is not None:
             raise ValueError('generator / return_sampling_logprobs / _uniforms are not available with gradients enabled')
@@ -844,7 +856,26 @@ class Captioner(nn.Module):
                 and self._features_in_domain(fc_feats, att_feats)):     # (beyond the domain: eager, exact engine)
             return self._graphed_rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len)
         return self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len,
-                             sample_max, _replay, _masks)[:3]
+                             sample_max, _replay, _masks, group=n_cap)[:3]
+
+    def _check_captions_per_image(self, n, sample_max, masks):
+        """forward_rl's `captions_per_image`, checked before anything touches the device.  Returns it as an int."""
+        if isinstance(n, bool) or not hasattr(n, '__index__'):
+            raise ValueError('captions_per_image must be an integer >= 1, got %r' % (n,))
+        n = int(n)
+        if n < 1:
+            raise ValueError('captions_per_image must be an integer >= 1, got %r' % (n,))
+        if n == 1:
+            return 1
+        if sample_max:
+            raise ValueError('captions_per_image > 1 applies to sampled roll-outs (sample_max=0): %d greedy captions of '
+                             'one image would be identical' % n)
+        if self.training or self._needs_grad():
+            raise ValueError('captions_per_image > 1 is inference-only: call it in eval mode under torch.no_grad() (the '
+                             'backward of the grouped attention scan is not built)')
+        if masks is not None:
+            raise ValueError('captions_per_image > 1 does not take _masks (dropout masks belong to training)')
+        return n
 
     def _sample_filter(self, temperature=1.0, top_k=0, top_p=1.0, generator=None, uniforms=None, want_slp=False):
         """The sampling controls of one sampled roll-out as `_rollout` takes them (`filt`); after the call `filt['slp']`
@@ -989,18 +1020,18 @@ class Captioner(nn.Module):
         return gb
 
     def _rollout(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                 masks, filt=None):
+                 masks, filt=None, group=1):
         self._p()                                  # raises on CPU parameters before anything touches the device
         if not self._features_in_domain(fc_feats, att_feats):
             # features beyond the split-f16 domain: the reference decodes whatever its encoder produced
             # (captioner.py:198-214, 294-315) - so does this call, on the exact-fp32 engine
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                          replay, masks, filt)
+                                          replay, masks, filt, group)
         # frozen weights for prologue + loop: split them once per call - or, with unchanged weights, once per run of calls
         with ops.h3_weights_scope(self._dev, key=self._weights_key()):
             return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                      replay, masks, filt)
+                                      replay, masks, filt, group)
 
     # ------------------------------------------------------------------ operand domain of the split-f16 engine
     SPLIT_F16_MAX = 65504.0
@@ -1066,24 +1097,29 @@ class Captioner(nn.Module):
                           'features to keep the fast engine.' % what)
 
     def _rollout_impl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                      masks, filt=None):
+                      masks, filt=None, group=1):
+        """group > 1 (forward_rl captions_per_image): the inputs and the prologue's tensors hold one entry per image, the
+        state, the workspaces and the outputs `group` rows per image; the step plan's row_div ties the two together.
+        Such a call stays on the general kernels at every row count (no fused gate tables, no few-row step)."""
         p = self._p()
         arm = ops.TIMER.arm_step          # bench.py: time the kernels of ONE step (-1: the prologue)
         ops.TIMER.armed, ops.TIMER.phase = (arm == -1), 'prologue'
         # frozen weights + enough token-steps: the relu(Emb) W_x^T table pays for itself (21 GFLOP once)
-        n_rows = fc_feats.shape[0]
+        n_rows = fc_feats.shape[0] * group
         want = False
         if not torch.is_grad_enabled() or not any(q.requires_grad for q in self.parameters()):
             want = 'build' if n_rows * T >= self.vocab_size // 4 else 'cached'
         P = self._prologue(p, 'rl', fc_feats, att_feats, cpt_words, senti_words, senti_labels, masks,
                            want_table=want, words_table=bool(want) and getattr(self, 'words_table', True),
-                           gate_rows=n_rows if want else 0)
+                           gate_rows=n_rows if want and group == 1 else 0)
         ops.TIMER.armed, ops.TIMER.phase = False, 'step'
-        B, V = P.B, self.vocab_size
+        P.row_div = group
+        B, V = P.B * group, self.vocab_size
         H, Wd = self.att_lstm.hidden_size, self.settings['word_emb_dim']
         # a handful of captions, no sampling: the few-row kernels (statistics per isc_rows_stats_tile columns)
         rows_ext = None
-        if (sample_max or replay is not None) and masks is None and not self.training and self._rows_step_ok(B, P):
+        if ((sample_max or replay is not None) and masks is None and not self.training and group == 1
+                and self._rows_step_ok(B, P)):
             rows_ext = _lib.RowsExt()
             rows_ext.stats_tile = ops.rows_stats_tile(V)
         planes = rows_ext is None and getattr(self, 'state_planes', True)
@@ -1237,12 +1273,14 @@ class Captioner(nn.Module):
 
     @torch.no_grad()
     def sample_captions(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, n=1, max_seq_len=16,
-                        temperature=1.0, top_k=0, top_p=1.0, generator=None, _uniforms=None):
+                        temperature=1.0, top_k=0, top_p=1.0, generator=None, _uniforms=None, share_image=False):
         """`n` sampled captions per image under the sampling controls of `forward_rl` (temperature / top_k / top_p):
         every image's inputs are repeated `n` times on the device (rows i*n ... i*n + n - 1 belong to image i) and ONE
         sampled roll-out draws all I*n captions.  Returns (captions[I][n], id_sequences[I][n]); the strings are built as
         `sample_batch` builds them (words up to <EOS>, <EOS> itself left out of the string and kept in the ids).
-        `_uniforms` [I*n, max_seq_len]: test hook, as in `forward_rl`."""
+        `_uniforms` [I*n, max_seq_len]: test hook, as in `forward_rl`.
+        `share_image=True` repeats nothing: the roll-out runs with `captions_per_image=n` on the I images' inputs (same
+        rows, same layout; `fc_feats` / `cpt_feats` are then [I, ...])."""
         n = int(n)
         if n < 1:
             raise ValueError('n must be >= 1, got %r' % (n,))
@@ -1252,9 +1290,14 @@ class Captioner(nn.Module):
 
         def rep(x):
             return None if x is None else x.repeat_interleave(n, dim=0)
-        seq, _, masks = self.forward_rl(rep(fc_feats), rep(att_feats), rep(cpt_words), rep(senti_words),
-                                        rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
-                                        top_p=top_p, generator=generator, _uniforms=_uniforms)
+        if share_image and n > 1:
+            seq, _, masks = self.forward_rl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0,
+                                            temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
+                                            _uniforms=_uniforms, captions_per_image=n)
+        else:
+            seq, _, masks = self.forward_rl(rep(fc_feats), rep(att_feats), rep(cpt_words), rep(senti_words),
+                                            rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
+                                            top_p=top_p, generator=generator, _uniforms=_uniforms)
         seq_h, len_h = seq.cpu().tolist(), masks.sum(1).long().cpu().tolist()      # the call's one host read
         i2w, eos = self.idx2word, self.eos_id
         captions, ids = [], []

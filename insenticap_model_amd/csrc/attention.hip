@@ -50,6 +50,54 @@ __device__ __forceinline__ float4 ld4(const float4 *p, bool nt) {
     return *p;
 }
 
+// ---- the per-row arithmetic of the forward scans: ONE definition of the contracted expressions (a lane's score sum, the
+// weighted accumulation) for attn_scan_kernel and attn_scan_group_kernel, so that both contract them the same way - the
+// grouped kernel's rows come out bit for bit as the plain one's (tests/test_gpu_group_rollout.py holds them together).
+// The query load and the softmax have nothing to contract (adds, max, exp, one multiply); attn_scan_kernel keeps its own
+// spelling of those statements - moved behind a call its loops compiled to other code - and the grouped kernel's are here.
+// query vector of one row: q (+ q2), the float4s lane, lane + 64, ... of A; lanes past A hold 0
+template <int NA>
+__device__ __forceinline__ void scan_load_query(const float *q, const float *q2, int na4, int lane, float4 (&qv)[NA]) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int a4 = lane + 64 * i;
+        if (a4 < na4) {
+            qv[i] = reinterpret_cast<const float4 *>(q)[a4];
+            if (q2) {
+                const float4 t = reinterpret_cast<const float4 *>(q2)[a4];
+                qv[i].x += t.x; qv[i].y += t.y; qv[i].z += t.z; qv[i].w += t.w;
+            }
+        } else {
+            qv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+// a lane's share of w . tanh(P[r,:] + q): its float4s in ascending order, x y z w inside each
+template <int NA>
+__device__ __forceinline__ float scan_lane_score(const float4 (&p)[NA], const float4 (&qv)[NA], const float4 (&wv)[NA]) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {            // lanes past A carry w = 0
+        acc += wv[i].x * isc_tanh(p[i].x + qv[i].x);
+        acc += wv[i].y * isc_tanh(p[i].y + qv[i].y);
+        acc += wv[i].z * isc_tanh(p[i].z + qv[i].z);
+        acc += wv[i].w * isc_tanh(p[i].w + qv[i].w);
+    }
+    return acc;
+}
+// maximum and 1 / sum exp of a row's R scores in LDS (folded in ascending order by whoever calls), then one weight
+__device__ __forceinline__ void scan_softmax_stats(const float *sc, int R, float &mx, float &inv) {
+    mx = -INFINITY;
+    for (int r = 0; r < R; ++r) mx = fmaxf(mx, sc[r]);
+    float z = 0.f;
+    for (int r = 0; r < R; ++r) z += __expf(sc[r] - mx);
+    inv = 1.0f / z;
+}
+__device__ __forceinline__ float scan_alpha(float e, float mx, float inv) { return __expf(e - mx) * inv; }
+__device__ __forceinline__ void scan_axpy4(float4 &o, float a, const float4 &v) {
+    o.x += a * v.x; o.y += a * v.y; o.z += a * v.z; o.w += a * v.w;
+}
+
 template <int NA, bool NT>  // float4 per lane along A: A <= 256*NA; NT: per-caption rows by non-temporal loads
 __global__ __launch_bounds__(256) void attn_scan_kernel(const DevScanLaunch L) {
     ISC_GATE_RETURN(L);
@@ -108,16 +156,7 @@ __global__ __launch_bounds__(256) void attn_scan_kernel(const DevScanLaunch L) {
         }
         float acc[3];
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            acc[u] = 0.f;
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {            // lanes past A carry w = 0
-                acc[u] += wv[i].x * isc_tanh(p[u][i].x + qv[i].x);
-                acc[u] += wv[i].y * isc_tanh(p[u][i].y + qv[i].y);
-                acc[u] += wv[i].z * isc_tanh(p[u][i].z + qv[i].z);
-                acc[u] += wv[i].w * isc_tanh(p[u][i].w + qv[i].w);
-            }
-        }
+        for (int u = 0; u < 3; ++u) acc[u] = scan_lane_score<NA>(p[u], qv, wv);
 #pragma unroll
         for (int u = 0; u < 3; ++u) acc[u] = half_sum(acc[u]);
 #pragma unroll
@@ -165,9 +204,7 @@ __global__ __launch_bounds__(256) void attn_scan_kernel(const DevScanLaunch L) {
                     a[u] = r < R ? sc[rc] : 0.f;
                 }
 #pragma unroll
-                for (int u = 0; u < 6; ++u) {       // ascending region order, as before
-                    o.x += a[u] * v[u].x; o.y += a[u] * v[u].y; o.z += a[u] * v[u].z; o.w += a[u] * v[u].w;
-                }
+                for (int u = 0; u < 6; ++u) scan_axpy4(o, a[u], v[u]);      // ascending region order, as before
             }
             reinterpret_cast<float4 *>(part)[grp * nd4 + d4] = o;
         }
@@ -187,12 +224,219 @@ __global__ __launch_bounds__(256) void attn_scan_kernel(const DevScanLaunch L) {
             for (int r = 0; r < R; ++r) {
                 const float a = sc[r];
                 const float4 v = Vb[(long long)(gather ? rid[r] : r) * nd4 + d4];
-                o.x += a * v.x; o.y += a * v.y; o.z += a * v.z; o.w += a * v.w;
+                scan_axpy4(o, a, v);
             }
             reinterpret_cast<float4 *>(S.out + (long long)b * D)[d4] = o;
             if (S.out_hi) store_planes4(S.out_hi, S.out_lo, b, 4 * d4, D, o);
         }
     }
+}
+
+// ------------------------------------------------------------------ grouped scan (isc_scan_problem.row_div > 1)
+// n captions drawn for one image attend to the SAME regions: P / V (and q2, row_ids) hold one entry per image and rows
+// i*n .. i*n + n - 1 share entry i.  One workgroup per (image, chunk of up to G_MAX of its rows, scan problem) loads every
+// P row and every V row ONCE and scores / weights it for the chunk's rows - the HBM stream of the scan shrinks n-fold
+// (a group of n > G_MAX rows takes several chunks, the last one smaller: the stream shrinks G_MAX-fold).  Per row the
+// arithmetic is attn_scan_kernel's (the shared functions above; same lane layout, same region groups, same ascending
+// combine), so every output is bit for bit what that kernel writes for the expanded inputs.  The per-row state - query
+// float4s, accumulators - sits in statically indexed registers; rows past the chunk's count are skipped by wave-uniform
+// guards.
+#define ISC_SCAN_G_MAX 8
+struct DevScanGroupLaunch {
+    DevScan p[2];
+    int nt;                    // the per-image P / V rows are streamed with non-temporal loads (host decides)
+    const int *gate;           // optional: *gate == 0 -> the launch returns at once (isc_set_stream_gate)
+    int n[2];                  // rows per image (row_div; 1: a plain problem riding in a grouped launch)
+    int chunks[2];             // workgroups per image = ceil(n / GM)
+};
+
+template <int NA, bool NT, int GM>  // GM: rows of one image per workgroup
+__global__ __launch_bounds__(256) void attn_scan_group_kernel(const DevScanGroupLaunch L) {
+    ISC_GATE_RETURN(L);
+    rows_kernarg_warm<ROWS_KERNARG_LINES(DevScanGroupLaunch)>();
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const DevScan &S = L.p[blockIdx.y];
+    const int n = L.n[blockIdx.y], chunks = L.chunks[blockIdx.y];
+    const int img = blockIdx.x / chunks, g0 = (blockIdx.x - img * chunks) * GM;
+    if ((long long)img * n >= S.rows) return;     // (workgroup-uniform: a shorter problem of a two-problem launch)
+    const int G = n - g0 < GM ? n - g0 : GM;       // rows of this chunk
+    const long long b0 = (long long)img * n + g0;  // its first row
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int R = S.R, A = S.A, D = S.D;
+    const int Rp = (R + 3) & ~3;
+    float *sc = smem;                              // [GM][Rp] scores -> alphas
+    float *part = smem + GM * Rp;                  // [GM][ngrp][D] partial weighted sums
+    int *rid = reinterpret_cast<int *>(smem + S.rid_off);
+    const bool gather = S.ids != nullptr;
+    const bool nt = NT && !gather;
+    if (gather) {
+        for (int r = tid; r < R; r += 256) rid[r] = (int)S.ids[(long long)img * S.ids_ld + r];
+        __syncthreads();
+    }
+
+    // ---- phase 1: scores of every region against the chunk's query vectors
+    const int na4 = A >> 2;
+    float4 qv[GM][NA], wv[NA];
+    const float *q2 = S.q2 ? S.q2 + (long long)img * A : nullptr;
+#pragma unroll
+    for (int g = 0; g < GM; ++g)
+        if (g < G) scan_load_query<NA>(S.q + (b0 + g) * A, q2, na4, lane, qv[g]);
+    scan_load_query<NA>(S.w, nullptr, na4, lane, wv);
+    const float4 *Pb = reinterpret_cast<const float4 *>(gather ? S.P : S.P + (long long)img * R * A);
+    const float w_bias = S.w_bias ? S.w_bias[0] : 0.f;
+    for (int r0 = wave; r0 < R; r0 += 12) {        // three regions in flight per wave, as attn_scan_kernel
+        float4 p[3][NA];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int r = r0 + 4 * u;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                const int a4 = lane + 64 * i;
+                const long long pr = (r < R && gather) ? rid[r] : r;
+                p[u][i] = (r < R && a4 < na4) ? ld4(&Pb[pr * na4 + a4], nt) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < GM; ++g) {
+            if (g < G) {
+                float acc[3];
+#pragma unroll
+                for (int u = 0; u < 3; ++u) acc[u] = scan_lane_score<NA>(p[u], qv[g], wv);
+#pragma unroll
+                for (int u = 0; u < 3; ++u) acc[u] = half_sum(acc[u]);
+#pragma unroll
+                for (int u = 0; u < 3; ++u) acc[u] += __shfl_xor(acc[u], 32, 64);
+                if (lane == 0) {
+#pragma unroll
+                    for (int u = 0; u < 3; ++u)
+                        if (r0 + 4 * u < R) sc[g * Rp + r0 + 4 * u] = acc[u] + w_bias;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: softmax per row; wave w takes rows w, w + 4 of the chunk (nobody else touches their scores, and a
+    // wave's LDS accesses complete in order: no barrier between the fold and the overwrite)
+    for (int g = wave; g < G; g += 4) {
+        float *sg = sc + g * Rp;
+        float mx, inv;
+        scan_softmax_stats(sg, R, mx, inv);
+        for (int r = lane; r < R; r += 64) {
+            const float a = scan_alpha(sg[r], mx, inv);
+            sg[r] = a;
+            if (S.alpha_out) S.alpha_out[(b0 + g) * S.alpha_ld + r] = a;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 3: weighted sums - every V row is loaded once for the chunk's rows
+    const int nd4 = D >> 2;
+    const float4 *Vb = reinterpret_cast<const float4 *>(gather ? S.V : S.V + (long long)img * R * D);
+    if (nd4 <= 256) {
+        const int ngrp = 256 / nd4;             // region groups working in parallel
+        const int d4 = tid % nd4, grp = tid / nd4;
+        if (grp < ngrp) {
+            float4 o[GM];
+#pragma unroll
+            for (int g = 0; g < GM; ++g) o[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int r0 = grp; r0 < R; r0 += 6 * ngrp) {
+                float4 v[6];
+                int rc[6];
+#pragma unroll
+                for (int u = 0; u < 6; ++u) {
+                    const int r = r0 + u * ngrp;
+                    rc[u] = r < R ? r : R - 1;
+                    v[u] = ld4(&Vb[(long long)(gather ? rid[rc[u]] : rc[u]) * nd4 + d4], nt);
+                }
+#pragma unroll
+                for (int g = 0; g < GM; ++g) {
+                    if (g < G) {
+#pragma unroll
+                        for (int u = 0; u < 6; ++u)       // ascending region order; rows past R: weight 0
+                            scan_axpy4(o[g], r0 + u * ngrp < R ? sc[g * Rp + rc[u]] : 0.f, v[u]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < GM; ++g)
+                if (g < G) reinterpret_cast<float4 *>(part)[((long long)g * ngrp + grp) * nd4 + d4] = o[g];
+        }
+        __syncthreads();
+        for (int idx = tid; idx < G * nd4; idx += 256) {
+            const int g = idx / nd4, t = idx - g * nd4;
+            const float4 *pg = reinterpret_cast<const float4 *>(part) + (long long)g * ngrp * nd4;
+            float4 s = pg[t];
+            for (int k = 1; k < ngrp; ++k) {
+                const float4 v = pg[k * nd4 + t];
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+            reinterpret_cast<float4 *>(S.out + (b0 + g) * D)[t] = s;
+            if (S.out_hi) store_planes4(S.out_hi, S.out_lo, b0 + g, 4 * t, D, s);
+        }
+    } else {
+        for (int d4 = tid; d4 < nd4; d4 += 256) {
+            float4 o[GM];
+#pragma unroll
+            for (int g = 0; g < GM; ++g) o[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int r = 0; r < R; ++r) {
+                const float4 v = Vb[(long long)(gather ? rid[r] : r) * nd4 + d4];
+#pragma unroll
+                for (int g = 0; g < GM; ++g)
+                    if (g < G) scan_axpy4(o[g], sc[g * Rp + r], v);
+            }
+#pragma unroll
+            for (int g = 0; g < GM; ++g) {
+                if (g < G) {
+                    reinterpret_cast<float4 *>(S.out + (b0 + g) * D)[d4] = o[g];
+                    if (S.out_hi) store_planes4(S.out_hi, S.out_lo, b0 + g, 4 * d4, D, o[g]);
+                }
+            }
+        }
+    }
+}
+
+template <int NA, int GM>
+static void launch_scan_group(const DevScanGroupLaunch &L, dim3 grid, size_t lds, hipStream_t st) {
+    if (L.nt) hipLaunchKernelGGL((attn_scan_group_kernel<NA, true, GM>), grid, dim3(256), lds, st, L);
+    else hipLaunchKernelGGL((attn_scan_group_kernel<NA, false, GM>), grid, dim3(256), lds, st, L);
+}
+
+// isc_attn_scan_fwd with at least one problem of row_div > 1 (arguments already checked there)
+static int scan_group_fwd(const isc_scan_problem *pr, int n_prob, const DevScanLaunch &L0, int maxA, hipStream_t st) {
+    DevScanGroupLaunch L = {};
+    L.gate = L0.gate;
+    // A <= 1024 keeps four float4 per lane and row in registers: half the rows per workgroup there
+    const int GM = maxA > 512 ? ISC_SCAN_G_MAX / 2 : ISC_SCAN_G_MAX;
+    size_t lds = 0;
+    long long streamed = 0, max_wg = 0;
+    for (int i = 0; i < n_prob; ++i) {
+        const isc_scan_problem &q = pr[i];
+        DevScan &d = L.p[i];
+        d = L0.p[i];
+        const int n = q.row_div > 1 ? q.row_div : 1;
+        if (d.rows % n) return ISC_E_SHAPE;
+        L.n[i] = n; L.chunks[i] = (n + GM - 1) / GM;
+        const long long images = d.rows / n, wg = images * L.chunks[i];
+        if (wg > max_wg) max_wg = wg;
+        const size_t Rp = ((size_t)q.R + 3) & ~(size_t)3;
+        const int nd4 = q.D / 4;
+        const size_t part = nd4 <= 256 ? (size_t)(256 / nd4) * q.D : 0;
+        size_t need = (size_t)GM * (Rp + part);
+        d.rid_off = (int)need;
+        if (q.row_ids) need += Rp;
+        if (need > lds) lds = need;
+        if (!q.row_ids) streamed += images * q.R * ((long long)q.A + q.D) * 4;    // per IMAGE: what the launch streams
+    }
+    lds *= sizeof(float);
+    if (lds > 60000 || max_wg > 0x7fffffffLL) return ISC_E_SHAPE;
+    L.nt = streamed > ISC_SCAN_NT_BYTES;
+    dim3 grid((unsigned)max_wg, n_prob);
+    if (maxA <= 256) launch_scan_group<1, ISC_SCAN_G_MAX>(L, grid, lds, st);
+    else if (maxA <= 512) launch_scan_group<2, ISC_SCAN_G_MAX>(L, grid, lds, st);
+    else launch_scan_group<4, ISC_SCAN_G_MAX / 2>(L, grid, lds, st);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
 }
 
 extern "C" int isc_attn_scan_fwd(const isc_scan_problem *pr, int n_prob, int B, void *stream) {
@@ -202,6 +446,7 @@ extern "C" int isc_attn_scan_fwd(const isc_scan_problem *pr, int n_prob, int B, 
     L.gate = isc_stream_gate_(stream);
     int maxA = 0, max_rows = 0;
     size_t lds = 0;
+    bool grouped = false;                                  // a problem with row_div > 1: attn_scan_group_kernel
     for (int i = 0; i < n_prob; ++i) {
         const isc_scan_problem &q = pr[i];
         if (!q.P || !q.V || !q.q || !q.w || !q.out) return ISC_E_NULL;
@@ -224,7 +469,9 @@ extern "C" int isc_attn_scan_fwd(const isc_scan_problem *pr, int n_prob, int B, 
         d.ids = q.row_ids; d.ids_ld = q.row_ids_ld; d.rid_off = (int)need;
         if (q.row_ids) need += ((size_t)q.R + 3) & ~(size_t)3;
         if (need > lds) lds = need;
+        if (q.row_div > 1) grouped = true;
     }
+    if (grouped) return scan_group_fwd(pr, n_prob, L, maxA, (hipStream_t)stream);
     lds *= sizeof(float);
     if (lds > 60000) return ISC_E_SHAPE;
     long long streamed = 0;                                // bytes of per-caption rows (gathered tables are shared)

@@ -83,6 +83,7 @@ struct DevProb {
     const uint8_t *mask;
     float mask_scale;
     int ldc, accumulate;
+    int pre_div;                      // lstm: > 1: `pre` holds one row per pre_div rows (isc_lstm_problem.pre_div)
     float *C, *C_pre;
     // lstm
     const float *c_prev;
@@ -363,7 +364,14 @@ __device__ __forceinline__ void lstm_cells(const DevProb &P, const int (&gm)[NE]
     }
 #pragma unroll
     for (int e = 0; e < NE; ++e) cp[e] = ok[e] ? P.c_prev[(long long)gm[e] * H + unit] : 0.f;
-    if (has_pre) {
+    if (has_pre && P.pre_div > 1) {      // one row of `pre` per image (uniform branch; one division per row)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const long long pm = ok[e] ? (unsigned)gm[e] / (unsigned)P.pre_div : 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[e][k] = ok[e] ? P.pre[pm * 4 * H + k * H + unit] : 0.f;
+        }
+    } else if (has_pre) {
 #pragma unroll
         for (int e = 0; e < NE; ++e)
 #pragma unroll
@@ -1090,7 +1098,16 @@ __device__ __forceinline__ void epi_lstm_frag16(const DevProb &P, f32x4 (&acc)[2
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             cp[r] = ok[r] ? *reinterpret_cast<const float2 *>(P.c_prev + (long long)gm[r] * H + u0) : make_float2(0.f, 0.f);
-        if (has_pre) {
+        if (has_pre && P.pre_div > 1) {  // one row of `pre` per image (uniform branch; one division per row)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long pm = ok[r] ? (unsigned)gm[r] / (unsigned)P.pre_div : 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    q[r][k] = ok[r] ? *reinterpret_cast<const float2 *>(P.pre + pm * 4 * H + k * H + u0)
+                                    : make_float2(0.f, 0.f);
+            }
+        } else if (has_pre) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -3580,6 +3597,7 @@ extern "C" int isc_lstm_fwd(const isc_lstm_problem *q, void *stream) {
     if (q->tab && !q->tab_ids) return ISC_E_NULL;
     if (q->M <= 0 || q->H <= 0 || (q->H % 32) != 0) return ISC_E_SHAPE;
     if (q->h_keep_mask && !q->hdrop_out) return ISC_E_NULL;
+    if (q->pre_div > 1 && (!q->pre || q->M % q->pre_div)) return ISC_E_SHAPE;
     DevLaunch L = {};
     L.nprob = 1;
     L.gate = isc_stream_gate_(stream);
@@ -3592,6 +3610,7 @@ extern "C" int isc_lstm_fwd(const isc_lstm_problem *q, void *stream) {
     if ((q->h_hi == nullptr) != (q->h_lo == nullptr)) return ISC_E_NULL;
     d.h_hi = static_cast<_Float16 *>(q->h_hi); d.h_lo = static_cast<_Float16 *>(q->h_lo);
     d.pre = q->pre; d.tab = q->tab; d.tab_ids = q->tab_ids; d.tab_ids_stride = q->tab_ids_stride;
+    d.pre_div = q->pre_div > 1 ? q->pre_div : 1;
     if (try_gemv<EPI_LSTM>(L, (hipStream_t)stream, rc)) return rc;
     if (try_h3s<EPI_LSTM>(L, q->splitk_ws, q->splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
     const int S = plan_splitk(L, q->splitk_ws, q->splitk_ws_floats);

@@ -30,6 +30,9 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
     const int rows_c = pair ? p->pair_rows_c : rows, rows_s = pair ? rows - p->pair_rows_c : rows;
     const long long off_s = pair ? p->pair_rows_c : 0;           // first sentiment row inside the step's row block
     if (pair && (p->s != p->v + off_s * E || p->gate_Gc || p->gate_Gs)) return ISC_E_SHAPE;
+    // captions per image (isc_step_plan.row_div): the image's tensors hold one entry per image
+    const int row_div = p->row_div > 1 ? p->row_div : 1;
+    if (row_div > 1 && (rows % row_div || pair || p->gate_Gc || p->gate_Gs)) return ISC_E_SHAPE;
     const int ld1 = H + E + W, ld2 = E + H;
     // f16 planes of the recurrent state (split-f16 path): all eight or none
     const bool planes = p->h1_prev_hi && p->h1_prev_lo && p->h2_prev_hi && p->h2_prev_lo && p->h1_hi && p->h1_lo &&
@@ -54,6 +57,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
         l.h_hi = PL(p->h1_hi); l.h_lo = PL(p->h1_lo);
         l.c_prev = p->c1_prev; l.h_out = p->h1; l.c_out = p->c1; l.gates_out = p->g1;
         l.pre = p->pre1; l.tab = p->tab; l.tab_ids = p->tok; l.tab_ids_stride = p->tok_stride;
+        l.pre_div = row_div;
         l.splitk_ws = p->splitk_ws; l.splitk_ws_floats = p->splitk_ws_floats;
         RET(isc_lstm_fwd(&l, stream));
     }
@@ -83,7 +87,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
             x.P = p->att_p; x.V = p->att_e; x.q = p->qa; x.w = p->w_alpha_c; x.w_bias = p->b_alpha_c;
             x.R = p->R; x.A = A; x.D = E; x.out = p->v; x.alpha_out = p->alpha_c; x.alpha_ld = p->alpha_c_ld;
             x.out_hi = PW(p->v_hi); x.out_lo = PW(p->v_lo);
-            x.rows = rows_c;
+            x.rows = rows_c; x.row_div = row_div;
         }
         if (has_s) {
             isc_scan_problem &x = sc[n++];
@@ -92,7 +96,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
             x.alpha_ld = p->alpha_s_ld;
             x.out_hi = PW(p->s_hi); x.out_lo = PW(p->s_lo);
             x.row_ids = p->words_ids; x.row_ids_ld = p->words_ids_ld;
-            x.rows = rows_s;
+            x.rows = rows_s; x.row_div = row_div;
         }
         if (fused_gate) {
             isc_scan_gate_args g = {};

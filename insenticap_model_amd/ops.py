@@ -499,8 +499,9 @@ def linear_fwd(problems):
 
 
 def lstm_fwd(segs, b_ih, b_hh, c_prev, h_out, c_out, gates_out=None, h_keep_mask=None,
-             mask_scale=1.0, hdrop_out=None, pre=None, tab=None, tab_ids=None, h_planes=None):
-    """h_planes: optional [2, M, H] f16 tensor receiving the split-f16 planes of h_out (for consumers' segments)."""
+             mask_scale=1.0, hdrop_out=None, pre=None, tab=None, tab_ids=None, h_planes=None, pre_div=1):
+    """h_planes: optional [2, M, H] f16 tensor receiving the split-f16 planes of h_out (for consumers' segments).
+    pre_div > 1: `pre` is [M / pre_div, 4H], one row per image, and row m adds pre[m // pre_div]."""
     lib = _lib.load()
     p = LstmProblem()
     _fill_segs(p.seg, segs)
@@ -509,8 +510,9 @@ def lstm_fwd(segs, b_ih, b_hh, c_prev, h_out, c_out, gates_out=None, h_keep_mask
     assert c_prev.is_contiguous() and h_out.is_contiguous() and c_out.is_contiguous()
     p.b_ih, p.b_hh = ptr(b_ih), ptr(b_hh)
     if pre is not None:
-        assert pre.is_contiguous() and pre.shape == (p.M, 4 * p.H)
-        p.pre = pre.data_ptr()
+        pre_div = max(int(pre_div), 1)
+        assert pre.is_contiguous() and p.M % pre_div == 0 and pre.shape == (p.M // pre_div, 4 * p.H)
+        p.pre, p.pre_div = pre.data_ptr(), pre_div
     if tab is not None:
         assert tab.is_contiguous() and tab.shape[1] == 4 * p.H and tab_ids.dtype == torch.int64
         p.tab, p.tab_ids, p.tab_ids_stride = tab.data_ptr(), tab_ids.data_ptr(), tab_ids.stride(0)
@@ -692,11 +694,13 @@ def _planes_ptrs(planes, like):
     return planes_ptrs(planes)
 
 
-def scan_problem(P, V, q, w, w_bias, out, alpha_out=None, q2=None, out_planes=None, row_ids=None):
+def scan_problem(P, V, q, w, w_bias, out, alpha_out=None, q2=None, out_planes=None, row_ids=None, row_div=1):
     """P [B,R,A], V [B,R,D] contiguous; q/q2 [B,A]; w [A] (or [1,A]); out [B,D];
     alpha_out: [B,R] view with unit inner stride (row stride arbitrary).
     row_ids (gather mode): int64 [B,R]; P / V are then tables [n,A] / [n,D] and region r of row b is their row
-    row_ids[b,r]."""
+    row_ids[b,r].
+    row_div > 1 (isc_scan_problem.row_div): P, V, q2 and row_ids hold one entry per image, [B / row_div, ...], and row b
+    of q / out / alpha_out reads entry b // row_div."""
     s = ScanProblem()
     assert P.is_contiguous() and V.is_contiguous() and q.is_contiguous() and out.is_contiguous()
     s.P, s.V, s.q, s.q2, s.w = P.data_ptr(), V.data_ptr(), q.data_ptr(), ptr(q2), w.data_ptr()
@@ -712,6 +716,11 @@ def scan_problem(P, V, q, w, w_bias, out, alpha_out=None, q2=None, out_planes=No
     if alpha_out is not None:
         assert alpha_out.stride(1) == 1
         s.alpha_out, s.alpha_ld = alpha_out.data_ptr(), alpha_out.stride(0)
+    row_div = max(int(row_div), 1)
+    if row_div > 1:
+        per_image = (row_ids if row_ids is not None else P).shape[0]
+        assert q.shape[0] == per_image * row_div and (q2 is None or q2.shape[0] == per_image)
+        s.row_div = row_div
     return s
 
 
@@ -722,7 +731,8 @@ def attn_scan_fwd(problems, B):
     check(lib.isc_attn_scan_fwd(arr, len(problems), B, stream()), 'isc_attn_scan_fwd')
     if e0 is not None:
         # algorithmic bytes: P and V streamed once per row (B*2*R*E*4 for the content scan)
-        nb = sum(4.0 * B * q.R * (q.A + q.D) for q in problems)
+        # (a grouped problem streams them once per image)
+        nb = sum(4.0 * B / max(q.row_div, 1) * q.R * (q.A + q.D) for q in problems)
         TIMER.end(e0, 'attn_scan[' + '+'.join('%dx%dx%d' % (B, q.R, q.A) for q in problems) + ']', 0.0, nb)
 
 
