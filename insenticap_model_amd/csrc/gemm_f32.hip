@@ -4,7 +4,7 @@
 //     backward launches alike - the large tiles gemm_h3_kernel (128 x 128) / gemm_h3x_kernel (256 x 128) /
 //     gemm_h3m_kernel (64 x 128), the skinny tiles gemm_h3s_kernel (32 x 32, 64 x 64, 32 x 128 vocabulary; K split over
 //     the waves of a workgroup and, for long contractions, over workgroups), h3_split_kernel for the weight planes
-//     (and both operands of the TN layout); dispatch in try_h3s / try_h3 / try_h3_tn further down.
+//     (and both operands of the TN layout); dispatch in h3s_plan / h3_plan / try_h3_tn further down.
 //
 //   acc[M,N] = sum_s A_s[M,K_s] * W_s[N,K_s]^T          (s = up to 4 K-segments)
 //
@@ -2364,7 +2364,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_rows_kernel(const DevLaunch L) {
             wave_vocab_tile128(P, m, tile, v, lane);
         }
     } else {
-        const int KS = P.ksplit;                         // 1, 2 or 4 (try_gemv)
+        const int KS = P.ksplit;                         // 1, 2 or 4 (gemv_run)
         const int qpw = NW / KS;                         // quads per workgroup
         const int qw = wave / KS, ks = wave - qw * KS;   // this wave: quad qw of the tile, k-slice ks
         const int quad = tile * qpw + qw;
@@ -2441,20 +2441,29 @@ static bool segs_any_f16(const isc_seg *seg, int nseg) {
     return false;
 }
 
+// A kernel launched with more than 64 KB of dynamic LDS has its limit raised once (k1: a second kernel under the same
+// flag).  `done` is the call site's own flag; idempotent: a race only repeats the same call.
+template <class K>
+static int lds_attr_once(std::atomic<bool> &done, size_t bytes, K k0, K k1 = nullptr) {
+    if (bytes <= 65536 || done.load()) return ISC_OK;
+    for (K k : {k0, k1}) {
+        if (!k) continue;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    done.store(true);
+    return ISC_OK;
+}
+
 template <int WM, int WN, int TN, int EPI, bool AKM, bool BKM>
 static int launch_cfg(const DevLaunch &L, hipStream_t st) {
     constexpr int BM = 32 * WM, BN = 32 * TN * WN;
     constexpr size_t k_bytes = (size_t)2 * (Tile<BM, AKM>::SIZE + Tile<BN, BKM>::SIZE) * sizeof(float);
     constexpr size_t c_bytes = (size_t)BM * (BN + 4) * sizeof(float);
     constexpr size_t lds = k_bytes > c_bytes ? k_bytes : c_bytes;
-    static std::atomic<bool> attr_set{false};  // idempotent: a race only repeats the same call
-    if (!attr_set.load() && lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void *>(&gemm_kernel<WM, WN, TN, EPI, AKM, BKM>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set.store(true);
-    }
+    static std::atomic<bool> attr_set{false};
+    if (int rc = lds_attr_once(attr_set, lds, &gemm_kernel<WM, WN, TN, EPI, AKM, BKM>)) return rc;
     hipLaunchKernelGGL((gemm_kernel<WM, WN, TN, EPI, AKM, BKM>), dim3(L.total_tiles), dim3(256), lds, st, L);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
@@ -2473,15 +2482,8 @@ static int launch_f32_dma(const DevLaunch &L, hipStream_t st) {
     static_assert(EPI == EPI_LINEAR || !std::is_same_v<G, F32TileMD>, "the 64-row kernel has the linear epilogue only");
     constexpr size_t lds = G::LDS_BYTES;       // XL 147456: one workgroup per CU; LD 65536: two; MD 49152: three
     constexpr auto kernel = f32_dma_kernel<G, EPI>();
-    if constexpr (lds > 65536) {
-        static std::atomic<bool> attr_set{false};  // idempotent: a race only repeats the same call
-        if (!attr_set.load()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            attr_set.store(true);
-        }
-    }
+    static std::atomic<bool> attr_set{false};
+    if (int rc = lds_attr_once(attr_set, lds, kernel)) return rc;
     hipLaunchKernelGGL(kernel, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
@@ -2509,6 +2511,13 @@ static int launch_any(const DevLaunch &L, int tile, hipStream_t st) {
     if (tile == 0) return launch_cfg<4, 1, 4, EPI, AKM, BKM>(L, st);
     if (tile == 1) return launch_cfg<2, 2, 2, EPI, AKM, BKM>(L, st);
     return launch_cfg<1, 4, 1, EPI, AKM, BKM>(L, st);
+}
+
+// bm x bn output tiles, summed over the problems of a launch
+static long long count_tiles(const DevLaunch &L, int bm, int bn) {
+    long long t = 0;
+    for (int i = 0; i < L.nprob; ++i) t += (long long)((L.p[i].M + bm - 1) / bm) * ((L.p[i].N + bn - 1) / bn);
+    return t;
 }
 
 // Tile shape choice by a small cost model.  The most loaded CU works through n = ceil(blocks / 256)
@@ -2546,10 +2555,7 @@ static int pick_tile(const DevLaunch &L, bool allow_xl, bool nt = true, bool use
         const int t = order[k];
         if (t == 3 && !allow_xl) continue;
         if (t == 4 && !(nt && use_ld)) continue;
-        long long blocks = 0;
-        for (int i = 0; i < L.nprob; ++i)
-            blocks += (long long)((L.p[i].M + kTileBM[t] - 1) / kTileBM[t]) * ((L.p[i].N + 127) / 128);
-        const long long n = (blocks + 255) / 256;
+        const long long n = (count_tiles(L, kTileBM[t], 128) + 255) / 256;
         const double cost = (double)n * kTileBM[t] / eff[t][n >= 3 ? 2 : (int)n - 1];
         if (cost < best_cost * 0.97) { best_cost = cost; best = t; }
     }
@@ -2607,29 +2613,36 @@ extern "C" int isc_set_gemv_rows(int rows) {           // 0 = off; returns the p
 }
 extern "C" long long isc_gemv_launches(void) { return g_gemv_launches.load(); }
 
-// Takes the launch when every problem has <= g_gemv_rows rows and fits the LDS image.  Returns 1 when it went out.
-// (`plan` - here and in try_h3s / try_h3: decide only; returns 1 where the launch would have gone out, launches nothing
-// and leaves the weights scope as it is - isc_linear_f16_native)
+// Every forward path is written as a pair: `*_plan` holds the path's conditions and nothing else - it launches nothing,
+// writes nothing into the launch and leaves the weights scope as it is - and returns what the launch needs; `*_run`
+// takes that answer and launches.  route_nt() strings the pairs together, isc_linear_f16_native asks the plans alone.
+
+// The matrix-vector kernels take the launch when every problem has <= g_gemv_rows rows and fits the LDS image.
+// Returns the longest contraction of the launch (it sizes the LDS image), 0 when the path does not apply.
 template <int EPI>
-static int try_gemv(DevLaunch &L, hipStream_t st, int &rc, bool plan = false) {
-    constexpr int NW = EPI == EPI_VOCAB ? 8 : 4;
+static int gemv_plan(const DevLaunch &L) {
     const int rows = g_gemv_rows.load(), mode = g_h3_mode.load();
     if (rows <= 0 || mode > 1 || g_tile_override.load() >= 0) return 0;
-    int start = 0, kmax = 0;
+    int kmax = 0;
     for (int i = 0; i < L.nprob; ++i) {
-        DevProb &p = L.p[i];
+        const DevProb &p = L.p[i];
         if (p.M > rows || p.ksplit > 1) return 0;
-        int K = 0, nchunk = 0;
+        int K = 0;
         for (int s = 0; s < p.nseg; ++s) {
             if ((p.seg[s].K & 3) || (p.seg[s].lda & 3) || (p.seg[s].ldw & 3)) return 0;
             K += p.seg[s].K;
-            nchunk += (p.seg[s].K + 255) >> 8;
         }
         if (K > GEMV_MAX_K) return 0;
         if (EPI == EPI_LSTM && (p.H <= 0 || p.N != 4 * p.H)) return 0;
         kmax = K > kmax ? K : kmax;
     }
-    if (plan) return 1;
+    return kmax;          // > 0 where the path applies: check_segs has turned K <= 0 away
+}
+
+template <int EPI>
+static int gemv_run(DevLaunch &L, int kmax, hipStream_t st) {
+    constexpr int NW = EPI == EPI_VOCAB ? 8 : 4;
+    int start = 0;
     for (int i = 0; i < L.nprob; ++i) {
         DevProb &p = L.p[i];
         int nchunk = 0;
@@ -2646,21 +2659,15 @@ static int try_gemv(DevLaunch &L, hipStream_t st, int &rc, bool plan = false) {
     }
     L.total_tiles = start;
     const size_t lds = ((size_t)GEMV_MAX_ROWS * kmax + (EPI == EPI_VOCAB ? GEMV_MAX_ROWS * 128 : NW * 32)) * sizeof(float);
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemv_rows_kernel<EPI, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(((size_t)GEMV_MAX_ROWS * GEMV_MAX_K + GEMV_MAX_ROWS * 128) * sizeof(float)));
-        if (e != hipSuccess) { rc = (int)e; return 1; }
-        attr_set.store(true);
-    }
+    static std::atomic<bool> attr_set{false};                     // (the limit of the largest image, once)
+    if (int rc = lds_attr_once(attr_set, ((size_t)GEMV_MAX_ROWS * GEMV_MAX_K + GEMV_MAX_ROWS * 128) * sizeof(float),
+                               &gemv_rows_kernel<EPI, NW>))
+        return rc;
     hipLaunchKernelGGL((gemv_rows_kernel<EPI, NW>), dim3(L.total_tiles), dim3(64 * NW), lds, st, L);
-    rc = ISC_OK;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = (int)e;
-    for (int i = 0; i < L.nprob; ++i) L.p[i].ksplit = 0;
+    for (int i = 0; i < L.nprob; ++i) L.p[i].ksplit = 0;          // (the kernel has its copy; a failed launch counts too)
     ++g_gemv_launches;
-    return 1;
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
 }
 
 #define H3_MIN_TILES 160
@@ -2668,7 +2675,37 @@ static int try_gemv(DevLaunch &L, hipStream_t st, int &rc, bool plan = false) {
 // (tests / A-B runs: 0 keeps long contractions on few large tiles in one slice of K)
 static std::atomic<int> g_h3_ksplit{1};
 extern "C" int isc_set_h3_ksplit(int on) { return g_h3_ksplit.exchange(on < 0 ? 0 : (on > 2 ? 2 : on)); }
-static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st);
+
+// The reduce launch behind a K-split launch, by epilogue: sums the slabs in fixed order and finishes the outputs.
+// (every split - the fp32 32-row tile's, the skinny and the large split-f16 kernels' - writes linear-epilogue slabs)
+static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st) {
+    long long mx = 0;
+    for (int i = 0; i < L.nprob; ++i) {
+        const long long n4 = (long long)L.p[i].M * (L.p[i].N >> 2);
+        if (n4 > mx) mx = n4;
+    }
+    hipLaunchKernelGGL(splitk_linear_kernel, dim3((unsigned)((mx + 255) / 256), L.nprob), dim3(256), 0, st, L);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
+template <int EPI>
+static int launch_splitk_reduce(const DevLaunch &L, hipStream_t st) {
+    const DevProb &p = L.p[0];
+    if constexpr (EPI == EPI_LSTM) {          // plain [M, 4H] pre-activation slabs, then the cell update
+        const long long n = (long long)p.M * p.H;
+        hipLaunchKernelGGL(splitk_lstm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, L);
+        ISC_LAUNCH_CHECK();
+        return ISC_OK;
+    } else if constexpr (EPI == EPI_VOCAB) {  // raw [S, M, V] slabs, then the per-128-column statistics: a wave per (row, tile)
+        const long long waves = (long long)p.M * p.ntile_total;
+        hipLaunchKernelGGL(splitk_vocab_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, L);
+        ISC_LAUNCH_CHECK();
+        return ISC_OK;
+    } else {
+        return launch_splitk_linear_reduce(L, st);
+    }
+}
 
 static bool h3_any_f32(const DevLaunch &L) {
     for (int i = 0; i < L.nprob; ++i)
@@ -2697,30 +2734,12 @@ static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
     static_assert(EPI == EPI_LINEAR || !std::is_same_v<G, H3Tile64>, "the 64-row kernel has the linear epilogue only");
     constexpr size_t lds = G::LDS_BYTES;
     constexpr auto planes = h3_tile_kernel<G, EPI, false>(), f32_rows = h3_tile_kernel<G, EPI, true>();
-    if constexpr (lds > 65536) {                                           // one workgroup per CU
-        static std::atomic<bool> attr_set{false};
-        if (!attr_set.load()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(planes),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(f32_rows),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            attr_set.store(true);
-        }
-    }
+    static std::atomic<bool> attr_set{false}, attr16_set{false};           // (above 64 KB: one workgroup per CU)
+    if (int rc = lds_attr_once(attr_set, lds, planes, f32_rows)) return rc;
     if (h3_any_f16(L)) {
         if constexpr (EPI == EPI_LINEAR) {
             constexpr auto f16_rows = &gemm_h3_f16a_kernel<G>;
-            if constexpr (lds > 65536) {
-                static std::atomic<bool> attr16_set{false};
-                if (!attr16_set.load()) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(f16_rows),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (e != hipSuccess) return (int)e;
-                    attr16_set.store(true);
-                }
-            }
+            if (int rc = lds_attr_once(attr16_set, lds, f16_rows)) return rc;
             hipLaunchKernelGGL(f16_rows, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
             ISC_LAUNCH_CHECK();
             ++g_h3_f16a_launches;
@@ -2886,15 +2905,26 @@ static const H3WEntry *h3w_find(const H3WScope *sc, const DevProb &p, int transp
 // measured 173 us: what is exposed is the epilogue's own VALU time, 8-10 us per tile, not the workgroup turnover).
 template <int EPI>
 static int launch_h3_big(DevLaunch &L, hipStream_t st) {
-    long long t256 = 0;
-    for (int i = 0; i < L.nprob; ++i) t256 += (long long)((L.p[i].M + 255) / 256) * ((L.p[i].N + 127) / 128);
-    if (EPI != EPI_VOCAB && t256 >= 224) {        // (round 3: 160 - the three h-projections on this kernel - measured the same)
+    if (EPI != EPI_VOCAB && count_tiles(L, 256, 128) >= 224) {        // (round 3: 160 - the three h-projections on this kernel - measured the same)
         ++g_h3x_launches;
         finish_tiling(L, 3);
         return launch_h3_tile<H3Tile256, EPI>(L, st);
     }
     finish_tiling(L, 4);
     return launch_h3_tile<H3Tile128, EPI>(L, st);
+}
+
+// The activation operand of a split-f16 launch: the caller's per-tensor planes where given; a segment without planes is
+// read as fp32 rows and split in registers after the fragment read (ap.hi == nullptr) - no split launch, no plane copy
+// in memory.  Also sets the packed contraction length.
+static void h3_set_a(DevProb &p) {
+    p.Kp = h3_kp(p);
+    p.nap = p.nseg;
+    for (int s = 0; s < p.nseg; ++s) {
+        const int K = p.seg[s].K;
+        const bool planes = p.seg[s].A_hi && p.seg[s].A_lo;
+        p.ap[s] = DevASeg{planes ? p.seg[s].A_hi : nullptr, planes ? p.seg[s].A_lo : nullptr, 2 * K, K};
+    }
 }
 
 // Operand-split jobs of one launch: add() lays the planes of an operand out in the workspace and queues its job.
@@ -2924,16 +2954,6 @@ struct H3Planner {
         hi = J.hi; lo = J.lo;
         blocks += transposed ? ((rows + 63) / 64) * (k0 >> 5) : (int)(((long long)rows * (k0 >> 3) + 255) / 256);
     }
-    // activation operand: the caller's per-tensor planes where given; a segment without planes is read as fp32 rows
-    // and split in registers after the fragment read (ap.hi == nullptr) - no split launch, no plane copy in memory
-    void add_a(DevProb &p) {
-        p.nap = p.nseg;
-        for (int s = 0; s < p.nseg; ++s) {
-            const int K = p.seg[s].K;
-            const bool planes = p.seg[s].A_hi && p.seg[s].A_lo;
-            p.ap[s] = DevASeg{planes ? p.seg[s].A_hi : nullptr, planes ? p.seg[s].A_lo : nullptr, 2 * K, K};
-        }
-    }
     // weight operand: cached planes if the caller opened a weights scope, else planes in the workspace
     void add_w(const DevProb &p, const _Float16 *&hi, const _Float16 *&lo, int transposed = 0) {
         if (const H3WEntry *e = h3w_find(scope, p, transposed)) { hi = e->hi; lo = e->lo; return; }
@@ -2959,86 +2979,93 @@ struct H3Planner {
     }
 };
 
-// Plans the planes of every problem inside the caller's workspace, launches the operand split and the GEMM.
-// Returns 1 when the launch went out on this path (rc = its status), 0 when the path does not apply.
+// What the large split-f16 kernels need to take a launch (take == false: the path does not apply).
+struct H3Plan {
+    bool take = false, half_tile = false;     // half_tile: the 64-row tile
+    int ksplit = 1;                           // slices of K (> 1: slabs behind the planes in the workspace, then the reduce)
+    long long need = 0;                       // floats of the workspace the weight planes take without a weights scope
+    H3WScope *scope = nullptr;                // the launch stream's weights scope, or null
+};
+
 template <int EPI>
-static int try_h3(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0,
-                  bool plan = false) {
+static H3Plan h3_plan(const DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int transposed) {
+    H3Plan h;
     const int h3_mode = g_h3_mode.load();
-    if (h3_mode == 0 || g_tile_override.load() >= 0 || !ws || ((uintptr_t)ws & 255)) return 0;
-    long long tiles = 0, need = 0;
+    if (h3_mode == 0 || g_tile_override.load() >= 0 || !ws || ((uintptr_t)ws & 255)) return h;
+    const long long tiles = count_tiles(L, 128, 128), tiles64 = count_tiles(L, 64, 128);
+    long long need = 0;
     for (int i = 0; i < L.nprob; ++i) {
         const DevProb &p = L.p[i];
-        if (p.ksplit > 1) return 0;
-        tiles += (long long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+        if (p.ksplit > 1) return h;
         const long long Kp = h3_kp(p);
-        if (Kp > (1 << 20)) return 0;
+        if (Kp > (1 << 20)) return h;
         need += (long long)p.N * Kp + 1024;               // floats: the weight planes (2 x 2 bytes per element) when the
                                                           // stream has no weights scope; activations are never copied
     }
     // linear launches that cannot give every CU a 128-row tile: the 64-row tile, unless it then needs more rounds of
     // the chip than it saves in bytes per workgroup (rounds x (rows + 128 columns) of operand lines per workgroup:
     // [4608 x 512] K=2048 is 288 64-row tiles = two rounds, 97 us, against one round of 144 128-row tiles)
-    long long tiles64 = 0;
-    for (int i = 0; i < L.nprob; ++i) tiles64 += (long long)((L.p[i].M + 63) / 64) * ((L.p[i].N + 127) / 128);
-    const bool half_tile = EPI == EPI_LINEAR && tiles < 256 &&
-                           ((tiles64 + 255) / 256) * 192 < ((tiles + 255) / 256) * 256;
-    H3WScope *scope = h3w_scope_of(st);
+    h.half_tile = EPI == EPI_LINEAR && tiles < 256 && ((tiles64 + 255) / 256) * 192 < ((tiles + 255) / 256) * 256;
+    h.scope = h3w_scope_of(st);
     // inside a weights scope the planes are already there and the skinny kernel has taken what it does better
-    // (try_h3s ran first): whatever is left with a few tiles is still faster here than on the fp32 tiles
-    const long long min_tiles = scope && h3_mode == 1 ? H3_MIN_TILES_SCOPE
-                                                      : (EPI == EPI_LINEAR && tiles < 256 ? H3_MIN_TILES / 2 : H3_MIN_TILES);
-    if (h3_mode != 2 && tiles < min_tiles) return 0;
-    if (need > ws_floats) return 0;
-    {
-        int jobs = 0;
-        for (int i = 0; i < L.nprob; ++i) jobs += 1;
-        if (jobs > H3_MAX_JOBS) return 0;
+    // (h3s_plan came first): whatever is left with a few tiles is still faster here than on the fp32 tiles
+    const long long min_tiles = h.scope && h3_mode == 1 ? H3_MIN_TILES_SCOPE
+                                                        : (EPI == EPI_LINEAR && tiles < 256 ? H3_MIN_TILES / 2 : H3_MIN_TILES);
+    if (h3_mode != 2 && tiles < min_tiles) return h;
+    if (need > ws_floats) return h;
+    if (L.nprob > H3_MAX_JOBS) return h;
+    h.need = need;
+    h.take = true;
+    // a long contraction on few 128 x 128 tiles (one problem, linear epilogue): S slices of K so that the launch fills
+    // the chip's 512 workgroup slots, raw partial tiles to slabs behind the planes in the workspace, then the reduce
+    // (backward dX contractions only - `transposed` - unless forced: a forward launch keeps ONE summation order at every
+    // batch size, so that a ReLU's sign at a pre-activation of ~0 does not depend on how many rows share the launch)
+    // (f16 rows are read in one slice of K: the line pairs of a slice would have to start on an even chunk)
+    if (!h.half_tile && EPI == EPI_LINEAR && L.nprob == 1 && (L.p[0].N & 3) == 0 && !h3_any_f16(L) &&
+        (g_h3_ksplit.load() == 2 || (transposed && g_h3_ksplit.load()))) {
+        const DevProb &p = L.p[0];
+        const int nblk = h3_kp(p) / 32;
+        if (count_tiles(L, 256, 128) < 224 && tiles <= 200 && nblk >= 64) {
+            int S = (int)(512 / tiles);
+            if (S > 8) S = 8;
+            while (S > 1 && nblk / S < 24) --S;
+            const long long used = (need + 255) & ~255LL, slab = (long long)p.M * p.N;
+            while (S > 1 && used + S * slab > ws_floats) --S;
+            h.ksplit = S;
+        }
     }
-    if (plan) return 1;
-    H3Planner pl(ws, scope);
+    return h;
+}
+
+// Lays the weight planes of every problem out (the scope's, or in the caller's workspace), launches the operand split
+// and the GEMM.  Returns the launches' status.
+template <int EPI>
+static int h3_run(DevLaunch &L, const H3Plan &h, float *ws, hipStream_t st, int transposed) {
+    H3Planner pl(ws, h.scope);
     for (int i = 0; i < L.nprob; ++i) {
         DevProb &p = L.p[i];
-        p.Kp = h3_kp(p);
-        pl.add_a(p);
+        h3_set_a(p);
         pl.add_w(p, p.Wh, p.Wl, transposed);
     }
-    rc = pl.launch(st);
-    if (rc) return 1;
-    if (half_tile) {
+    int rc = pl.launch(st);
+    if (rc) return rc;
+    if (h.half_tile) {
         finish_tiling(L, 1);
         rc = launch_h3_tile<H3Tile64, EPI_LINEAR>(L, st);
     } else {
-        // a long contraction on few 128 x 128 tiles (one problem, linear epilogue): S slices of K so that the launch fills
-        // the chip's 512 workgroup slots, raw partial tiles to slabs behind the planes in the workspace, then the reduce
-        int S = 1;
-        // (backward dX contractions only - `transposed` - unless forced: a forward launch keeps ONE summation order at every
-        // batch size, so that a ReLU's sign at a pre-activation of ~0 does not depend on how many rows share the launch)
-        // (f16 rows are read in one slice of K: the line pairs of a slice would have to start on an even chunk)
-        if (EPI == EPI_LINEAR && L.nprob == 1 && (L.p[0].N & 3) == 0 && !h3_any_f16(L) &&
-            (g_h3_ksplit.load() == 2 || (transposed && g_h3_ksplit.load()))) {
+        const int S = h.ksplit;
+        if (S > 1) {
             DevProb &p = L.p[0];
-            const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-            const int nblk = p.Kp / 32;
-            if (t256 < 224 && tiles <= 200 && nblk >= 64) {
-                S = (int)(512 / tiles);
-                if (S > 8) S = 8;
-                while (S > 1 && nblk / S < 24) --S;
-                const long long used = (need + 255) & ~255LL, slab = (long long)p.M * p.N;
-                while (S > 1 && used + S * slab > ws_floats) --S;
-                if (S > 1) {
-                    p.ksplit = S;
-                    p.slab = ws + used;
-                    p.slab_stride = slab;
-                }
-            }
+            p.ksplit = S;
+            p.slab = ws + ((h.need + 255) & ~255LL);
+            p.slab_stride = (long long)p.M * p.N;
         }
         rc = launch_h3_big<EPI>(L, st);
         if (!rc && S > 1) rc = launch_splitk_linear_reduce(L, st);
         if (S > 1) L.p[0].ksplit = 0;
     }
     ++g_h3_launches;
-    return 1;
+    return rc;
 }
 
 // ---- skinny split-f16 path (gemm_h3s_kernel): few-row launches inside a weights scope ----
@@ -3052,18 +3079,18 @@ extern "C" long long isc_h3s_launches(void) { return g_h3s_launches.load(); }
 // (tests / A-B runs: 0 sends vocabulary launches of the skinny path back to gemm_h3s_kernel<EPI_VOCAB>)
 static std::atomic<int> g_h3v_on{1};
 extern "C" int isc_set_h3v(int on) { return g_h3v_on.exchange(on < 0 ? 0 : on); }
+// workgroups up to which a vocabulary launch stays skinny: isc_set_h3v(0) off, (1) on, (n > 1) on with the limit n
+static long long h3s_max_wgs_vocab() {
+    const int v = g_h3v_on.load();
+    return v > 1 ? v : (v == 1 ? 512 : H3S_MAX_WGS_VOCAB);
+}
 
 template <int EPI, int T, int NW = 4>
 static int launch_h3s(const DevLaunch &L, hipStream_t st) {
     // waves x ring slots x (A image + W image): 128 KB for the K-split tiles, 64 KB for the vocabulary projection
     constexpr size_t lds = (size_t)NW * (EPI != EPI_VOCAB && T == 1 && NW == 4 ? 4 : 2) * 8192 * T;
     static std::atomic<bool> attr_set{false};
-    if (lds > 65536 && !attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3s_kernel<EPI, T, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set.store(true);
-    }
+    if (int rc = lds_attr_once(attr_set, lds, &gemm_h3s_kernel<EPI, T, NW>)) return rc;
     hipLaunchKernelGGL((gemm_h3s_kernel<EPI, T, NW>), dim3(L.total_tiles), dim3(64 * NW), lds, st, L);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
@@ -3081,18 +3108,14 @@ static int launch_h3s(const DevLaunch &L, hipStream_t st) {
 #define H3S_MAX_COST 4.6
 template <int EPI>
 static int h3s_pick_tile(const DevLaunch &L, int mode) {
-    long long w1 = 0, w2 = 0;
+    const long long w1 = count_tiles(L, 32, EPI == EPI_VOCAB ? 128 : 32), w2 = count_tiles(L, 64, 64);
     bool wide_ok = EPI != EPI_VOCAB;
-    for (int i = 0; i < L.nprob; ++i) {
-        const DevProb &p = L.p[i];
-        w1 += (long long)((p.M + 31) / 32) * ((p.N + (EPI == EPI_VOCAB ? 127 : 31)) / (EPI == EPI_VOCAB ? 128 : 32));
-        w2 += (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-        if (EPI == EPI_LSTM && (p.H & 15)) wide_ok = false;
-    }
+    for (int i = 0; i < L.nprob; ++i)
+        if (EPI == EPI_LSTM && (L.p[i].H & 15)) wide_ok = false;
     if (mode == 4) return wide_ok ? 2 : 1;
     if (mode == 3) return 1;
     // (with gemm_h3v_kernel up to 512 workgroups = one round at two per CU: M = 160 / 192 roll-outs 1.67 / 1.79 -> 1.63 / 1.78 ms)
-    if (EPI == EPI_VOCAB) return w1 < (g_h3v_on.load() > 1 ? g_h3v_on.load() : g_h3v_on.load() == 1 ? 512 : H3S_MAX_WGS_VOCAB) ? 1 : 0;
+    if (EPI == EPI_VOCAB) return w1 < h3s_max_wgs_vocab() ? 1 : 0;
     const double c1 = (double)((w1 + 255) / 256), c2 = wide_ok ? H3S_WIDE_COST * (double)((w2 + 255) / 256) : 1e30;
     if ((c1 < c2 ? c1 : c2) >= H3S_MAX_COST) return 0;
     return c2 < c1 ? 2 : 1;
@@ -3110,18 +3133,16 @@ static void h3s_tile_problem(DevProb &p, int bm, int bn, int &start, int ksplit 
     start += p.tiles_m * p.tiles_n * ksplit;
 }
 
-static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st);
-
 // Cross-workgroup K split of a skinny linear launch: a long contraction on few tiles (the classifier's dX at B = 128:
 // [2560 x 512] over K = 9984 is 320 wide tiles = 1.25 rounds of ~130 us each) packs the chip better in S slices -
 // cost in k per workgroup-round, as h3s_pick_tile, plus ~1000 for the reduce launch.  S <= 8, >= 16 k-blocks per slice.
 static int h3s_pick_ksplit(const DevLaunch &L, int T, long long slab_floats) {
-    long long w = 0, mn = 0;
+    const long long w = count_tiles(L, 32 * T, 32 * T);
+    long long mn = 0;
     int kp_min = 1 << 30, kp_max = 0;
     for (int i = 0; i < L.nprob; ++i) {
         const DevProb &p = L.p[i];
         if (p.N & 3) return 1;
-        w += (long long)((p.M + 32 * T - 1) / (32 * T)) * ((p.N + 32 * T - 1) / (32 * T));
         mn += (long long)p.M * p.N;
         const int kp = h3_kp(p);
         if (kp < kp_min) kp_min = kp;
@@ -3161,15 +3182,9 @@ static int launch_h3s_t(const DevLaunch &L, int T, hipStream_t st) {
         if (v_ok) {
             const size_t lds = H3V_STAGES * H3V_STAGE_BYTES;
             static std::atomic<bool> attr_set{false};
-            if (lds > 65536 && !attr_set.load()) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3v_kernel<true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_h3v_kernel<false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return (int)e;
-                attr_set.store(true);
-            }
+            if (int rc = lds_attr_once(attr_set, lds, &gemm_h3v_kernel<true>,
+                                       &gemm_h3v_kernel<false>))
+                return rc;
             if (h3_any_f32(L)) hipLaunchKernelGGL((gemm_h3v_kernel<true>), dim3(L.total_tiles), dim3(256), lds, st, L);
             else hipLaunchKernelGGL((gemm_h3v_kernel<false>), dim3(L.total_tiles), dim3(256), lds, st, L);
             ISC_LAUNCH_CHECK();
@@ -3181,48 +3196,53 @@ static int launch_h3s_t(const DevLaunch &L, int T, hipStream_t st) {
     return launch_h3s<EPI, 1>(L, st);
 }
 
-// Returns 1 when the launch went out on the skinny path (rc = its status), 0 when it does not apply: mode off / tile
-// override, no weights scope on this stream in auto mode (the weight planes would have to be rebuilt per launch),
-// more rows than H3S_MAX_ROWS, or a launch the large split-f16 kernels do better (h3s_pick_tile).
+// What the skinny kernels need to take a launch.  T == 0: the path does not apply - mode off / tile override, no weights
+// scope on this stream in auto mode (the weight planes would have to be rebuilt per launch), more rows than
+// H3S_MAX_ROWS, or a launch the large split-f16 kernels do better (h3s_pick_tile).
 // Modes 3 / 4 force the 32 x 32 / 64 x 64 tile (tests): without a scope the weight planes then go to the workspace.
+struct H3sPlan {
+    int T = 0;                                // tile factor: 32 T x 32 T outputs
+    int ksplit = 1;                           // slices of K across workgroups (> 1: slabs, then the reduce)
+    H3WScope *scope = nullptr;                // the launch stream's weights scope, or null
+};
+
 template <int EPI>
-static int try_h3s(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int &rc, int transposed = 0,
-                   bool plan = false) {
+static H3sPlan h3s_plan(const DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, int transposed) {
+    H3sPlan h;
     const int mode = g_h3_mode.load();
-    if ((mode != 1 && mode != 3 && mode != 4) || g_tile_override.load() >= 0) return 0;
-    H3WScope *sc = h3w_scope_of(st);
-    if (!sc && mode == 1) return 0;
+    if ((mode != 1 && mode != 3 && mode != 4) || g_tile_override.load() >= 0) return h;
+    h.scope = h3w_scope_of(st);
+    if (!h.scope && mode == 1) return h;
     long long need = 0;
     for (int i = 0; i < L.nprob; ++i) {
         const DevProb &p = L.p[i];
         // (dX contractions over a vocabulary-sized K - long K, few tiles - also run here above H3S_MAX_ROWS, K-split)
-        if (p.M > (transposed && h3_kp(p) >= 4096 ? H3S_MAX_ROWS_NN : H3S_MAX_ROWS)) return 0;
-        if (EPI == EPI_LSTM && (p.H & 7)) return 0;
+        if (p.M > (transposed && h3_kp(p) >= 4096 ? H3S_MAX_ROWS_NN : H3S_MAX_ROWS)) return h;
+        if (EPI == EPI_LSTM && (p.H & 7)) return h;
         for (int sg = 0; sg < p.nseg; ++sg)
-            if (p.seg[sg].K & 31) return 0;                 // (the backward entry point accepts other K)
+            if (p.seg[sg].K & 31) return h;                 // (the backward entry point accepts other K)
         const long long Kp = h3_kp(p);
-        if (Kp > (1 << 20)) return 0;
+        if (Kp > (1 << 20)) return h;
         need += (long long)p.N * Kp + 256;
     }
     const int T = h3s_pick_tile<EPI>(L, mode);
-    if (!T) return 0;                                     // the large kernels' launch
-    if (!ws || ((uintptr_t)ws & 255) || need > ws_floats) return 0;   // planes that do not fit the scope go here
-    if (L.nprob > H3_MAX_JOBS) return 0;
-    if (plan) return 1;
-    int S = 1;
-    if constexpr (EPI == EPI_LINEAR) S = h3s_pick_ksplit(L, T, ws_floats - need - 64);
+    if (!T) return h;                                     // the large kernels' launch
+    if (!ws || ((uintptr_t)ws & 255) || need > ws_floats) return h;   // planes that do not fit the scope go here
+    if (L.nprob > H3_MAX_JOBS) return h;
+    h.T = T;
+    if constexpr (EPI == EPI_LINEAR) h.ksplit = h3s_pick_ksplit(L, T, ws_floats - need - 64);
+    return h;
+}
+
+template <int EPI>
+static int h3s_run(DevLaunch &L, const H3sPlan &h, float *ws, long long ws_floats, hipStream_t st, int transposed) {
+    const int T = h.T, S = h.ksplit;
     float *slab = ws + ((ws_floats - 64) & ~63LL);        // slabs from the end of the workspace, planes from its start
-    H3Planner pl(ws, sc);
+    H3Planner pl(ws, h.scope);
     int start = 0;
     for (int i = 0; i < L.nprob; ++i) {
         DevProb &p = L.p[i];
-        p.Kp = h3_kp(p);
-        p.nap = p.nseg;
-        for (int s = 0; s < p.nseg; ++s) {
-            const bool planes = p.seg[s].A_hi && p.seg[s].A_lo;
-            p.ap[s] = DevASeg{planes ? p.seg[s].A_hi : nullptr, planes ? p.seg[s].A_lo : nullptr, 2 * p.seg[s].K,
-                              p.seg[s].K};
-        }
+        h3_set_a(p);
         pl.add_w(p, p.Wh, p.Wl, transposed);
         h3s_tile_problem(p, 32 * T, EPI == EPI_VOCAB ? 128 : 32 * T, start, S);
         if (S > 1) {
@@ -3232,12 +3252,90 @@ static int try_h3s(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st,
         }
     }
     L.total_tiles = start;
-    rc = pl.launch(st);                                   // weight planes not yet in the scope (first use only)
-    if (rc) return 1;
+    int rc = pl.launch(st);                               // weight planes not yet in the scope (first use only)
+    if (rc) return rc;
     rc = launch_h3s_t<EPI>(L, T, st);
     ++g_h3s_launches;
     if (!rc && S > 1) rc = launch_splitk_linear_reduce(L, st);
-    return 1;
+    return rc;
+}
+
+// 2 M N K summed over the K-segments of a problem (isc_linear_problem or DevProb)
+template <class P>
+static double contraction_flops(const P &p) {
+    double f = 0;
+    for (int s = 0; s < p.nseg; ++s) f += 2.0 * p.M * p.N * (double)p.seg[s].K;
+    return f;
+}
+// dW contractions below this: the fp32 tiles' launch is as quick as the transposing split plus the split-f16 launch
+#define H3_TN_MIN_FLOPS 2.5e8
+
+// Rows [k0, k0 + kc) of a single-segment TN problem: A and W advanced by k0 rows.  `later` (a slice after the first, or
+// a later pass over the problem): accumulate onto what is in C, the biases went in with the first.
+// (a multi-segment problem is only ever taken whole: k0 = 0, kc = its packed K)
+static DevProb tn_k_slice(const DevProb &p, long long k0, long long kc, bool later) {
+    DevProb q = p;
+    if (p.nseg == 1) {
+        q.seg[0].A = p.seg[0].A + k0 * p.seg[0].lda;
+        q.seg[0].W = p.seg[0].W + k0 * p.seg[0].ldw;
+        q.seg[0].K = (int)kc;
+    }
+    if (later) { q.accumulate = 1; q.bias0 = q.bias1 = q.bias2 = nullptr; }
+    return q;
+}
+
+// One launch of TN problems that share their A (= dY; one problem, or several): plans the transposed planes of A once
+// and of each W in the workspace, launches the split, tiles and launches the GEMM - the large tiles, the 64-row tile or
+// the skinny tile by the tile count (`skinny_only`: a group is always skinny: each of its problems alone is) - and counts
+// the launch in g_h3_launches whichever kernel ran.
+static int tn_launch(DevLaunch &Lc, float *ws, int mode, bool skinny_only, hipStream_t st) {
+    H3Planner pl(ws, nullptr);
+    const _Float16 *ah = nullptr, *al = nullptr;
+    const int kc = h3_kp(Lc.p[0]);
+    pl.add(Lc.p[0], false, Lc.p[0].M, ah, al, 0, -1, 1);
+    for (int i = 0; i < Lc.nprob; ++i) {
+        DevProb &q = Lc.p[i];
+        pl.add(q, true, q.N, q.Wh, q.Wl, 0, -1, 1);
+        q.nap = 1;
+        q.ap[0] = DevASeg{ah, al, 2 * kc, kc};
+        q.nseg = 1;                                           // the kernels see one packed K-segment
+        q.seg[0].K = kc;
+        q.Kp = kc;
+        q.ksplit = 1;
+    }
+    int rc = pl.launch(st);
+    if (rc) return rc;
+    const long long tiles = count_tiles(Lc, 128, 128);
+    if (!skinny_only && tiles >= H3_MIN_TILES) {
+        rc = launch_h3_big<EPI_LINEAR>(Lc, st);
+    } else if (!skinny_only && tiles >= H3_MIN_TILES / 2) {
+        finish_tiling(Lc, 1);
+        rc = launch_h3_tile<H3Tile64, EPI_LINEAR>(Lc, st);
+    } else {
+        int T = h3s_pick_tile<EPI_LINEAR>(Lc, mode == 2 ? 1 : mode), start = 0;
+        if (!T) T = 2;
+        for (int i = 0; i < Lc.nprob; ++i) h3s_tile_problem(Lc.p[i], 32 * T, 32 * T, start);
+        Lc.total_tiles = start;
+        rc = launch_h3s_t<EPI_LINEAR>(Lc, T, st);
+    }
+    if (rc) return rc;
+    ++g_h3_launches;
+    return ISC_OK;
+}
+
+// The problems of Lp (packed K each) in slices of `step` rows of K, one tn_launch per slice.
+// (every slice is a fresh launch descriptor with its problems copied by value - one host copy of a DevProb per problem and
+// slice more than slicing in place would make, next to a split launch and a GEMM launch per slice)
+static int tn_run_chunks(const DevLaunch &Lp, long long K, long long step, bool later, float *ws, int mode,
+                         bool skinny_only, hipStream_t st) {
+    for (long long k0 = 0; k0 < K; k0 += step) {
+        const long long kc = K - k0 < step ? K - k0 : step;
+        DevLaunch Lc = {};
+        Lc.nprob = Lp.nprob;
+        for (int i = 0; i < Lp.nprob; ++i) Lc.p[i] = tn_k_slice(Lp.p[i], k0, kc, later || k0 > 0);
+        if (int rc = tn_launch(Lc, ws, mode, skinny_only, st)) return rc;
+    }
+    return ISC_OK;
 }
 
 // dW = dY^T X (ISC_LAYOUT_TN: both operands are [K_s, .] with the contraction over their ROWS) on the split-f16
@@ -3254,13 +3352,10 @@ static unsigned try_h3_tn(DevLaunch &L, float *ws, long long ws_floats, hipStrea
     unsigned take = 0;
     for (int i = 0; i < L.nprob; ++i) {
         const DevProb &p = L.p[i];
-        long long Kp = 0;
+        const long long Kp = h3_kp(p);
         bool ok = true;
-        for (int s = 0; s < p.nseg; ++s) {
-            ok = ok && (p.seg[s].K & 31) == 0;
-            Kp += p.seg[s].K;
-        }
-        if (2.0 * p.M * p.N * (double)Kp < 2.5e8 && mode != 2) ok = false;    // small: the fp32 tiles' launch is as quick
+        for (int s = 0; s < p.nseg; ++s) ok = ok && (p.seg[s].K & 31) == 0;
+        if (contraction_flops(p) < H3_TN_MIN_FLOPS && mode != 2) ok = false;
         const long long per_k = (long long)p.M + p.N;
         chunk[i] = Kp;
         if (ok && per_k * Kp + 1024 > ws_floats) {
@@ -3295,99 +3390,25 @@ static unsigned try_h3_tn(DevLaunch &L, float *ws, long long ws_floats, hipStrea
         if (same && K > 0 && kc_max >= 2048) {
             const long long nchunk = (K + kc_max - 1) / kc_max;
             const long long kc0 = ((K + nchunk - 1) / nchunk + 31) & ~31LL;
-            for (long long k0 = 0; k0 < K; k0 += kc0) {
-                const long long kc = K - k0 < kc0 ? K - k0 : kc0;
-                DevLaunch Lc = {};
-                Lc.nprob = L.nprob;
-                H3Planner pl(ws, nullptr);
-                const _Float16 *ah = nullptr, *al = nullptr;
-                DevProb a0 = p0;
-                a0.seg[0].A = p0.seg[0].A + k0 * p0.seg[0].lda;
-                a0.seg[0].K = (int)kc;
-                pl.add(a0, false, a0.M, ah, al, 0, -1, 1);
-                for (int i = 0; i < L.nprob; ++i) {
-                    DevProb &q = Lc.p[i];
-                    q = L.p[i];
-                    q.seg[0].A = L.p[i].seg[0].A + k0 * L.p[i].seg[0].lda;
-                    q.seg[0].W = L.p[i].seg[0].W + k0 * L.p[i].seg[0].ldw;
-                    q.seg[0].K = (int)kc;
-                    if (k0 > 0) { q.accumulate = 1; q.bias0 = q.bias1 = q.bias2 = nullptr; }
-                    pl.add(q, true, q.N, q.Wh, q.Wl, 0, -1, 1);
-                    q.nap = 1;
-                    q.ap[0] = DevASeg{ah, al, 2 * (int)kc, (int)kc};
-                    q.nseg = 1;
-                    q.Kp = (int)kc;
-                    q.ksplit = 1;
-                }
-                rc = pl.launch(st);
-                if (rc) return take;
-                int T = h3s_pick_tile<EPI_LINEAR>(Lc, mode == 2 ? 1 : mode), start = 0;
-                if (!T) T = 2;
-                for (int i = 0; i < Lc.nprob; ++i) h3s_tile_problem(Lc.p[i], 32 * T, 32 * T, start);
-                Lc.total_tiles = start;
-                rc = launch_h3s_t<EPI_LINEAR>(Lc, T, st);
-                if (rc) return take;
-                ++g_h3_launches;
-            }
+            rc = tn_run_chunks(L, K, kc0, false, ws, mode, true, st);
             return take;
         }
     }
     for (int i = 0; i < L.nprob; ++i) {
         if (!(take & (1u << i))) continue;
         const DevProb &pfull = L.p[i];
-        long long Kfull = 0;
-        for (int s = 0; s < pfull.nseg; ++s) Kfull += pfull.seg[s].K;
-        const bool by_seg = pfull.nseg > 1 && chunk[i] < Kfull;      // does not fit: one single-segment pass per segment
+        const bool by_seg = pfull.nseg > 1 && chunk[i] < h3_kp(pfull);   // does not fit: one single-segment pass per segment
         const int npass = by_seg ? pfull.nseg : 1;
         for (int pass = 0; pass < npass; ++pass) {
-        DevProb p0 = pfull;
-        if (by_seg) {
-            p0.nseg = 1;
-            p0.seg[0] = pfull.seg[pass];
-            if (pass > 0) { p0.accumulate = 1; p0.bias0 = p0.bias1 = p0.bias2 = nullptr; }
-        }
-        long long Kp = 0;
-        for (int s = 0; s < p0.nseg; ++s) Kp += p0.seg[s].K;
-        for (long long k0 = 0; k0 < Kp; k0 += chunk[i]) {
-            const long long kc = Kp - k0 < chunk[i] ? Kp - k0 : chunk[i];
             DevLaunch L1 = {};
             L1.nprob = 1;
-            DevProb &q = L1.p[0];
-            q = p0;
-            if (p0.nseg == 1) {                                   // (a multi-segment problem that fits is one launch)
-                q.seg[0].A = p0.seg[0].A + k0 * p0.seg[0].lda;
-                q.seg[0].W = p0.seg[0].W + k0 * p0.seg[0].ldw;
-                q.seg[0].K = (int)kc;
+            L1.p[0] = pfull;
+            if (by_seg) {
+                L1.p[0].nseg = 1;
+                L1.p[0].seg[0] = pfull.seg[pass];
             }
-            q.Kp = (int)kc;
-            if (k0 > 0) { q.accumulate = 1; q.bias0 = q.bias1 = q.bias2 = nullptr; }
-            H3Planner pl(ws, nullptr);
-            const _Float16 *ah, *al;
-            pl.add(q, false, q.M, ah, al, 0, -1, 1);
-            pl.add(q, true, q.N, q.Wh, q.Wl, 0, -1, 1);
-            q.nap = 1;
-            q.ap[0] = DevASeg{ah, al, 2 * (int)kc, (int)kc};
-            q.nseg = 1;                                           // the kernels see one packed K-segment
-            q.seg[0].K = (int)kc;
-            q.ksplit = 1;
-            rc = pl.launch(st);
+            rc = tn_run_chunks(L1, h3_kp(L1.p[0]), chunk[i], pass > 0, ws, mode, false, st);
             if (rc) return take;
-            const long long tiles = (long long)((q.M + 127) / 128) * ((q.N + 127) / 128);
-            if (tiles >= H3_MIN_TILES) {
-                rc = launch_h3_big<EPI_LINEAR>(L1, st);
-            } else if (tiles >= H3_MIN_TILES / 2) {
-                finish_tiling(L1, 1);
-                rc = launch_h3_tile<H3Tile64, EPI_LINEAR>(L1, st);
-            } else {
-                int T = h3s_pick_tile<EPI_LINEAR>(L1, mode == 2 ? 1 : mode), start = 0;
-                if (!T) T = 2;
-                h3s_tile_problem(q, 32 * T, 32 * T, start);
-                L1.total_tiles = start;
-                rc = launch_h3s_t<EPI_LINEAR>(L1, T, st);
-            }
-            if (rc) return take;
-            ++g_h3_launches;
-        }
         }
     }
     return take;
@@ -3398,12 +3419,12 @@ static unsigned try_h3_tn(DevLaunch &L, float *ws, long long ws_floats, hipStrea
 // (1 = no split) and carves one [S, M, N] slab region per problem out of the caller's workspace.
 static int plan_splitk(DevLaunch &L, float *ws, long long ws_floats) {
     if (!ws || ws_floats <= 0) return 1;
-    long long blocks = 0, need1 = 0;
+    const long long blocks = count_tiles(L, 32, 128);
+    long long need1 = 0;
     int min_chunks = 1 << 30;
     for (int i = 0; i < L.nprob; ++i) {
         const DevProb &p = L.p[i];
         if (p.N & 3) return 1;
-        blocks += (long long)((p.M + 31) / 32) * ((p.N + 127) / 128);
         need1 += (long long)p.M * p.N;
         int ch = 0;
         for (int s = 0; s < p.nseg; ++s) ch += (p.seg[s].K + BK - 1) / BK;
@@ -3426,20 +3447,35 @@ static int plan_splitk(DevLaunch &L, float *ws, long long ws_floats) {
     return (int)S;
 }
 
-static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st) {
-    long long mx = 0;
-    for (int i = 0; i < L.nprob; ++i) {
-        const long long n4 = (long long)L.p[i].M * (L.p[i].N >> 2);
-        if (n4 > mx) mx = n4;
+// The one routing chain of the forward (NT) entry points, in this order:
+//   1. the matrix-vector kernels (few rows)                      gemv_plan
+//   2. the skinny split-f16 kernels (inside a weights scope)     h3s_plan
+//   3. fp32 split-K: the 32-row tile with the linear epilogue writes slabs, the reduce kernel of EPI finishes them
+//   4. the large split-f16 kernels                               h3_plan
+//   5. the fp32 tiles by the cost model (allow_xl: the 256-row tile may be chosen)
+// decide_only: launches nothing and leaves the weights scope alone; returns 1 when step 4 - the one path that reads
+// isc_seg.a_f16 rows - would take the launch, 0 when another step would.  Otherwise returns the launches' status.
+template <int EPI>
+static int route_nt(DevLaunch &L, float *ws, long long ws_floats, hipStream_t st, bool allow_xl, bool decide_only) {
+    if (const int kmax = gemv_plan<EPI>(L)) return decide_only ? 0 : gemv_run<EPI>(L, kmax, st);
+    const H3sPlan hs = h3s_plan<EPI>(L, ws, ws_floats, st, 0);
+    if (hs.T) return decide_only ? 0 : h3s_run<EPI>(L, hs, ws, ws_floats, st, 0);
+    if (plan_splitk(L, ws, ws_floats) > 1) {
+        if (decide_only) return 0;
+        finish_tiling(L, 2);
+        const int rc = launch_any<EPI_LINEAR, false, false>(L, 2, st);
+        return rc ? rc : launch_splitk_reduce<EPI>(L, st);
     }
-    hipLaunchKernelGGL(splitk_linear_kernel, dim3((unsigned)((mx + 255) / 256), L.nprob), dim3(256), 0, st, L);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
+    const H3Plan h = h3_plan<EPI>(L, ws, ws_floats, st, 0);
+    if (h.take) return decide_only ? 1 : h3_run<EPI>(L, h, ws, st, 0);
+    if (decide_only) return 0;
+    const int tile = pick_tile(L, allow_xl, true, true);
+    finish_tiling(L, tile);
+    return launch_any<EPI, false, false>(L, tile, st);
 }
 
-// isc_linear_fwd.  plan: the dispatch without a launch - returns 1 when the large split-f16 kernels would take these
-// problems (the one path that reads isc_seg.a_f16 segments), 0 when another path would, < 0 for a bad argument.
-static int linear_fwd_run(const isc_linear_problem *pr, int n_prob, void *stream, bool plan) {
+// isc_linear_fwd.  decide_only: route_nt's answer (< 0 for a bad argument).
+static int linear_fwd_run(const isc_linear_problem *pr, int n_prob, void *stream, bool decide_only) {
     if (!pr) return ISC_E_NULL;
     if (n_prob < 1 || n_prob > 3) return ISC_E_SHAPE;
     DevLaunch L = {};
@@ -3459,18 +3495,7 @@ static int linear_fwd_run(const isc_linear_problem *pr, int n_prob, void *stream
         d.mask = q.keep_mask; d.mask_scale = q.mask_scale;
         d.ldc = q.ldc; d.C = q.C; d.C_pre = q.C_pre; d.accumulate = q.accumulate;
     }
-    int rc = ISC_OK;
-    if (try_gemv<EPI_LINEAR>(L, (hipStream_t)stream, rc, plan)) return plan ? 0 : rc;
-    if (try_h3s<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc, 0, plan)) return plan ? 0 : rc;
-    const int S = plan_splitk(L, pr[0].splitk_ws, pr[0].splitk_ws_floats);
-    if (S == 1 && try_h3<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc, 0, plan))
-        return plan ? 1 : rc;
-    if (plan) return 0;
-    const int tile = S > 1 ? 2 : pick_tile(L, true);
-    finish_tiling(L, tile);
-    rc = launch_any<EPI_LINEAR, false, false>(L, tile, (hipStream_t)stream);
-    if (rc || S == 1) return rc;
-    return launch_splitk_linear_reduce(L, (hipStream_t)stream);
+    return route_nt<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, true, decide_only);
 }
 
 // What the native form asks of an f16 segment (K % 32 == 0 is check_segs')
@@ -3497,6 +3522,69 @@ extern "C" int isc_linear_fwd(const isc_linear_problem *pr, int n_prob, void *st
     return linear_fwd_run(pr, n_prob, stream, false);
 }
 
+// dX contractions outside a weights scope still go to the split-f16 kernels from this size on (the classifier's dX over
+// a zero-padded copy of W_c that autograd.py keeps out of the scope on purpose - B = 512: 105 GFLOP, 606 us on the fp32
+// tiles -, the prologue's d att_e = d att_p W at B >= 256: 19 GFLOP, 283 us at B = 1024): planes of this call's W^T go to
+// the workspace, one split launch of at most 20 MB against 0.2-0.3 ms saved
+#define H3_NN_MIN_FLOPS 5.0e9
+
+// One backward launch: validates, fills the launch, routes it (isc_gemm_bwd below).
+static int gemm_bwd_run(const isc_linear_problem *pr, int n_prob, int layout, hipStream_t st) {
+    DevLaunch L = {};
+    L.nprob = n_prob;
+    bool k32 = true;
+    for (int i = 0; i < n_prob; ++i) {
+        const isc_linear_problem &q = pr[i];
+        if (q.nseg < 1 || q.nseg > ISC_MAX_SEG || !q.C) return q.C ? ISC_E_SHAPE : ISC_E_NULL;
+        if (q.M <= 0 || q.N <= 0 || (q.N & 3) || (q.ldc & 3)) return ISC_E_SHAPE;
+        if (layout == ISC_LAYOUT_TN && (q.M & 3)) return ISC_E_SHAPE;
+        for (int s = 0; s < q.nseg; ++s) {
+            const isc_seg &g = q.seg[s];
+            if (!g.A || !g.W) return ISC_E_NULL;
+            // NN with K % 4 != 0 (vocabulary-sized K): the caller pads A's rows to lda with zeros
+            if (g.K <= 0) return ISC_E_SHAPE;
+            if ((g.lda & 3) || (g.ldw & 3) || !isc_aligned16(g.A) || !isc_aligned16(g.W)) return ISC_E_ALIGN;
+            k32 = k32 && (g.K & 31) == 0;
+        }
+        DevProb &d = L.p[i];
+        copy_segs(d, q.seg, q.nseg);
+        d.M = q.M; d.N = q.N; d.relu = 0;
+        d.bias0 = q.bias0; d.bias1 = q.bias1; d.bias2 = q.bias2;
+        d.ldc = q.ldc; d.C = q.C; d.accumulate = q.accumulate;
+    }
+    float *ws = pr[0].splitk_ws;
+    const long long ws_floats = pr[0].splitk_ws_floats;
+    const int mode = g_h3_mode.load();
+    const bool nn_big = mode == 1 && n_prob == 1 && contraction_flops(pr[0]) >= H3_NN_MIN_FLOPS;
+    if (layout == ISC_LAYOUT_NN && k32 && (h3w_scope_of(st) || mode >= 2 || nn_big)) {
+        // inside a weights scope (the BPTT sweep): dX = dY W on planes of W^T built once per scope - the skinny tiles for
+        // few rows, the large split-f16 kernels otherwise; dY is read as fp32 rows and split in registers
+        const H3sPlan hs = h3s_plan<EPI_LINEAR>(L, ws, ws_floats, st, 1);
+        if (hs.T) return h3s_run<EPI_LINEAR>(L, hs, ws, ws_floats, st, 1);
+        const H3Plan h = h3_plan<EPI_LINEAR>(L, ws, ws_floats, st, 1);
+        if (h.take) return h3_run<EPI_LINEAR>(L, h, ws, st, 1);
+    }
+    if (layout == ISC_LAYOUT_TN) {
+        int rc_h3 = ISC_OK;
+        const unsigned took = try_h3_tn(L, ws, ws_floats, st, rc_h3);
+        if (rc_h3) return rc_h3;
+        if (took) {                                     // the rest of the launch stays on the fp32 tiles
+            int n = 0;
+            for (int i = 0; i < L.nprob; ++i)
+                if (!(took & (1u << i))) { if (n != i) L.p[n] = L.p[i]; ++n; }
+            if (n == 0) return ISC_OK;
+            L.nprob = n;
+        }
+    }
+    const int S = plan_splitk(L, ws, ws_floats);
+    const int tile = S > 1 ? 2 : pick_tile(L, false, false);
+    finish_tiling(L, tile);
+    int rc = layout == ISC_LAYOUT_NN ? launch_any<EPI_LINEAR, false, true>(L, tile, st)
+                                     : launch_any<EPI_LINEAR, true, true>(L, tile, st);
+    if (rc || S == 1) return rc;
+    return launch_splitk_linear_reduce(L, st);
+}
+
 // Backward-pass contractions on the same kernel (include/insenticap_hip.h: isc_gemm_bwd).
 extern "C" int isc_gemm_bwd(const isc_linear_problem *pr, int n_prob, int layout, void *stream) {
     if (!pr) return ISC_E_NULL;
@@ -3510,80 +3598,18 @@ extern "C" int isc_gemm_bwd(const isc_linear_problem *pr, int n_prob, int layout
     if (layout == ISC_LAYOUT_TN && n_prob == 1 && pr[0].nseg > 1 && pr[0].nseg <= ISC_MAX_SEG && g_h3_mode.load() != 0) {
         isc_linear_problem a = pr[0], b = pr[0];
         a.nseg = b.nseg = 0;
-        double fa = 0;
         for (int s = 0; s < pr[0].nseg; ++s) {
-            if (pr[0].seg[s].K > 0 && (pr[0].seg[s].K & 31) == 0) {
-                a.seg[a.nseg++] = pr[0].seg[s];
-                fa += 2.0 * pr[0].M * pr[0].N * (double)pr[0].seg[s].K;
-            } else {
-                b.seg[b.nseg++] = pr[0].seg[s];
-            }
+            isc_linear_problem &to = pr[0].seg[s].K > 0 && (pr[0].seg[s].K & 31) == 0 ? a : b;
+            to.seg[to.nseg++] = pr[0].seg[s];
         }
-        if (a.nseg > 0 && b.nseg > 0 && fa >= 2.5e8) {
-            const int rc = isc_gemm_bwd(&a, 1, layout, stream);
+        if (a.nseg > 0 && b.nseg > 0 && contraction_flops(a) >= H3_TN_MIN_FLOPS) {
+            const int rc = gemm_bwd_run(&a, 1, layout, (hipStream_t)stream);
             if (rc) return rc;
             b.accumulate = 1; b.bias0 = b.bias1 = b.bias2 = nullptr;
-            return isc_gemm_bwd(&b, 1, layout, stream);
+            return gemm_bwd_run(&b, 1, layout, (hipStream_t)stream);
         }
     }
-    DevLaunch L = {};
-    L.nprob = n_prob;
-    for (int i = 0; i < n_prob; ++i) {
-        const isc_linear_problem &q = pr[i];
-        if (q.nseg < 1 || q.nseg > ISC_MAX_SEG || !q.C) return q.C ? ISC_E_SHAPE : ISC_E_NULL;
-        if (q.M <= 0 || q.N <= 0 || (q.N & 3) || (q.ldc & 3)) return ISC_E_SHAPE;
-        if (layout == ISC_LAYOUT_TN && (q.M & 3)) return ISC_E_SHAPE;
-        for (int s = 0; s < q.nseg; ++s) {
-            const isc_seg &g = q.seg[s];
-            if (!g.A || !g.W) return ISC_E_NULL;
-            // NN with K % 4 != 0 (vocabulary-sized K): the caller pads A's rows to lda with zeros
-            if (g.K <= 0) return ISC_E_SHAPE;
-            if ((g.lda & 3) || (g.ldw & 3) || !isc_aligned16(g.A) || !isc_aligned16(g.W)) return ISC_E_ALIGN;
-        }
-        DevProb &d = L.p[i];
-        copy_segs(d, q.seg, q.nseg);
-        d.M = q.M; d.N = q.N; d.relu = 0;
-        d.bias0 = q.bias0; d.bias1 = q.bias1; d.bias2 = q.bias2;
-        d.ldc = q.ldc; d.C = q.C; d.accumulate = q.accumulate;
-    }
-    int rc_h3 = ISC_OK;
-    bool k32 = true;
-    for (int i = 0; i < n_prob; ++i)
-        for (int s = 0; s < pr[i].nseg; ++s) k32 = k32 && (pr[i].seg[s].K & 31) == 0;
-    // ... or outside one when the contraction is large (>= 5 GFLOP: the classifier's dX over a zero-padded copy of W_c that
-    // autograd.py keeps out of the scope on purpose - B = 512: 105 GFLOP, 606 us on the fp32 tiles -, the prologue's
-    // d att_e = d att_p W at B >= 256: 19 GFLOP, 283 us at B = 1024): planes of this call's W^T go to the workspace, one
-    // split launch of at most 20 MB against 0.2-0.3 ms saved
-    bool nn_big = g_h3_mode.load() == 1 && n_prob == 1;
-    if (nn_big) {
-        double fl = 0;
-        for (int s = 0; s < pr[0].nseg; ++s) fl += 2.0 * pr[0].M * pr[0].N * (double)pr[0].seg[s].K;
-        nn_big = fl >= 5.0e9;
-    }
-    if (layout == ISC_LAYOUT_NN && k32 && (h3w_scope_of((hipStream_t)stream) || g_h3_mode.load() >= 2 || nn_big)) {
-        // inside a weights scope (the BPTT sweep): dX = dY W on planes of W^T built once per scope - the skinny tiles for
-        // few rows, the large split-f16 kernels otherwise; dY is read as fp32 rows and split in registers
-        if (try_h3s<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc_h3, 1)) return rc_h3;
-        if (try_h3<EPI_LINEAR>(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc_h3, 1)) return rc_h3;
-    }
-    if (layout == ISC_LAYOUT_TN) {
-        const unsigned took = try_h3_tn(L, pr[0].splitk_ws, pr[0].splitk_ws_floats, (hipStream_t)stream, rc_h3);
-        if (rc_h3) return rc_h3;
-        if (took) {                                     // the rest of the launch stays on the fp32 tiles
-            int n = 0;
-            for (int i = 0; i < L.nprob; ++i)
-                if (!(took & (1u << i))) { if (n != i) L.p[n] = L.p[i]; ++n; }
-            if (n == 0) return ISC_OK;
-            L.nprob = n;
-        }
-    }
-    const int S = plan_splitk(L, pr[0].splitk_ws, pr[0].splitk_ws_floats);
-    const int tile = S > 1 ? 2 : pick_tile(L, false, false);
-    finish_tiling(L, tile);
-    int rc = layout == ISC_LAYOUT_NN ? launch_any<EPI_LINEAR, false, true>(L, tile, (hipStream_t)stream)
-                                     : launch_any<EPI_LINEAR, true, true>(L, tile, (hipStream_t)stream);
-    if (rc || S == 1) return rc;
-    return launch_splitk_linear_reduce(L, (hipStream_t)stream);
+    return gemm_bwd_run(pr, n_prob, layout, (hipStream_t)stream);
 }
 
 extern "C" int isc_lstm_fwd(const isc_lstm_problem *q, void *stream) {
@@ -3611,27 +3637,11 @@ extern "C" int isc_lstm_fwd(const isc_lstm_problem *q, void *stream) {
     d.h_hi = static_cast<_Float16 *>(q->h_hi); d.h_lo = static_cast<_Float16 *>(q->h_lo);
     d.pre = q->pre; d.tab = q->tab; d.tab_ids = q->tab_ids; d.tab_ids_stride = q->tab_ids_stride;
     d.pre_div = q->pre_div > 1 ? q->pre_div : 1;
-    if (try_gemv<EPI_LSTM>(L, (hipStream_t)stream, rc)) return rc;
-    if (try_h3s<EPI_LSTM>(L, q->splitk_ws, q->splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
-    const int S = plan_splitk(L, q->splitk_ws, q->splitk_ws_floats);
-    if (S > 1) {   // plain [M,4H] pre-activation slabs, then the cell update in the reduce kernel
-        finish_tiling(L, 2);
-        int rc2 = launch_any<EPI_LINEAR, false, false>(L, 2, (hipStream_t)stream);
-        if (rc2) return rc2;
-        const long long n = (long long)q->M * q->H;
-        hipLaunchKernelGGL(splitk_lstm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, L);
-        ISC_LAUNCH_CHECK();
-        return ISC_OK;
-    }
     // XL only for the bias-only cell: a hoisted `pre` term or an embedding-table gather adds 8-16 B of
     // epilogue reads per output, which the XL tile's lone workgroup per CU cannot overlap with MFMA work
     // (in the roll-out: att-LSTM 168 us on the 128x128 tile vs 178 us on XL; lang-LSTM 223 vs 206; with the
     // batched epilogue loads of lstm_cells the two are within 2 % of each other on either cell)
-    if (try_h3<EPI_LSTM>(L, q->splitk_ws, q->splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
-    const int tile = pick_tile(L, !q->pre && !q->tab, true, true);
-    finish_tiling(L, tile);
-    return launch_any<EPI_LSTM, false, false>(L, tile, (hipStream_t)stream);
+    return route_nt<EPI_LSTM>(L, q->splitk_ws, q->splitk_ws_floats, (hipStream_t)stream, !q->pre && !q->tab, false);
 }
 
 extern "C" int isc_vocab_fwd(const float *h, int ldh, const float *W, int ldw, const float *bias,
@@ -3653,25 +3663,9 @@ extern "C" int isc_vocab_fwd(const float *h, int ldh, const float *W, int ldw, c
     d.C = logits; d.ld_logits = ld_logits;
     d.pmax = part_max; d.psum = part_sum; d.pidx = part_idx;
     d.ntile_total = (V + 127) / 128;
-    // few rows (beam search, small batches): the 16-chunk contraction of a 32-row tile is a serial walk
-    // of ~27 us; split it over K into raw [S,M,V] slabs and let the reduce kernel form the statistics
-    if (try_gemv<EPI_VOCAB>(L, (hipStream_t)stream, rc)) return rc;
-    if (try_h3s<EPI_VOCAB>(L, splitk_ws, splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
-    const int S = plan_splitk(L, splitk_ws, splitk_ws_floats);
-    if (S > 1) {
-        finish_tiling(L, 2);
-        rc = launch_any<EPI_LINEAR, false, false>(L, 2, (hipStream_t)stream);
-        if (rc) return rc;
-        const long long waves = (long long)M * d.ntile_total;
-        hipLaunchKernelGGL(splitk_vocab_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, L);
-        ISC_LAUNCH_CHECK();
-        return ISC_OK;
-    }
-    // The vocabulary projection runs on the 128x128 LDS-DMA tile: at [4096 x 10000 x 512] 121 TFLOP/s there, 115 on
-    // the register-staged 128x128 tile and 108 on XL, whose lone workgroup per CU has nothing to hide the per-row
+    // Few rows (beam search, small batches): the 16-chunk contraction of a 32-row tile is a serial walk of ~27 us, so
+    // route_nt splits it over K.  Many rows end on the 128x128 LDS-DMA tile: at [4096 x 10000 x 512] 121 TFLOP/s there,
+    // 115 on the register-staged 128x128 tile and 108 on XL, whose lone workgroup per CU has nothing to hide the per-row
     // softmax statistics of the epilogue behind (3k VALU instructions per wave at the end of a 16-chunk tile).
-    if (try_h3<EPI_VOCAB>(L, splitk_ws, splitk_ws_floats, (hipStream_t)stream, rc)) return rc;
-    const int tile = pick_tile(L, false, true, true);
-    finish_tiling(L, tile);
-    return launch_any<EPI_VOCAB, false, false>(L, tile, (hipStream_t)stream);
+    return route_nt<EPI_VOCAB>(L, splitk_ws, splitk_ws_floats, (hipStream_t)stream, false, false);
 }

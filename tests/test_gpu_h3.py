@@ -511,3 +511,66 @@ def test_dw_contractions_that_share_their_dy_split_it_once(K, launches):
         ref = dy.double().cpu().t() @ x.double().cpu() + (prior.double().cpu() if i == 2 else 0.0)
         np.testing.assert_allclose(a.cpu().numpy(), ref.float().numpy(), atol=6e-6, rtol=1e-5)
         np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), atol=2e-6, rtol=2e-6)
+
+
+def test_dw_contractions_that_share_their_dy_in_k_chunks_of_a_small_workspace():
+    """Two dW problems over one dY [4160, 256] (X 256 and 128 wide, the second accumulating) with a workspace of
+    640 * 2048 + 3072 floats: neither problem's planes fit, the group's chunk limit is (1313792 - 3072) / 640 = 2048 rows,
+    so three equal chunks (1408 / 1408 / 1344) - one split of dY and one skinny launch each; chunks 2 and 3 accumulate in
+    both problems, the second problem's first chunk adds to its prior."""
+    g = torch.Generator().manual_seed(6)
+    K, M = 4160, 256
+    dy = _rand(g, K, M, scale=1e-2).to(dev())
+    xs = [_rand(g, K, n).to(dev()) for n in (256, 128)]
+    prior = _rand(g, M, 128).to(dev())
+    outs = [torch.full((M, 256), float('nan'), device=dev()), prior.clone()]
+    probs = [ops.gemm_problem([(dy, x)], o, ops.TN, accumulate=(i == 1)) for i, (x, o) in enumerate(zip(xs, outs))]
+    ws = torch.empty(640 * 2048 + 3072, dtype=torch.float32, device=dev())
+    probs[0].splitk_ws, probs[0].splitk_ws_floats = ws.data_ptr(), ws.numel()
+    lib = ops._lib.load()
+    n0 = lib.isc_h3_launches()
+    ops.gemm_bwd(probs, ops.TN)
+    torch.cuda.synchronize()
+    assert lib.isc_h3_launches() - n0 == 3
+    for i, (o, x) in enumerate(zip(outs, xs)):
+        ref = dy.double().cpu().t() @ x.double().cpu() + (prior.double().cpu() if i == 1 else 0.0)
+        np.testing.assert_allclose(o.cpu().numpy(), ref.float().numpy(), atol=6e-6, rtol=1e-5)
+
+
+# (where, mode, M, N) -> isc_linear_f16_native's answer, K = 512, fp32 rows; taken from the build in front of the one
+# that separated deciding from launching.  Outside a scope the 384-block line of the fp32 split-K comes first
+# ([1280 x 1024] 320 blocks of 32 rows: split-K; [1536 x 1024] 384: the large kernels at 96 >= H3_MIN_TILES / 2 tiles);
+# inside one the skinny kernel takes up to 2048 rows and the large kernels need H3_MIN_TILES_SCOPE tiles only; mode 2
+# skips the matrix-vector and the skinny kernels but not the fp32 split-K.
+_NATIVE_CASES = [('plain', 1, 8, 512, 0), ('plain', 1, 9, 512, 0), ('plain', 1, 1280, 1024, 0), ('plain', 1, 1536, 1024, 1),
+                 ('plain', 1, 2560, 512, 0), ('plain', 1, 4608, 512, 1),
+                 ('scope', 1, 8, 512, 0), ('scope', 1, 9, 1024, 0), ('scope', 1, 1536, 1024, 0), ('scope', 1, 2560, 512, 0),
+                 ('scope', 1, 2560, 1024, 1), ('scope', 1, 4608, 512, 1),
+                 ('plain', 2, 9, 512, 0), ('plain', 2, 1280, 512, 0), ('plain', 2, 1536, 1024, 1)]
+
+
+@pytest.mark.parametrize('where,mode,M,N,native', _NATIVE_CASES)
+def test_f16_native_answer_is_the_route_the_launch_then_takes(where, mode, M, N, native):
+    """isc_linear_f16_native decides without launching; the launch that follows must take the large split-f16 kernels
+    (isc_h3_launches + 1, no skinny and no matrix-vector launch) exactly when it said 1."""
+    import contextlib
+    g = torch.Generator().manual_seed(M + N)
+    K = 512
+    x, w = _rand(g, M, K).to(dev()), _rand(g, N, K, scale=K ** -0.5).to(dev())
+    out = torch.empty(M, N, device=dev())
+    lib = ops._lib.load()
+    ops.set_h3_mode(mode)
+    with (ops.h3_weights_scope(dev()) if where == 'scope' else contextlib.nullcontext()):
+        p = ops.linear_problem([(x, w)], out)
+        ops._attach_ws(p, torch.cuda.current_device())
+        before = (lib.isc_h3_launches(), lib.isc_h3s_launches(), lib.isc_gemv_launches())
+        said = lib.isc_linear_f16_native((ops.LinearProblem * 1)(p), 1, ops.stream())
+        assert (lib.isc_h3_launches(), lib.isc_h3s_launches(), lib.isc_gemv_launches()) == before   # nothing launched
+        ops.linear_fwd([p])
+        torch.cuda.synchronize()
+    after = (lib.isc_h3_launches(), lib.isc_h3s_launches(), lib.isc_gemv_launches())
+    large = after[0] - before[0] == 1 and after[1] == before[1] and after[2] == before[2]
+    assert said == native
+    assert large == bool(native), (before, after)
+    ref = x.double().cpu() @ w.double().cpu().t()
+    np.testing.assert_allclose(out.cpu().numpy(), ref.float().numpy(), atol=3e-5, rtol=1e-5)

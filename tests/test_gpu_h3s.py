@@ -267,3 +267,60 @@ def test_backward_tn_contraction_on_split_f16(K1, K2, M, N):
         np.testing.assert_allclose(out.cpu().numpy(), ref.float().numpy(), atol=5e-5, rtol=1e-5)
         errs[mode] = (out.double().cpu() - ref).pow(2).mean().sqrt().item()
     assert errs[1] <= errs[0] * 1.05 + 1e-9, errs
+
+
+def _small_ws(problem, floats):
+    """A caller-supplied workspace on the first problem of a launch (ops._attach_ws then leaves it alone): the chunked
+    forms of the TN path at test-sized shapes instead of planes beyond the 128 MB one."""
+    ws = torch.empty(floats, dtype=torch.float32, device=dev())
+    problem.splitk_ws, problem.splitk_ws_floats = ws.data_ptr(), ws.numel()
+    return ws
+
+
+def test_backward_tn_one_segment_in_k_chunks_accumulates_and_adds_the_bias_once():
+    """dW = dY^T X over K = 2048 rows with a workspace of 512 * 512 + 1024 floats: (M + N) K + 1024 does not fit, the
+    chunk is (263168 - 1024) / 512 = 512 rows, so four launches of the skinny 32 x 32 tile (4 tiles of 128 x 128: below
+    H3_MIN_TILES / 2), each counted as a large-path launch and none as a skinny one; chunks 2 .. 4 accumulate onto
+    chunk 1, which itself accumulates onto the prior, and the bias goes in once."""
+    g = torch.Generator().manual_seed(2048 + 256)
+    K, M, N = 2048, 256, 256
+    a, w = _rand(g, K, M), _rand(g, K, N, scale=K ** -0.5)
+    prior, bias = _rand(g, M, N), _rand(g, N)
+    ref = prior.double() + a.double().t() @ w.double() + bias.double()
+    ops.set_h3_mode(1)
+    out = prior.clone().to(dev())
+    da, dw, db = a.to(dev()), w.to(dev()), bias.to(dev())          # (the problem keeps pointers, not tensors)
+    p = ops.gemm_problem([(da, dw)], out, ops.TN, accumulate=True, bias0=db)
+    ws = _small_ws(p, 512 * 512 + 1024)
+    lib = ops._lib.load()
+    n0, s0 = lib.isc_h3_launches(), _launches()
+    ops.gemm_bwd([p], ops.TN)
+    torch.cuda.synchronize()
+    assert lib.isc_h3_launches() - n0 == 4
+    assert _launches() == s0
+    np.testing.assert_allclose(out.cpu().numpy(), ref.float().numpy(), atol=5e-5, rtol=1e-5)
+    del ws
+
+
+def test_backward_tn_two_segments_that_do_not_fit_run_one_pass_per_segment():
+    """Segments of K = 1536 and 512 rows, M = N = 256, the same 263168-float workspace: the packed planes do not fit, so
+    one pass per segment in chunks of 512 rows - three launches for the first segment, one for the second.  Without
+    `accumulate` the first chunk overwrites C (filled with NaN here) and everything after it, pass 2 included, adds."""
+    g = torch.Generator().manual_seed(1536 + 512)
+    M, N = 256, 256
+    segs, ref = [], 0.0
+    for K in (1536, 512):
+        a, w = _rand(g, K, M), _rand(g, K, N, scale=K ** -0.5)
+        ref = ref + a.double().t() @ w.double()
+        segs.append((a.to(dev()), w.to(dev())))
+    ops.set_h3_mode(1)
+    out = torch.full((M, N), float('nan'), device=dev())
+    p = ops.gemm_problem(segs, out, ops.TN, accumulate=False)
+    ws = _small_ws(p, 512 * 512 + 1024)
+    lib = ops._lib.load()
+    n0 = lib.isc_h3_launches()
+    ops.gemm_bwd([p], ops.TN)
+    torch.cuda.synchronize()
+    assert lib.isc_h3_launches() - n0 == 4
+    np.testing.assert_allclose(out.cpu().numpy(), ref.float().numpy(), atol=5e-5, rtol=1e-5)
+    del ws

@@ -3,8 +3,12 @@ the backward NN / TN contractions) with a split-f16 engine forced per case - the
 kernel with 32 x 32 or 64 x 64 tiles (modes 3 / 4), or auto inside a weights scope - each case against an fp64 reference: ragged M, K-segments, partial
 column tiles, grouped problems, producer-written planes, accumulate.
 
-    python tools/fuzz_gemm_paths.py [seed] [cases]        (on the MI355X box; tests/test_gpu_fuzz.py runs a short one)
+    python tools/fuzz_gemm_paths.py [seed] [cases] [routes.txt]   (on the MI355X box; tests/test_gpu_fuzz.py runs a short one)
+
+With a third argument every case appends one line to that file - kind, shapes, mode, the SHA-256 of the output tensors'
+bytes and the deltas of the five launch counters: two builds route and compute alike when their files are identical.
 """
+import hashlib
 import os
 import random
 import sys
@@ -14,8 +18,13 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from insenticap_model_amd import ops  # noqa: E402
 
-def run(seed=0, cases=120, verbose=True):
+COUNTERS = ('isc_h3_launches', 'isc_h3x_launches', 'isc_h3s_launches', 'isc_gemv_launches', 'isc_h3_f16a_launches')
+
+
+def run(seed=0, cases=120, verbose=True, routes=None):
     dev = torch.device('cuda:0')
+    lib = ops._lib.load()
+    def counters(): return [getattr(lib, c)() for c in COUNTERS]
     random.seed(seed)
     g = torch.Generator().manual_seed(1)
     def R(*s, scale=1.0): return ((torch.rand(*s, generator=g) * 2 - 1) * scale)
@@ -29,6 +38,7 @@ def run(seed=0, cases=120, verbose=True):
         ops.set_h3_mode(mode)
         scope = ops.h3_weights_scope(dev)
         scope.__enter__()
+        cnt0, shapes, result = counters(), None, []
         try:
             if kind in ('linear', 'linear3'):
                 nprob = 1 if kind == 'linear' else random.randint(2, 3)
@@ -49,6 +59,7 @@ def run(seed=0, cases=120, verbose=True):
                     refs.append(ref); outs.append(o)
                 ops.linear_fwd(probs)
                 torch.cuda.synchronize()
+                shapes, result = (M, [o.shape[1] for o in outs], Ks), outs
                 for o, r in zip(outs, refs):
                     err = (o.double().cpu() - r).abs().max().item()
                     if not err < 3e-5: bad += 1; print('BAD', kind, M, Ks, err)
@@ -66,6 +77,7 @@ def run(seed=0, cases=120, verbose=True):
                 planes = torch.zeros(2, M, H, dtype=torch.float16, device=dev)
                 ops.lstm_fwd(dseg, b1.to(dev), b2.to(dev), c0.to(dev), h, c, h_planes=planes)
                 torch.cuda.synchronize()
+                shapes, result = (M, H, Ks), [h, c, planes]
                 err = max((h.double().cpu() - h_ref).abs().max().item(), (c.double().cpu() - c_ref).abs().max().item())
                 # planes decode back to h
                 buf = planes.cpu().view(-1).float().view(M, H // 32, 2, 32)
@@ -90,6 +102,7 @@ def run(seed=0, cases=120, verbose=True):
                 ops.gemm_bwd([ops.gemm_problem([(a.to(dev), w.to(dev)) for a, w in zip(As, Ws)], out, lay,
                                                accumulate=True)], lay)
                 torch.cuda.synchronize()
+                shapes, result = (M, N, Ks), [out]
                 err = (out.double().cpu() - ref).abs().max().item()
                 if not err < 5e-5: bad += 1; print('BAD', kind, mode, M, N, Ks, err)
             else:
@@ -103,6 +116,7 @@ def run(seed=0, cases=120, verbose=True):
                 lg = torch.empty(M, V, device=dev)
                 ops.vocab_fwd(h.to(dev), W.to(dev), b.to(dev), pm, ps, pi, lg)
                 torch.cuda.synchronize()
+                shapes, result = (M, V, K), [lg, pm, ps, pi]
                 err = (lg.double().cpu() - ref).abs().max().item()
                 mx = pm.max(1).values
                 lse = mx + torch.log((ps * torch.exp(pm - mx[:, None])).sum(1))
@@ -114,6 +128,11 @@ def run(seed=0, cases=120, verbose=True):
             bad += 1; print('EXC', kind, M, Ks, repr(e)[:200])
         finally:
             scope.__exit__(None, None, None)
+        if routes:
+            sha = hashlib.sha256()
+            for t in result: sha.update(t.cpu().contiguous().view(torch.uint8).numpy().tobytes())
+            with open(routes, 'a') as f:
+                print(it, kind, shapes, mode, sha.hexdigest(), [b - a for a, b in zip(cnt0, counters())], file=f)
     ops.set_h3_mode(1)
     if verbose:
         print('cases done, bad =', bad, 'large / skinny split-f16 launches', ops._lib.load().isc_h3_launches(),
@@ -122,4 +141,5 @@ def run(seed=0, cases=120, verbose=True):
 
 
 if __name__ == '__main__':
-    sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 0, int(sys.argv[2]) if len(sys.argv) > 2 else 120) else 0)
+    sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 0, int(sys.argv[2]) if len(sys.argv) > 2 else 120,
+                      routes=sys.argv[3] if len(sys.argv) > 3 else None) else 0)
