@@ -496,8 +496,10 @@ typedef struct {
      * isc_step_fwd hands it to the att-LSTM (isc_lstm_problem.pre_div) and to both scans (isc_scan_problem.row_div);
      * everything else of the step is per row as always.  rows % row_div == 0; not with pair_rows_c and not with the
      * fused gate scan (gate_Gc / gate_Gs) of the general kernels.  isc_rows_step_fwd ignores it: the few-row step
-     * takes isc_rows_ext.row_div.  0 or 1 = off. */
-    int32_t row_div, _pad3;
+     * takes isc_rows_ext.row_div.  0 or 1 = off.
+     * pre_rows != 0 (with row_div > 1, isc_step_fwd only): pre1 holds one row per decode ROW all the same - grouped
+     * teacher-forced training, whose sentiment labels (part of the hoisted term) differ between an image's captions. */
+    int32_t row_div, pre_rows;
 } isc_step_plan;
 
 int isc_step_fwd(const isc_step_plan *plan_host, void *stream);
@@ -665,6 +667,10 @@ typedef struct {
     int64_t splitk_ws_floats;
     float *de_c, *de_s;                 /* optional [rows,R] / [rows,Mw]: this step's d e of the two scans (isc_scan_bwd_problem.de_out);
                                            dP_att / dP_w and dV_att / dV_w may then be NULL (isc_attn_dp_from_de, _dv_from_alpha) */
+    int32_t row_div, _pad;              /* > 1: rows = images x row_div (isc_step_plan.row_div): att_p / att_e, words_p /
+                                           words_e and label_w hold one entry per IMAGE - handed to both scans
+                                           (isc_scan_bwd_problem.row_div: dP_* / dV_* must be NULL); everything else is
+                                           per row.  rows % row_div == 0, not with pair_rows_c.  0 or 1 = off */
 } isc_step_bwd_plan;
 
 int isc_step_bwd(const isc_step_bwd_plan *plan_host, void *stream);
@@ -694,7 +700,13 @@ typedef struct {
     int32_t R, A, D, accumulate;
     float *dP, *dV, *dq, *dw_rows;
     float *de_out;            /* optional [B,R]: this step's d e (softmax backward); required when dP is NULL */
-    int32_t rows, _pad;       /* rows of THIS problem; 0 = the launch's B (see isc_scan_problem.rows) */
+    int32_t rows;             /* rows of THIS problem; 0 = the launch's B (see isc_scan_problem.rows) */
+    /* row_div > 1: the rows come in groups of row_div that attended to the SAME features (isc_scan_problem.row_div):
+     * P, V and q2 hold one entry per group and row b reads entry b / row_div; q, alpha, dout, dq, dw_rows and de_out
+     * stay per row - the per-row arithmetic, and the bits, of the plain launch on the expanded tensors.  dP and dV must
+     * then be NULL (row_div workgroups would read-modify-write one image's entry: ISC_E_SHAPE) - they are formed after
+     * the sweep by isc_attn_dp_from_de_group / isc_attn_dv_from_alpha_group.  rows % row_div == 0; 0 or 1 = per row. */
+    int32_t row_div;
 } isc_scan_bwd_problem;
 
 int isc_attn_scan_bwd(const isc_scan_bwd_problem *probs_host, int n_prob, int B, void *stream);
@@ -710,6 +722,19 @@ int isc_attn_dv_from_alpha(const float *alpha, int64_t alpha_ld_b, int64_t alpha
  * region chunks: the reference encoder's 14 x 14 = 196 regions are six chunks at A = 512), any A, D with A % 4 == D % 4 == 0. */
 int isc_attn_dp_from_de(const float *P, const float *q, const float *q2, const float *w, const float *de,
                         int B, int T, int R, int A, float *dP, void *stream);
+/* The two reductions over the rows of an IMAGE (isc_scan_bwd_problem.row_div = group): the B decode rows are B / group
+ * images x group rows, row i*group + j = row j of image i; alpha, dout, q and de stay per row, P, q2, dV and dP hold one
+ * entry per image:
+ *   dV[i,r,:] = sum_j sum_t alpha[(i*group + j)*alpha_ld_b + t*alpha_ld_t + r] * dout[(t*dout_step_rows + i*group + j)*D + :]
+ *   dP[i,r,a] = sum_j sum_t de[(t*B + i*group + j)*R + r] * w[a] * (1 - tanh^2(P[i,r,a] + q[(t*B + i*group + j)*A + a] (+ q2[i*A + a])))
+ * added in ONE fixed order - j ascending outermost, t = T-1 down to 0 inside - by one thread per output element (no
+ * atomics: two runs give the same bits).  group == 1 is isc_attn_dv_from_alpha / isc_attn_dp_from_de, which forward
+ * here: same kernels, same bits.  The LDS image of alpha / de is [group*T][regions of a chunk]: group*T beyond the 15000
+ * rows that 60000 bytes hold for one region, or B % group != 0: ISC_E_SHAPE. */
+int isc_attn_dv_from_alpha_group(const float *alpha, int64_t alpha_ld_b, int64_t alpha_ld_t, const float *dout,
+                                 int B, int group, int T, int R, int D, float *dV, int dout_step_rows, void *stream);
+int isc_attn_dp_from_de_group(const float *P, const float *q, const float *q2, const float *w, const float *de,
+                              int B, int group, int T, int R, int A, float *dP, void *stream);
 
 /* Backward of isc_gate_mix_fwd: dv = beta*dfeat, ds = (1-beta)*dfeat, dz, per-row partials of
  * d w (dw_rows [B,A]) and d w_bias (db_rows [B]). */

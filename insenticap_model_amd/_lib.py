@@ -54,7 +54,7 @@ class ScanBwdProblem(C.Structure):
                 ('w', C.c_void_p), ('alpha', C.c_void_p), ('dout', C.c_void_p), ('alpha_ld', C.c_int64),
                 ('R', C.c_int32), ('A', C.c_int32), ('D', C.c_int32), ('accumulate', C.c_int32),
                 ('dP', C.c_void_p), ('dV', C.c_void_p), ('dq', C.c_void_p), ('dw_rows', C.c_void_p),
-                ('de_out', C.c_void_p), ('rows', C.c_int32), ('_pad', C.c_int32)]
+                ('de_out', C.c_void_p), ('rows', C.c_int32), ('row_div', C.c_int32)]
 
 
 class ScanGateArgs(C.Structure):
@@ -83,7 +83,7 @@ class StepPlan(C.Structure):
                  ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)] +
                 _f('h1_prev_hi h1_prev_lo h2_prev_hi h2_prev_lo h1_hi h1_lo h2_hi h2_lo '
                    'v_hi v_lo s_hi s_lo f_hi f_lo words_ids', C.c_void_p) + [('words_ids_ld', C.c_int64)] +
-                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c _pad2 row_div _pad3', C.c_int32))
+                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c _pad2 row_div pre_rows', C.c_int32))
 
 
 class StepBwdPlan(C.Structure):
@@ -95,7 +95,8 @@ class StepBwdPlan(C.Structure):
                 _f('alpha_c_ld alpha_s_ld beta_ld', C.c_int64) +
                 _f('dhd dG1 dG2 dG1_sum d_feat dh1 dv ds dh2_rec dh1_rec dc1_in dc2_in dc1_out dc2_out '
                    'dqa dqw dz dP_att dV_att dP_w dV_w dwc_rows dws_rows dwg_rows dbg_rows splitk_ws',
-                   C.c_void_p) + [('splitk_ws_floats', C.c_int64), ('de_c', C.c_void_p), ('de_s', C.c_void_p)])
+                   C.c_void_p) + [('splitk_ws_floats', C.c_int64), ('de_c', C.c_void_p), ('de_s', C.c_void_p),
+                              ('row_div', C.c_int32), ('_pad', C.c_int32)])
 
 
 class BeamMergeArgs(C.Structure):
@@ -231,6 +232,10 @@ SIGNATURES = {
                                          C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     'isc_attn_dp_from_de': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'isc_attn_dv_from_alpha_group': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    'isc_attn_dp_from_de_group': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'isc_gate_mix_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -214,8 +214,11 @@ def _classify(cap, S, L):
 
 
 # ------------------------------------------------------------------------------ forward
-def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks, lazy=None):
-    """Returns (logp [B,T,V], S). tokens_in [B,T]: ground-truth inputs (column 0 = <SOS>) - or, for the sampled
+def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks, lazy=None,
+                   group=1):
+    """group = n > 1 (forward_xe captions_per_image): the prologue runs on the I images, the unroll on the I*n rows of
+    tokens_in; the step plans carry row_div = n.
+    Returns (logp [B,T,V], S). tokens_in [B,T]: ground-truth inputs (column 0 = <SOS>) - or, for the sampled
     roll-out with gradients, a dict {'T', 'u' (uniforms [B,T]) or 'forced' (raw draws [B,T])}: every step then
     draws its own next token on the device (isc_rollout_finalize) while the activations the backward pass
     needs are kept, so sampling and the differentiable forward are ONE unroll (captioner.py:290-349 does the
@@ -225,7 +228,7 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     [B,T] straight from the raw logits + tile statistics (isc_gather_logp_raw; the bits the tensor would have held), and
     the backward recomputes the softmax term from them (isc_logsoftmax_bwd_raw)."""
     p = cap._p()
-    P = cap._prologue(p, mode, fc, att, cpt_words, senti_words, senti_labels, masks)
+    P = cap._prologue(p, mode, fc, att, cpt_words, senti_words, senti_labels, masks, group=group)
     Wd, V = cap.settings['word_emb_dim'], cap.vocab_size
     sampling = isinstance(tokens_in, dict)
     B, T = (P.B, tokens_in['T']) if sampling else tokens_in.shape
@@ -239,7 +242,8 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     # skipped row would have written must read as ZERO (gradients) or at least finite (activations next to a zero
     # gradient in the contractions over all T*B rows) - every buffer such a row belongs to comes out of a fill.
     counts = cap.__dict__.get('_row_counts')
-    if counts is not None and (sampling or lazy is None or sched or len(counts) != T or counts[0] != B):
+    # (captions per image: the rows are image-major, not sorted by length - the full unroll, same loss and gradients)
+    if counts is not None and (sampling or lazy is None or sched or len(counts) != T or counts[0] != B or group > 1):
         counts = None
     S.row_counts = counts
     L = S.L = _Rows([(0, B, T)], counts)
@@ -462,6 +466,7 @@ def _step_bwd_plan(cap, p, Pc, Ps):
         setattr(bp, field, p[key].data_ptr())
     if Pc is not None:
         bp.R, bp.att_p, bp.att_e = Pc.R, Pc.att_p3.data_ptr(), Pc.att_e3.data_ptr()
+        bp.row_div = Pc.row_div if Pc.row_div > 1 else 0       # rows = images x row_div: att_p / att_e one entry per image
     if Ps is not None:
         bp.Mw, bp.words_p, bp.words_e = Ps.Mw, Ps.words_p3.data_ptr(), Ps.words_e3.data_ptr()
         bp.label_w = ops.ptr(Ps.label_w)
@@ -596,12 +601,13 @@ def _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, label_e, lo=0, d_label_e=Non
     return d_label_w
 
 
-def _scan_bwd(cap, p3, e3, alpha, q, dfeat, de, w, step_rows=0, q2=None):
+def _scan_bwd(cap, p3, e3, alpha, q, dfeat, de, w, step_rows=0, q2=None, group=1):
     """An attention's dV = sum_t alpha_t x d feat_t and dP from every step's d e, formed once after the sweep (dfeat:
-    [T, B, D], or the rows of a [T, step_rows, D] stack).  Returns (dP, dV), shaped as the projections p3 / e3."""
+    [T, B, D], or the rows of a [T, step_rows, D] stack).  Returns (dP, dV), shaped as the projections p3 / e3 - with
+    group = n > 1 those hold one entry per image and the sums run over the image's n rows as well."""
     dP, dV = cap._new(*p3.shape), cap._new(*e3.shape)
-    ops.attn_dv_from_alpha(alpha, dfeat, dV, step_rows=step_rows)
-    ops.attn_dp_from_de(p3, q, w, de, dP, q2=q2)
+    ops.attn_dv_from_alpha(alpha, dfeat, dV, step_rows=step_rows, group=group)
+    ops.attn_dp_from_de(p3, q, w, de, dP, q2=q2, group=group)
     return dP, dV
 
 
@@ -764,6 +770,16 @@ def _dropout_bwd(S, dhd):
         ops.relu_mask_bwd(dhd, None, dhd, keep_mask=S.keep.view(dhd.shape), scale=S.out_scale)
 
 
+def _group_sum(x, n):
+    """[I*n, C] per-row gradients -> [I, C] per image: row j = 0 .. n-1 of an image added in that order, whatever n (a
+    chain of n - 1 elementwise additions on [I, C]: a few KB, not a hot path, and the order is the documented one)."""
+    x3 = x.view(-1, n, x.shape[1])
+    out = x3[:, 0].clone()
+    for j in range(1, n):
+        out += x3[:, j]
+    return out
+
+
 # ------------------------------------------------------------------------------ backward
 def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     """Returns {param name: gradient}.  The gradient of the log-probs arrives as `dlogp` [B,T,V] (contiguous; None when
@@ -816,7 +832,7 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     dG1_sum = D.dG1_sum
     if has_c:
         dP_att, dV_att = _scan_bwd(cap, P.att_p3, P.att_e3, S.aC, S.qa, D.dv if gate else D.d_feat, D.de_c,
-                                   p['attention.cont_att.att_alpha.weight'])
+                                   p['attention.cont_att.att_alpha.weight'], group=P.row_div)
     if has_s:
         dP_w, dV_w = _scan_bwd(cap, P.words_p3, P.words_e3, S.aS, S.qw, D.ds if gate else D.d_feat, D.de_s,
                                p['attention.senti_att.word_alpha.weight'], q2=P.label_w)
@@ -837,8 +853,13 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
         tok_tb = pack(tok_tb.view(TB, 1)).view(-1)
         if pk['Np'] > pk['N']:
             tok_tb[pk['N']:].fill_(cap.pad_id)
-    _lstm_dw(g, dG1f, dG2f, h1_prev, h1_cur_l, h2_prev, xt_tb, feat_tb, dG1_sum, P.fc_e, P.label_e)
+    # (captions per image: dG1_sum is per row - its partner is fc_e with each image's row repeated, and d fc_e [I*n, E]
+    # sums over an image's n rows, in row order, into the per-image [I, E])
+    _lstm_dw(g, dG1f, dG2f, h1_prev, h1_cur_l, h2_prev, xt_tb, feat_tb, dG1_sum, P.fc_e if P.fc_rows is None else P.fc_rows,
+             P.label_e)
     d_fc_e, d_label_e, dEmb = _dx_bwd(cap, g, dG1f, dG1_sum, tok_tb, P.label_e is not None)
+    if P.row_div > 1:
+        d_fc_e = _group_sum(d_fc_e, P.row_div)
     if has_c:
         _content_att_grads(g, D.dqa, h1_cur, D.dwc_rows)
     if has_s:
@@ -855,7 +876,7 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     # ---- prologue backward
     if d_label_e is not None:
         ops.embed_relu_bwd(p['senti_label_embed.0.weight'], P.label_ids, d_label_e, g.gout('senti_label_embed.0.weight'),
-                           B, keep_mask=P.m_label, mask_scale=P.sc)
+                           d_label_e.shape[0], keep_mask=P.m_label, mask_scale=P.sc)
     if has_c:
         _region_embed_bwd(cap, g, P, dP_att, dV_att)
     if has_s:
@@ -863,7 +884,7 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     if P.fc_pre is not None:
         _fc_embed_bwd(cap, g, P, d_fc_e, d_fc_feats)
     if P.fc_pre is None or d_cpt_feats is not None:
-        d_cpt = new(B, E)
+        d_cpt = new(P.B, E)
         _cpt_bwd(cap, P, d_fc_e, d_cpt_feats, d_cpt)
         _cpt2fc_bwd(cap, g, d_cpt, (P,), dEmb)
     return g.finish()
@@ -875,9 +896,12 @@ class DecodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks,
                 names, lazy, *params):
+        group = 1
+        if isinstance(mode, tuple):                  # ('xe', n): forward_xe with captions_per_image = n
+            mode, group = mode
         with torch.no_grad():
             logp, S = _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels,
-                                     ss_prob, masks, lazy)
+                                     ss_prob, masks, lazy, group)
         S.P.fc_pre = cap.fc_feats if mode != 'seq2seq' else None
         S.P.cpt_pre = cap.cpt_feats
         cap._last_sample = getattr(S, 'sample', None)
@@ -908,7 +932,8 @@ class DecodeFn(torch.autograd.Function):
         return (None,) * 12 + grads
 
 
-def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_labels, ss_prob, masks, targets=None):
+def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_labels, ss_prob, masks, targets=None,
+                 group=1):
     # a backward will run: float16 features become fp32 once, here - forward and backward read that copy (the dW
     # contractions and the exact engine read fp32), so losses and gradients are those of feats.float()
     fc, att = (None if x is None else cap._f32(x) for x in (fc, att))
@@ -921,8 +946,8 @@ def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_lab
     lazy = None
     if cap.__dict__.get('_token_logprobs'):
         lazy = ids[:, 1:].contiguous() if targets is None else cap._ids(targets).contiguous()
-    outs = DecodeFn.apply(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks,
-                          names, lazy, *params)
+    outs = DecodeFn.apply(cap, mode if group == 1 else (mode, group), fc, att, cpt_words, senti_words, tokens_in,
+                          senti_labels, ss_prob, masks, names, lazy, *params)
     logp = outs[0]
     cap.cpt_feats = outs[1]
     if mode != 'seq2seq':

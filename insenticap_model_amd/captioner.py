@@ -55,7 +55,11 @@ class _Pro:
     label_e = None   # [B,W]   sentiment-label embedding (added to every xt)
     label_w = None   # [B,A]   label2word(label_e): step-invariant term of the senti attention
     pre1 = None      # [B,4H]  fc_e W_fc^T + label_e W_x^T + b_ih + b_hh: step-invariant att-LSTM input
-    row_div = 1      # decode rows per image (forward_rl captions_per_image): everything above is per IMAGE
+    row_div = 1      # decode rows per image (captions_per_image of forward_rl / forward_xe): the image's tensors above
+                     # hold one entry per IMAGE
+    pre_rows = False  # row_div > 1, forward_xe: label_e / pre1 (and fc_rows) are per ROW all the same - the labels differ
+                      # between an image's captions
+    fc_rows = None   # [B*row_div,E] fc_e, each image's row repeated (forward_xe captions_per_image: pre1's GEMM operand)
     tab = None       # [V,4H]  relu(Emb) W_x^T (inference only): replaces the word-embedding K-segment
     gate_Gc = None   # [B*R,A] att_e through cont2att.weight (few-row inference: isc_attn_scan_gate_fwd)
     gate_Gs = None   # [B*M,A] / [V,A] words_e through senti2att.weight
@@ -226,8 +230,11 @@ class Captioner(nn.Module):
     ROLLOUT_GRAPH_MAX_ROWS = 256   # greedy eval roll-outs up to this many captions are served from HIP graphs
 
     def _prologue(self, p, mode, fc=None, att=None, cpt_words=None, senti_words=None, senti_labels=None,
-                  masks=None, want_table=False, words_table=False, gate_rows=0, pre1_out=None):
-        """want_table: False | 'cached' (use the embedding table only if already built) | 'build'.
+                  masks=None, want_table=False, words_table=False, gate_rows=0, pre1_out=None, group=1):
+        """group = n > 1 (forward_xe captions_per_image, 'xe' only): fc / att / cpt_words hold one entry per image and so
+        does everything derived from them (dropout masks 'fc' [I,E] and 'att' [I*R,E] included); senti_labels, the 'label'
+        mask, label_e and the hoisted att-LSTM term pre1 are per caption row, [I*n, ...] (P.pre_rows).
+        want_table: False | 'cached' (use the embedding table only if already built) | 'build'.
         words_table: serve the sentiment words from the vocabulary-sized tables (no dropout on them, no autograd).
         gate_rows: number of decode rows of an INFERENCE call (0: training / not applicable): up to
         GATE_FUSED_MAX_ROWS the scans' features are also carried through the gate's projections here, once, so that
@@ -272,11 +279,14 @@ class Captioner(nn.Module):
                 first.append(ops.linear_problem([(cmean, p['cpt2fc.0.weight'])], cpt, p['cpt2fc.0.bias'],
                                                 relu=True))
         ops.linear_fwd(first)
+        Bl = B * group                                    # rows of the per-caption tensors
         if senti_labels is not None:
-            P.label_e = self._new(B, Wd)
+            P.label_e = self._new(Bl, Wd)
             P.label_ids = self._ids(senti_labels).reshape(-1)
+            if group > 1 and P.label_ids.numel() == B:      # one label per image: every caption of the image carries it
+                P.label_ids = P.label_ids.repeat_interleave(group)
             ops.embed_relu_fwd(p['senti_label_embed.0.weight'], P.label_ids, P.label_e)
-            m, sc = mask_for('label', B, Wd)
+            m, sc = mask_for('label', Bl, Wd)
             P.m_label, P.sc = m, sc
             if m is not None:
                 P.label_e = P.label_e * (m.float() * sc)   # [B,W] elementwise, train mode only
@@ -332,12 +342,14 @@ class Captioner(nn.Module):
         # xt = relu(Emb[it]) + label_e): fc_e W_fc^T + label_e W_x^T + b_ih + b_hh is computed once.
         H = st['rnn_hid_dim']
         Wih = p['att_lstm.weight_ih']
-        segs = [(P.fc_e, Wih[:, H:H + E])]
+        if group > 1:
+            P.row_div, P.pre_rows, P.fc_rows = group, True, P.fc_e.repeat_interleave(group, 0)
+        segs = [(P.fc_e if group == 1 else P.fc_rows, Wih[:, H:H + E])]
         if P.label_e is not None:
             segs.append((P.label_e, Wih[:, H + E:]))
         # (pre1_out: the caller's [B,4H] row block of a larger buffer - the merged unroll of two sibling calls keeps
         # both calls' rows in one [B1+B2,4H] tensor)
-        P.pre1 = self._new(B, 4 * H) if pre1_out is None else pre1_out
+        P.pre1 = self._new(Bl, 4 * H) if pre1_out is None else pre1_out
         ops.linear_fwd([ops.linear_problem(segs, P.pre1, p['att_lstm.bias_ih'], p['att_lstm.bias_hh'])])
         if want_table:
             P.tab = self._embedding_table(p, build=(want_table == 'build'))
@@ -474,6 +486,7 @@ class Captioner(nn.Module):
         ws = ops.splitk_ws(self._dev)
         pl.splitk_ws, pl.splitk_ws_floats = ws.data_ptr(), ws.numel()
         pl.row_div = P.row_div if P.row_div > 1 else 0       # rows = images x row_div: P holds one entry per image
+        pl.pre_rows = int(P.pre_rows)                        # (... but pre1 one per row: forward_xe captions_per_image)
         return pl
 
     def _step(self, p, P, ws, xt, h_cur, c_cur, h_nxt, c_nxt, alpha_c=None, alpha_s=None, beta=None,
@@ -560,7 +573,7 @@ class Captioner(nn.Module):
             segs.insert(1, (xt, Wih[:, H + E:]))
         ops.lstm_fwd(segs, None, None, c_cur[0], h_nxt[0], c_nxt[0], gates_out=save.get('g1'),
                      pre=P.pre1, tab=P.tab, tab_ids=tok if P.tab is not None else None, h_planes=pn(0),
-                     pre_div=P.row_div)
+                     pre_div=1 if P.pre_rows else P.row_div)
         h1 = h_nxt[0]
         has_cont, has_senti = P.att_e3 is not None, P.words_e3 is not None
         probs, scans = [], []
@@ -761,16 +774,51 @@ class Captioner(nn.Module):
                 self.__dict__['_row_counts'] = prev
         return scope()
 
-    def forward_xe(self, fc_feats, att_feats, cpt_words, captions, senti_labels, ss_prob=0.0, _masks=None, _targets=None):
+    def forward_xe(self, fc_feats, att_feats, cpt_words, captions, senti_labels, ss_prob=0.0, _masks=None, _targets=None,
+                   captions_per_image=1):
         """(_targets: test hook for token_logprobs() - the criterion's targets when `captions` carries replayed FED tokens
-        instead of the ground truth; default captions[:, 1:].)"""
+        instead of the ground truth; default captions[:, 1:].)
+        `captions_per_image=n` > 1 trains on n captions per image without repeating the image: `fc_feats`, `att_feats`
+        and `cpt_words` hold one entry per image, [I, ...]; `captions` is [I*n, L] with row i*n + j = caption j of image i
+        (the layout of `repeat_interleave(n, 0)`, as in `forward_rl`); `senti_labels` is [I*n], one per caption, or [I],
+        one per image.  The embedded regions, their projection and the embedded fc vector are computed, kept and
+        differentiated once per image; the decode and its backward sweep run on the I*n rows, and an image's dP / dV sum
+        over its rows in a fixed order (row ascending, steps from the last to the first inside).  The return value is per
+        row, [I*n, T, V] (or [I*n, T] under `token_logprobs()`); the `fc_feats` / `cpt_feats` attributes - and their
+        incoming gradients - are per image, [I, E].  With dropout off, or with explicit `_masks` (keys 'fc' [I,E], 'att'
+        [I*R,E] per image, 'label' and 'out<t>' per row), it is the function of the same call on the repeated inputs with
+        each per-image mask repeated.  The ONE semantic difference, in training mode: the dropout masks of the per-image
+        tensors are drawn once per image, where the repeated form draws one per copy.  Scheduled sampling works as
+        always (it is per row).  The rows are image-major, not sorted by length: an active `row_counts(...)` is
+        ignored - the full unroll gives the same loss and gradients, the criterion masks by row.  1 = the plain call."""
+        n_cap = self._check_group_xe(captions_per_image, fc_feats, captions, senti_labels)
         if self._needs_grad():
             from .autograd import xe_with_grad
             return xe_with_grad(self, 'xe', fc_feats, att_feats, cpt_words, None, captions, senti_labels,
-                                ss_prob, _masks, _targets)
+                                ss_prob, _masks, _targets, group=n_cap)
         p = self._p()
-        P = self._prologue(p, 'xe', fc_feats, att_feats, cpt_words, None, senti_labels, _masks)
+        P = self._prologue(p, 'xe', fc_feats, att_feats, cpt_words, None, senti_labels, _masks, group=n_cap)
         return self._teacher_forced(p, P, self._ids(captions)[:, :-1], ss_prob, _masks)
+
+    @staticmethod
+    def _check_group_xe(n, fc_feats, captions, senti_labels):
+        """forward_xe's `captions_per_image`, checked before anything touches the device.  Returns it as an int."""
+        if isinstance(n, bool) or not hasattr(n, '__index__'):
+            raise ValueError('captions_per_image must be an integer >= 1, got %r' % (n,))
+        n = int(n)
+        if n < 1:
+            raise ValueError('captions_per_image must be an integer >= 1, got %r' % (n,))
+        if n == 1:
+            return 1
+        images, rows = int(fc_feats.shape[0]), int(captions.shape[0])
+        if rows != images * n:
+            raise ValueError('captions_per_image=%d: %d images need %d caption rows (row i*n + j = caption j of image i), '
+                             'got %d' % (n, images, images * n, rows))
+        labels = None if senti_labels is None else int(senti_labels.numel())
+        if labels is not None and labels not in (images, rows):
+            raise ValueError('captions_per_image=%d: senti_labels must hold one label per caption (%d) or per image (%d), '
+                             'got %d' % (n, rows, images, labels))
+        return n
 
     def forward_seq2seq(self, senti_captions, cpt_words, senti_words, senti_labels, ss_prob=0.0, _masks=None,
                         _targets=None):
@@ -784,13 +832,16 @@ class Captioner(nn.Module):
 
     def forward_xe_seq2seq(self, fc_feats, att_feats, cpt_words, captions, senti_labels, ss_prob,
                            s_captions, s_cpt_words, s_senti_words, s_senti_labels, s_ss_prob=None,
-                           _masks=None, _s_masks=None, _targets=None, _s_targets=None):
+                           _masks=None, _s_masks=None, _targets=None, _s_targets=None, captions_per_image=1):
         """`forward_xe(...)` and `forward_seq2seq(...)` of ONE training iteration (train_xe.py:160-181,
         models/decoder.py:138-157) as one call: returns (pred, pred2), leaves `fc_feats` / `cpt_feats` as the XE call
         leaves them (the domain-align loss reads them right after it, train_xe.py:163) and the seq2seq call's
         `cpt_feats` in `s2s_cpt_feats`.  With gradients the two unrolls share one step chain (autograd_pair: both LSTM
         cells, the classifier and every backward contraction once over the rows of both calls); without, or when
         `self.pair_unrolls` is False, it is exactly the two calls in the reference's order."""
+        if self._check_group_xe(captions_per_image, fc_feats, captions, senti_labels) > 1:
+            raise ValueError('captions_per_image > 1 is not built for the merged xe_seq2seq step: call forward_xe and '
+                             'forward_seq2seq (train.xe_forward_backward does)')
         s_ss_prob = ss_prob if s_ss_prob is None else s_ss_prob
         from .autograd_pair import pair_applicable, pair_with_grad
         if self._needs_grad() and self.pair_unrolls is not False and pair_applicable(self, _masks, _s_masks):

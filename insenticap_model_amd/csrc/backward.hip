@@ -392,6 +392,7 @@ struct DevScanBwd {
     int R, A, D, accumulate;
     float *dP, *dV, *dq, *dw_rows, *de_out;
     int rows;                 // rows of THIS problem (the grid spans the longest problem of the launch)
+    int row_div;              // rows per image of the per-image P / V / q2 (isc_scan_bwd_problem.row_div; 1: per row)
 };
 struct DevScanBwdLaunch {
     DevScanBwd p[2];
@@ -421,8 +422,9 @@ __global__ __launch_bounds__(1024) void attn_scan_bwd_kernel(const DevScanBwdLau
     const int A4 = A >> 2, D4 = D >> 2;
     float *de = smem;                         // [R]
     float *red = smem + ((R + 3) & ~3);       // [2][ngrp][A]
-    const float4 *Vb = reinterpret_cast<const float4 *>(S.V + (long long)b * R * D);
-    const float4 *Pb = reinterpret_cast<const float4 *>(S.P + (long long)b * R * A);
+    const int bi = S.row_div > 1 ? b / S.row_div : b;          // the image of this row: P / V / q2 are per image
+    const float4 *Vb = reinterpret_cast<const float4 *>(S.V + (long long)bi * R * D);
+    const float4 *Pb = reinterpret_cast<const float4 *>(S.P + (long long)bi * R * A);
     const float4 *dout4 = reinterpret_cast<const float4 *>(S.dout + (long long)b * D);
     const float *alpha = S.alpha + (long long)b * S.alpha_ld;
 
@@ -471,7 +473,7 @@ __global__ __launch_bounds__(1024) void attn_scan_bwd_kernel(const DevScanBwdLau
     if (grp < ngrp) {
         float4 qa = reinterpret_cast<const float4 *>(S.q + (long long)b * A)[a4];
         if (S.q2) {
-            const float4 t = reinterpret_cast<const float4 *>(S.q2 + (long long)b * A)[a4];
+            const float4 t = reinterpret_cast<const float4 *>(S.q2 + (long long)bi * A)[a4];
             qa.x += t.x; qa.y += t.y; qa.z += t.z; qa.w += t.w;
         }
         const float4 wa = reinterpret_cast<const float4 *>(S.w)[a4];
@@ -511,8 +513,9 @@ extern "C" int isc_attn_scan_bwd(const isc_scan_bwd_problem *pr, int n_prob, int
     {   // P / V rows by non-temporal loads once they exceed what stays in the Infinity Cache next to the accumulated
         // dP / dV (attention.hip, isc_attn_scan_fwd): XE iteration at B = 1024 19.9 -> 19.6 ms, B = 512 unchanged
         long long streamed = 0;
-        for (int i = 0; i < n_prob; ++i)
-            streamed += (long long)(pr[i].rows > 0 ? pr[i].rows : B) * pr[i].R * ((long long)pr[i].A + pr[i].D) * 4;
+        for (int i = 0; i < n_prob; ++i)     // (grouped problems: bytes per IMAGE, as isc_attn_scan_fwd counts them)
+            streamed += (long long)(pr[i].rows > 0 ? pr[i].rows : B) / (pr[i].row_div > 1 ? pr[i].row_div : 1) * pr[i].R *
+                        ((long long)pr[i].A + pr[i].D) * 4;
         L.nt = streamed > (128LL << 20);
     }
     size_t lds = 0;
@@ -525,6 +528,8 @@ extern "C" int isc_attn_scan_bwd(const isc_scan_bwd_problem *pr, int n_prob, int
         if (!q.P || !q.V || !q.q || !q.w || !q.alpha || !q.dout || !q.dq || !q.dw_rows)
             return ISC_E_NULL;                     // (dV / dP may be null: isc_attn_dv_from_alpha / isc_attn_dp_from_de)
         if (!q.dP && !q.de_out) return ISC_E_NULL;
+        // rows of one image: its dP / dV entry would be read-modify-written by row_div workgroups at once
+        if (q.row_div > 1 && (q.dP || q.dV || L.p[i].rows % q.row_div)) return ISC_E_SHAPE;
         if (q.R <= 0 || q.A <= 0 || q.D <= 0 || q.A > 1024) return ISC_E_SHAPE;
         if ((q.A & 3) || (q.D & 3) || (1024 % (q.A / 4)) != 0 || (1024 % (q.D / 4)) != 0) return ISC_E_SHAPE;
         if (!isc_aligned16(q.P) || !isc_aligned16(q.V) || (q.dP && !isc_aligned16(q.dP)) || (q.dV && !isc_aligned16(q.dV)) ||
@@ -534,6 +539,7 @@ extern "C" int isc_attn_scan_bwd(const isc_scan_bwd_problem *pr, int n_prob, int
         d.P = q.P; d.V = q.V; d.q = q.q; d.q2 = q.q2; d.w = q.w; d.alpha = q.alpha; d.dout = q.dout;
         d.alpha_ld = q.alpha_ld; d.R = q.R; d.A = q.A; d.D = q.D; d.accumulate = q.accumulate;
         d.dP = q.dP; d.dV = q.dV; d.dq = q.dq; d.dw_rows = q.dw_rows; d.de_out = q.de_out;
+        d.row_div = q.row_div > 1 ? q.row_div : 1;
         const int ngrp = 1024 / (q.A / 4);
         const size_t need = (((size_t)q.R + 3) & ~(size_t)3) + (size_t)2 * ngrp * q.A;
         if (need > lds) lds = need;
@@ -551,24 +557,47 @@ extern "C" int isc_attn_scan_bwd(const isc_scan_bwd_problem *pr, int n_prob, int
 // Any R, any D % 4 == 0: the grid is (B, region chunks, column blocks of 256 float4); a chunk holds as many regions as
 // fit the [T][Rc] LDS image (the 14x14 = 196-region grid of the reference's encoder at T = 20: 4 chunks).  An output
 // element's additions do not depend on the chunking.
+// n > 1 (isc_attn_dv_from_alpha_group): the grid is over IMAGES, image i owns rows i*n .. i*n + n - 1 and
+// dV[i,r,:] sums their n*T terms - row j ascending outermost, t = T-1 down inside; the LDS image is [n*T][Rc].  The
+// register-resident g[] form serves one row of at most ISC_DV_TMAX steps (n == 1); a group takes the plain loop.
 #define ISC_DV_TMAX 24
 #define ISC_POST_LDS_BYTES 60000
 __global__ __launch_bounds__(256) void attn_dv_from_alpha_kernel(const float *alpha, long long ld_b, long long ld_t,
-                                                                 const float *dout, int B, int T, int R, int D, int Rc,
+                                                                 const float *dout, int n, int T, int R, int D, int Rc,
                                                                  float *dV, int step_rows) {
 #pragma clang fp contract(off)
-    extern __shared__ float sa[];                  // [T][Rc]
-    const int b = blockIdx.x, tid = threadIdx.x;
+    extern __shared__ float sa[];                  // [n*T][Rc]: row (j, t) of the image at j*T + t
+    const int b = blockIdx.x, tid = threadIdx.x;   // b: the image (n == 1: the row)
     const int r_lo = blockIdx.y * Rc, nr = min(Rc, R - r_lo);
-    for (int i = tid; i < T * nr; i += 256)
-        sa[(i / nr) * Rc + (i % nr)] = alpha[(long long)b * ld_b + (long long)(i / nr) * ld_t + r_lo + (i % nr)];
+    if (n == 1) {
+        for (int i = tid; i < T * nr; i += 256)
+            sa[(i / nr) * Rc + (i % nr)] = alpha[(long long)b * ld_b + (long long)(i / nr) * ld_t + r_lo + (i % nr)];
+    } else {
+        for (int i = tid; i < n * T * nr; i += 256) {
+            const int jt = i / nr, j = jt / T, t = jt - j * T;
+            sa[jt * Rc + (i % nr)] = alpha[((long long)b * n + j) * ld_b + (long long)t * ld_t + r_lo + (i % nr)];
+        }
+    }
     __syncthreads();
     const int D4 = D >> 2, c_lo = blockIdx.z * 256, cols = min(256, D4 - c_lo);
     const int ngrp = 256 / cols, d4 = c_lo + tid % cols, grp = tid / cols;
     if (grp >= ngrp) return;
     const float4 *g4 = reinterpret_cast<const float4 *>(dout);
     float4 *o4 = reinterpret_cast<float4 *>(dV + (long long)b * R * D);
-    if (T <= ISC_DV_TMAX) {
+    if (n > 1) {
+        for (int r = grp; r < nr; r += ngrp) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int j = 0; j < n; ++j) {
+                const float4 *gj = g4 + ((long long)b * n + j) * D4 + d4;
+                for (int t = T - 1; t >= 0; --t) {
+                    const float al = sa[(j * T + t) * Rc + r];
+                    const float4 g = gj[(long long)t * step_rows * D4];
+                    acc.x = al * g.x + acc.x; acc.y = al * g.y + acc.y; acc.z = al * g.z + acc.z; acc.w = al * g.w + acc.w;
+                }
+            }
+            o4[(long long)(r_lo + r) * D4 + d4] = acc;
+        }
+    } else if (T <= ISC_DV_TMAX) {
         float4 g[ISC_DV_TMAX];
 #pragma unroll
         for (int t = 0; t < ISC_DV_TMAX; ++t)
@@ -600,27 +629,35 @@ __global__ __launch_bounds__(256) void attn_dv_from_alpha_kernel(const float *al
     }
 }
 
-extern "C" int isc_attn_dv_from_alpha(const float *alpha, int64_t alpha_ld_b, int64_t alpha_ld_t, const float *dout,
-                                      int B, int T, int R, int D, float *dV, int dout_step_rows, void *stream) {
+extern "C" int isc_attn_dv_from_alpha_group(const float *alpha, int64_t alpha_ld_b, int64_t alpha_ld_t,
+                                            const float *dout, int B, int group, int T, int R, int D, float *dV,
+                                            int dout_step_rows, void *stream) {
     if (!alpha || !dout || !dV) return ISC_E_NULL;
-    if (B <= 0 || T <= 0 || R <= 0 || D <= 0 || (D & 3)) return ISC_E_SHAPE;
+    if (B <= 0 || group <= 0 || B % group || T <= 0 || R <= 0 || D <= 0 || (D & 3)) return ISC_E_SHAPE;
     if (dout_step_rows == 0) dout_step_rows = B;
     if (dout_step_rows < B) return ISC_E_SHAPE;
     if (!isc_aligned16(dout) || !isc_aligned16(dV)) return ISC_E_ALIGN;
-    int Rc = ISC_POST_LDS_BYTES / (int)sizeof(float) / T;      // regions per chunk: [T][Rc] floats of LDS
-    if (Rc < 1) return ISC_E_SHAPE;                             // T > 15000 steps
+    const long long nT = (long long)group * T;                  // terms of an output element: the LDS image's rows
+    if (nT > ISC_POST_LDS_BYTES / (int)sizeof(float)) return ISC_E_SHAPE;      // more than 15000 (row, step) pairs
+    int Rc = ISC_POST_LDS_BYTES / (int)sizeof(float) / (int)nT; // regions per chunk: [group*T][Rc] floats of LDS
     if (Rc > R) Rc = R;
+    B /= group;                                                 // the grid is over images
     const int ncol = (D / 4 + 255) / 256;
     // few rows: more region chunks until the grid covers the chip twice (an output element's additions do not depend on
     // the chunking; B = 128 with 36 regions was 128 workgroups)
     while (Rc > 4 && (long long)B * ((R + Rc - 1) / Rc) * ncol < 512) Rc = (Rc + 1) / 2;
     const int nchunk = (R + Rc - 1) / Rc;
     if (nchunk > 65535 || ncol > 65535) return ISC_E_SHAPE;
-    const size_t lds = (size_t)T * Rc * sizeof(float);
+    const size_t lds = (size_t)nT * Rc * sizeof(float);
     hipLaunchKernelGGL(attn_dv_from_alpha_kernel, dim3(B, nchunk, ncol), dim3(256), lds, (hipStream_t)stream, alpha,
-                       (long long)alpha_ld_b, (long long)alpha_ld_t, dout, B, T, R, D, Rc, dV, dout_step_rows);
+                       (long long)alpha_ld_b, (long long)alpha_ld_t, dout, group, T, R, D, Rc, dV, dout_step_rows);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
+}
+
+extern "C" int isc_attn_dv_from_alpha(const float *alpha, int64_t alpha_ld_b, int64_t alpha_ld_t, const float *dout,
+                                      int B, int T, int R, int D, float *dV, int dout_step_rows, void *stream) {
+    return isc_attn_dv_from_alpha_group(alpha, alpha_ld_b, alpha_ld_t, dout, B, 1, T, R, D, dV, dout_step_rows, stream);
 }
 
 // dP[b,r,a] = sum over the steps, in the sweep's order, of d e[t,b,r] * w[a] * (1 - tanh^2(P[b,r,a] + q_t[b,a] (+ q2[b,a]))):
@@ -629,15 +666,24 @@ extern "C" int isc_attn_dv_from_alpha(const float *alpha, int64_t alpha_ld_b, in
 // them anyway for d q).  Same expression, same order of additions as the per-step accumulation.
 // Grid (B, region chunks, column blocks): a thread keeps ISC_DP_RMAX regions in registers, so a chunk is
 // ISC_DP_RMAX x (region groups of the workgroup) regions (A = 512: 36 - the 36-region features in one chunk, 196 in six).
+// n > 1 (isc_attn_dp_from_de_group): the grid is over IMAGES; P[i] stays in registers over the n*T terms of the image's
+// rows i*n + j - j ascending outermost, t = T-1 down inside; the LDS image is [n*T][Rc]; q2 is per image.
 #define ISC_DP_RMAX 18
 __global__ __launch_bounds__(256) void attn_dp_from_de_kernel(const float *P, const float *q, const float *q2,
-                                                              const float *w, const float *de, int B, int T, int R,
-                                                              int A, int Rc, float *dP) {
-    extern __shared__ float sde[];                 // [T][Rc]
-    const int b = blockIdx.x, tid = threadIdx.x;
+                                                              const float *w, const float *de, int B, int n, int T,
+                                                              int R, int A, int Rc, float *dP) {
+    extern __shared__ float sde[];                 // [n*T][Rc]: row (j, t) of the image at j*T + t
+    const int b = blockIdx.x, tid = threadIdx.x;   // b: the image (n == 1: the row); B: decode rows per step
     const int r_lo = blockIdx.y * Rc, nr = min(Rc, R - r_lo);
-    for (int i = tid; i < T * nr; i += 256)
-        sde[(i / nr) * Rc + (i % nr)] = de[((long long)(i / nr) * B + b) * R + r_lo + (i % nr)];
+    if (n == 1) {
+        for (int i = tid; i < T * nr; i += 256)
+            sde[(i / nr) * Rc + (i % nr)] = de[((long long)(i / nr) * B + b) * R + r_lo + (i % nr)];
+    } else {
+        for (int i = tid; i < n * T * nr; i += 256) {
+            const int jt = i / nr, j = jt / T, t = jt - j * T;
+            sde[jt * Rc + (i % nr)] = de[((long long)t * B + (long long)b * n + j) * R + r_lo + (i % nr)];
+        }
+    }
     __syncthreads();
     const int A4 = A >> 2, c_lo = blockIdx.z * 256, cols = min(256, A4 - c_lo);
     const int ngrp = 256 / cols, a4 = c_lo + tid % cols, grp = tid / cols;
@@ -654,14 +700,16 @@ __global__ __launch_bounds__(256) void attn_dp_from_de_kernel(const float *P, co
         pv[i] = r < nr ? Pb[(long long)r * A4 + a4] : make_float4(0.f, 0.f, 0.f, 0.f);
         acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    for (int t = T - 1; t >= 0; --t) {
-        float4 qa = reinterpret_cast<const float4 *>(q + ((long long)t * B + b) * A)[a4];
+    for (int jt = 0; jt < n * T; ++jt) {           // row j of the image ascending, t = T-1 down inside
+        const int j = jt / T, t = T - 1 - (jt - j * T);
+        float4 qa = reinterpret_cast<const float4 *>(q + ((long long)t * B + (long long)b * n + j) * A)[a4];
         if (q2) { qa.x += q2v.x; qa.y += q2v.y; qa.z += q2v.z; qa.w += q2v.w; }
+        const float *sd = sde + (j * T + t) * Rc;
 #pragma unroll
         for (int i = 0; i < ISC_DP_RMAX; ++i) {
             const int r = grp + i * ngrp;
             if (r < nr) {
-                const float der = sde[t * Rc + r];
+                const float der = sd[r];
                 const float tx = isc_tanh(pv[i].x + qa.x), ty = isc_tanh(pv[i].y + qa.y);
                 const float tz = isc_tanh(pv[i].z + qa.z), tw = isc_tanh(pv[i].w + qa.w);
                 const float4 gr = make_float4(isc_dtanh_term(der, wa.x, tx), isc_dtanh_term(der, wa.y, ty),
@@ -679,10 +727,14 @@ __global__ __launch_bounds__(256) void attn_dp_from_de_kernel(const float *P, co
     }
 }
 
-extern "C" int isc_attn_dp_from_de(const float *P, const float *q, const float *q2, const float *w, const float *de,
-                                   int B, int T, int R, int A, float *dP, void *stream) {
+extern "C" int isc_attn_dp_from_de_group(const float *P, const float *q, const float *q2, const float *w,
+                                         const float *de, int B, int group, int T, int R, int A, float *dP,
+                                         void *stream) {
     if (!P || !q || !w || !de || !dP) return ISC_E_NULL;
-    if (B <= 0 || T <= 0 || R <= 0 || A <= 0 || (A & 3)) return ISC_E_SHAPE;
+    if (B <= 0 || group <= 0 || B % group || T <= 0 || R <= 0 || A <= 0 || (A & 3)) return ISC_E_SHAPE;
+    const long long nT = (long long)group * T;                  // terms of an output element: the LDS image's rows
+    if (nT > ISC_POST_LDS_BYTES / (int)sizeof(float)) return ISC_E_SHAPE;      // more than 15000 (row, step) pairs
+    const int I = B / group;                                    // the grid is over images
     if (!isc_aligned16(P) || !isc_aligned16(q) || !isc_aligned16(w) || !isc_aligned16(dP) || (q2 && !isc_aligned16(q2)))
         return ISC_E_ALIGN;
     const int A4 = A / 4, cols = A4 < 256 ? A4 : 256;          // (a ragged last column block only has MORE groups)
@@ -690,19 +742,23 @@ extern "C" int isc_attn_dp_from_de(const float *P, const float *q, const float *
     const int ncol0 = (A4 + 255) / 256;
     // few rows (B = 128, 36 regions: 128 workgroups on 256 CUs, each bound by its 47 M tanh): fewer regions per thread,
     // more region chunks - every (row, region, column) is computed by one thread either way: the same values
-    while (rmax > 3 && (long long)B * ((R + rmax * (256 / cols) - 1) / (rmax * (256 / cols))) * ncol0 < 512) rmax = (rmax + 1) / 2;
+    while (rmax > 3 && (long long)I * ((R + rmax * (256 / cols) - 1) / (rmax * (256 / cols))) * ncol0 < 512) rmax = (rmax + 1) / 2;
     int Rc = rmax * (256 / cols);                               // what a workgroup's threads hold in registers
-    const int lds_cap = ISC_POST_LDS_BYTES / (int)sizeof(float) / T;
-    if (lds_cap < 1) return ISC_E_SHAPE;
+    const int lds_cap = ISC_POST_LDS_BYTES / (int)sizeof(float) / (int)nT;
     if (Rc > lds_cap) Rc = lds_cap;
     if (Rc > R) Rc = R;
     const int nchunk = (R + Rc - 1) / Rc, ncol = (A4 + 255) / 256;
     if (nchunk > 65535 || ncol > 65535) return ISC_E_SHAPE;
-    const size_t lds = (size_t)T * Rc * sizeof(float);
-    hipLaunchKernelGGL(attn_dp_from_de_kernel, dim3(B, nchunk, ncol), dim3(256), lds, (hipStream_t)stream, P, q, q2, w,
-                       de, B, T, R, A, Rc, dP);
+    const size_t lds = (size_t)nT * Rc * sizeof(float);
+    hipLaunchKernelGGL(attn_dp_from_de_kernel, dim3(I, nchunk, ncol), dim3(256), lds, (hipStream_t)stream, P, q, q2, w,
+                       de, B, group, T, R, A, Rc, dP);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
+}
+
+extern "C" int isc_attn_dp_from_de(const float *P, const float *q, const float *q2, const float *w, const float *de,
+                                   int B, int T, int R, int A, float *dP, void *stream) {
+    return isc_attn_dp_from_de_group(P, q, q2, w, de, B, 1, T, R, A, dP, stream);
 }
 
 // ------------------------------------------------------------------ gate mix backward

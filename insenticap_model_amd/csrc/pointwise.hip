@@ -1622,5 +1622,5 @@ extern "C" int isc_xe_loss_tokens_fwd(const float *tlp, const int32_t *lengths, 
     return ISC_OK;
 }
 
-extern "C" int isc_abi_version(void) { return 1; }
+extern "C" int isc_abi_version(void) { return 2; }
 extern "C" const char *isc_target_arch(void) { return "gfx950"; }

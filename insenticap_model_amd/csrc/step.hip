@@ -57,7 +57,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
         l.h_hi = PL(p->h1_hi); l.h_lo = PL(p->h1_lo);
         l.c_prev = p->c1_prev; l.h_out = p->h1; l.c_out = p->c1; l.gates_out = p->g1;
         l.pre = p->pre1; l.tab = p->tab; l.tab_ids = p->tok; l.tab_ids_stride = p->tok_stride;
-        l.pre_div = row_div;
+        l.pre_div = p->pre_rows ? 1 : row_div;
         l.splitk_ws = p->splitk_ws; l.splitk_ws_floats = p->splitk_ws_floats;
         RET(isc_lstm_fwd(&l, stream));
     }
@@ -174,6 +174,9 @@ extern "C" int isc_step_bwd(const isc_step_bwd_plan *p, void *stream) {
     const long long off_s = pair ? p->pair_rows_c : 0;
     const int ld1 = H + E + W, ld2 = E + H, G = 4 * H;
     const int acc = p->first ? 0 : 1;      // time-accumulated buffers: the first processed step writes
+    // captions per image (isc_step_bwd_plan.row_div): the scans' P / V / q2 hold one entry per image
+    const int row_div = p->row_div > 1 ? p->row_div : 1;
+    if (row_div > 1 && (rows % row_div || pair)) return ISC_E_SHAPE;
 
     // lang-LSTM cell
     RET(isc_lstm_bwd(p->dhd, p->first ? nullptr : p->dh2_rec, p->first ? nullptr : p->dc2_in, p->g2,
@@ -205,14 +208,14 @@ extern "C" int isc_step_bwd(const isc_step_bwd_plan *p, void *stream) {
             x.P = p->att_p; x.V = p->att_e; x.q = p->qa; x.w = p->w_alpha_c; x.alpha = p->alpha_c;
             x.alpha_ld = p->alpha_c_ld; x.dout = dv; x.R = p->R; x.A = A; x.D = E; x.accumulate = acc;
             x.dP = p->dP_att; x.dV = p->dV_att; x.dq = p->dqa; x.dw_rows = p->dwc_rows; x.de_out = p->de_c;
-            x.rows = rows_c;
+            x.rows = rows_c; x.row_div = row_div;
         }
         if (has_s) {
             isc_scan_bwd_problem &x = sc[n++];
             x.P = p->words_p; x.V = p->words_e; x.q = p->qw; x.q2 = p->label_w; x.w = p->w_alpha_s;
             x.alpha = p->alpha_s; x.alpha_ld = p->alpha_s_ld; x.dout = dsw; x.R = p->Mw; x.A = A; x.D = W;
             x.accumulate = acc; x.dP = p->dP_w; x.dV = p->dV_w; x.dq = p->dqw; x.dw_rows = p->dws_rows; x.de_out = p->de_s;
-            x.rows = rows_s;
+            x.rows = rows_s; x.row_div = row_div;
         }
         RET(isc_attn_scan_bwd(sc, n, rows, stream));
     }

@@ -116,13 +116,42 @@ class RowGather:
 
 
 def create_collate_fn(name, pad_index=0, max_seq_len=17, num_concepts=5, num_sentiments=10, caption_width=None,
-                      dedup=False):
+                      dedup=False, captions_per_image=None):
     """The reference's collate functions (dataloader.py:11-58).  `caption_width` (not in the reference): None pads a batch's
     captions to its longest one, as the reference does - every distinct longest length is then another input geometry for
     the graph-served training steps (train_graph: a capture per geometry, four kept); 'full' pads every batch to
     max_seq_len, an int m rounds the unroll length (width - 1) up to a multiple of m.  Lengths are returned unchanged and the
     criteria mask by row, so losses and gradients are those of the tight batch - the extra steps run on <PAD>.
-    `dedup` ('caption' only; not in the reference): features as RowGather (each image once + a row index)."""
+    `dedup` ('caption' only; not in the reference): features as RowGather (each image once + a row index).
+    `captions_per_image=n` ('caption' only; not in the reference): the batch of Captioner.forward_xe(...,
+    captions_per_image=n) - features and `cpts` of the I images, each ONCE, in dataset order; captions image-major with
+    exactly n per image, [I*n, L] (row i*n + j = caption j of image i): the first n of the image's captions, cycled from
+    its first one when it has fewer (no random choice); `fns` and the lengths per caption row.  The rows are the default
+    collate's rows of those captions in another order (image-major instead of sorted by length).  `dedup` has nothing
+    left to do then."""
+    if captions_per_image is not None:
+        if (isinstance(captions_per_image, bool) or not hasattr(captions_per_image, '__index__')
+                or int(captions_per_image) < 1):
+            raise ValueError('captions_per_image must be an integer >= 1, got %r' % (captions_per_image,))
+        if name != 'caption':
+            raise ValueError('captions_per_image belongs to the caption collate, not to %r' % (name,))
+        captions_per_image = int(captions_per_image)
+
+    def caption_grouped(dataset):
+        n = captions_per_image
+        fns, caps = [], []
+        for fn, _, _, caps_idx, _ in dataset:
+            if len(caps_idx) == 0:
+                raise ValueError('captions_per_image: image %r has no caption' % (fn,))
+            fns += [fn] * n
+            caps += [caps_idx[j % len(caps_idx)] for j in range(n)]
+        lengths = [min(len(c), max_seq_len) for c in caps]
+        # (_caps pads to its FIRST row's length - its rows are sorted; here the longest row may stand anywhere)
+        longest = max(range(len(caps)), key=lengths.__getitem__)
+        tensor, _ = _caps([caps[longest]] + caps, max_seq_len, pad_index, caption_width)
+        return tuple(fns), _feats([d[1] for d in dataset]), _feats([d[2] for d in dataset]), \
+            (tensor[1:], [l - 1 for l in lengths]), _pad_rows([d[4] for d in dataset], num_concepts, pad_index)
+
     def caption(dataset):
         rows = [(fn, fc, att, cap, cpts, u) for u, (fn, fc, att, caps_idx, cpts) in enumerate(dataset) for cap in caps_idx]
         rows.sort(key=lambda p: len(p[3]), reverse=True)          # stable, like the reference
@@ -160,7 +189,7 @@ def create_collate_fn(name, pad_index=0, max_seq_len=17, num_concepts=5, num_sen
         return fns, _feats(fcs), _feats(atts), _pad_rows(cpts, num_concepts, pad_index), \
             _pad_rows(sentis, num_sentiments, pad_index), torch.from_numpy(np.asarray(labels, dtype=np.int64))
 
-    table = {'caption': caption, 'scs': scs, 'senti_corpus_with_sentis': scs, 'rl_fact': rl_fact,
+    table = {'caption': caption if captions_per_image is None else caption_grouped, 'scs': scs, 'senti_corpus_with_sentis': scs, 'rl_fact': rl_fact,
              'rl_senti': rl_senti}
     if name not in table:
         raise KeyError('collate %r is outside the decoder path (have: %s)' % (name, sorted(table)))
@@ -409,11 +438,14 @@ def _loader(dataset, batch_size, num_workers, shuffle, collate):
 
 
 def get_caption_dataloader(fc_feats, att_feats, img_captions, img_det_concepts, pad_index, max_seq_len,
-                           num_concepts, batch_size, num_workers=0, shuffle=True, caption_width=None, dedup=False):
-    """dataloader.py:267-278 (note max_seq_len + 1: the <SOS> column).  caption_width, dedup: create_collate_fn."""
+                           num_concepts, batch_size, num_workers=0, shuffle=True, caption_width=None, dedup=False,
+                           captions_per_image=None):
+    """dataloader.py:267-278 (note max_seq_len + 1: the <SOS> column).  caption_width, dedup, captions_per_image:
+    create_collate_fn."""
     return _loader(CaptionDataset(fc_feats, att_feats, img_captions, img_det_concepts), batch_size, num_workers,
                    shuffle, create_collate_fn('caption', pad_index, max_seq_len + 1, num_concepts,
-                                              caption_width=caption_width, dedup=dedup))
+                                              caption_width=caption_width, dedup=dedup,
+                                              captions_per_image=captions_per_image))
 
 
 def get_senti_corpus_with_sentis_dataloader(senti_corpus_with_sentis, pad_index, max_seq_len, num_concepts,

@@ -1033,8 +1033,11 @@ def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=Non
                            stream()), 'isc_lstm_bwd')
 
 
-def scan_bwd_problem(P, V, q, w, alpha, dout, dP, dV, dq, dw_rows, accumulate, q2=None, de_out=None):
+def scan_bwd_problem(P, V, q, w, alpha, dout, dP, dV, dq, dw_rows, accumulate, q2=None, de_out=None, row_div=1):
+    """row_div > 1 (isc_scan_bwd_problem.row_div): P, V and q2 hold one entry per image, [rows / row_div, ...], and row b
+    reads entry b // row_div; dP and dV must be None (attn_dp_from_de / attn_dv_from_alpha with group= form them)."""
     s = _lib.ScanBwdProblem()
+    s.row_div = int(row_div) if int(row_div) > 1 else 0
     for x in (P, V, q, dout, dP, dV, dq, dw_rows):
         assert x is None or x.is_contiguous()          # (dV None: attn_dv_from_alpha forms it after the sweep)
     assert alpha.stride(1) == 1
@@ -1047,32 +1050,49 @@ def scan_bwd_problem(P, V, q, w, alpha, dout, dP, dV, dq, dw_rows, accumulate, q
     return s
 
 
-def attn_dv_from_alpha(alpha, dout_all, dV, step_rows=0):
+def attn_dv_from_alpha(alpha, dout_all, dV, step_rows=0, group=1):
     """dV[b,r,:] = sum_t alpha[b,t,r] * dout_all[t,b,:] in the backward sweep's order (isc_attn_dv_from_alpha).
     alpha: [B,T,R] view with unit inner stride; dout_all [T,B,D] contiguous - or, step_rows > 0, the [:, :B] rows of a
-    [T,step_rows,D] stack (merged unroll); dV [B,R,D] contiguous."""
+    [T,step_rows,D] stack (merged unroll); dV [B,R,D] contiguous.
+    group = n > 1 (isc_attn_dv_from_alpha_group): dV is [B / n, R, D], one entry per image, summed over the image's rows
+    i*n + j as well - j ascending outermost, t = T-1 down inside."""
     B, T, R = alpha.shape
     D = dV.shape[2]
+    group = int(group)
+    assert group >= 1 and dV.shape[0] * group == B and dV.shape[1] == R
     assert alpha.stride(2) == 1 and dV.is_contiguous() and dout_all.shape == (T, B, D)
     if step_rows:
         assert dout_all.stride(2) == 1 and dout_all.stride(1) == D and dout_all.stride(0) == step_rows * D
     else:
         assert dout_all.is_contiguous()
-    check(_lib.load().isc_attn_dv_from_alpha(alpha.data_ptr(), alpha.stride(0), alpha.stride(1), dout_all.data_ptr(),
-                                             B, T, R, D, dV.data_ptr(), int(step_rows), stream()),
-          'isc_attn_dv_from_alpha')
+    e0 = TIMER.begin()
+    check(_lib.load().isc_attn_dv_from_alpha_group(alpha.data_ptr(), alpha.stride(0), alpha.stride(1),
+                                                   dout_all.data_ptr(), B, group, T, R, D, dV.data_ptr(),
+                                                   int(step_rows), stream()), 'isc_attn_dv_from_alpha_group')
+    if e0 is not None:          # what must move: alpha and dout once, dV once
+        TIMER.end(e0, 'attn_dv_from_alpha[%dx%dx%dx%d/%d]' % (B, T, R, D, group), 0.0,
+                  4.0 * (B * T * (R + D) + dV.numel()))
 
 
-def attn_dp_from_de(P, q_all, w, de_all, dP, q2=None):
+def attn_dp_from_de(P, q_all, w, de_all, dP, q2=None, group=1):
     """dP[b,r,:] = sum_t de_all[t,b,r] * w * (1 - tanh^2(P[b,r,:] + q_all[t,b,:] (+ q2[b,:]))) in the backward sweep's
-    order (isc_attn_dp_from_de).  P, dP [B,R,A]; q_all [T,B,A]; de_all [T,B,R]; all contiguous."""
-    B, R, A = P.shape
-    T = q_all.shape[0]
+    order (isc_attn_dp_from_de).  P, dP [B,R,A]; q_all [T,B,A]; de_all [T,B,R]; all contiguous.
+    group = n > 1 (isc_attn_dp_from_de_group): P, dP and q2 hold one entry per image, [B / n, ...]; the sum also runs over
+    the image's rows i*n + j - j ascending outermost, t = T-1 down inside."""
+    I, R, A = P.shape
+    T, B = q_all.shape[:2]
+    group = int(group)
     for x in (P, q_all, de_all, dP, q2):
         assert x is None or x.is_contiguous()
+    assert group >= 1 and I * group == B and (q2 is None or q2.shape == (I, A))
     assert q_all.shape == (T, B, A) and de_all.shape == (T, B, R) and dP.shape == P.shape
-    check(_lib.load().isc_attn_dp_from_de(P.data_ptr(), q_all.data_ptr(), ptr(q2), w.data_ptr(), de_all.data_ptr(),
-                                          B, T, R, A, dP.data_ptr(), stream()), 'isc_attn_dp_from_de')
+    e0 = TIMER.begin()
+    check(_lib.load().isc_attn_dp_from_de_group(P.data_ptr(), q_all.data_ptr(), ptr(q2), w.data_ptr(),
+                                                de_all.data_ptr(), B, group, T, R, A, dP.data_ptr(), stream()),
+          'isc_attn_dp_from_de_group')
+    if e0 is not None:          # what must move: P, q and de once, dP once
+        TIMER.end(e0, 'attn_dp_from_de[%dx%dx%dx%d/%d]' % (B, T, R, A, group), 0.0,
+                  4.0 * (2 * P.numel() + B * T * (R + A)))
 
 
 def attn_scan_bwd(problems, B):
@@ -1081,7 +1101,7 @@ def attn_scan_bwd(problems, B):
     e0 = TIMER.begin()
     check(lib.isc_attn_scan_bwd(arr, len(problems), B, stream()), 'isc_attn_scan_bwd')
     if e0 is not None:
-        nb = sum(4.0 * B * q.R * 3 * (q.A + q.D) for q in problems)   # read P,V; read-modify-write dP,dV
+        nb = sum(4.0 * B / max(q.row_div, 1) * q.R * 3 * (q.A + q.D) for q in problems)   # read P,V; read-modify-write dP,dV
         TIMER.end(e0, 'attn_scan_bwd[' + '+'.join('%dx%dx%d' % (B, q.R, q.A) for q in problems) + ']', 0.0, nb)
 
 

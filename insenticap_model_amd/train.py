@@ -49,8 +49,12 @@ def _xe_loss(xe_crit, pred, target, lengths):
 
 
 def xe_forward_backward(captioner, optim, xe_crit, da_crit, fact, xe_senti_labels, scs=None, ss_prob=0.0, arena=None,
-                        weights3=None, overlap_unrolls=True, side_stream=None, pair=None, sink=None):
-    """train_xe.py:160-190 on device tensors: both unrolls, the three losses, backward.  `fact` = (fc, att, caps,
+                        weights3=None, overlap_unrolls=True, side_stream=None, pair=None, sink=None, captions_per_image=1):
+    """`captions_per_image=n` > 1 (Captioner.forward_xe): `fact` holds fc / att / cpts once per image, [I, ...], and caps /
+    lengths / `xe_senti_labels` per caption row, image-major [I*n] (data.create_collate_fn('caption',
+    captions_per_image=n)); the step then takes the un-merged route - the XE unroll, and the seq2seq unroll on the side
+    stream.  The domain-alignment loss is a mean over the I images (equal to the mean over rows: every image has n).
+    train_xe.py:160-190 on device tensors: both unrolls, the three losses, backward.  `fact` = (fc, att, caps,
     lengths, cpts), `scs` = (caps, lengths, cpts, sentis, labels) or None; `weights3` = this rank's shares of the three
     global normalisers (XE tokens, seq2seq tokens, rows) as a device tensor (or a callable returning it, resolved after
     the unrolls' forward: dp_shares_async), or None (single process: graph untouched).  Returns the detached [xe, da, seq2seq] losses as one device tensor.  No collective, no host read:
@@ -58,6 +62,14 @@ def xe_forward_backward(captioner, optim, xe_crit, da_crit, fact, xe_senti_label
     fc_feats, att_feats, caps_tensor, lengths, cpts_tensor = fact
     device = fc_feats.device
     share = (lambda x, w: x * w) if weights3 is not None else (lambda x, w: x)
+    if (isinstance(captions_per_image, bool) or not hasattr(captions_per_image, '__index__')
+            or int(captions_per_image) < 1):
+        raise ValueError('captions_per_image must be an integer >= 1, got %r' % (captions_per_image,))
+    grouped = int(captions_per_image) > 1
+    if grouped:
+        if pair or sink is not None:
+            raise ValueError('captions_per_image > 1 is not built for the merged xe_seq2seq step (pair / sink)')
+        pair = False
     if pair is None:
         from .autograd_pair import use_pair
         pair = use_pair(captioner, False)
@@ -76,7 +88,8 @@ def xe_forward_backward(captioner, optim, xe_crit, da_crit, fact, xe_senti_label
                                     s_caps, s_cpts, s_sentis, s_labels, ss_prob, mode='xe_seq2seq')
     else:
         with captioner.token_logprobs(), captioner.row_counts(lengths):
-            pred = captioner(fc_feats, att_feats, cpts_tensor, caps_tensor, xe_senti_labels, ss_prob, mode='xe')
+            kw = dict(captions_per_image=captions_per_image) if grouped else {}
+            pred = captioner(fc_feats, att_feats, cpts_tensor, caps_tensor, xe_senti_labels, ss_prob, mode='xe', **kw)
     if callable(weights3):            # (dp_shares_async: the counts' all-reduce ran next to the unroll; wait for it here)
         weights3 = weights3()
     w_xe, w_s2s, w_rows = weights3.unbind(0) if weights3 is not None else (None, None, None)
@@ -155,8 +168,10 @@ def dp_shares_async(lengths, s_lengths, rows, device, group):
 
 
 def xe_train_step(captioner, optim, xe_crit, da_crit, fact_batch, xe_senti_labels, scs_batch=None,
-                  ss_prob=0.0, grad_clip=0.1, arena=None, group=None, device=None, overlap_unrolls=True, bucketed=True):
-    """One iteration. Returns dict(xe_loss, da_loss, cap_loss, seq2seq_loss, all_loss) of 0-dim
+                  ss_prob=0.0, grad_clip=0.1, arena=None, group=None, device=None, overlap_unrolls=True, bucketed=True,
+                  captions_per_image=1):
+    """`captions_per_image`: xe_forward_backward's (a batch of the 'caption' collate with the same keyword).
+    One iteration. Returns dict(xe_loss, da_loss, cap_loss, seq2seq_loss, all_loss) of 0-dim
     tensors (global values under DP).  `arena`: dp.GradArena when gradients are all-reduced.
     `overlap_unrolls`: the seq2seq unroll (80 text-only rows) runs on a side HIP stream.  It shares nothing
     with the XE unroll but the weights, and at these batch sizes both are chains of small launches that leave
@@ -184,12 +199,12 @@ def xe_train_step(captioner, optim, xe_crit, da_crit, fact_batch, xe_senti_label
     from .autograd_pair import use_pair
     sink = None
     if (arena is not None and bucketed and scs is not None and device.type == 'cuda' and use_pair(captioner, False)
-            and isinstance(optim, FusedClampAdam)):
+            and isinstance(optim, FusedClampAdam) and captions_per_image == 1):
         sink = captioner.__dict__.get('_dp_sink')
         if sink is None or sink.arena is not arena or sink.group is not group:
             sink = captioner.__dict__['_dp_sink'] = dp.GradSink(captioner, arena, group)
     vec = xe_forward_backward(captioner, optim, xe_crit, da_crit, fact, xe_senti_labels, scs, ss_prob, arena, weights3,
-                              overlap_unrolls, sink=sink)
+                              overlap_unrolls, sink=sink, captions_per_image=captions_per_image)
     if sink is not None and sink.order:
         # the loss statistics: queued behind the buckets on the backend's stream, NOT waited for here - the compute stream
         # would otherwise stand behind every bucket's reduction before the first bucket's update
