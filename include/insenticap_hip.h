@@ -297,7 +297,8 @@ int isc_gate_mix_fwd(const float *z, const float *w, const float *w_bias, const 
                      const float *s, int B, int A, int D, float *out, float *beta_out,
                      int64_t beta_ld, void *out_hi, void *out_lo, void *stream);   /* out_hi/lo: optional planes of out */
 
-/* xt[b,:] = relu(Emb[ids[b]]) (+ add[b,:])   (captioner.py:170-172), ids int64. */
+/* xt[b,:] = relu(Emb[ids[b]]) (+ add[b,:])   (captioner.py:170-172), ids int64.  W % 4 == 0; emb, out and (when given)
+ * add are moved as 16-byte vectors: a pointer that is not 16-byte aligned -> ISC_E_ALIGN before any launch. */
 int isc_embed_relu_fwd(const float *emb, int V, int W, const int64_t *ids, int64_t ids_stride,
                        const float *add, int B, float *out, void *stream);
 
@@ -334,6 +335,8 @@ typedef struct {
     float *xt_next;              /* [B,W] input of step t+1 */
 } isc_rollout_step;
 
+/* W % 4 == 0.  With xt_next set, emb, xt_next and (when given) xt_add are moved as 16-byte vectors: one of them not
+ * 16-byte aligned -> ISC_E_ALIGN before any launch (without xt_next none of the three is read). */
 int isc_rollout_finalize(const isc_rollout_step *s_host, void *stream);
 long long isc_rollout_finalize_launches(void);   /* launches so far (tests: isc_rows_ext.fin_prev saves them) */
 

@@ -29,6 +29,8 @@ extern "C" int isc_embed_relu_fwd(const float *emb, int V, int W, const int64_t 
                                   void *stream) {
     if (!emb || !ids || !out) return ISC_E_NULL;
     if (B <= 0 || V <= 0 || W <= 0 || (W & 3)) return ISC_E_SHAPE;
+    // the kernel reads and writes rows as float4
+    if (!isc_aligned16(emb) || !isc_aligned16(out) || (add && !isc_aligned16(add))) return ISC_E_ALIGN;
     hipLaunchKernelGGL(embed_relu_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, emb, W,
                        ids, (long long)ids_stride, add, B, out);
     ISC_LAUNCH_CHECK();
@@ -409,6 +411,9 @@ extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
         return ISC_E_NULL;
     if ((s->forced || s->sample_u) && !s->logits) return ISC_E_NULL;
     if (s->B <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3)) return ISC_E_SHAPE;
+    // xt_next = relu(emb[token]) (+ xt_add) moves float4s (rollout_finalize_row)
+    if (s->xt_next && (!isc_aligned16(s->emb) || !isc_aligned16(s->xt_next) || (s->xt_add && !isc_aligned16(s->xt_add))))
+        return ISC_E_ALIGN;
     DevRollout R;
     R.B = s->B; R.V = s->V; R.T = s->T; R.t = s->t; R.n_tile = s->n_tile; R.W = s->W;
     R.part_max = s->part_max; R.part_sum = s->part_sum; R.part_idx = s->part_idx;
