@@ -357,6 +357,31 @@ typedef struct {
 } isc_sample_filter;
 int isc_rollout_finalize_filtered(const isc_rollout_step *s_host, const isc_sample_filter *f_host, void *stream);
 
+/* Token constraints of the roll-out - the beam search's rules (captioner.py:394-399) carried to it.  At step t a live
+ * row may not choose: one of ban_ids[0 .. n_ban) (the caller's <PAD>, <SOS>, <UNK>); under no_repeat the token fed into
+ * the step - seq[b, t-1], first_id (<SOS>) at t = 0; eos_id while t < min_len.  Duplicated ids are legal (<SOS> may equal
+ * <PAD>, the previous token may be a banned special).  f NULL: isc_rollout_finalize's choice over the allowed ids -
+ * arg-max with ties to the smaller id, or the inverse CDF in vocabulary order against sample_u * (allowed mass); the
+ * 128-column tiles that hold a banned id (at most n_ban + 2 per row) are re-read and their statistics recomputed over
+ * the allowed columns, nothing is subtracted from the row sum.  f given: isc_rollout_finalize_filtered's choice with the
+ * banned ids out of the ranking, the histograms, the kept mass and the draw (ban, then temperature, top-k, top-p; masses
+ * relative to the largest ALLOWED logit; integer sums, bit-repeatable).  seq_logprobs stays the MODEL's
+ * log_softmax(x)[token] over the full row, sampling_logprobs is taken under the restricted distribution; finished rows,
+ * the `alive` counters, raw_tokens and xt_next as without constraints.  A step at which nothing is banned (an all-zero
+ * struct; min_len alone once t >= min_len) is served by the two entry points above, bit for bit.
+ * Before any launch: a null struct -> ISC_E_NULL; n_ban outside [0, 8], an id outside [0, V), min_len outside [0, T],
+ * `forced` together with any constraint, V <= n_ban + 2 (no allowed id left), n_tile != ceil(V / 128) -> ISC_E_SHAPE;
+ * logits missing (every constrained form reads them) -> ISC_E_NULL. */
+typedef struct {
+    int64_t ban_ids[8];
+    int32_t n_ban;
+    int32_t no_repeat;
+    int64_t first_id;
+    int32_t min_len;
+} isc_decode_constraints;
+int isc_rollout_finalize_constrained(const isc_rollout_step *s_host, const isc_sample_filter *f_host /* may be NULL */,
+                                     const isc_decode_constraints *c_host, void *stream);
+
 /* Scheduled sampling of the teacher-forced unrolls (captioner.py:219-228): out_ids[b] = u_select[b] < ss_prob
  * ? a draw from exp(logp[b,:]) (inverse CDF with uniform u_draw[b], vocabulary order) : base_ids[b*stride].
  * logp = the previous step's normalised output, part_* = that step's tile statistics from isc_vocab_fwd. */

@@ -148,6 +148,12 @@ class SampleFilter(C.Structure):
                 ('sampling_logprobs', C.c_void_p)]
 
 
+class DecodeConstraints(C.Structure):
+    """isc_decode_constraints: the banned ids of isc_rollout_finalize_constrained."""
+    _fields_ = [('ban_ids', C.c_int64 * 8), ('n_ban', C.c_int32), ('no_repeat', C.c_int32), ('first_id', C.c_int64),
+                ('min_len', C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -216,6 +222,8 @@ SIGNATURES = {
     'isc_rollout_finalize': (C.c_int, [C.POINTER(RolloutStep), C.c_void_p]),
     'isc_rollout_finalize_launches': (C.c_longlong, []),
     'isc_rollout_finalize_filtered': (C.c_int, [C.POINTER(RolloutStep), C.POINTER(SampleFilter), C.c_void_p]),
+    'isc_rollout_finalize_constrained': (C.c_int, [C.POINTER(RolloutStep), C.POINTER(SampleFilter),
+                                                   C.POINTER(DecodeConstraints), C.c_void_p]),
     'isc_beam_merge': (C.c_int, [C.POINTER(BeamMergeArgs), C.c_void_p]),
     'isc_beam_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'isc_beam_topk': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -275,7 +275,10 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
             rs.t, rs.logits = t, out[:, t].data_ptr()
             rs.part_max, rs.part_sum, rs.part_idx = S.pm[t].data_ptr(), S.ps[t].data_ptr(), S.pi[t].data_ptr()
             rs.xt_next = S.xt[t + 1].data_ptr() if t + 1 < T else None
-            ops.rollout_finalize(rs)
+            if tokens_in.get('cons') is not None:     # (token constraints: the draw runs over the allowed ids)
+                ops.rollout_finalize_constrained(rs, tokens_in['cons'])
+            else:
+                ops.rollout_finalize(rs)
             if t + 1 < T:
                 S.tok[t + 1].copy_(seq[:, t])         # it * unfinished, written by this finalize
     _keep_mask(cap, S, L, [masks])
@@ -955,15 +958,17 @@ def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_lab
     return logp
 
 
-def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks):
+def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks, cons=None):
     """Sampled roll-out with REINFORCE gradients (captioner.py:290-349, sample_max=0, train mode): one unroll
     that samples each next token on the device and keeps the activations for the backward pass; the returned
-    log-probs are log p(drawn token), zero after the reference's early `break`."""
+    log-probs are log p(drawn token), zero after the reference's early `break`.
+    cons: forward_rl's token constraints (an isc_decode_constraints struct) - they decide which token is drawn; the
+    log-probability, and so the gradient, stays the model's own of that token."""
     fc, att = cap._f32(fc), cap._f32(att)          # (as xe_with_grad: fp32 once, in front of the prologue)
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
     B = fc.shape[0]
-    draws = {'T': T}
+    draws = {'T': T, 'cons': cons}
     if replay is not None:
         draws['forced'] = cap._ids(replay)
     else:

@@ -860,7 +860,8 @@ class Captioner(nn.Module):
 
     def forward_rl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, sample_max,
                    _replay=None, _masks=None, temperature=1.0, top_k=0, top_p=1.0, generator=None,
-                   return_sampling_logprobs=False, _uniforms=None, captions_per_image=1):
+                   return_sampling_logprobs=False, _uniforms=None, captions_per_image=1, suppress_special=False,
+                   decoding_constraint=0, min_len=0):
         """Greedy (`sample_max=1`) or sampled roll-out (captioner.py:290-349) with the whole T-step loop
         enqueued without a host sync; `_replay` [B,T] forces the raw draws (parity tests).
         Sampled roll-outs (`sample_max=0`) take the sampling controls `temperature` (> 0), `top_k` (0: off) and `top_p`
@@ -875,8 +876,23 @@ class Captioner(nn.Module):
         region row once for an image's rows).  `_uniforms`, `_replay`, the returned tensors, the sampling log-probs and
         the attention-weight attributes are [I*n, ...], row i*n + j = draw j of image i - the layout of the same call on
         inputs repeated with `repeat_interleave(n, 0)`; `fc_feats` / `cpt_feats` stay [I, ...].  Sampled roll-outs only
-        (n equal greedy captions would be a mistake), inference only (no gradients, eval mode, no `_masks`)."""
+        (n equal greedy captions would be a mistake), inference only (no gradients, eval mode, no `_masks`).
+        Token constraints - the beam search's rules (`sample_batch`, captioner.py:394-399), all off by default: under
+        `suppress_special` a live row never chooses <PAD>, <SOS> or <UNK> (as there: only when pad_id != eos_id), under
+        `decoding_constraint=1` never the token it was just fed (seq[b, t-1]; <SOS> at t = 0), and never <EOS> while
+        t < `min_len` (0 <= min_len <= max_seq_len).  Greedy takes the arg-max over the allowed ids (ties to the smaller
+        id: greedy under the first two rules is `sample_batch(beam_size=1)`); a sampled draw runs over the allowed ids
+        only - ban, then temperature, top-k, top-p.  `seq_logprobs` stays the MODEL's log_softmax(x)[token] over the full
+        row (what the beam's scores sum); the sampling log-probs are those of the restricted distribution.  They combine
+        with the sampling controls, `captions_per_image` and the differentiable sampled roll-out (the gradient is that
+        of the model's log-probability of the drawn token); `_replay` excludes them.  The token is chosen on the device
+        (isc_rollout_finalize_constrained), still without a host read.  A constrained greedy roll-out materialises each
+        step's [B, V] logits (the plain one decides on the tile statistics alone), and a constrained call stays on the
+        general kernels, served eagerly: no few-row step, no fused finalize, no roll-out graph (follow-ups)."""
         n_cap = self._check_captions_per_image(captions_per_image, sample_max, _masks)
+        cons = self._decode_constraints(suppress_special, decoding_constraint, min_len, max_seq_len)
+        if cons is not None and _replay is not None:
+            raise ValueError('_replay forces the tokens: it excludes suppress_special / decoding_constraint / min_len')
         temperature, top_k, top_p = ops.check_sample_filter(temperature, top_k, top_p)
         filtered = temperature != 1.0 or 0 < top_k < self.vocab_size or top_p < 1.0
         if sample_max and (filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
@@ -891,15 +907,15 @@ class Captioner(nn.Module):
                 filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
             filt = self._sample_filter(temperature, top_k, top_p, generator, _uniforms, return_sampling_logprobs)
             out = self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0, None,
-                                _masks, filt, group=n_cap)
+                                _masks, filt, group=n_cap, cons=cons)
             return out[:3] + ((filt['slp'],) if return_sampling_logprobs else ())
         if return_sampling_logprobs or _uniforms is not None or generator is not None:
             raise ValueError('generator / return_sampling_logprobs / _uniforms are not available with gradients enabled')
         if not sample_max and self._needs_grad():
             from .autograd import rollout_with_grad
             return rollout_with_grad(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels,
-                                     max_seq_len, _replay, _masks)
-        if (sample_max and self.__dict__.get('_rollout_graphs') is not None and not self._needs_grad()
+                                     max_seq_len, _replay, _masks, cons)
+        if (sample_max and cons is None and self.__dict__.get('_rollout_graphs') is not None and not self._needs_grad()
                 and not self.training and _replay is None and _masks is None and ops.TIMER.arm_step is None
                 and fc_feats.shape[0] <= self.ROLLOUT_GRAPH_MAX_ROWS and ops.graphs_allowed_here()
                 and fc_feats.is_cuda and not torch.cuda.is_current_stream_capturing()   # (a training graph's capture runs its greedy baseline
@@ -907,7 +923,23 @@ class Captioner(nn.Module):
                 and self._features_in_domain(fc_feats, att_feats)):     # (beyond the domain: eager, exact engine)
             return self._graphed_rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len)
         return self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len,
-                             sample_max, _replay, _masks, group=n_cap)[:3]
+                             sample_max, _replay, _masks, group=n_cap, cons=cons)[:3]
+
+    def _decode_constraints(self, suppress_special, decoding_constraint, min_len, max_seq_len):
+        """forward_rl's token constraints, checked before anything touches the device: None when nothing is constrained
+        (the call is then the unconstrained one, launch for launch), else the isc_decode_constraints struct."""
+        special, no_repeat, min_len = ops.check_decode_constraints(suppress_special, decoding_constraint, min_len,
+                                                                   max_seq_len)
+        ban = []
+        if special and self.pad_id != self.eos_id:          # (captioner.py:394)
+            for i in (self.pad_id, self.sos_id, self.unk_id):
+                if i not in ban:
+                    ban.append(i)
+        if not ban and not no_repeat and not min_len:
+            return None
+        if self.vocab_size <= len(ban) + 2:
+            raise ValueError('a vocabulary of %d words leaves nothing to choose under the constraints' % self.vocab_size)
+        return ops.decode_constraints(ban, no_repeat, self.sos_id, min_len)
 
     def _check_captions_per_image(self, n, sample_max, masks):
         """forward_rl's `captions_per_image`, checked before anything touches the device.  Returns it as an int."""
@@ -1071,18 +1103,18 @@ class Captioner(nn.Module):
         return gb
 
     def _rollout(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                 masks, filt=None, group=1):
-        self._p()                                  # raises on CPU parameters before anything touches the device
+                 masks, filt=None, group=1, cons=None):
+        self._p()                                 # raises on CPU parameters before anything touches the device
         if not self._features_in_domain(fc_feats, att_feats):
             # features beyond the split-f16 domain: the reference decodes whatever its encoder produced
             # (captioner.py:198-214, 294-315) - so does this call, on the exact-fp32 engine
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                          replay, masks, filt, group)
+                                          replay, masks, filt, group, cons)
         # frozen weights for prologue + loop: split them once per call - or, with unchanged weights, once per run of calls
         with ops.h3_weights_scope(self._dev, key=self._weights_key()):
             return self._rollout_impl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max,
-                                      replay, masks, filt, group)
+                                      replay, masks, filt, group, cons)
 
     # ------------------------------------------------------------------ operand domain of the split-f16 engine
     SPLIT_F16_MAX = 65504.0
@@ -1148,8 +1180,10 @@ class Captioner(nn.Module):
                           'features to keep the fast engine.' % what)
 
     def _rollout_impl(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, T, sample_max, replay,
-                      masks, filt=None, group=1):
-        """group > 1 (forward_rl captions_per_image): the inputs and the prologue's tensors hold one entry per image, the
+                      masks, filt=None, group=1, cons=None):
+        """cons (forward_rl's token constraints, an isc_decode_constraints struct): every step's finalize is
+        isc_rollout_finalize_constrained and reads the step's logits - on the general kernels only.
+        group > 1 (forward_rl captions_per_image): the inputs and the prologue's tensors hold one entry per image, the
         state, the workspaces and the outputs `group` rows per image; the step plan's row_div ties the two together.
         Such a call stays on the general kernels at every row count (no fused gate tables, no few-row step)."""
         p = self._p()
@@ -1170,7 +1204,7 @@ class Captioner(nn.Module):
         # a handful of captions, no sampling: the few-row kernels (statistics per isc_rows_stats_tile columns)
         rows_ext = None
         if ((sample_max or replay is not None) and masks is None and not self.training and group == 1
-                and self._rows_step_ok(B, P)):
+                and cons is None and self._rows_step_ok(B, P)):
             rows_ext = _lib.RowsExt()
             rows_ext.stats_tile = ops.rows_stats_tile(V)
         planes = rows_ext is None and getattr(self, 'state_planes', True)
@@ -1203,7 +1237,7 @@ class Captioner(nn.Module):
         sos = torch.full((B,), self.sos_id, dtype=torch.int64, device=self._dev)
         if not use_tab:
             ops.embed_relu_fwd(emb, sos, xt[0])
-        need_logits = (not sample_max)
+        need_logits = (not sample_max) or cons is not None
         logits = self._new(B, V) if need_logits else None
         forced = sample_u = None
         if not sample_max:
@@ -1221,8 +1255,8 @@ class Captioner(nn.Module):
         # temperature / top-k / top-p: the filtered finalize takes the plain one's place (same launch count per step)
         filtered = filt is not None and filt['filtered']
         slp = None
-        if filt is not None and filt['want_slp'] and filtered:
-            slp = self._zeros(B, T)
+        if filt is not None and filt['want_slp'] and (filtered or cons is not None):
+            slp = self._zeros(B, T)        # (constraints: the sampled distribution is the restricted one)
         mask_for = self._mask_source(masks)
         rs = RolloutStep()
         rs.B, rs.V, rs.T, rs.n_tile, rs.W = B, V, T, ws['pmax'].shape[1], Wd
@@ -1258,14 +1292,18 @@ class Captioner(nn.Module):
                 rs.t = t
                 rs.unfinished = unf[t].data_ptr() if fuse else unfinished.data_ptr()
                 rs.xt_next = None if use_tab else xt[nxt].data_ptr()
-                if filtered:
+                if cons is not None:
+                    ops.rollout_finalize_constrained(
+                        rs, cons, (filt['temperature'], filt['top_k'], filt['top_p']) if filtered or slp is not None
+                        else None, slp)
+                elif filtered:
                     ops.rollout_finalize_filtered(rs, filt['temperature'], filt['top_k'], filt['top_p'], slp)
                 else:
                     ops.rollout_finalize(rs)
         ops.TIMER.armed = False
         if filt is not None and filt['want_slp']:
             # (default controls: the sampled distribution IS the model's)
-            filt['slp'] = slp if filtered else seq_logprobs.clone()
+            filt['slp'] = slp if slp is not None else seq_logprobs.clone()
         # no host read: the executed-step count stays on the device (`alive`) until someone needs it
         self._set_weights(aC, aS, bG, alive)
         return seq, seq_logprobs, seq_masks, raw, alive
@@ -1324,18 +1362,22 @@ class Captioner(nn.Module):
 
     @torch.no_grad()
     def sample_captions(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels, n=1, max_seq_len=16,
-                        temperature=1.0, top_k=0, top_p=1.0, generator=None, _uniforms=None, share_image=False):
+                        temperature=1.0, top_k=0, top_p=1.0, generator=None, _uniforms=None, share_image=False,
+                        suppress_special=False, decoding_constraint=0, min_len=0):
         """`n` sampled captions per image under the sampling controls of `forward_rl` (temperature / top_k / top_p):
         every image's inputs are repeated `n` times on the device (rows i*n ... i*n + n - 1 belong to image i) and ONE
         sampled roll-out draws all I*n captions.  Returns (captions[I][n], id_sequences[I][n]); the strings are built as
         `sample_batch` builds them (words up to <EOS>, <EOS> itself left out of the string and kept in the ids).
         `_uniforms` [I*n, max_seq_len]: test hook, as in `forward_rl`.
         `share_image=True` repeats nothing: the roll-out runs with `captions_per_image=n` on the I images' inputs (same
-        rows, same layout; `fc_feats` / `cpt_feats` are then [I, ...])."""
+        rows, same layout; `fc_feats` / `cpt_feats` are then [I, ...]).
+        `suppress_special`, `decoding_constraint`, `min_len`: the token constraints of `forward_rl`, in both forms."""
         n = int(n)
         if n < 1:
             raise ValueError('n must be >= 1, got %r' % (n,))
         ops.check_sample_filter(temperature, top_k, top_p)
+        cons = dict(zip(('suppress_special', 'decoding_constraint', 'min_len'),
+                        ops.check_decode_constraints(suppress_special, decoding_constraint, min_len, max_seq_len)))
         if self.training:
             self.eval()
 
@@ -1344,11 +1386,11 @@ class Captioner(nn.Module):
         if share_image and n > 1:
             seq, _, masks = self.forward_rl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0,
                                             temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
-                                            _uniforms=_uniforms, captions_per_image=n)
+                                            _uniforms=_uniforms, captions_per_image=n, **cons)
         else:
             seq, _, masks = self.forward_rl(rep(fc_feats), rep(att_feats), rep(cpt_words), rep(senti_words),
                                             rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
-                                            top_p=top_p, generator=generator, _uniforms=_uniforms)
+                                            top_p=top_p, generator=generator, _uniforms=_uniforms, **cons)
         seq_h, len_h = seq.cpu().tolist(), masks.sum(1).long().cpu().tolist()      # the call's one host read
         i2w, eos = self.idx2word, self.eos_id
         captions, ids = [], []

@@ -267,9 +267,11 @@ struct DevRollout {
 // Element mass = exp(x[i] - shift) * scale: (gmax, 1) for raw logits, (0, S) for log-probabilities, so that
 // both agree with the tile masses psum[j] * exp(pmax[j] - gmax) and with target = u * S.
 // Returns the drawn id, or -1 when rounding put the target past the total mass.
-__device__ __forceinline__ int sample_two_level(const float *x, float shift, float scale, const float *pm,
-                                                const float *ps, int n_tile, int V, float gmax, float target,
-                                                int lane) {
+// (tile_w(j) = the mass of tile j, skip(i) = column i may not be drawn: the constrained finalize hands in corrected tile
+// masses and its banned ids; sample_two_level below is the plain form.)
+template <class TileW, class Skip>
+__device__ __forceinline__ int sample_two_level_t(const float *x, float shift, float scale, TileW tile_w, Skip skip,
+                                                  int n_tile, int V, float target, int lane) {
     auto wave_incl = [&](float v) __attribute__((always_inline)) {
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -282,7 +284,7 @@ __device__ __forceinline__ int sample_two_level(const float *x, float shift, flo
     int tile = -1;
     for (int base = 0; base < n_tile && tile < 0; base += 64) {
         const int j = base + lane;
-        const float w = (j < n_tile) ? ps[j] * expf(pm[j] - gmax) : 0.f;
+        const float w = (j < n_tile) ? tile_w(j) : 0.f;
         const float incl = wave_incl(w);
         const unsigned long long hit = __ballot((run + incl > target) && j < n_tile);
         if (hit) {
@@ -297,17 +299,25 @@ __device__ __forceinline__ int sample_two_level(const float *x, float shift, flo
     int pick = -1;
     for (int c = 0; c < 2 && pick < 0; ++c) {
         const int i = tile * 128 + c * 64 + lane;
-        const float e = (i < V) ? expf(x[i] - shift) * scale : 0.f;
+        const float e = (i < V && !skip(i)) ? expf(x[i] - shift) * scale : 0.f;
         const float incl = wave_incl(e);
-        const unsigned long long hit = __ballot((run + incl > target) && i < V);
+        const unsigned long long hit = __ballot((run + incl > target) && i < V && !skip(i));
         if (hit) pick = tile * 128 + c * 64 + __ffsll((long long)hit) - 1;
         run += __shfl(incl, 63, 64);
     }
-    if (pick < 0) {                               // the tile's own sum rounded differently: its last column
-        pick = tile * 128 + 127;
-        if (pick > V - 1) pick = V - 1;
+    for (int c = 1; c >= 0 && pick < 0; --c) {    // the tile's own sum rounded differently: its last column that may be
+        const int i = tile * 128 + c * 64 + lane; // drawn (nothing skipped: min(tile * 128 + 127, V - 1))
+        const unsigned long long ok = __ballot(i < V && !skip(i));
+        if (ok) pick = tile * 128 + c * 64 + 63 - __clzll((long long)ok);
     }
     return pick;
+}
+
+__device__ __forceinline__ int sample_two_level(const float *x, float shift, float scale, const float *pm,
+                                                const float *ps, int n_tile, int V, float gmax, float target,
+                                                int lane) {
+    return sample_two_level_t(x, shift, scale, [&](int j) { return ps[j] * expf(pm[j] - gmax); },
+                              [](int) { return false; }, n_tile, V, target, lane);
 }
 
 #define ISC_FIN_ROWS_PER_WAVE 4
@@ -401,8 +411,169 @@ __global__ __launch_bounds__(1024) void rollout_finalize_wide_kernel(const DevRo
     }
 }
 
+// ------------------------------------------------------------------ token constraints (the beam's rules in the roll-out)
+// At most ISC_CON_MAX ids of a row may not be chosen at a step: the caller's ban list (with <EOS> appended while
+// t < min_len; unused slots -1) and, under no_repeat, the token fed into the step - seq[b, t-1], first_id at t = 0.
+// Duplicates are fine.  The tile statistics know nothing of them, and subtracting a banned mass from the row sum would
+// cancel to noise under a dominant banned token: the (max, arg-max, sum-exp) of every 128-column tile that holds a banned
+// id - at most ISC_CON_MAX tiles - are recomputed over its allowed columns, and the fold and the two-level draw run on the
+// corrected statistics.  A tile without an allowed column has maximum -inf and mass 0.
+#define ISC_CON_MAX 10
+struct DevCons {
+    int ban[ISC_CON_MAX - 1];
+    int no_repeat, first_id;
+};
+
+// the row's banned ids (-1: unused slot)
+__device__ __forceinline__ void con_row_ids(const DevRollout &R, const DevCons &C, int b, int (&ids)[ISC_CON_MAX]) {
+#pragma unroll
+    for (int k = 0; k < ISC_CON_MAX - 1; ++k) ids[k] = C.ban[k];
+    ids[ISC_CON_MAX - 1] = !C.no_repeat ? -1 : R.t == 0 ? C.first_id : (int)R.seq[(long long)b * R.T + R.t - 1];
+}
+
+__device__ __forceinline__ bool con_banned(const int (&ids)[ISC_CON_MAX], int i) {
+    bool hit = false;
+#pragma unroll
+    for (int k = 0; k < ISC_CON_MAX; ++k) hit |= ids[k] == i;
+    return hit;
+}
+
+__device__ __forceinline__ int rollout_finalize_con_row(const DevRollout &R, const DevCons &C, int b, int lane) {
+    const float *pm = R.part_max + (long long)b * R.n_tile, *ps = R.part_sum + (long long)b * R.n_tile;
+    const int *pi = R.part_idx + (long long)b * R.n_tile;
+    const float *x = R.logits + (long long)b * R.ld_logits;
+    float gmax, S;                          // the full row: seq_logprobs stays the MODEL's log_softmax(x)[token]
+    int gidx;
+    fold_row_stats(pm, ps, pi, R.n_tile, lane, gmax, gidx, S);
+    int ids[ISC_CON_MAX], ct[ISC_CON_MAX], ci[ISC_CON_MAX];
+    float cm[ISC_CON_MAX], cs[ISC_CON_MAX];
+    con_row_ids(R, C, b, ids);
+    // ---- the tiles that hold a banned id, each once: their statistics over the allowed columns (wave-uniform)
+#pragma unroll
+    for (int k = 0; k < ISC_CON_MAX; ++k) {
+        int tl = ids[k] >= 0 ? ids[k] >> 7 : -1;
+#pragma unroll
+        for (int j = 0; j < k; ++j)
+            if (ct[j] == tl) tl = -1;
+        ct[k] = tl; cm[k] = -INFINITY; cs[k] = 0.f; ci[k] = 0;
+        if (tl < 0) continue;
+        const int i0 = tl * 128 + lane, i1 = i0 + 64;
+        const bool ok0 = i0 < R.V && !con_banned(ids, i0), ok1 = i1 < R.V && !con_banned(ids, i1);
+        const float x0 = ok0 ? x[i0] : -INFINITY, x1 = ok1 ? x[i1] : -INFINITY;
+        float mx = -INFINITY;
+        int ix = 0x7fffffff;
+        if (ok0) { mx = x0; ix = i0; }
+        if (ok1 && (x1 > mx || ix == 0x7fffffff)) { mx = x1; ix = i1; }       // (equal values: i0 < i1 stays)
+        half_argmax(mx, ix);
+        {
+            const float ov = __shfl_xor(mx, 32, 64);
+            const int oi = __shfl_xor(ix, 32, 64);
+            if (ov > mx || (ov == mx && oi < ix)) { mx = ov; ix = oi; }
+        }
+        if (ix != 0x7fffffff) {             // (uniform) else: every column of the tile is banned - it contributes nothing
+            float s = half_sum((ok0 ? expf(x0 - mx) : 0.f) + (ok1 ? expf(x1 - mx) : 0.f));
+            s += __shfl_xor(s, 32, 64);
+            cm[k] = mx; cs[k] = s; ci[k] = ix;
+        }
+    }
+    auto tile = [&](int j, float &m, float &s, int &id) __attribute__((always_inline)) {
+        m = pm[j]; s = ps[j]; id = pi[j];
+#pragma unroll
+        for (int k = 0; k < ISC_CON_MAX; ++k)
+            if (ct[k] == j) { m = cm[k]; s = cs[k]; id = cs[k] > 0.f ? ci[k] : 0x7fffffff; }
+    };
+    // ---- the fold of fold_row_stats_impl over the corrected statistics: (amax, aidx, A) of the allowed ids
+    float amax = -INFINITY, A = 0.f;
+    int aidx = 0x7fffffff;
+    for (int j = lane; j < R.n_tile; j += 64) {
+        float m, s;
+        int id;
+        tile(j, m, s, id);
+        if (m > amax || (m == amax && id < aidx)) { amax = m; aidx = id; }
+    }
+    half_argmax(amax, aidx);
+    {
+        const float ov = __shfl_xor(amax, 32, 64);
+        const int oi = __shfl_xor(aidx, 32, 64);
+        if (ov > amax || (ov == amax && oi < aidx)) { amax = ov; aidx = oi; }
+    }
+    for (int j = lane; j < R.n_tile; j += 64) {
+        float m, s;
+        int id;
+        tile(j, m, s, id);
+        if (s > 0.f) A += s * expf(m - amax);
+    }
+    A = half_sum(A);
+    A += __shfl_xor(A, 32, 64);
+    if (aidx == 0x7fffffff) aidx = gidx;    // (a non-finite row: flagged by the fold above)
+    long long it = aidx;                    // arg-max over the allowed ids, ties to the smaller id
+    if (R.sample_u) {
+        const int pick = sample_two_level_t(
+            x, amax, 1.0f,
+            [&](int j) { float m, s; int id; tile(j, m, s, id); return s > 0.f ? s * expf(m - amax) : 0.f; },
+            [&](int i) { return con_banned(ids, i); }, R.n_tile, R.V,
+            R.sample_u[(long long)b * R.T + R.t] * A, lane);
+        if (pick >= 0) it = pick;           // (else: target == A after rounding)
+    }
+    const float lp = (x[it] - gmax) - logf(S);
+    const int u = R.unfinished[b];
+    const long long itm = u ? it : 0;       // the step's outputs: as rollout_finalize_row writes them
+    const int u2 = u && (itm != R.eos_id);
+    if (lane == 0) {
+        const long long o = (long long)b * R.T + R.t;
+        R.seq_masks[o] = (float)u;
+        R.seq[o] = itm;
+        R.seq_logprobs[o] = lp;
+        if (R.raw_tokens) R.raw_tokens[o] = it;
+        R.unfinished[b] = u2;
+    }
+    if (R.xt_next) {
+        const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
+        const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
+        float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
+        for (int i = lane; i < (R.W >> 2); i += 64) {
+            float4 v = src[i];
+            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
+            dst[i] = v;
+        }
+    }
+    return u2;
+}
+
+// the two launch shapes of the plain finalize (WAVES = 4: up to 1024 rows, 16: the wide one), one row per wave
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void rollout_finalize_con_kernel(const DevRollout R, const DevCons C) {
+    __shared__ int cnt[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (R.alive[R.t] == 0) return;          // block-uniform
+    const int b = blockIdx.x * WAVES + wave;
+    int alive = 0;
+    if (b < R.B) alive = rollout_finalize_con_row(R, C, b, lane);
+    if (lane == 0) cnt[wave] = alive;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) tot += cnt[w];
+        if (tot) atomicAdd(&R.alive[R.t + 1], tot);
+    }
+}
+
 static std::atomic<long long> g_finalize_launches{0};
 extern "C" long long isc_rollout_finalize_launches(void) { return g_finalize_launches.load(); }
+
+static DevRollout dev_rollout(const isc_rollout_step *s) {
+    DevRollout R;
+    R.B = s->B; R.V = s->V; R.T = s->T; R.t = s->t; R.n_tile = s->n_tile; R.W = s->W;
+    R.part_max = s->part_max; R.part_sum = s->part_sum; R.part_idx = s->part_idx;
+    R.logits = s->logits; R.ld_logits = s->ld_logits; R.forced = s->forced; R.sample_u = s->sample_u;
+    R.eos_id = s->eos_id; R.seq = s->seq; R.seq_logprobs = s->seq_logprobs; R.seq_masks = s->seq_masks;
+    R.unfinished = s->unfinished; R.alive = s->alive; R.raw_tokens = s->raw_tokens;
+    R.emb = s->emb; R.xt_add = s->xt_add; R.xt_next = s->xt_next;
+    R.rows_per_wave = 1;
+    return R;
+}
 
 extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
     if (!s) return ISC_E_NULL;
@@ -414,15 +585,8 @@ extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
     // xt_next = relu(emb[token]) (+ xt_add) moves float4s (rollout_finalize_row)
     if (s->xt_next && (!isc_aligned16(s->emb) || !isc_aligned16(s->xt_next) || (s->xt_add && !isc_aligned16(s->xt_add))))
         return ISC_E_ALIGN;
-    DevRollout R;
-    R.B = s->B; R.V = s->V; R.T = s->T; R.t = s->t; R.n_tile = s->n_tile; R.W = s->W;
-    R.part_max = s->part_max; R.part_sum = s->part_sum; R.part_idx = s->part_idx;
-    R.logits = s->logits; R.ld_logits = s->ld_logits; R.forced = s->forced; R.sample_u = s->sample_u;
-    R.eos_id = s->eos_id; R.seq = s->seq; R.seq_logprobs = s->seq_logprobs; R.seq_masks = s->seq_masks;
-    R.unfinished = s->unfinished; R.alive = s->alive; R.raw_tokens = s->raw_tokens;
-    R.emb = s->emb; R.xt_add = s->xt_add; R.xt_next = s->xt_next;
     // one row per wavefront; many rows: 16 waves per workgroup, so that the `alive` counter sees one atomic per 16 rows
-    R.rows_per_wave = 1;
+    const DevRollout R = dev_rollout(s);
     if (s->B > 1024)
         hipLaunchKernelGGL(rollout_finalize_wide_kernel, dim3((s->B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, R);
     else
@@ -498,7 +662,13 @@ __device__ __forceinline__ void flt_scan(unsigned &c, isc_u64 &m, unsigned *s32,
     m = bm + mi - m;
 }
 
-__global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const DevRollout R, const DevFilter F) {
+// CON (isc_rollout_finalize_constrained): the row's banned ids read as -inf - written over the staged row in LDS, or
+// replaced as the unstaged row is read.  The selection starts from Kstar = the last finite key instead of "every token",
+// so that they are out of the ranking, the histograms, the kept mass and the draw; the masses are taken relative to the
+// largest ALLOWED logit (an extra pass over the row finds it, with its id), seq_logprobs relative to the full row's.
+#define ISC_FLT_KEY_FINITE 0xff7fffffffffffffull
+template <bool CON>
+__device__ __forceinline__ void rollout_finalize_filtered_body(const DevRollout &R, const DevFilter &F, const DevCons &C) {
     extern __shared__ float flt_row[];
     __shared__ isc_u64 h_mass[256], c_key[256], c_mass[256], s64[4], sh64[4];
     __shared__ unsigned h_cnt[256], s32[4];
@@ -509,16 +679,64 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
     int alive = 0;
     for (int b = blockIdx.x; b < R.B; b += gridDim.x) {
         const float *xg = R.logits + (long long)b * R.ld_logits;
-        const float *xs = F.staged ? flt_row : xg;
+        const float *xs_ = F.staged ? flt_row : xg;
+        int ids[ISC_CON_MAX];
+        if (CON) con_row_ids(R, C, b, ids);
+        // (the unstaged constrained row: a banned id reads as -inf)
+        auto xs = [&](int i) __attribute__((always_inline)) {
+            return CON && !F.staged && con_banned(ids, i) ? -INFINITY : xs_[i];
+        };
         const int unf = R.unfinished[b];    // (thread 0 rewrites it behind the barriers below)
         float gmax, S;
         int gidx;
         fold_row_stats(R.part_max + (long long)b * R.n_tile, R.part_sum + (long long)b * R.n_tile,
                        R.part_idx + (long long)b * R.n_tile, R.n_tile, lane, gmax, gidx, S);
+        const float lp_max = gmax;          // the full row's: seq_logprobs is the MODEL's log-probability
+        unsigned n_ban = 0;
+        if (CON) {
+            if (F.staged) {
+                for (int i = tid; i < V; i += 256) flt_row[i] = xg[i];
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < ISC_CON_MAX; ++k)
+                    if (tid == k && ids[k] >= 0) flt_row[ids[k]] = -INFINITY;
+                __syncthreads();
+            }
+#pragma unroll
+            for (int k = 0; k < ISC_CON_MAX; ++k) {      // distinct banned ids
+                bool fresh = ids[k] >= 0;
+#pragma unroll
+                for (int j = 0; j < k; ++j) fresh &= ids[j] != ids[k];
+                n_ban += fresh;
+            }
+            // the largest allowed logit and its id (ties to the smaller id): the smallest key
+            isc_u64 kb = ~0ull;
+            for (int i = tid; i < V; i += 256) {
+                const isc_u64 K = flt_key(xs(i), i);
+                kb = K < kb ? K : kb;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const isc_u64 K = __shfl_xor(kb, o, 64);
+                kb = K < kb ? K : kb;
+            }
+            if (lane == 0) sh64[wave] = kb;
+            __syncthreads();
+            for (int w = 0; w < 4; ++w) kb = sh64[w] < kb ? sh64[w] : kb;
+            gidx = (int)(unsigned)kb;
+            gmax = xs(gidx);
+            __syncthreads();                // (sh64 is the selection's below)
+        }
         // ---- pass 1: stage the row, its minimum, its total mass
         isc_u64 wsum = 0;
         float mn = INFINITY;
-        if (F.staged && !(R.ld_logits & 3) && !(V & 3) && !((uintptr_t)R.logits & 15)) {
+        if (CON) {
+            for (int i = tid; i < V; i += 256) {
+                const float x = xs(i);
+                if (x > -INFINITY) mn = fminf(mn, x);
+                wsum += flt_mass(x, gmax, F.c_exp);
+            }
+        } else if (F.staged && !(R.ld_logits & 3) && !(V & 3) && !((uintptr_t)R.logits & 15)) {
             for (int i = tid * 4; i < V; i += 1024) {
                 const float4 v = *reinterpret_cast<const float4 *>(xg + i);
                 *reinterpret_cast<float4 *>(flt_row + i) = v;
@@ -543,8 +761,8 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
         __syncthreads();
         isc_u64 Wk = s64[0] + s64[1] + s64[2] + s64[3];            // mass of the survivors so far: every token
         const float xmin = fminf(fminf(shf[0], shf[1]), fminf(shf[2], shf[3]));
-        unsigned Nk = (unsigned)V;
-        isc_u64 Kstar = ~0ull;                                      // kept = {K <= Kstar}: every token
+        unsigned Nk = (unsigned)V - n_ban;
+        isc_u64 Kstar = CON ? ISC_FLT_KEY_FINITE : ~0ull;           // kept = {K <= Kstar}: every (allowed) token
         // ---- selection: pass 0 by count (top-k), pass 1 by mass (top-p) among pass 0's survivors
         for (int mode = 0; mode < 2; ++mode) {
             if (mode == 0 ? !(F.top_k > 0 && F.top_k < V) : !(F.top_p < 1.0f)) continue;      // uniform
@@ -563,7 +781,7 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
             // bucket 255 takes everything beyond the span (by mass: the zero-mass tail): it gets no atomics, its count and
             // mass are what the others leave of the totals
             for (int i = tid; i < V; i += 256) {
-                const float x = xs[i];
+                const float x = xs(i);
                 if (flt_key(x, i) > Klim) continue;
                 const int bk = flt_bucket(x, gmax, cb);
                 if (bk < 255) {
@@ -589,7 +807,7 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
             if (nstar <= 256) {
                 // the boundary bucket's elements, ranked against each other
                 for (int i = tid; i < V; i += 256) {
-                    const float x = xs[i];
+                    const float x = xs(i);
                     const isc_u64 K = flt_key(x, i);
                     if (K <= Klim && flt_bucket(x, gmax, cb) == bstar) {
                         const int slot = atomicAdd(&shi[1], 1);
@@ -622,7 +840,7 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
                     if (tid == 0) shi[0] = -1;
                     __syncthreads();
                     for (int i = tid; i < V; i += 256) {
-                        const float x = xs[i];
+                        const float x = xs(i);
                         const isc_u64 K = flt_key(x, i);
                         if (K <= Klim && flt_bucket(x, gmax, cb) == bstar && (shift == 56 || (K >> (shift + 8)) == prefix)) {
                             const int d = (int)((K >> shift) & 255);
@@ -654,7 +872,7 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
         const int i0 = tid * chunk < V ? tid * chunk : V, i1 = i0 + chunk < V ? i0 + chunk : V;
         isc_u64 own = 0;
         for (int i = i0; i < i1; ++i) {
-            const float x = xs[i];
+            const float x = xs(i);
             if (flt_key(x, i) <= Kstar) own += flt_mass(x, gmax, F.c_exp);
         }
         unsigned c0 = 0;
@@ -667,7 +885,7 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
             isc_u64 run = ex;
             int pick = i1 - 1;
             for (int i = i0; i < i1; ++i) {
-                const float x = xs[i];
+                const float x = xs(i);
                 if (flt_key(x, i) <= Kstar) run += flt_mass(x, gmax, F.c_exp);
                 if (run > target) { pick = i; break; }
             }
@@ -680,11 +898,11 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
         const long long itm = unf ? it : 0;
         const int u2 = unf && (itm != R.eos_id);
         if (tid == 0) {
-            const float xi = xs[it];
+            const float xi = xs_[it];
             const long long o = (long long)b * R.T + R.t;
             R.seq_masks[o] = (float)unf;
             R.seq[o] = itm;
-            R.seq_logprobs[o] = (xi - gmax) - logf(S);               // the MODEL's log-probability of the token
+            R.seq_logprobs[o] = (xi - lp_max) - logf(S);             // the MODEL's log-probability of the token
             if (F.slp)
                 F.slp[o] = (float)(((double)xi - (double)gmax) / (double)F.tau - log((double)Wk * (1.0 / 4294967296.0)));
             if (R.raw_tokens) R.raw_tokens[o] = it;
@@ -707,6 +925,23 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const De
     if (tid == 0 && alive) atomicAdd(&R.alive[R.t + 1], alive);
 }
 
+__global__ __launch_bounds__(256) void rollout_finalize_filtered_kernel(const DevRollout R, const DevFilter F) {
+    rollout_finalize_filtered_body<false>(R, F, DevCons());
+}
+
+__global__ __launch_bounds__(256) void rollout_finalize_filtered_con_kernel(const DevRollout R, const DevFilter F,
+                                                                            const DevCons C) {
+    rollout_finalize_filtered_body<true>(R, F, C);
+}
+
+static DevFilter dev_filter(const isc_rollout_step *s, const isc_sample_filter *f) {
+    DevFilter F;
+    F.c_exp = (float)(1.4426950408889634 / (double)f->temperature);
+    F.tau = f->temperature; F.top_k = f->top_k; F.top_p = f->top_p; F.slp = f->sampling_logprobs;
+    F.staged = s->V <= ISC_FLT_STAGE_MAX;
+    return F;
+}
+
 extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, void *stream) {
     if (!s || !f) return ISC_E_NULL;
     if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
@@ -716,21 +951,61 @@ extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const is
     if (s->B <= 0 || s->V <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3) || s->n_tile <= 0 ||
         s->ld_logits < s->V || s->forced)
         return ISC_E_SHAPE;
-    DevRollout R;
-    R.B = s->B; R.V = s->V; R.T = s->T; R.t = s->t; R.n_tile = s->n_tile; R.W = s->W;
-    R.part_max = s->part_max; R.part_sum = s->part_sum; R.part_idx = s->part_idx;
-    R.logits = s->logits; R.ld_logits = s->ld_logits; R.forced = nullptr; R.sample_u = s->sample_u;
-    R.eos_id = s->eos_id; R.seq = s->seq; R.seq_logprobs = s->seq_logprobs; R.seq_masks = s->seq_masks;
-    R.unfinished = s->unfinished; R.alive = s->alive; R.raw_tokens = s->raw_tokens;
-    R.emb = s->emb; R.xt_add = s->xt_add; R.xt_next = s->xt_next;
-    R.rows_per_wave = 1;
-    DevFilter F;
-    F.c_exp = (float)(1.4426950408889634 / (double)f->temperature);
-    F.tau = f->temperature; F.top_k = f->top_k; F.top_p = f->top_p; F.slp = f->sampling_logprobs;
-    F.staged = s->V <= ISC_FLT_STAGE_MAX;
+    const DevRollout R = dev_rollout(s);
+    const DevFilter F = dev_filter(s, f);
     const int grid = s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID;
     hipLaunchKernelGGL(rollout_finalize_filtered_kernel, dim3(grid), dim3(256),
                        F.staged ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0, (hipStream_t)stream, R, F);
+    ISC_LAUNCH_CHECK();
+    ++g_finalize_launches;
+    return ISC_OK;
+}
+
+// The roll-out's finalize under token constraints (include/insenticap_hip.h: isc_decode_constraints).  `f` NULL: the
+// plain finalize's choice (arg-max, or sample_u) over the allowed ids; given: the filtered one's.  A step at which
+// nothing is banned IS the unconstrained step: it goes to the two entry points above, bit for bit.
+extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const isc_sample_filter *f,
+                                                const isc_decode_constraints *c, void *stream) {
+    if (!s || !c) return ISC_E_NULL;
+    if (c->n_ban < 0 || c->n_ban > 8 || c->min_len < 0 || c->min_len > s->T) return ISC_E_SHAPE;
+    const bool any = c->n_ban > 0 || c->no_repeat || c->min_len > 0;
+    if (any) {
+        // (every constrained form reads the logits; forced tokens leave nothing to choose)
+        if (!s->logits) return ISC_E_NULL;
+        if (s->forced || s->V <= c->n_ban + 2) return ISC_E_SHAPE;
+        for (int k = 0; k < c->n_ban; ++k)
+            if (c->ban_ids[k] < 0 || c->ban_ids[k] >= s->V) return ISC_E_SHAPE;
+        if (c->no_repeat && (c->first_id < 0 || c->first_id >= s->V)) return ISC_E_SHAPE;
+        if (c->min_len > 0 && (s->eos_id < 0 || s->eos_id >= s->V)) return ISC_E_SHAPE;
+    }
+    DevCons C;
+    int n = 0;
+    for (; n < c->n_ban; ++n) C.ban[n] = (int)c->ban_ids[n];
+    if (s->t >= 0 && s->t < c->min_len) C.ban[n++] = (int)s->eos_id;
+    C.no_repeat = c->no_repeat != 0; C.first_id = (int)c->first_id;
+    if (n == 0 && !C.no_repeat) return f ? isc_rollout_finalize_filtered(s, f, stream) : isc_rollout_finalize(s, stream);
+    for (; n < ISC_CON_MAX - 1; ++n) C.ban[n] = -1;
+    if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
+        !s->unfinished || !s->alive || !s->emb || (f && !s->sample_u))
+        return ISC_E_NULL;
+    if (f && (!(f->temperature > 0.f) || !(f->temperature <= 3.0e38f) || f->top_k < 0 || !(f->top_p > 0.f)))
+        return ISC_E_SHAPE;
+    if (s->B <= 0 || s->V <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3) || s->n_tile != (s->V + 127) / 128 ||
+        s->ld_logits < s->V)
+        return ISC_E_SHAPE;
+    if (s->xt_next && (!isc_aligned16(s->emb) || !isc_aligned16(s->xt_next) || (s->xt_add && !isc_aligned16(s->xt_add))))
+        return ISC_E_ALIGN;
+    const DevRollout R = dev_rollout(s);
+    if (f) {
+        const DevFilter F = dev_filter(s, f);
+        const int grid = s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID;
+        hipLaunchKernelGGL(rollout_finalize_filtered_con_kernel, dim3(grid), dim3(256),
+                           F.staged ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0, (hipStream_t)stream, R, F, C);
+    } else if (s->B > 1024) {
+        hipLaunchKernelGGL(rollout_finalize_con_kernel<16>, dim3((s->B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, R, C);
+    } else {
+        hipLaunchKernelGGL(rollout_finalize_con_kernel<4>, dim3((s->B + 3) / 4), dim3(256), 0, (hipStream_t)stream, R, C);
+    }
     ISC_LAUNCH_CHECK();
     ++g_finalize_launches;
     return ISC_OK;

@@ -57,6 +57,10 @@ class Detector(nn.Module):
         # between them).  False: every iteration runs the eager sequence below.
         self.train_graphs = True
         self._rl_graph = None
+        # Token constraints of both roll-outs of an iteration (the sampled one and the greedy baseline): None, or a dict
+        # of Captioner.forward_rl's keywords `suppress_special`, `decoding_constraint`, `min_len`.  While it is set every
+        # iteration runs the eager sequence (capture under constraints is not built).
+        self.rollout_constraints = None
 
     def enable_data_parallel(self, group=None, broadcast=True):
         """Data-parallel RL training over the ranks of `group` (default process group; backend nccl = RCCL over xGMI,
@@ -110,6 +114,12 @@ class Detector(nn.Module):
             sums[key] = sums[key] + (value.detach() if torch.is_tensor(value) else value)
 
         device = next(self.parameters()).device
+        rl_kw = dict(self.rollout_constraints or {})
+        if set(rl_kw) - {'suppress_special', 'decoding_constraint', 'min_len'}:
+            raise ValueError('rollout_constraints takes suppress_special / decoding_constraint / min_len, got %r'
+                             % sorted(rl_kw))
+        if not any(rl_kw.values()):
+            rl_kw = {}                       # (all off: the unconstrained iteration, graphs included)
         # data-parallel branches: taken whenever DP is enabled and a process group exists - also a one-rank group
         # (shares are then exactly 1.0), so a one-GPU RCCL run crosses the code an 8-rank run does
         dist_on = self.dp_arena is not None and dp.distributed(self.dp_group)
@@ -149,7 +159,7 @@ class Detector(nn.Module):
                 """One iteration (models/decoder.py:69-167).  `exact`: on the exact-fp32 GEMM engine, eagerly - the retry of
                 an iteration whose roll-outs left the split-f16 operand domain (OutOfDomain is raised at the iteration's
                 own synchronisation point, before anything is updated)."""
-                if (training and self.train_graphs and device.type == 'cuda'
+                if (training and self.train_graphs and not rl_kw and device.type == 'cuda'
                         and ops.TIMER.arm_step is None and ops.graphs_allowed_here() and not exact):
                     # the same iteration from HIP graphs (train_graph.RLTrainGraph): same calls in the same order
                     from .train_graph import RLTrainGraph
@@ -185,7 +195,7 @@ class Detector(nn.Module):
                 # sampled roll-out (graph kept in train mode) and the domain-alignment loss on its prologue
                 sample_captions, sample_logprobs, seq_masks = cap(
                     fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
-                    sample_max=0, mode='rl')
+                    sample_max=0, mode='rl', **rl_kw)
                 da_loss = self.cap_da_crit(cap.cpt_feats, cap.fc_feats.detach())
                 # DP: each term's share of the global normaliser (mask sum, XE tokens, seq2seq tokens, rows)
                 w_rl = w_xe = w_s2s = w_rows = None
@@ -203,7 +213,7 @@ class Detector(nn.Module):
                 with torch.no_grad():
                     greedy_captions, _, greedy_masks = cap(
                         fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
-                        sample_max=1, mode='rl')
+                        sample_max=1, mode='rl', **rl_kw)
                 cap.train(training)
 
                 # The rewards need the token matrices on the host (CIDEr-D is host code).  Start their copies

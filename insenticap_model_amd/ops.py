@@ -832,6 +832,47 @@ def rollout_finalize_filtered(step, temperature=1.0, top_k=0, top_p=1.0, samplin
     TIMER.end(e0, 'rollout_finalize_filtered[%d]' % step.B, 0.0, 4.0 * step.B * (step.V + 2 * step.n_tile + 2 * step.W))
 
 
+def check_decode_constraints(suppress_special, decoding_constraint, min_len, max_seq_len):
+    """The domain of the roll-out's token constraints: ValueError before anything touches the device.  Returns them as
+    (bool, bool, int)."""
+    if not isinstance(suppress_special, (bool, int)) or suppress_special not in (0, 1):
+        raise ValueError('suppress_special must be a bool, got %r' % (suppress_special,))
+    if not isinstance(decoding_constraint, (bool, int)) or decoding_constraint not in (0, 1):
+        raise ValueError('decoding_constraint must be 0 or 1, got %r' % (decoding_constraint,))
+    if isinstance(min_len, bool) or not hasattr(min_len, '__index__') or not 0 <= int(min_len) <= int(max_seq_len):
+        raise ValueError('min_len must be an integer in [0, max_seq_len = %r], got %r' % (max_seq_len, min_len))
+    return bool(suppress_special), bool(decoding_constraint), int(min_len)
+
+
+def decode_constraints(ban_ids=(), no_repeat=False, first_id=0, min_len=0):
+    """An isc_decode_constraints struct."""
+    ban_ids = [int(i) for i in ban_ids]
+    if len(ban_ids) > 8:
+        raise ValueError('at most 8 banned ids, got %d' % len(ban_ids))
+    c = _lib.DecodeConstraints()
+    for k, i in enumerate(ban_ids):
+        c.ban_ids[k] = i
+    c.n_ban, c.no_repeat, c.first_id, c.min_len = len(ban_ids), int(bool(no_repeat)), int(first_id), int(min_len)
+    return c
+
+
+def rollout_finalize_constrained(step, cons, filt=None, sampling_logprobs=None):
+    """isc_rollout_finalize_constrained: the roll-out's finalize under the token constraints `cons` (decode_constraints).
+    filt None: the plain finalize's choice (arg-max, or step.sample_u) over the allowed ids; (temperature, top_k, top_p):
+    the filtered one's.  One launch."""
+    f = None
+    if filt is not None:
+        f = _lib.SampleFilter()
+        f.temperature, f.top_k, f.top_p = check_sample_filter(*filt)
+        f.sampling_logprobs = ptr(sampling_logprobs)
+    lib = _lib.load()
+    e0 = TIMER.begin()
+    check(lib.isc_rollout_finalize_constrained(C.byref(step), None if f is None else C.byref(f), C.byref(cons), stream()),
+          'isc_rollout_finalize_constrained')
+    TIMER.end(e0, 'rollout_finalize_constrained[%d]' % step.B, 0.0,
+              4.0 * step.B * ((step.V if f is not None else 0) + 3 * step.n_tile + 2 * step.W))
+
+
 def sched_sample(logp, part_max, part_sum, part_idx, u_select, u_draw, ss_prob, base_ids, out_ids, raw=False):
     """out_ids[b] = u_select[b] < ss_prob ? draw from exp(logp[b]) : base_ids[b]  (base_ids may be a strided column).
     raw: `logp` holds the row's raw logits (isc_sched_sample_raw)."""
