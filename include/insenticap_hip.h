@@ -833,6 +833,24 @@ int isc_reward_loss_fwd(const float *seq_logprobs, const float *seq_masks, const
 int isc_reward_loss_bwd(const float *seq_masks, const float *reward, int B, int T, const float *gout,
                         const float *sum_count, float *d_seq_logprobs, void *stream);
 
+/* Group reward of self-critical RL on n sampled captions per image (rows image-major: row r = i*n + j is sample j of
+ * image i): a sample's baseline is the mean score of the image's OTHER n - 1 samples, so no greedy roll-out is needed.
+ *   baseline[i,j] = (sum over k != j, k ascending, of scores[i,k]) / (n - 1)            fp64
+ *   adv[i,j]      = scores[i,j] - baseline[i,j]                                         fp64
+ *   reward[r,t]   = (float)(adv[r] + cls_flag * (double)cls_reward[r,t]) for every t    (unmasked: the criterion masks;
+ *                   the product is rounded before the addition - no fused multiply-add); (float)adv[r] when
+ *                   cls_reward == NULL
+ *   stats4        = { mean of scores, mean of adv, mean of cls_reward over all I*n*T entries (0 when NULL), mean of the
+ *                   stored reward floats }, accumulated in fp64
+ * scores [I*n] fp64 (the host's CIDEr-D scores, uploaded as they are), cls_reward / reward [I*n, T] fp32 contiguous,
+ * stats4 four doubles - all device memory.  Two launches, no atomics: one thread per (row, step) for the reward, then one
+ * workgroup of 256 threads for the statistics - thread x adds its elements x, x + 256, ... ascending, the 256 partial sums
+ * are added pairwise (stride 128, 64, ..., 1) - so two runs give the same bits.  The statistics pass is one workgroup
+ * over I*n*T values: meant for training batches (thousands of rows), not for millions.
+ * n < 2, I < 1 or T < 1: ISC_E_SHAPE, nothing is launched or written. */
+int isc_group_reward(const double *scores, int I, int n, const float *cls_reward, double cls_flag, int T,
+                     float *reward, double *stats4, void *stream);
+
 /* Log-softmax backward with the criteria's gradient handed over SPARSE: XECriterion (captioner.py:427-440) and the
  * REINFORCE gather (captioner.py:336) touch one column per (caption, step) row, so their d log-prob is `coef[m]` at
  * column `ids[m]` - up to ISC_SPARSE_MAX such (ids, coef) pairs (HOST arrays of device pointers to [M] vectors, rows

@@ -217,7 +217,9 @@ def _classify(cap, S, L):
 def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks, lazy=None,
                    group=1):
     """group = n > 1 (forward_xe captions_per_image): the prologue runs on the I images, the unroll on the I*n rows of
-    tokens_in; the step plans carry row_div = n.
+    tokens_in; the step plans carry row_div = n.  With the sampled roll-out (mode 'rl', forward_rl captions_per_image)
+    EVERYTHING step-invariant is per image - label_e, label_w and the hoisted att-LSTM term pre1 included (the image's
+    label serves all of its rows: the step reads pre1 at row // n) - and the unroll runs on I*n rows.
     Returns (logp [B,T,V], S). tokens_in [B,T]: ground-truth inputs (column 0 = <SOS>) - or, for the sampled
     roll-out with gradients, a dict {'T', 'u' (uniforms [B,T]) or 'forced' (raw draws [B,T])}: every step then
     draws its own next token on the device (isc_rollout_finalize) while the activations the backward pass
@@ -228,10 +230,12 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     [B,T] straight from the raw logits + tile statistics (isc_gather_logp_raw; the bits the tensor would have held), and
     the backward recomputes the softmax term from them (isc_logsoftmax_bwd_raw)."""
     p = cap._p()
-    P = cap._prologue(p, mode, fc, att, cpt_words, senti_words, senti_labels, masks, group=group)
-    Wd, V = cap.settings['word_emb_dim'], cap.vocab_size
     sampling = isinstance(tokens_in, dict)
-    B, T = (P.B, tokens_in['T']) if sampling else tokens_in.shape
+    P = cap._prologue(p, mode, fc, att, cpt_words, senti_words, senti_labels, masks, group=1 if sampling else group)
+    if sampling and group > 1:
+        P.row_div = group                     # (pre_rows stays False: pre1 [I,4H], one row per image)
+    Wd, V = cap.settings['word_emb_dim'], cap.vocab_size
+    B, T = (P.B * group, tokens_in['T']) if sampling else tokens_in.shape
     sched = not sampling and cap.training and ss_prob > 0.0
     S = _Saved()
     S.p, S.P, S.mode, S.B, S.T = p, P, mode, B, T
@@ -582,10 +586,11 @@ def _content_att_grads(g, dqa, h1_cur, dwc_rows):
     g.gout('attention.cont_att.att_alpha.bias')          # softmax is shift invariant
 
 
-def _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, label_e, lo=0, d_label_e=None):
+def _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, label_e, lo=0, d_label_e=None, group=1):
     """Sentiment attention's own parameters from the sweep's dqw [T, n, A] (the branch's rows: [lo, n) - the others are
     zero) and alpha partials.  label2word(label_e) enters every step's score: d label_w = sum_t dqw[t], returned (None
-    without labels) and, given d_label_e, accumulated into it."""
+    without labels) and, given d_label_e, accumulated into it.  group > 1: label_e / label_w hold one entry per image -
+    d label_w is summed over the image's rows, in row order."""
     T, n, A = dqw.shape
     dqwf = dqw.view(T * n, A)
     g.tn(dqwf, h1_cur, 'attention.senti_att.h2word.weight')
@@ -597,6 +602,8 @@ def _senti_att_grads(cap, g, dqw, h1_cur, dws_rows, label_e, lo=0, d_label_e=Non
     d_label_w = cap._new(n * A)
     ops.colsum(dqw.view(T, n * A), d_label_w)
     d_label_w = d_label_w.view(n, A)[lo:]
+    if group > 1:
+        d_label_w = _group_sum(d_label_w, group)
     g.tn(d_label_w, label_e, 'attention.senti_att.label2word.weight')
     g.csum(d_label_w, 'attention.senti_att.label2word.bias')
     if d_label_e is not None:
@@ -833,12 +840,18 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
         cap, S, L, {(True,): _step_bwd_plan(cap, p, P if has_c else None, P if has_s else None)}, D, dhd.view(T, B, H),
         not L.short, pk is not None)
     dG1_sum = D.dG1_sum
+    # captions per image, everything per image (the sampled roll-out): an image's rows of sum_t dG1 added in row order -
+    # what follows (the once-per-caption dW partners fc_e / label_e, d fc_e, d label_e) is then per image as it stands
+    per_image = P.row_div > 1 and not P.pre_rows
+    if per_image:
+        dG1_sum = _group_sum(dG1_sum, P.row_div)
     if has_c:
         dP_att, dV_att = _scan_bwd(cap, P.att_p3, P.att_e3, S.aC, S.qa, D.dv if gate else D.d_feat, D.de_c,
                                    p['attention.cont_att.att_alpha.weight'], group=P.row_div)
     if has_s:
+        # (P.row_div > 1 with sentiment words: the sampled roll-out - words_p / words_e / label_w per image)
         dP_w, dV_w = _scan_bwd(cap, P.words_p3, P.words_e3, S.aS, S.qw, D.ds if gate else D.d_feat, D.de_s,
-                               p['attention.senti_att.word_alpha.weight'], q2=P.label_w)
+                               p['attention.senti_att.word_alpha.weight'], q2=P.label_w, group=P.row_div)
 
     # ---- weight gradients: one contraction over all T*B rows each
     tok_tb = S.tok.view(-1)
@@ -861,12 +874,13 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     _lstm_dw(g, dG1f, dG2f, h1_prev, h1_cur_l, h2_prev, xt_tb, feat_tb, dG1_sum, P.fc_e if P.fc_rows is None else P.fc_rows,
              P.label_e)
     d_fc_e, d_label_e, dEmb = _dx_bwd(cap, g, dG1f, dG1_sum, tok_tb, P.label_e is not None)
-    if P.row_div > 1:
+    if P.row_div > 1 and not per_image:
         d_fc_e = _group_sum(d_fc_e, P.row_div)
     if has_c:
         _content_att_grads(g, D.dqa, h1_cur, D.dwc_rows)
     if has_s:
-        _senti_att_grads(cap, g, D.dqw, h1_cur, D.dws_rows, P.label_e, d_label_e=d_label_e)
+        _senti_att_grads(cap, g, D.dqw, h1_cur, D.dws_rows, P.label_e, d_label_e=d_label_e,
+                         group=P.row_div if per_image else 1)
     if gate:
         dzf = D.dz.view(TB, A)
         g.tn(dzf, S.v.view(TB, E), 'attention.cont2att.weight')
@@ -900,7 +914,7 @@ class DecodeFn(torch.autograd.Function):
     def forward(ctx, cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels, ss_prob, masks,
                 names, lazy, *params):
         group = 1
-        if isinstance(mode, tuple):                  # ('xe', n): forward_xe with captions_per_image = n
+        if isinstance(mode, tuple):                  # ('xe' | 'rl', n): forward_xe / forward_rl with captions_per_image = n
             mode, group = mode
         with torch.no_grad():
             logp, S = _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_labels,
@@ -958,26 +972,31 @@ def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_lab
     return logp
 
 
-def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks, cons=None):
+def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks, cons=None, group=1):
     """Sampled roll-out with REINFORCE gradients (captioner.py:290-349, sample_max=0, train mode): one unroll
     that samples each next token on the device and keeps the activations for the backward pass; the returned
     log-probs are log p(drawn token), zero after the reference's early `break`.
     cons: forward_rl's token constraints (an isc_decode_constraints struct) - they decide which token is drawn; the
-    log-probability, and so the gradient, stays the model's own of that token."""
+    log-probability, and so the gradient, stays the model's own of that token.
+    group = n > 1 (forward_rl captions_per_image): the inputs hold one entry per image, the draws (`replay`, the
+    uniforms) and the returned tensors n rows per image, row i*n + j = draw j of image i."""
     fc, att = cap._f32(fc), cap._f32(att)          # (as xe_with_grad: fp32 once, in front of the prologue)
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
-    B = fc.shape[0]
+    B = fc.shape[0] * group
     draws = {'T': T, 'cons': cons}
     if replay is not None:
         draws['forced'] = cap._ids(replay)
+        if group > 1 and tuple(draws['forced'].shape) != (B, T):
+            raise ValueError('_replay must hold the draws of every row, [%d, %d], got %r'
+                             % (B, T, tuple(draws['forced'].shape)))
     else:
         draws['u'] = torch.rand(B, T, device=cap._dev)
     was = cap.training
     # the roll-out's [B,T,V] log-probs are never an API output (captioner.py:336 keeps log p(drawn token) only): the
     # decode node returns that column - already times `live` - from the raw logits (lazy = True; DecodeFn.backward)
-    outs = DecodeFn.apply(cap, 'rl', fc, att, cpt_words, senti_words, draws, senti_labels, 0.0,
-                          masks, names, True, *params)
+    outs = DecodeFn.apply(cap, 'rl' if group == 1 else ('rl', group), fc, att, cpt_words, senti_words, draws,
+                          senti_labels, 0.0, masks, names, True, *params)
     cap.train(was)
     lp = outs[0]
     cap.cpt_feats, cap.fc_feats = outs[1], outs[2]

@@ -869,14 +869,27 @@ class Captioner(nn.Module):
         and `generator` for the uniforms; `_uniforms` [B,T] float32 replaces the drawn uniforms (tests, the counterpart of
         `_replay`).  `seq_logprobs` stays the MODEL's log-probability of the drawn token; `return_sampling_logprobs=True`
         appends a fourth tensor, the log-probability under the distribution that was sampled.  With the default controls
-        the call is today's plain multinomial roll-out, bit for bit.  Inference only for now.
+        the call is today's plain multinomial roll-out, bit for bit.  The sampling controls are inference-only.
         `captions_per_image=n` > 1 draws n captions per image without repeating the image: the five inputs hold one
         entry per image, [I, ...]; everything step-invariant (embedded regions, their projection, the att-LSTM's hoisted
         term) is computed and kept once per image, and the decode runs on I*n rows that share it (the scan loads a
         region row once for an image's rows).  `_uniforms`, `_replay`, the returned tensors, the sampling log-probs and
         the attention-weight attributes are [I*n, ...], row i*n + j = draw j of image i - the layout of the same call on
         inputs repeated with `repeat_interleave(n, 0)`; `fc_feats` / `cpt_feats` stay [I, ...].  Sampled roll-outs only
-        (n equal greedy captions would be a mistake), inference only (no gradients, eval mode, no `_masks`).
+        (n equal greedy captions would be a mistake), in one of two forms: inference (eval mode under torch.no_grad(),
+        no `_masks`), or the differentiable training roll-out (training mode with gradients enabled: self-critical RL
+        on n samples per image).  In the training form `senti_labels` is [I] - the labels come from the image - and
+        everything step-invariant (fc_e, att_e / att_p, the sentiment words' words_e / words_p, label_e / label_w, cpt
+        and the hoisted att-LSTM term) is computed, kept and differentiated once per image: the decode and its reverse
+        sweep run on the I*n rows, an image's dP / dV of BOTH attentions sum over its rows in a fixed order (row
+        ascending, steps from the last to the first inside), d fc_e / d label_e / d label_w over its rows in row order;
+        no atomics, two runs give the same bits.  `fc_feats` / `cpt_feats` and their incoming gradients are [I, E].
+        `_replay` [I*n, T] and `_masks` are accepted there; the dropout masks of per-image tensors are per image ('fc'
+        [I,E], 'att' [I*R,E], 'words' [I*Mw,Wd], 'label' [I,Wd]), the h_lang keep-masks 'out<t>' per row [I*n,H].  With
+        explicit `_masks`, or with dropout off, the call is the function of the same call on the repeated inputs with
+        each per-image mask repeated; in training mode the per-image masks are DRAWN once per image, where the repeated
+        form draws one per copy (the one deliberate difference, as in `forward_xe`).  The uniforms are
+        torch.rand(I*n, T); temperature / top_k / top_p stay inference-only.
         Token constraints - the beam search's rules (`sample_batch`, captioner.py:394-399), all off by default: under
         `suppress_special` a live row never chooses <PAD>, <SOS> or <UNK> (as there: only when pad_id != eos_id), under
         `decoding_constraint=1` never the token it was just fed (seq[b, t-1]; <SOS> at t = 0), and never <EOS> while
@@ -889,7 +902,7 @@ class Captioner(nn.Module):
         (isc_rollout_finalize_constrained), still without a host read.  A constrained greedy roll-out materialises each
         step's [B, V] logits (the plain one decides on the tile statistics alone), and a constrained call stays on the
         general kernels, served eagerly: no few-row step, no fused finalize, no roll-out graph (follow-ups)."""
-        n_cap = self._check_captions_per_image(captions_per_image, sample_max, _masks)
+        n_cap = self._check_captions_per_image(captions_per_image, sample_max, _masks, fc_feats, senti_labels)
         cons = self._decode_constraints(suppress_special, decoding_constraint, min_len, max_seq_len)
         if cons is not None and _replay is not None:
             raise ValueError('_replay forces the tokens: it excludes suppress_special / decoding_constraint / min_len')
@@ -914,7 +927,7 @@ class Captioner(nn.Module):
         if not sample_max and self._needs_grad():
             from .autograd import rollout_with_grad
             return rollout_with_grad(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels,
-                                     max_seq_len, _replay, _masks, cons)
+                                     max_seq_len, _replay, _masks, cons, group=n_cap)
         if (sample_max and cons is None and self.__dict__.get('_rollout_graphs') is not None and not self._needs_grad()
                 and not self.training and _replay is None and _masks is None and ops.TIMER.arm_step is None
                 and fc_feats.shape[0] <= self.ROLLOUT_GRAPH_MAX_ROWS and ops.graphs_allowed_here()
@@ -941,8 +954,9 @@ class Captioner(nn.Module):
             raise ValueError('a vocabulary of %d words leaves nothing to choose under the constraints' % self.vocab_size)
         return ops.decode_constraints(ban, no_repeat, self.sos_id, min_len)
 
-    def _check_captions_per_image(self, n, sample_max, masks):
-        """forward_rl's `captions_per_image`, checked before anything touches the device.  Returns it as an int."""
+    def _check_captions_per_image(self, n, sample_max, masks, fc_feats=None, senti_labels=None):
+        """forward_rl's `captions_per_image`, checked before anything touches the device.  Returns it as an int.
+        (fc_feats / senti_labels: the call's, for the label count of the differentiable form.)"""
         if isinstance(n, bool) or not hasattr(n, '__index__'):
             raise ValueError('captions_per_image must be an integer >= 1, got %r' % (n,))
         n = int(n)
@@ -953,11 +967,19 @@ class Captioner(nn.Module):
         if sample_max:
             raise ValueError('captions_per_image > 1 applies to sampled roll-outs (sample_max=0): %d greedy captions of '
                              'one image would be identical' % n)
-        if self.training or self._needs_grad():
-            raise ValueError('captions_per_image > 1 is inference-only: call it in eval mode under torch.no_grad() (the '
-                             'backward of the grouped attention scan is not built)')
-        if masks is not None:
-            raise ValueError('captions_per_image > 1 does not take _masks (dropout masks belong to training)')
+        grad = self._needs_grad()
+        if bool(self.training) != grad:
+            raise ValueError('captions_per_image > 1 runs in two forms: inference-only (eval mode under torch.no_grad()) '
+                             'or the differentiable training roll-out (training mode with gradients enabled); got '
+                             'training=%s with gradients %s' % (bool(self.training), 'enabled' if grad else 'disabled'))
+        if masks is not None and not grad:
+            raise ValueError('captions_per_image > 1 without gradients does not take _masks (dropout masks belong to '
+                             'training)')
+        if grad and fc_feats is not None and senti_labels is not None:
+            images, labels = int(fc_feats.shape[0]), int(senti_labels.numel())
+            if labels != images:
+                raise ValueError('captions_per_image=%d with gradients: senti_labels must hold one label per image (%d) - '
+                                 'the roll-out takes its labels from the image - got %d' % (n, images, labels))
         return n
 
     def _sample_filter(self, temperature=1.0, top_k=0, top_p=1.0, generator=None, uniforms=None, want_slp=False):

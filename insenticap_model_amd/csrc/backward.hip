@@ -334,6 +334,87 @@ extern "C" int isc_reward_loss_bwd(const float *seq_masks, const float *reward, 
     return ISC_OK;
 }
 
+// ------------------------------------------------------------------ group reward (self-critical RL on n samples per image)
+// adv[i,j] = scores[i,j] - (sum over k != j, k ascending, of scores[i,k]) / (n - 1), in fp64: the baseline of a sample is
+// the mean CIDEr-D of the image's other n - 1 samples.  Nothing may be fused into the sum, the division or the
+// subtraction - the host formula (rewards.get_group_self_critical_reward) has to give the same bits.
+__device__ __forceinline__ double group_adv(const double *scores, long long r, int n) {
+#pragma clang fp contract(off)
+    const long long i = r / n;
+    const int j = (int)(r - i * n);
+    const double *s = scores + i * n;
+    double acc = 0.0;
+    for (int k = 0; k < n; ++k)
+        if (k != j) acc += s[k];
+    const double baseline = acc / (double)(n - 1);
+    return s[j] - baseline;
+}
+
+// reward[r,t] = (float)(adv[r] + cls_flag * (double)cls_reward[r,t]) (the product rounded before the addition: no fma),
+// (float)adv[r] without a classifier term.  One thread per (row, step).
+__global__ __launch_bounds__(256) void group_reward_kernel(const double *scores, int n, const float *cls_reward,
+                                                           double cls_flag, int T, long long total, float *reward) {
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const double adv = group_adv(scores, e / T, n);
+    if (cls_reward) {
+        const double term = cls_flag * (double)cls_reward[e];
+        reward[e] = (float)(adv + term);
+    } else {
+        reward[e] = (float)adv;
+    }
+}
+
+// stats4 = { mean scores, mean adv, mean cls_reward (0 without one), mean reward (of the stored floats) } in fp64: one
+// workgroup; thread x adds its elements x, x + 256, ... in ascending order, then the 256 partial sums are added pairwise
+// (stride 128, 64, ... 1): a fixed order, two runs give the same bits.
+__global__ __launch_bounds__(256) void group_reward_stats_kernel(const double *scores, int n, long long rows,
+                                                                 const float *cls_reward, const float *reward,
+                                                                 long long total, double *stats4) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][256];
+    const int tid = threadIdx.x;
+    double s_sc = 0.0, s_adv = 0.0, s_cls = 0.0, s_rw = 0.0;
+    for (long long r = tid; r < rows; r += 256) {
+        s_sc += scores[r];
+        s_adv += group_adv(scores, r, n);
+    }
+    for (long long e = tid; e < total; e += 256) {
+        if (cls_reward) s_cls += (double)cls_reward[e];
+        s_rw += (double)reward[e];
+    }
+    red[0][tid] = s_sc; red[1][tid] = s_adv; red[2][tid] = s_cls; red[3][tid] = s_rw;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st)
+            for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        stats4[0] = red[0][0] / (double)rows;
+        stats4[1] = red[1][0] / (double)rows;
+        stats4[2] = red[2][0] / (double)total;
+        stats4[3] = red[3][0] / (double)total;
+    }
+}
+
+extern "C" int isc_group_reward(const double *scores, int I, int n, const float *cls_reward, double cls_flag, int T,
+                                float *reward, double *stats4, void *stream) {
+    if (!scores || !reward || !stats4) return ISC_E_NULL;
+    if (I < 1 || n < 2 || T < 1) return ISC_E_SHAPE;
+    const long long rows = (long long)I * n, total = rows * T;
+    const long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return ISC_E_SHAPE;
+    hipLaunchKernelGGL(group_reward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, scores, n,
+                       cls_reward, cls_flag, T, total, reward);
+    ISC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(group_reward_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, n, rows, cls_reward,
+                       reward, total, stats4);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
 // ------------------------------------------------------------------ LSTM cell backward (pointwise)
 // gates = activated (i,f,g,o) saved by the forward kernel.
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float *dh, const float *dh2, const float *dc_next,

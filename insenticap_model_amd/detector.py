@@ -7,6 +7,10 @@ CIDEr-D and classifier rewards + XE pass (ss_prob 0.5) + seq2seq pass (ss_prob 0
 clamp(0.1) + Adam (decoder.py:65-167).  The decoder work runs on the HIP kernels through
 `Captioner`; CIDEr-D runs in the native host library; the two frozen helper nets are stock
 PyTorch-ROCm modules (helper_nets.py).
+
+`rl_samples_per_image = n` > 1 (opt-in): n sampled captions per image from one grouped differentiable roll-out, the
+baseline of a sample = the mean CIDEr-D of the image's other n - 1 samples (no greedy roll-out), the reward formed on
+the device from the uploaded scores (isc_group_reward).
 """
 from collections import defaultdict
 
@@ -19,7 +23,8 @@ from .helper_nets import SentenceSentimentClassifier, SentimentDetector
 from .optim import clip_gradient
 from .train import run_on_side_stream
 from .ops import OutOfDomain
-from .rewards import RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward
+from .rewards import (RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward,
+                      group_self_critical_scores)
 
 
 def _helper_input(feats):
@@ -61,6 +66,22 @@ class Detector(nn.Module):
         # of Captioner.forward_rl's keywords `suppress_special`, `decoding_constraint`, `min_len`.  While it is set every
         # iteration runs the eager sequence (capture under constraints is not built).
         self.rollout_constraints = None
+        # Sampled captions per image of a TRAINING iteration (1: the reference's iteration, sample + greedy baseline).
+        # n > 1: self-critical RL on n samples per image whose baseline is the mean CIDEr-D of the image's other n - 1
+        # samples - one grouped differentiable roll-out (Captioner.forward_rl captions_per_image=n: the image is not
+        # repeated), no greedy roll-out, the reward built on the device from the uploaded scores (isc_group_reward).
+        # Such iterations run the eager sequence; evaluation keeps the n = 1 path; not built under a process group.
+        self.rl_samples_per_image = 1
+
+    @property
+    def rl_samples_per_image(self):
+        return self.__dict__.get('_rl_samples_per_image', 1)
+
+    @rl_samples_per_image.setter
+    def rl_samples_per_image(self, n):
+        if isinstance(n, bool) or not hasattr(n, '__index__') or int(n) < 1:
+            raise ValueError('rl_samples_per_image must be an integer >= 1, got %r' % (n,))
+        self.__dict__['_rl_samples_per_image'] = int(n)
 
     def enable_data_parallel(self, group=None, broadcast=True):
         """Data-parallel RL training over the ranks of `group` (default process group; backend nccl = RCCL over xGMI,
@@ -123,6 +144,10 @@ class Detector(nn.Module):
         # data-parallel branches: taken whenever DP is enabled and a process group exists - also a one-rank group
         # (shares are then exactly 1.0), so a one-GPU RCCL run crosses the code an 8-rank run does
         dist_on = self.dp_arena is not None and dp.distributed(self.dp_group)
+        n_rl = self.rl_samples_per_image if training else 1      # (evaluation keeps the n = 1 path)
+        if n_rl > 1 and dist_on:
+            raise ValueError('rl_samples_per_image=%d is not built for data-parallel training (a process group is '
+                             'active): set it to 1' % n_rl)
         seq2seq_iter = iter(data[1]) if training else None
         caption_iter = iter(data[0])
         n_iter = min(self.MAX_BATCHES_PER_CALL, len(data[0]))
@@ -159,7 +184,7 @@ class Detector(nn.Module):
                 """One iteration (models/decoder.py:69-167).  `exact`: on the exact-fp32 GEMM engine, eagerly - the retry of
                 an iteration whose roll-outs left the split-f16 operand domain (OutOfDomain is raised at the iteration's
                 own synchronisation point, before anything is updated)."""
-                if (training and self.train_graphs and not rl_kw and device.type == 'cuda'
+                if (training and self.train_graphs and not rl_kw and n_rl == 1 and device.type == 'cuda'
                         and ops.TIMER.arm_step is None and ops.graphs_allowed_here() and not exact):
                     # the same iteration from HIP graphs (train_graph.RLTrainGraph): same calls in the same order
                     from .train_graph import RLTrainGraph
@@ -193,9 +218,11 @@ class Detector(nn.Module):
                     return
 
                 # sampled roll-out (graph kept in train mode) and the domain-alignment loss on its prologue
+                # (grouped: n_rl rows per image, [I*n, T]; the prologue and its attributes stay per image, [I, E])
+                grouped = n_rl > 1
                 sample_captions, sample_logprobs, seq_masks = cap(
                     fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
-                    sample_max=0, mode='rl', **rl_kw)
+                    sample_max=0, mode='rl', **(dict(captions_per_image=n_rl) if grouped else {}), **rl_kw)
                 da_loss = self.cap_da_crit(cap.cpt_feats, cap.fc_feats.detach())
                 # DP: each term's share of the global normaliser (mask sum, XE tokens, seq2seq tokens, rows)
                 w_rl = w_xe = w_s2s = w_rows = None
@@ -209,22 +236,26 @@ class Detector(nn.Module):
                 da_loss = share(da_loss, w_rows)
                 put('da_loss', da_loss)
 
-                cap.eval()                                   # greedy baseline
-                with torch.no_grad():
-                    greedy_captions, _, greedy_masks = cap(
-                        fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
-                        sample_max=1, mode='rl', **rl_kw)
-                cap.train(training)
+                greedy_captions = greedy_masks = None
+                if not grouped:                              # greedy baseline (grouped: the image's other samples are)
+                    cap.eval()
+                    with torch.no_grad():
+                        greedy_captions, _, greedy_masks = cap(
+                            fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
+                            sample_max=1, mode='rl', **rl_kw)
+                    cap.train(training)
 
                 # The rewards need the token matrices on the host (CIDEr-D is host code).  Start their copies
                 # now, enqueue the XE / seq2seq forward passes, and only then wait: the host scores the captions
                 # while the device works through the two unrolls.  The order of the captioner calls - hence of
                 # every random draw - is the reference's; only host-side waiting moved.
                 host_sample = torch.empty(sample_captions.shape, dtype=sample_captions.dtype).pin_memory()
-                host_greedy = torch.empty(greedy_captions.shape, dtype=greedy_captions.dtype).pin_memory()
+                if not grouped:
+                    host_greedy = torch.empty(greedy_captions.shape, dtype=greedy_captions.dtype).pin_memory()
                 host_lens = torch.empty(seq_masks.shape[0], dtype=torch.int32).pin_memory()
                 host_sample.copy_(sample_captions, non_blocking=True)
-                host_greedy.copy_(greedy_captions, non_blocking=True)
+                if not grouped:
+                    host_greedy.copy_(greedy_captions, non_blocking=True)
                 host_lens.copy_(seq_masks.sum(dim=-1).type(torch.int32), non_blocking=True)
                 copied = torch.cuda.Event()
                 copied.record()
@@ -274,9 +305,25 @@ class Detector(nn.Module):
                 copied.synchronize()
                 if not exact and getattr(cap, 'numerics_checks', True) and ops.device_status(reset=True):
                     raise OutOfDomain()      # the roll-outs met non-finite values: nothing has been updated yet
-                cls_reward = get_cls_reward(sample_captions, seq_masks, greedy_captions, greedy_masks, senti_labels,
+                cls_reward = get_cls_reward(sample_captions, seq_masks, greedy_captions, greedy_masks,
+                                            senti_labels.repeat_interleave(n_rl) if grouped else senti_labels,
                                             self.sent_senti_cls, sample_lens=host_lens.tolist(), on_device=True)
-                if data_type == 'fact':
+                if grouped:
+                    # the I*n float64 CIDEr-D scores are all that is uploaded ('senti': zeros - the classifier term
+                    # alone, as in the reference); baseline, advantage, the sum with the classifier term and the four
+                    # logged means are formed on the device: isc_group_reward, two launches
+                    if data_type == 'fact':
+                        scores = ops.upload(torch.from_numpy(group_self_critical_scores(
+                            host_sample.numpy(), fns, ground_truth, self.ciderd_scorer, n_rl)), torch.float64, device)
+                    else:
+                        scores = torch.zeros(sample_captions.shape[0], dtype=torch.float64, device=device)
+                    rewards, stats4 = ops.group_reward(scores, n_rl, cls_reward.float().contiguous(), self.cls_flag,
+                                                       sample_captions.shape[1])
+                    put('sample_score', stats4[0])
+                    put('fact_reward', stats4[1])            # the mean advantage: 0 up to rounding by construction
+                    put('cls_reward', stats4[2])
+                    put('all_rewards', stats4[3])
+                elif data_type == 'fact':
                     fact_reward = get_self_critical_reward(
                         host_sample.numpy(), host_greedy.numpy(), fns, ground_truth, cap.sos_id, cap.eos_id,
                         self.ciderd_scorer)
@@ -284,10 +331,10 @@ class Detector(nn.Module):
                     put('fact_reward', share(fact_reward[:, 0].mean(), w_rows))
                 else:
                     fact_reward = 0
-                put('cls_reward', share(cls_reward.mean(-1).mean(-1), w_rows))
-
-                rewards = fact_reward + self.cls_flag * cls_reward
-                put('all_rewards', share(rewards.mean(-1).mean(-1), w_rows))
+                if not grouped:
+                    put('cls_reward', share(cls_reward.mean(-1).mean(-1), w_rows))
+                    rewards = fact_reward + self.cls_flag * cls_reward
+                    put('all_rewards', share(rewards.mean(-1).mean(-1), w_rows))
                 cap_loss = share(self.cap_rl_crit(sample_logprobs, seq_masks, rewards), w_rl)
                 put('cap_loss', cap_loss)
 

@@ -1064,6 +1064,27 @@ def reward_loss_bwd(seq_masks, reward, gout, sum_count, dlogp):
                                           sum_count.data_ptr(), dlogp.data_ptr(), stream()), 'isc_reward_loss_bwd')
 
 
+def group_reward(scores, n, cls_reward, cls_flag, T, reward=None, stats4=None):
+    """isc_group_reward: the reward of self-critical RL on n samples per image from the I*n float64 scores on the device
+    (row i*n + j = sample j of image i) and the optional classifier reward [I*n, T] fp32.  Returns (reward [I*n, T] fp32,
+    stats4 float64 = mean score, mean advantage, mean classifier reward, mean reward)."""
+    require_device(scores, cls_reward)
+    assert scores.dtype == torch.float64 and scores.dim() == 1 and scores.is_contiguous()
+    rows, n, T = scores.numel(), int(n), int(T)
+    assert n >= 1 and rows % n == 0
+    if cls_reward is not None:
+        assert cls_reward.dtype == torch.float32 and cls_reward.is_contiguous() and tuple(cls_reward.shape) == (rows, T)
+    if reward is None:
+        reward = torch.empty(rows, T, dtype=torch.float32, device=scores.device)
+    if stats4 is None:
+        stats4 = torch.empty(4, dtype=torch.float64, device=scores.device)
+    assert reward.dtype == torch.float32 and reward.is_contiguous() and reward.numel() == rows * T
+    assert stats4.dtype == torch.float64 and stats4.is_contiguous() and stats4.numel() == 4
+    check(_lib.load().isc_group_reward(scores.data_ptr(), rows // n, n, ptr(cls_reward), float(cls_flag), T,
+                                       reward.data_ptr(), stats4.data_ptr(), stream()), 'isc_group_reward')
+    return reward, stats4
+
+
 def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=None):
     lib = _lib.load()
     M, H = c.shape

@@ -172,6 +172,55 @@ def get_self_critical_reward(sample_captions, greedy_captions, fns, ground_truth
     return np.repeat(scores[:, np.newaxis], sample_captions.shape[1], 1)
 
 
+def _check_group(n, rows, images=None):
+    if isinstance(n, bool) or not hasattr(n, '__index__') or int(n) < 2:
+        raise ValueError('a group reward needs n >= 2 samples per image (an integer), got %r' % (n,))
+    n = int(n)
+    if images is None:
+        if rows % n:
+            raise ValueError('n=%d: %d rows are no whole number of images' % (n, rows))
+    elif rows != images * n:
+        raise ValueError('n=%d: %d images need %d sampled rows (row i*n + j = sample j of image i), got %d'
+                         % (n, images, images * n, rows))
+    return n
+
+
+def group_self_critical_scores(sample_captions, fns, ground_truth, scorer, n):
+    """CIDEr-D of n sampled captions per image: `fns` / `ground_truth` per image, `sample_captions` [I*n, T] (host ndarray
+    or tensor), row i*n + j = sample j of image i.  Every row is scored against ITS image's references by the native
+    scorer -> float64 [I*n]."""
+    if torch.is_tensor(sample_captions):
+        sample_captions = sample_captions.cpu().numpy()
+    n = _check_group(n, sample_captions.shape[0], len(fns))
+    return self_critical_scores(sample_captions, [fn for fn in fns for _ in range(n)], ground_truth, scorer)
+
+
+def group_advantages(scores, n):
+    """Self-critical advantages with the image's other samples as the baseline, float64 [I*n] -> float64 [I*n]:
+    adv[i,j] = scores[i,j] - (sum over k != j, k ascending, of scores[i,k]) / (n - 1).  The additions run in that order
+    (isc_group_reward forms the same bits on the device)."""
+    scores = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    n = _check_group(n, scores.shape[0])
+    s = scores.reshape(-1, n)
+    adv = np.empty_like(s)
+    for j in range(n):
+        acc = np.zeros(s.shape[0], dtype=np.float64)
+        for k in range(n):
+            if k != j:
+                acc = acc + s[:, k]
+        adv[:, j] = s[:, j] - acc / np.float64(n - 1)
+    return adv.reshape(-1)
+
+
+def get_group_self_critical_reward(sample_captions, fns, ground_truth, scorer, n):
+    """The fact reward of the grouped RL iteration: CIDEr-D(sample) minus the mean CIDEr-D of the image's other n - 1
+    samples, repeated over T unmasked as utils.py:83 repeats the score -> float64 ndarray [I*n, T].  This is the host
+    form (and the reference) of what isc_group_reward builds on the device from the uploaded scores."""
+    scores = group_self_critical_scores(sample_captions, fns, ground_truth, scorer, n)
+    T = sample_captions.shape[1]
+    return np.repeat(group_advantages(scores, n)[:, np.newaxis], T, 1)
+
+
 def get_cls_reward(sample_captions, sample_masks, greedy_captions, greedy_masks, senti_labels, sent_senti_cls,
                    sample_lens=None, on_device=False):
     """utils.py:120-151: 1[classifier(sample) == label] x per-token squeeze-excite weights, zero-padded
