@@ -886,6 +886,45 @@ int isc_logsoftmax_bwd_raw(const float *raw, int64_t ld_b, int64_t ld_t, int B, 
                            const float *const *coef_host, int n_sparse, const float *scale, float *dlogits, int64_t ld_out,
                            int out_step_rows, void *stream);
 
+/* The frozen sentence-sentiment classifier of the RL rewards, forward in eval mode (sent_senti_cls.py:38-56; called by
+ * self_critical/utils.py:120-151 for the classifier reward and by decoder.py:133-136 for the XE sentiment labels):
+ *   x = relu(Emb[tokens]);  out = LSTM(x);  w[b,t] = mean_h sigmoid(ex2(relu(ex0(out[t,b])))) for t < lens[b], else 0;
+ *   feats[b] = sum_t w[b,t] out[t,b];  logits = cls3(relu(cls0(feats)));  pred = argmax (lowest index on ties);
+ *   reward[b,:] = pred[b] == labels[b] ? w[b,:] : 0.
+ * tokens [B,L] int64 (row stride tokens_ld); EVERY entry, also past a row's length, must be a valid id (they are read -
+ * clamped into [0, V) - but never reach a sum: the recurrence is causal and the pooling stops at the length).
+ * lens [B] int32 on the device, each in [1, L] (clamped there).  The thirteen parameter tensors as the module's state_dict
+ * stores them (contiguous): emb [V,W]; w_ih [4H,W], w_hh [4H,H], b_ih, b_hh [4H] (gate rows i,f,g,o); ex0 / ex2 / cls0
+ * [H,H] + [H]; cls3 [k,H] + [k].  labels [B] int64, optional (required iff reward).
+ * Outputs: logits [B,k]; weights [B,T_out] and reward [B,T_out] (optional) contiguous, exactly 0 at and beyond a row's
+ * length and in columns L..T_out-1; pred [B] int32; feats [B,H] (optional: the pooled features, for tests).
+ * T + 7 launches on `stream`, no host read, no allocation: the time-major embedding gather (which also clears the zero
+ * state), ONE input GEMM over all L*B rows (isc_linear_fwd), L fused cells (isc_lstm_fwd, one K-segment h W_hh^T, pre =
+ * the step's rows of the input GEMM), two excitation GEMMs, the pooling kernel, the head GEMM and the k-way head.  The
+ * GEMMs get no split-K workspace: one launch each, on the fp32 MFMA tiles (or, on a stream that holds a weights scope,
+ * the scope's kernels).  Pooling and head sum in a fixed order without atomics: two calls give the same bits.
+ * W % 32 == H % 32 == 0 (they may differ), V >= 1, 1 <= k <= 8, 1 <= L <= 4096, T_out >= L, B >= 1: anything else
+ * ISC_E_SHAPE; a workspace smaller than isc_sent_cls_workspace_bytes(B, L, W, H) ISC_E_WORKSPACE, not 16-byte aligned
+ * ISC_E_ALIGN - all before any launch, nothing is written then. */
+typedef struct {
+    int32_t B, L, W, H, V, k, T_out, _pad;
+    const int64_t *tokens;
+    int64_t tokens_ld;
+    const int32_t *lens;
+    const float *emb, *w_ih, *w_hh, *b_ih, *b_hh;
+    const float *ex0_w, *ex0_b, *ex2_w, *ex2_b;
+    const float *cls0_w, *cls0_b, *cls3_w, *cls3_b;
+    const int64_t *labels;
+    void *workspace;
+    int64_t workspace_bytes;
+    float *logits, *weights;
+    int32_t *pred;
+    float *reward, *feats;
+} isc_sent_cls_problem;
+int64_t isc_sent_cls_workspace_bytes(int B, int L, int W, int H);
+int isc_sent_cls_fwd(const isc_sent_cls_problem *prob_host, void *stream);
+long long isc_sent_cls_launches(void);    /* kernels enqueued by isc_sent_cls_fwd so far (measurement / test hook) */
+
 /* Power-of-two gradient scale for a backward sweep whose contractions run on the split-f16 engine: out4[0..1] = { S, 1/S },
  * S = 2^k with max |x| over the given tensors (HOST arrays of device pointers / element counts, <= ISC_SCALE_SRC_MAX)
  * brought into [2^-4, 2^-3); S = 1 when they are all zero.  out4[2..3] are state words of the multi-workgroup reduction:

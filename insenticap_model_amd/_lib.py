@@ -154,6 +154,13 @@ class DecodeConstraints(C.Structure):
                 ('min_len', C.c_int32)]
 
 
+class SentClsProblem(C.Structure):
+    """isc_sent_cls_problem: the frozen sentence-sentiment classifier's forward (csrc/sent_cls.hip)."""
+    _fields_ = (_f('B L W H V k T_out _pad', C.c_int32) + [('tokens', C.c_void_p), ('tokens_ld', C.c_int64)] +
+                _f('lens emb w_ih w_hh b_ih b_hh ex0_w ex0_b ex2_w ex2_b cls0_w cls0_b cls3_w cls3_b labels workspace',
+                   C.c_void_p) + [('workspace_bytes', C.c_int64)] + _f('logits weights pred reward feats', C.c_void_p))
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -274,6 +281,9 @@ SIGNATURES = {
     'isc_logsoftmax_bwd_raw': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'isc_sent_cls_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_sent_cls_fwd': (C.c_int, [C.POINTER(SentClsProblem), C.c_void_p]),
+    'isc_sent_cls_launches': (C.c_longlong, []),
     'isc_grad_scale': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
     'isc_splitk_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'isc_h3_weights_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),

@@ -93,6 +93,11 @@ static __device__ long long *g_rows_stamp;
 // Returns 1 when it took the launch (*rc = its status), 0 when the shape is not its own.
 int rows_scan_gate_try(const isc_scan_gate_args *a, int rows, hipStream_t st, int *rc);
 
+// pointwise.hip: the embedding gather of isc_sent_cls_fwd (sent_cls.hip) - x[t * B + b, :] = relu(emb[tokens[b * ld + t], :])
+// for all L * B rows (ids clamped into [0, V)) and zero4 float4s at `zero` cleared, in ONE launch of the embed kernel.
+int isc_embed_relu_tm_(const float *emb, int V, int W, const int64_t *tokens, int64_t ld, int B, int L, float *out,
+                       float *zero, long long zero4, hipStream_t st);
+
 // ---- the split-f16 number format (operands of the f16 matrix cores: gemm_f32.hip) -------------------------------
 //     x = hi + lo * 2^-11,   hi = f16(x),   lo = f16((x - hi) * 2^11)        (the subtraction is exact in fp32)
 constexpr float ISC_SPLIT_LO_SCALE = 2048.f;

@@ -6,13 +6,31 @@
 #include "common.h"
 
 // ------------------------------------------------------------------ embeddings
+// TM (isc_sent_cls_fwd, sent_cls.hip): the ids are a [B, L] matrix read TIME-MAJOR - output row r = t * tm_B + b takes
+// ids[b * ids_stride + t], clamped into the table - and the workgroups behind the last row clear `zero` (zero4 float4s:
+// the zero state in front of the first recurrent step), so that the call needs no fill of its own.
+template <bool TM>
 __global__ __launch_bounds__(256) void embed_relu_kernel(const float *emb, int W, const int64_t *ids,
                                                          long long ids_stride, const float *add,
-                                                         int B, float *out) {
+                                                         int B, float *out, int tm_B, int V, float *zero, long long zero4) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (TM) {
+        const int row_blocks = (B + 3) / 4;
+        if ((int)blockIdx.x >= row_blocks) {
+            const long long i = (long long)(blockIdx.x - row_blocks) * 256 + threadIdx.x;
+            if (i < zero4) reinterpret_cast<float4 *>(zero)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
     if (b >= B) return;
-    const long long id = ids[(long long)b * ids_stride];
+    long long id;
+    if (TM) {
+        id = ids[(long long)(b % tm_B) * ids_stride + b / tm_B];
+        id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    } else {
+        id = ids[(long long)b * ids_stride];
+    }
     const float4 *src = reinterpret_cast<const float4 *>(emb + id * W);
     const float4 *ad = add ? reinterpret_cast<const float4 *>(add + (long long)b * W) : nullptr;
     float4 *dst = reinterpret_cast<float4 *>(out + (long long)b * W);
@@ -24,6 +42,18 @@ __global__ __launch_bounds__(256) void embed_relu_kernel(const float *emb, int W
     }
 }
 
+// x[t * B + b, :] = relu(emb[tokens[b * ld + t], :]) for all L * B rows, and zero4 float4s at `zero` cleared: ONE launch.
+int isc_embed_relu_tm_(const float *emb, int V, int W, const int64_t *tokens, int64_t ld, int B, int L, float *out,
+                       float *zero, long long zero4, hipStream_t st) {
+    const long long rows = (long long)B * L;
+    const long long blocks = (rows + 3) / 4 + (zero4 + 255) / 256;
+    if (blocks > 0x7fffffffLL) return ISC_E_SHAPE;
+    hipLaunchKernelGGL(embed_relu_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, emb, W, tokens, (long long)ld,
+                       (const float *)nullptr, (int)rows, out, B, V, zero, zero4);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
 extern "C" int isc_embed_relu_fwd(const float *emb, int V, int W, const int64_t *ids,
                                   int64_t ids_stride, const float *add, int B, float *out,
                                   void *stream) {
@@ -31,8 +61,8 @@ extern "C" int isc_embed_relu_fwd(const float *emb, int V, int W, const int64_t 
     if (B <= 0 || V <= 0 || W <= 0 || (W & 3)) return ISC_E_SHAPE;
     // the kernel reads and writes rows as float4
     if (!isc_aligned16(emb) || !isc_aligned16(out) || (add && !isc_aligned16(add))) return ISC_E_ALIGN;
-    hipLaunchKernelGGL(embed_relu_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, emb, W,
-                       ids, (long long)ids_stride, add, B, out);
+    hipLaunchKernelGGL(embed_relu_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, emb, W,
+                       ids, (long long)ids_stride, add, B, out, 0, V, (float *)nullptr, 0LL);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }

@@ -83,6 +83,16 @@ class Detector(nn.Module):
             raise ValueError('rl_samples_per_image must be an integer >= 1, got %r' % (n,))
         self.__dict__['_rl_samples_per_image'] = int(n)
 
+    @property
+    def native_sentence_classifier(self):
+        """True: the frozen sentence-sentiment classifier runs on the library's kernels (helper_nets.
+        SentenceSentimentClassifier.native) - the classifier reward and both XE-label sites; default False: stock torch ops."""
+        return bool(self.sent_senti_cls.native)
+
+    @native_sentence_classifier.setter
+    def native_sentence_classifier(self, on):
+        self.sent_senti_cls.enable_native(on)
+
     def enable_data_parallel(self, group=None, broadcast=True):
         """Data-parallel RL training over the ranks of `group` (default process group; backend nccl = RCCL over xGMI,
         gloo in tests).  The reference is single-device; under DP every rank runs `forward` on ITS shard of the fact /

@@ -5,7 +5,8 @@ They are harness dependencies of the hot path, not part of it (SURVEY 2, 8(a-20)
 self_critical/utils.py:120-151), their dense conv / LSTM work goes to MIOpen / rocBLAS through
 stock torch ops, and only their *outputs* (sentiment labels, per-token reward weights) enter the
 hand-written kernels.  Parameter names and shapes equal the reference's, so its checkpoints load
-(train_rl.py:42-53,88-97).
+(train_rl.py:42-53,88-97).  The sentence classifier has an opt-in native forward on the library's own kernels
+(`enable_native`, include/insenticap_hip.h: isc_sent_cls_fwd); off by default.
 
 * SentimentDetector            /root/reference/models/sentiment_detector.py:5-64
 * SentenceSentimentClassifier  /root/reference/models/sent_senti_cls.py:6-72
@@ -71,6 +72,7 @@ class SentimentDetector(nn.Module):
 class SentenceSentimentClassifier(nn.Module):
     """Sentence-level sentiment: word embedding -> one-layer LSTM -> squeeze-excite style token
     weights (mean over channels of a sigmoid MLP of every hidden state) -> weighted sum -> MLP."""
+    native = False          # (class default: an instance unpickled from before the switch existed reads it)
 
     def __init__(self, idx2word, sentiment_categories, settings):
         super().__init__()
@@ -86,6 +88,50 @@ class SentenceSentimentClassifier(nn.Module):
         self.squeeze = nn.AdaptiveAvgPool1d(1)
         self.sent_senti_cls = nn.Sequential(nn.Linear(H, H), nn.ReLU(), nn.Dropout(settings['dropout_p']),
                                             nn.Linear(H, len(sentiment_categories)))
+        # Opt-in: the eval-mode forward on the library's own kernels (isc_sent_cls_fwd: embed gather, ONE input GEMM over
+        # all steps, the fused LSTM cell per step, pooling and head kernels - L + 7 launches, capturable) instead of stock
+        # torch ops (an nn.LSTM of the vendor library plus a dozen small launches).  enable_native() / `native = True`.
+        self.native = False
+
+    def enable_native(self, on=True):
+        self.native = bool(on)
+        return self
+
+    def native_params(self):
+        """The thirteen tensors of the state_dict in ops.SENT_CLS_PARAMS order."""
+        ex, cls = self.excitation, self.sent_senti_cls
+        return (self.word_embed[0].weight, self.rnn.weight_ih_l0, self.rnn.weight_hh_l0, self.rnn.bias_ih_l0,
+                self.rnn.bias_hh_l0, ex[0].weight, ex[0].bias, ex[2].weight, ex[2].bias, cls[0].weight, cls[0].bias,
+                cls[3].weight, cls[3].bias)
+
+    def native_active(self, seqs):
+        """Whether forward(seqs, ...) takes the native path now: the flag is on, the module is in eval mode (no dropout),
+        the tensors live on the ROCm device and nothing asks for a gradient of a parameter (the classifier's own
+        pre-training, train mode and CPU tensors run the torch code below)."""
+        if not self.native or self.training or not seqs.is_cuda:
+            return False
+        params = self.native_params()
+        if params[0].device != seqs.device:
+            return False
+        return not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+
+    def forward_native(self, seqs, lengths, labels=None, pad_to=None):
+        """The native forward in full: -> (logits [B,k], weights [B,T_out], pred [B] int32, reward [B,T_out] or None) with
+        T_out = pad_to or L, L = max(lengths) for host lengths and seqs.shape[1] for a device tensor [B]; weights and
+        reward (= weights where pred == labels, else 0) are exactly 0 at and beyond a row's length.  Every entry of
+        seqs[:, :L] must be a valid id (entries behind a row's length are read, never summed)."""
+        from . import ops
+        if torch.is_tensor(lengths) and lengths.device == seqs.device:
+            L, lens = seqs.shape[1], lengths.to(torch.int32)
+        else:
+            lengths = [int(x) for x in lengths]
+            L = max(lengths)
+            lens = torch.tensor(lengths, dtype=torch.int32).pin_memory().to(seqs.device, non_blocking=True)
+        if labels is not None:
+            labels = labels.to(device=seqs.device, dtype=torch.int64).contiguous()
+        with torch.no_grad():
+            return ops.sent_cls_fwd([p.detach() for p in self.native_params()], seqs[:, :L], lens.contiguous(), labels,
+                                    pad_to=pad_to)
 
     def forward(self, seqs, lengths):
         """seqs [B,L] int64, lengths: B ints (>= 1), or a device tensor [B]. Returns (logits [B,k], token weights
@@ -93,6 +139,8 @@ class SentenceSentimentClassifier(nn.Module):
         Positions at or beyond a row's length contribute nothing (the reference packs the sequences;
         here the padded LSTM outputs are masked instead - the recurrence is causal, so valid positions
         are unaffected by what follows them)."""
+        if self.native_active(seqs):
+            return self.forward_native(seqs, lengths)[:2]
         if torch.is_tensor(lengths) and lengths.device == seqs.device and seqs.is_cuda:
             # lengths that live on the device: no host read - the LSTM runs over all L columns (it is causal and the
             # positions at or beyond a row's length are masked below, so the valid positions are what the packed form

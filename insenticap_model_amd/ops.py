@@ -918,6 +918,74 @@ def xe_loss_fwd(logp, target, lengths_i32, out2):
                               out2.data_ptr(), stream()), 'isc_xe_loss_fwd')
 
 
+SENT_CLS_PARAMS = ('emb', 'w_ih', 'w_hh', 'b_ih', 'b_hh', 'ex0_w', 'ex0_b', 'ex2_w', 'ex2_b', 'cls0_w', 'cls0_b', 'cls3_w',
+                   'cls3_b')
+_SENT_CLS_WS = {}           # (device index, stream, B, L, W, H) -> workspace of isc_sent_cls_fwd
+
+
+def sent_cls_workspace_bytes(B, L, W, H):
+    return int(_lib.load().isc_sent_cls_workspace_bytes(B, L, W, H))
+
+
+def sent_cls_launches():
+    return _lib.load().isc_sent_cls_launches()
+
+
+def sent_cls_fwd(params, tokens, lens_i32, labels=None, pad_to=None, want_feats=False, workspace=None, out=None):
+    """The frozen sentence-sentiment classifier's forward (isc_sent_cls_fwd): `params` = the thirteen tensors of the
+    module's state_dict in SENT_CLS_PARAMS order, tokens [B,L] int64 (unit column stride; every entry a valid id),
+    lens_i32 [B] int32 on the device (each in [1, L]), labels [B] int64 or None.  pad_to >= L: columns of the weights /
+    reward rows (zeros behind L).  -> (logits [B,k], weights [B,T_out], pred [B] int32, reward [B,T_out] or None[, feats
+    [B,H]]).  The workspace is kept per (device, stream, B, L, W, H) - two streams may run the classifier side by side -
+    except inside a graph capture, where the caller hands `workspace` (and `out` = (logits, weights, pred, reward)) or
+    a fresh one is drawn from the capture's pool.  A shape the library does not take raises (ISC_E_SHAPE); nothing is
+    launched or written then."""
+    lib = _lib.load()
+    assert len(params) == len(SENT_CLS_PARAMS)
+    require_device(tokens, lens_i32, labels, *params)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.stride(1) == 1
+    assert lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.shape == (tokens.shape[0],)
+    for t in params:
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'classifier parameters: contiguous fp32'
+    B, L = tokens.shape
+    V, W = params[0].shape
+    H = params[2].shape[1]
+    k = params[11].shape[0]
+    T_out = L if pad_to is None else int(pad_to)
+    dev = tokens.device
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)
+    need = sent_cls_workspace_bytes(B, L, W, H)         # (0: a shape the library refuses - it says so below)
+    if workspace is None:
+        if torch.cuda.is_current_stream_capturing():
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        else:
+            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, B, L, W, H)
+            workspace = _SENT_CLS_WS.get(key)
+            if workspace is None:
+                workspace = _SENT_CLS_WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty(B, k, dtype=torch.float32, device=dev), torch.empty(B, T_out, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, T_out, dtype=torch.float32, device=dev) if labels is not None else None)
+    logits, weights, pred, reward = out
+    assert logits.shape == (B, k) and weights.shape == (B, T_out) and pred.shape == (B,) and pred.dtype == torch.int32
+    assert logits.is_contiguous() and weights.is_contiguous() and (reward is None or
+                                                                   (reward.is_contiguous() and reward.shape == (B, T_out)))
+    feats = torch.empty(B, H, dtype=torch.float32, device=dev) if want_feats else None
+    p = _lib.SentClsProblem()
+    p.B, p.L, p.W, p.H, p.V, p.k, p.T_out = B, L, W, H, V, k, T_out
+    p.tokens, p.tokens_ld, p.lens = tokens.data_ptr(), tokens.stride(0), lens_i32.data_ptr()
+    for name, t in zip(SENT_CLS_PARAMS, params):
+        setattr(p, name, t.data_ptr())
+    p.labels = ptr(labels)
+    p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    p.logits, p.weights, p.pred, p.reward, p.feats = (logits.data_ptr(), weights.data_ptr(), pred.data_ptr(), ptr(reward),
+                                                      ptr(feats))
+    check(lib.isc_sent_cls_fwd(C.byref(p), stream()), 'isc_sent_cls_fwd')
+    return (logits, weights, pred, reward) + ((feats,) if want_feats else ())
+
+
 __all__ = [n for n in dir() if n.endswith('_fwd') or n.endswith('_problem')] + [
     'RolloutStep', 'rollout_finalize', 'rollout_finalize_filtered', 'beam_topk', 'logsoftmax_apply', 'require_device']
 

@@ -233,13 +233,21 @@ def get_cls_reward(sample_captions, sample_masks, greedy_captions, greedy_masks,
     if sample_lens is None:
         sample_lens = list(sample_masks.sum(dim=-1).type(torch.int).cpu().numpy())
     sent_senti_cls.eval()
+    max_len = sample_captions.shape[1]
+    with torch.no_grad():
+        native = getattr(sent_senti_cls, 'native', False) and sent_senti_cls.native_active(sample_captions)
+        if native:      # the native forward's head kernel writes 1[pred == label] x weights itself, zero-padded to T
+            sample_scores = sent_senti_cls.forward_native(sample_captions, sample_lens, labels=senti_labels,
+                                                          pad_to=max_len)[3]
+    if native:
+        sent_senti_cls.train(training)
+        return sample_scores if on_device else sample_scores.cpu().numpy()
     with torch.no_grad():
         sample_preds, sample_att_weights = sent_senti_cls(sample_captions, sample_lens)
         sample_preds = sample_preds.softmax(dim=-1).argmax(dim=-1)
         sample_preds = (sample_preds == senti_labels).type_as(sample_att_weights).unsqueeze(1)
         sample_scores = (sample_preds * sample_att_weights).detach()
     sent_senti_cls.train(training)
-    max_len = sample_captions.shape[1]
     if on_device:
         return torch.nn.functional.pad(sample_scores, (0, max_len - sample_scores.shape[1]))
     sample_scores = sample_scores.cpu().numpy()

@@ -439,6 +439,7 @@ class RLTrainGraph(XETrainGraph):
                  (it draws no random numbers and writes nothing they read)                        [decoder.py:93-98]
         eager    the classifier reward on the side stream, behind g_roll (a frozen helper net: an LSTM of the stock library;
                  lengths stay on the device, so its launches are enqueued at once)                [utils.py:120-151]
+                 - with Detector.native_sentence_classifier on: a sixth small graph (isc_sent_cls_fwd), replayed there
         host     scores CIDEr-D of the sampled captions (host library) as soon as their tokens have landed, while the device
                  decodes the greedy ones and runs g_fwd; then theirs
         g_fwd    XE unroll (ss_prob 0.5), forward, on a stream of its own NEXT TO the roll-outs (it reads the batch and the
@@ -464,6 +465,7 @@ class RLTrainGraph(XETrainGraph):
                          grad_clip=0.1, arena=detector.dp_arena, group=detector.dp_group, warmup=warmup,
                          max_geometries=max_geometries)
         self.det = detector
+        self.cls_captures = 0           # captures of the native classifier's reward chain (_cls_graph)
         self.share_rl = torch.ones(1, dtype=torch.float32, device=self.device)
         # A third stream: the XE unroll's forward runs there, so autograd replays its reverse sweep there as well - next
         # to the sampled roll-out's on self.stream.  At 512 rows a sweep's launches are 128-192 workgroups on 256 compute
@@ -590,17 +592,53 @@ class RLTrainGraph(XETrainGraph):
         return geo.stats
 
     # ---- between the graphs -----------------------------------------------------------------------------------------
-    def _cls_reward(self, geo, roll):
+    def _cls_reward(self, geo, roll, served=False):
         """The classifier reward of the sampled captions (utils.py:120-151) -> geo.cls, enqueued on the side stream behind the
         sampled roll-out: eager launches of a frozen helper net (an LSTM of the stock library), with the lengths read on the
-        device - the host does not wait for anything here, the launches queue up while the roll-out runs."""
+        device - the host does not wait for anything here, the launches queue up while the roll-out runs.
+        With the classifier's native forward on (Detector.native_sentence_classifier) and the iteration served from graphs
+        (`served`: the roll-out's buffers are static), the chain is a small graph of its own, replayed here."""
         from .rewards import get_cls_reward
         seq, mk = roll[0], roll[2]
         self.side.wait_event(geo.copied_s)
         with torch.cuda.stream(self.side):
+            if served and self.det.sent_senti_cls.native and self._cls_graph(geo, seq):
+                return
             cls = get_cls_reward(seq, mk, None, None, geo.inputs['labels'], self.det.sent_senti_cls,
                                  sample_lens=geo.lens_d, on_device=True)
             geo.cls.copy_(cls)
+
+    def _cls_graph(self, geo, seq):
+        """Replays (after capturing it once) the native classifier's reward chain - isc_sent_cls_fwd from the roll-out's
+        static token buffer, geo.lens_d and the labels buffer straight into geo.cls - on the current (side) stream.  Keyed
+        by the addresses of everything the captured kernels read: a `.to()` of the classifier gives its parameters new
+        storage and captures again (load_state_dict copies in place: nothing to do).  False: not native here - the caller
+        runs the eager path."""
+        net, labels = self.det.sent_senti_cls, geo.inputs['labels']
+        with torch.no_grad():
+            if not net.native_active(seq) or labels.dtype != torch.int64 or not labels.is_contiguous() or \
+                    seq.stride(1) != 1 or geo.lens_d.dtype != torch.int32:
+                return False
+            params = [p.detach() for p in net.native_params()]
+            if any(p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+                return False
+            key = tuple(p.data_ptr() for p in params) + (seq.data_ptr(), seq.stride(0), geo.lens_d.data_ptr(),
+                                                         labels.data_ptr(), geo.cls.data_ptr())
+            if getattr(geo, 'g_cls_key', None) != key:
+                B, L = seq.shape
+                k = params[11].shape[0]
+                ws = torch.empty(ops.sent_cls_workspace_bytes(B, L, params[0].shape[1], params[2].shape[1]),
+                                 dtype=torch.uint8, device=self.device)
+                out = (torch.empty(B, k, dtype=torch.float32, device=self.device),
+                       torch.empty(B, geo.cls.shape[1], dtype=torch.float32, device=self.device),
+                       torch.empty(B, dtype=torch.int32, device=self.device), geo.cls)
+                g = torch.cuda.CUDAGraph(keep_graph=self.KEEP_GRAPHS)
+                with ops.graph_capture(g, stream=self.side):
+                    ops.sent_cls_fwd(params, seq, geo.lens_d, labels, pad_to=geo.cls.shape[1], workspace=ws, out=out)
+                geo.g_cls, geo.g_cls_key, geo.g_cls_keep = g, key, (ws, out, params)
+                self.cls_captures += 1
+            geo.g_cls.replay()
+        return True
 
     def _rewards(self, geo, roll, item):
         """CIDEr-D on the host -> with geo.cls the static reward buffer the captured RewardCriterion reads.  The sampled
@@ -747,7 +785,7 @@ class RLTrainGraph(XETrainGraph):
         with torch.cuda.stream(self.greedy_stream):
             geo.g_greedy.replay()
             geo.copied.record(self.greedy_stream)
-        self._cls_reward(geo, roll)
+        self._cls_reward(geo, roll, served=True)
         self._fork_fwd(geo, roll, lengths, s_lengths)
         with torch.cuda.stream(self.xe_stream):
             self._late_inputs(geo)
