@@ -612,7 +612,9 @@ extern "C" int isc_attn_scan_bwd(const isc_scan_bwd_problem *pr, int n_prob, int
         // rows of one image: its dP / dV entry would be read-modify-written by row_div workgroups at once
         if (q.row_div > 1 && (q.dP || q.dV || L.p[i].rows % q.row_div)) return ISC_E_SHAPE;
         if (q.R <= 0 || q.A <= 0 || q.D <= 0 || q.A > 1024) return ISC_E_SHAPE;
-        if ((q.A & 3) || (q.D & 3) || (1024 % (q.A / 4)) != 0 || (1024 % (q.D / 4)) != 0) return ISC_E_SHAPE;
+        // (A / 4 resp. D / 4 threads span a row and the 1024 / (A / 4) WHOLE groups of them work in parallel: a width whose
+        // quarter does not divide 1024 - att_hid_dim = 96, 288 - leaves the threads behind the last whole group idle)
+        if ((q.A & 3) || (q.D & 3) || q.D > 4096) return ISC_E_SHAPE;
         if (!isc_aligned16(q.P) || !isc_aligned16(q.V) || (q.dP && !isc_aligned16(q.dP)) || (q.dV && !isc_aligned16(q.dV)) ||
             !isc_aligned16(q.q) || !isc_aligned16(q.w) || !isc_aligned16(q.dout) || (q.q2 && !isc_aligned16(q.q2)))
             return ISC_E_ALIGN;

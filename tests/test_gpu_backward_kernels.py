@@ -400,12 +400,14 @@ def _scan_pre(g, B, R_, A, D):
 
 
 @pytest.mark.parametrize('with_q2', [False, True], ids=['q', 'q+q2'])
-@pytest.mark.parametrize('B,R_,A,D', [(1, 1, 4, 4), (3, 6, 32, 32), (5, 37, 64, 128), (2, 196, 512, 512), (4, 11, 1024, 64)])
+@pytest.mark.parametrize('B,R_,A,D', [(1, 1, 4, 4), (3, 6, 32, 32), (5, 37, 64, 128), (2, 196, 512, 512), (4, 11, 1024, 64),
+                                      (3, 50, 96, 32), (2, 5, 288, 96)])
 def test_attn_scan_bwd_all_five_outputs_vs_fp64(B, R_, A, D, with_q2):
     """d e, d q, dw_rows, dP, dV of ONE step against fp64 autograd of e = w . tanh(P + q (+ q2)), out = alpha V at the
     saved alpha (a strided [B, T, R] view).  One region / one float4 column up to A = 1024 (four region groups) and 196
-    regions; accumulate 0 / 1 on pre-filled dP, dV, dw_rows (dq is overwritten either way); dP = None or dV = None with
-    de_out given leaves every other output's bits alone.
+    regions; widths whose quarter does not divide the 1024 threads (A = 96: 42 region groups and 16 idle threads, more
+    regions than groups; A = 288: 14 groups; D = 96); accumulate 0 / 1 on pre-filled dP, dV, dw_rows (dq is overwritten
+    either way); dP = None or dV = None with de_out given leaves every other output's bits alone.
     err_kernel / max(err32, 2^-23 max|ref|) measured on an MI355X (the bound is 8), worst case:
     d e 1.91, dq 1.38, dw_rows 1.26, dP 1.42, dV 0.44"""
     g = gen(B * 1000 + R_ + A + D + int(with_q2))
@@ -459,7 +461,7 @@ def test_attn_scan_bwd_two_problem_launch():
 
 def test_attn_scan_bwd_refuses_what_it_cannot_run():
     """Every one of these returns from the entry point's checks, in front of the launch (csrc/backward.hip,
-    isc_attn_scan_bwd: A > 1024 and 1024 % (A / 4) != 0 -> ISC_E_SHAPE; the dynamic LDS need (R + 2 * 1024 / (A / 4) * A
+    isc_attn_scan_bwd: A > 1024 and D > 4096 -> ISC_E_SHAPE; the dynamic LDS need (R + 2 * 1024 / (A / 4) * A
     floats) above 60000 bytes -> ISC_E_SHAPE; a P that is not 16-byte aligned -> ISC_E_ALIGN): the outputs stay untouched."""
     lib, g = _lib.load(), gen(6)
 
@@ -482,7 +484,8 @@ def test_attn_scan_bwd_refuses_what_it_cannot_run():
             for k in ('dP', 'dV', 'dw_rows'):
                 assert torch.equal(bufs[k][0][:B].cpu(), pre[k])
         return rc
-    assert rc_of(1, 2, 96, 4) == -2            # 1024 % 24 != 0
+    assert rc_of(1, 2, 4, 8192) == -2          # D > 4096: more float4 columns than threads
+    assert rc_of(1, 2, 96, 4) == 0             # (1024 % 24 != 0 runs: test_attn_scan_bwd_all_five_outputs_vs_fp64)
     assert rc_of(1, 2, 2048, 4) == -2          # A > 1024
     assert (7000 + 2 * 1024 * 4) * 4 > 60000
     assert rc_of(1, 7000, 4, 4) == -2          # LDS

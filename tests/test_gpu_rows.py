@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _widths as Wd
 from insenticap_model_amd import Captioner, _lib, ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -113,7 +114,11 @@ def _inputs(B, V, st, R=36, T=20, seed=11):
 @pytest.mark.parametrize('rows,V,st,R', [(5, 10000, synth.DEFAULT_SETTINGS, 36), (3, 10000, synth.DEFAULT_SETTINGS, 36),
                                          (8, 10000, synth.DEFAULT_SETTINGS, 36), (5, 10000, synth.DEFAULT_SETTINGS, 196),
                                          (1, 10000, synth.DEFAULT_SETTINGS, 6), (5, 256, synth.TINY_SETTINGS, 12),
-                                         (2, 64, synth.TINY_SETTINGS, 1)])
+                                         (2, 64, synth.TINY_SETTINGS, 1),
+                                         # H != A = E = W (tests/_widths.py): two LSTM units per wave (H = 768: 6 and 7 slices),
+                                         # 10 slices against the 8 in flight and a ragged 256 + 32 slice (H = 1024, E = 288)
+                                         (5, 300, Wd.H_WIDE, 7), (2, 300, Wd.H_768, 7), (8, 300, Wd.H_768, 7),
+                                         (3, 300, Wd.H_1024_E_288, 7), (6, 300, Wd.H_1024_E_288, 12)])
 def test_whole_step_against_the_general_kernels(rows, V, st, R):
     """isc_rows_step_fwd vs isc_step_fwd on the same plan (random non-zero state); then with a re-ordering index
     against the general step on explicitly gathered state."""
@@ -236,7 +241,8 @@ def test_select_equals_topk_then_merge():
                                                # (beam 6 .. 8: the select's lists move up past their fifth place; 1, 2: its smallest workgroups)
                                                (10000, synth.DEFAULT_SETTINGS, 1, 8, 36), (10000, synth.DEFAULT_SETTINGS, 1, 6, 36),
                                                (256, synth.TINY_SETTINGS, 1, 7, 12), (256, synth.TINY_SETTINGS, 1, 1, 12),
-                                               (256, synth.TINY_SETTINGS, 4, 2, 12)])
+                                               (256, synth.TINY_SETTINGS, 4, 2, 12),
+                                               (300, Wd.H_768, 1, 3, 7), (300, Wd.H_1024_E_288, 2, 3, 7)])
 def test_beam_search_on_this_path_equals_the_general_path(V, st, n_img, beam, R):
     cap = _captioner(V, st, seed=2)
     cap.enable_beam_graphs(False)

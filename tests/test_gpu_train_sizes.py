@@ -20,10 +20,12 @@ GRAD_RTOL = 1e-4            # gradients within 1e-4 relative to the
 DEV = 'cuda:0'
 
 
-def _oracle_iteration(w, V, d, s2s, chunk=256, dtype=torch.float32):
+def _oracle_iteration(w, V, d, s2s, chunk=256, dtype=torch.float32, masks=None, s_masks=None, p_drop=0.5):
     """xe + domain-align + seq2seq losses and the gradient of their sum by the oracle's autograd, in row chunks (each
     loss is a sum over rows divided by a global normaliser, so chunk gradients add).  dtype float64: the same
-    restatement as the arbiter between two fp32 implementations."""
+    restatement as the arbiter between two fp32 implementations.  masks / s_masks: the oracle's dropout keep-masks of
+    the two calls (training mode; one chunk only)."""
+    assert (masks is None and s_masks is None) or max(len(d['lengths']), len(s2s['lengths'])) <= chunk
     from oracle import captioner_oracle as O
     torch.set_num_threads(max(1, min(64, len(__import__('os').sched_getaffinity(0)))))
     p = O.to_params(w, dtype=dtype, requires_grad=True)
@@ -38,7 +40,7 @@ def _oracle_iteration(w, V, d, s2s, chunk=256, dtype=torch.float32):
     for lo in range(0, n_rows, chunk):
         hi = min(n_rows, lo + chunk)
         logp, P, _ = O.forward_xe(p, ids, t(d['fc_feats'][lo:hi]), t(d['att_feats'][lo:hi]), t(d['cpt_words'][lo:hi]),
-                                  t(d['captions'][lo:hi]), t(d['senti_labels'][lo:hi]))
+                                  t(d['captions'][lo:hi]), t(d['senti_labels'][lo:hi]), masks=masks, p_drop=p_drop)
         lens = list(d['lengths'][lo:hi])
         xe = O.xe_criterion(logp[:, :max(lens)], t(d['captions'][lo:hi, 1:1 + max(lens)]), lens) * (sum(lens) / n_tok)
         da = O.domain_align_loss(P.cpt, P.fc_raw) * ((hi - lo) / n_rows)
@@ -50,7 +52,8 @@ def _oracle_iteration(w, V, d, s2s, chunk=256, dtype=torch.float32):
     for lo in range(0, len(s2s['lengths']), chunk):
         hi = min(len(s2s['lengths']), lo + chunk)
         logp, _, _ = O.forward_seq2seq(p, ids, t(s2s['captions'][lo:hi]), t(s2s['cpt_words'][lo:hi]),
-                                       t(s2s['senti_words'][lo:hi]), t(s2s['senti_labels'][lo:hi]))
+                                       t(s2s['senti_words'][lo:hi]), t(s2s['senti_labels'][lo:hi]), masks=s_masks,
+                                       p_drop=p_drop)
         lens = list(s2s['lengths'][lo:hi])
         l2 = O.xe_criterion(logp[:, :max(lens)], t(s2s['captions'][lo:hi, 1:1 + max(lens)]), lens) * (sum(lens) / n_tok2)
         l2.backward()
@@ -64,20 +67,34 @@ def _oracle_iteration(w, V, d, s2s, chunk=256, dtype=torch.float32):
     return losses, grads, {k: q.numpy() for k, q in params.items()}
 
 
-def _hip_iteration(w, V, st, d, s2s):
+def _hip_iteration(w, V, st, d, s2s, pair=None, masks=None, s_masks=None, train=False):
+    """pair: None = the two calls of the reference's iteration; True / False = one forward_xe_seq2seq call with
+    cap.pair_unrolls set so (the merged step chain / the two calls behind that entry point).  masks / s_masks: the two
+    calls' explicit dropout keep-masks (`_masks`), with train=True."""
     cap = Captioner(synth.make_idx2word(V), synth.SENTIMENT_CATEGORIES, st)
     cap.load_state_dict({k: torch.from_numpy(x) for k, x in w.items()})
     cap.to(DEV).eval()                 # eval-mode dropout (identity), gradients still flow: SURVEY 8(d) config 2
+    if train:
+        cap.train()
     optim, _, _ = cap.get_optim_criterion(4e-4)
     T = lambda a, k: torch.from_numpy(np.asarray(a[k])).to(DEV)
     xe_crit, da_crit = XECriterion(), torch.nn.MSELoss()
     cap.zero_grad()
-    pred = cap(T(d, 'fc_feats'), T(d, 'att_feats'), T(d, 'cpt_words'), T(d, 'captions'), T(d, 'senti_labels'), 0.0,
-               mode='xe')
-    xe = xe_crit(pred, T(d, 'captions')[:, 1:], d['lengths'])
-    da = da_crit(cap.cpt_feats, cap.fc_feats.detach())
-    pred2 = cap(T(s2s, 'captions'), T(s2s, 'cpt_words'), T(s2s, 'senti_words'), T(s2s, 'senti_labels'), 0.0,
-                mode='seq2seq')
+    if pair is None:
+        pred = cap.forward_xe(T(d, 'fc_feats'), T(d, 'att_feats'), T(d, 'cpt_words'), T(d, 'captions'),
+                              T(d, 'senti_labels'), 0.0, _masks=masks)
+        xe = xe_crit(pred, T(d, 'captions')[:, 1:], d['lengths'])
+        da = da_crit(cap.cpt_feats, cap.fc_feats.detach())
+        pred2 = cap.forward_seq2seq(T(s2s, 'captions'), T(s2s, 'cpt_words'), T(s2s, 'senti_words'),
+                                    T(s2s, 'senti_labels'), 0.0, _masks=s_masks)
+    else:
+        cap.pair_unrolls = bool(pair)
+        pred, pred2 = cap.forward_xe_seq2seq(T(d, 'fc_feats'), T(d, 'att_feats'), T(d, 'cpt_words'), T(d, 'captions'),
+                                             T(d, 'senti_labels'), 0.0, T(s2s, 'captions'), T(s2s, 'cpt_words'),
+                                             T(s2s, 'senti_words'), T(s2s, 'senti_labels'), _masks=masks,
+                                             _s_masks=s_masks)
+        xe = xe_crit(pred, T(d, 'captions')[:, 1:], d['lengths'])
+        da = da_crit(cap.cpt_feats, cap.fc_feats.detach())
     l2 = xe_crit(pred2, T(s2s, 'captions')[:, 1:], s2s['lengths'])
     (xe + da + l2).backward()
     grads = {k: q.grad.detach().cpu().numpy().copy() for k, q in cap.named_parameters() if q.grad is not None}
