@@ -76,6 +76,13 @@ long long isc_gemv_launches(void);
 long long isc_h3x_launches(void);
 /* Launches that took the skinny split-f16 kernel (few rows: one launch per GEMM instead of split-K + reduce). */
 long long isc_h3s_launches(void);
+/* Launches of the exact-fp32 GEMM kernels since the library was loaded, by kind (process-wide, read-only; test hook:
+ * the one way to tell which fp32 kernel a launch took).  kind 0 / 1 / 2 = the register-staged gemm_kernel on the
+ * 128 / 64 / 32-row tile, every layout (NT, NN, TN) and epilogue summed; 3 = the 256-row LDS-DMA tile (XL); 4 = the
+ * 128-row LDS-DMA tile (LD); 5 = the 64-row LDS-DMA tile (MD: what tile 1 runs for plain linear NT launches); 6 = a
+ * split-K reduce launch of any epilogue (linear, LSTM, vocabulary; the reduce behind a K-split of the split-f16
+ * kernels included).  Any other kind returns -1.  A call turned away on the host counts nowhere. */
+long long isc_f32_launches(int kind);
 /* Weights scope of the split-f16 path.  Between _begin and _end the caller guarantees that no weight matrix passed
  * to the forward entry points changes (a roll-out's decode loop): each weight operand is then split into its planes
  * once, into `buf` (device memory, 256-byte aligned; 64 MB holds the decoder's matrices), and later launches with

@@ -2456,6 +2456,14 @@ static int lds_attr_once(std::atomic<bool> &done, size_t bytes, K k0, K k1 = nul
     return ISC_OK;
 }
 
+// isc_f32_launches(kind): launches of the exact-fp32 kernels so far, by kind (a failed launch counts too).  0 / 1 / 2 =
+// gemm_kernel on the 128 / 64 / 32-row tile (every layout and epilogue), 3 = XL, 4 = LD, 5 = MD, 6 = a split-K reduce.
+enum { F32_KIND_XL = 3, F32_KIND_LD = 4, F32_KIND_MD = 5, F32_KIND_REDUCE = 6, F32_KINDS = 7 };
+static std::atomic<long long> g_f32_launches[F32_KINDS];
+extern "C" long long isc_f32_launches(int kind) {
+    return kind >= 0 && kind < F32_KINDS ? g_f32_launches[kind].load() : -1;
+}
+
 template <int WM, int WN, int TN, int EPI, bool AKM, bool BKM>
 static int launch_cfg(const DevLaunch &L, hipStream_t st) {
     constexpr int BM = 32 * WM, BN = 32 * TN * WN;
@@ -2465,6 +2473,7 @@ static int launch_cfg(const DevLaunch &L, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
     if (int rc = lds_attr_once(attr_set, lds, &gemm_kernel<WM, WN, TN, EPI, AKM, BKM>)) return rc;
     hipLaunchKernelGGL((gemm_kernel<WM, WN, TN, EPI, AKM, BKM>), dim3(L.total_tiles), dim3(256), lds, st, L);
+    ++g_f32_launches[WM == 4 ? 0 : (WM == 2 ? 1 : 2)];
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -2485,6 +2494,7 @@ static int launch_f32_dma(const DevLaunch &L, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
     if (int rc = lds_attr_once(attr_set, lds, kernel)) return rc;
     hipLaunchKernelGGL(kernel, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
+    ++g_f32_launches[std::is_same_v<G, F32TileXL> ? F32_KIND_XL : (std::is_same_v<G, F32TileLD> ? F32_KIND_LD : F32_KIND_MD)];
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -2685,6 +2695,7 @@ static int launch_splitk_linear_reduce(const DevLaunch &L, hipStream_t st) {
         if (n4 > mx) mx = n4;
     }
     hipLaunchKernelGGL(splitk_linear_kernel, dim3((unsigned)((mx + 255) / 256), L.nprob), dim3(256), 0, st, L);
+    ++g_f32_launches[F32_KIND_REDUCE];
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -2695,11 +2706,13 @@ static int launch_splitk_reduce(const DevLaunch &L, hipStream_t st) {
     if constexpr (EPI == EPI_LSTM) {          // plain [M, 4H] pre-activation slabs, then the cell update
         const long long n = (long long)p.M * p.H;
         hipLaunchKernelGGL(splitk_lstm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, L);
+        ++g_f32_launches[F32_KIND_REDUCE];
         ISC_LAUNCH_CHECK();
         return ISC_OK;
     } else if constexpr (EPI == EPI_VOCAB) {  // raw [S, M, V] slabs, then the per-128-column statistics: a wave per (row, tile)
         const long long waves = (long long)p.M * p.ntile_total;
         hipLaunchKernelGGL(splitk_vocab_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, L);
+        ++g_f32_launches[F32_KIND_REDUCE];
         ISC_LAUNCH_CHECK();
         return ISC_OK;
     } else {

@@ -475,6 +475,12 @@ def h3_f16a_launches():
     return _lib.load().isc_h3_f16a_launches()
 
 
+def f32_launches(kind):
+    """Launches of the exact-fp32 GEMM kernels so far (isc_f32_launches): kind 0 / 1 / 2 = the register-staged 128 / 64 /
+    32-row tile, 3 = XL, 4 = LD, 5 = MD, 6 = a split-K reduce; -1 for any other kind."""
+    return _lib.load().isc_f32_launches(int(kind))
+
+
 def linear_fwd(problems):
     lib = _lib.load()
     _attach_ws(problems[0], torch.cuda.current_device())
@@ -499,9 +505,11 @@ def linear_fwd(problems):
 
 
 def lstm_fwd(segs, b_ih, b_hh, c_prev, h_out, c_out, gates_out=None, h_keep_mask=None,
-             mask_scale=1.0, hdrop_out=None, pre=None, tab=None, tab_ids=None, h_planes=None, pre_div=1):
+             mask_scale=1.0, hdrop_out=None, pre=None, tab=None, tab_ids=None, h_planes=None, pre_div=1, ws=None):
     """h_planes: optional [2, M, H] f16 tensor receiving the split-f16 planes of h_out (for consumers' segments).
-    pre_div > 1: `pre` is [M / pre_div, 4H], one row per image, and row m adds pre[m // pre_div]."""
+    pre_div > 1: `pre` is [M / pre_div, 4H], one row per image, and row m adds pre[m // pre_div].
+    ws: optional fp32 tensor used as the launch's split-K workspace instead of the stream's (as a pre-set
+    `splitk_ws` on a linear problem)."""
     lib = _lib.load()
     p = LstmProblem()
     _fill_segs(p.seg, segs)
@@ -524,6 +532,9 @@ def lstm_fwd(segs, b_ih, b_hh, c_prev, h_out, c_out, gates_out=None, h_keep_mask
     if h_planes is not None:
         assert h_planes.dtype == torch.float16 and h_planes.is_contiguous() and h_planes.shape == (2, p.M, p.H)
         p.h_hi, p.h_lo = planes_ptrs(h_planes)
+    if ws is not None:
+        assert ws.dtype == torch.float32 and ws.is_contiguous()
+        p.splitk_ws, p.splitk_ws_floats = ws.data_ptr(), ws.numel()
     _attach_ws(p, c_prev.device)
     e0 = TIMER.begin()
     check(lib.isc_lstm_fwd(C.byref(p), stream()), 'isc_lstm_fwd')
@@ -639,7 +650,8 @@ def step_bwd(plan):
     check(_lib.load().isc_step_bwd(C.byref(plan), stream()), 'isc_step_bwd')
 
 
-def vocab_fwd(h, W, bias, part_max, part_sum, part_idx, logits=None, h_planes=None):
+def vocab_fwd(h, W, bias, part_max, part_sum, part_idx, logits=None, h_planes=None, ws=None):
+    """ws: optional fp32 tensor used as the launch's split-K workspace instead of the stream's."""
     lib = _lib.load()
     hi = lo = None
     if h_planes is not None:
@@ -650,7 +662,10 @@ def vocab_fwd(h, W, bias, part_max, part_sum, part_idx, logits=None, h_planes=No
     assert h.stride(1) == 1 and W.stride(1) == 1
     ld = logits.stride(0) if logits is not None else 0
     e0 = TIMER.begin()
-    ws = splitk_ws(h.device)
+    if ws is None:
+        ws = splitk_ws(h.device)
+    else:
+        assert ws.dtype == torch.float32 and ws.is_contiguous()
     check(lib.isc_vocab_fwd(h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr(), M, V, K,
                             ptr(logits), ld, part_max.data_ptr(), part_sum.data_ptr(),
                             part_idx.data_ptr(), hi, lo, ws.data_ptr(), ws.numel(), stream()), 'isc_vocab_fwd')

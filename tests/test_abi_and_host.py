@@ -171,6 +171,15 @@ def test_argument_validation_without_a_gpu():
     assert lib.isc_colsum(None, 0, 1, 1, None, 0, None, 0, None) == -1
 
 
+def test_f32_launch_counter_kinds_without_a_gpu():
+    """isc_f32_launches: kinds 0-6 exist and read 0 or more, any other kind answers -1; reading touches no device."""
+    lib = _lib.load()
+    assert lib.isc_f32_launches(-1) == -1 and lib.isc_f32_launches(7) == -1
+    assert all(lib.isc_f32_launches(k) >= 0 for k in range(7))
+    from insenticap_model_amd import ops
+    assert ops.f32_launches(7) == -1 and ops.f32_launches(6) >= 0
+
+
 def make(V=64, st=synth.TINY_SETTINGS):
     return Captioner(synth.make_idx2word(V), synth.SENTIMENT_CATEGORIES, st)
 

@@ -1,6 +1,16 @@
 """Every GEMM tile shape (128x128, 64x128, 32x128 register-staged; 256x128, 128x128 and - what tile 1 runs for plain
 linear NT launches - 64x128 by LDS-DMA) behind the same entry points: each must match an fp64 reference and - because
-every shape accumulates an output element over k in the same order - must agree bit for bit with the others."""
+every shape accumulates an output element over k in the same order - must agree bit for bit with the others.
+
+Which override reaches which kernel (asserted with ops.f32_launches in every test below):
+  linear   0 gemm_kernel 128-row, 1 gemm_md_kernel, 2 gemm_kernel 32-row, 3 gemm_xl_kernel, 4 gemm_ld_kernel
+  LSTM     0 / 1 / 2 gemm_kernel 128 / 64 / 32-row, 4 gemm_ld_kernel, 3 gemm_xl_kernel for the bias-only cell and the
+           128-row gemm_kernel as soon as `pre` or `tab` is given
+  vocab    0 / 1 / 2 gemm_kernel 128 / 64 / 32-row, 4 gemm_ld_kernel, 3 the 128-row gemm_kernel (XL is never allowed)
+The split-K plan comes before the tile choice and does not look at the override: a launch of fewer than 384 32x128
+blocks and at least 8 K-chunks on the stream's workspace runs the 32-row tile + a reduce whatever the override
+(split = 'auto' at the two long-K linear shapes); split = 'off' hands those launches a private workspace too small to
+split, so that they run per tile.  tests/test_gpu_gemm_f32_kernels.py holds the kernels one by one."""
 import numpy as np
 import pytest
 import torch
@@ -26,8 +36,28 @@ def _rand(g, *shape, scale=1.0):
     return (torch.rand(*shape, generator=g) * 2 - 1) * scale
 
 
+NT_KIND = {0: 0, 1: 5, 2: 2, 3: 3, 4: 4}        # override -> counter kind of a plain linear launch (tile 1 = MD)
+REG_KIND = {0: 0, 1: 1, 2: 2, 3: 0, 4: 4}       # LSTM with pre / tab, vocabulary: no MD, and override 3 falls back to 0
+
+
+def _counts():
+    lib = ops._lib.load()
+    return [ops.f32_launches(k) for k in range(7)] + [lib.isc_h3_launches(), lib.isc_h3s_launches(),
+                                                      lib.isc_gemv_launches()]
+
+
+def _assert_ran(before, want, what):
+    """The fp32 kinds of `want` went up by exactly that much, nothing else (split-f16, skinny, matrix-vector) moved."""
+    delta = [a - b for a, b in zip(_counts(), before)]
+    assert delta == [want.get(k, 0) for k in range(7)] + [0, 0, 0], (what, delta)
+
+
+@pytest.mark.parametrize('split', ['auto', 'off'])
 @pytest.mark.parametrize('M,N,K1,K2', [(512, 256, 64, 0), (1000, 520, 512, 96), (777, 128, 2048, 0), (256, 1000, 32, 32)])
-def test_linear_all_tiles(M, N, K1, K2):
+def test_linear_all_tiles(M, N, K1, K2, split):
+    """split = 'auto': the stream's workspace - the two long-K shapes take the split-K route under every override (the
+    counters say so: the 32-row tile + a reduce); split = 'off': a private workspace of one float (sentinels behind it
+    stay) - every shape runs the override's own kernel."""
     g = torch.Generator().manual_seed(M + N)
     x1, w1, b = _rand(g, M, K1), _rand(g, N, K1, scale=K1 ** -0.5), _rand(g, N)
     keep = (torch.rand(M, N, generator=g) > 0.5).to(torch.uint8)
@@ -42,13 +72,20 @@ def test_linear_all_tiles(M, N, K1, K2):
     ref_out = ref_pre * keep.double() * 2.0
     db, dkeep = b.to(dev()), keep.to(dev())
     outs = {}
+    splits = split == 'auto' and (K1 + K2) // 32 >= 8          # (both such shapes have fewer than 384 32x128 blocks)
+    ws = torch.full((65,), 7.25, device=dev())
     for t in TILES:
         ops.set_tile_override(t)
         out = prior.clone().to(dev())
         pre = torch.full((M, N), float('nan'), device=dev())
-        ops.linear_fwd([ops.linear_problem(segs, out, db, relu=True, keep_mask=dkeep,
-                                           mask_scale=2.0, out_pre=pre, accumulate=True)])
+        prob = ops.linear_problem(segs, out, db, relu=True, keep_mask=dkeep, mask_scale=2.0, out_pre=pre, accumulate=True)
+        if split == 'off':
+            prob.splitk_ws, prob.splitk_ws_floats = ws.data_ptr(), 1
+        before = _counts()
+        ops.linear_fwd([prob])
         torch.cuda.synchronize()
+        _assert_ran(before, {2: 1, 6: 1} if splits else {NT_KIND[t]: 1}, 'tile %d' % t)
+        assert bool((ws[1:] == 7.25).all())
         np.testing.assert_allclose(out.cpu().numpy(), ref_out.float().numpy(), atol=3e-5, rtol=1e-5, err_msg='tile %d' % t)
         np.testing.assert_allclose(pre.cpu().numpy(), ref_pre.float().numpy(), atol=3e-5, rtol=1e-5, err_msg='tile %d' % t)
         outs[t] = out.cpu()
@@ -66,8 +103,10 @@ def test_linear_grouped_three_problems_all_tiles():
     for t in TILES:
         ops.set_tile_override(t)
         outs = [torch.empty(m, n, device=dev()) for m, n, _ in shapes]
+        before = _counts()
         ops.linear_fwd([ops.linear_problem([aw], o) for aw, o in zip(ddata, outs)])
         torch.cuda.synchronize()
+        _assert_ran(before, {NT_KIND[t]: 1}, 'tile %d' % t)        # (one K-chunk in the third problem: no split)
         for o, r in zip(outs, refs):
             np.testing.assert_allclose(o.cpu().numpy(), r.numpy(), atol=2e-5, rtol=1e-5, err_msg='tile %d' % t)
         if base is None:
@@ -100,9 +139,11 @@ def test_lstm_all_tiles(M, H):
         gates = torch.empty(M, 4 * H, device=dev())
         hdrop = torch.empty(M, H, device=dev())
         hp = torch.empty(2, M, H, dtype=torch.float16, device=dev())
+        before = _counts()
         ops.lstm_fwd(dsegs, dargs[0], dargs[1], dargs[2], h, c, gates_out=gates, pre=dargs[3], tab=dargs[4],
                      tab_ids=dargs[5], h_planes=hp, h_keep_mask=dargs[6], mask_scale=2.0, hdrop_out=hdrop)
         torch.cuda.synchronize()
+        _assert_ran(before, {REG_KIND[t]: 1}, 'tile %d' % t)       # with `pre` / `tab`, override 3 runs tile 0
         np.testing.assert_allclose(h.cpu().numpy(), h_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
         np.testing.assert_allclose(c.cpu().numpy(), c_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
         np.testing.assert_allclose(gates.cpu().numpy(), gates_ref.float().numpy(), atol=2e-5, err_msg='tile %d' % t)
@@ -128,8 +169,10 @@ def test_vocab_all_tiles(M, V, K):
         pm, ps = torch.empty(M, nt, device=dev()), torch.empty(M, nt, device=dev())
         pi = torch.empty(M, nt, device=dev(), dtype=torch.int32)
         logits = torch.empty(M, V, device=dev())
+        before = _counts()
         ops.vocab_fwd(dh, dW, dbias, pm, ps, pi, logits)
         torch.cuda.synchronize()
+        _assert_ran(before, {REG_KIND[t]: 1}, 'tile %d' % t)       # the vocabulary never takes XL: override 3 runs tile 0
         np.testing.assert_allclose(logits.cpu().numpy(), logits_ref.float().numpy(), atol=3e-5, rtol=1e-5, err_msg='tile %d' % t)
         mx = pm.max(1).values
         lse = mx + torch.log((ps * torch.exp(pm - mx[:, None])).sum(1))
@@ -158,6 +201,7 @@ def test_large_shapes_bit_identical_across_big_tiles():
     base = {}
     for t in (0, 3, 4):
         ops.set_tile_override(t)
+        before = _counts()
         out = torch.empty(B, 2048, device=dev())
         ops.linear_fwd([ops.linear_problem([(x[:, :1024], w[:, :1024]), (x[:, 1024:], w[:, 1024:])], out, b, relu=True)])
         h, c = torch.empty(B, 512, device=dev()), torch.empty(B, 512, device=dev())
@@ -167,6 +211,8 @@ def test_large_shapes_bit_identical_across_big_tiles():
         pi = torch.empty(B, nt, device=dev(), dtype=torch.int32)
         ops.vocab_fwd(h, hW, hb, pm, ps, pi)
         torch.cuda.synchronize()
+        # linear and the bias-only LSTM on the override's tile; the vocabulary on it too, except that XL falls back to 0
+        _assert_ran(before, {0: {0: 3}, 3: {3: 2, 0: 1}, 4: {4: 3}}[t], 'tile %d' % t)
         cur = dict(lin=out.cpu(), h=h.cpu(), c=c.cpu(), pm=pm.cpu(), pi=pi.cpu())
         if not base:
             base = cur

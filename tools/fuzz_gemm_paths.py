@@ -3,10 +3,16 @@ the backward NN / TN contractions) with a split-f16 engine forced per case - the
 kernel with 32 x 32 or 64 x 64 tiles (modes 3 / 4), or auto inside a weights scope - each case against an fp64 reference: ragged M, K-segments, partial
 column tiles, grouped problems, producer-written planes, accumulate.
 
-    python tools/fuzz_gemm_paths.py [seed] [cases] [routes.txt]   (on the MI355X box; tests/test_gpu_fuzz.py runs a short one)
+engine='f32' sweeps the exact-fp32 engine instead: mode 0 and a tile override drawn from {-1, 0, 1, 2, 3, 4} per case (no
+weights scope), and for the backward contractions segment lengths the split-f16 kernels cannot take - NN any K_s >= 1
+(A's rows zero-padded to a multiple of 4), TN any row count >= 1.  The default engine draws exactly the random stream it
+always drew: its seeds keep their cases.
+
+    python tools/fuzz_gemm_paths.py [seed] [cases] [routes.txt] [engine]   (on the MI355X box; tests/test_gpu_fuzz.py runs short ones)
 
 With a third argument every case appends one line to that file - kind, shapes, mode, the SHA-256 of the output tensors'
-bytes and the deltas of the five launch counters: two builds route and compute alike when their files are identical.
+bytes and the deltas of the five launch counters (engine='f32': the override and the seven isc_f32_launches kinds as
+well): two builds route and compute alike when their files are identical.
 """
 import hashlib
 import os
@@ -21,7 +27,9 @@ from insenticap_model_amd import ops  # noqa: E402
 COUNTERS = ('isc_h3_launches', 'isc_h3x_launches', 'isc_h3s_launches', 'isc_gemv_launches', 'isc_h3_f16a_launches')
 
 
-def run(seed=0, cases=120, verbose=True, routes=None):
+def run(seed=0, cases=120, verbose=True, routes=None, engine='split_f16'):
+    assert engine in ('split_f16', 'f32'), engine
+    f32 = engine == 'f32'
     dev = torch.device('cuda:0')
     lib = ops._lib.load()
     def counters(): return [getattr(lib, c)() for c in COUNTERS]
@@ -34,11 +42,21 @@ def run(seed=0, cases=120, verbose=True, routes=None):
         M = random.choice([1, 5, 31, 33, 127, 129, 255, 257, 700, 1023, 2050, random.randint(1, 3000)])
         nseg = random.randint(1, 3)
         Ks = [32 * random.randint(1, 16) for _ in range(nseg)]
-        mode = random.choice([2, 3, 4, 1])
+        if f32:
+            mode, tile = 0, random.choice([-1, 0, 1, 2, 3, 4])
+            ops.set_tile_override(tile)
+            if kind == 'nn':              # any K_s >= 1; K_s % 4 != 0: A's rows are zero-padded (below)
+                Ks = [random.choice([1, 5, 33, 100, 290, random.randint(1, 512)]) for _ in range(nseg)]
+            elif kind == 'tn':            # any row count >= 1
+                Ks = [random.choice([1, 6, 31, 33, 80, random.randint(1, 512)]) for _ in range(nseg)]
+        else:
+            mode = random.choice([2, 3, 4, 1])
         ops.set_h3_mode(mode)
-        scope = ops.h3_weights_scope(dev)
-        scope.__enter__()
+        scope = None if f32 else ops.h3_weights_scope(dev)
+        if scope is not None:
+            scope.__enter__()
         cnt0, shapes, result = counters(), None, []
+        f32_0 = [ops.f32_launches(k) for k in range(7)]
         try:
             if kind in ('linear', 'linear3'):
                 nprob = 1 if kind == 'linear' else random.randint(2, 3)
@@ -91,6 +109,7 @@ def run(seed=0, cases=120, verbose=True, routes=None):
                     As = [R(M, k) for k in Ks]
                     Ws = [R(k, N, scale=k ** -0.5) for k in Ks]
                     ref = prior.double() + sum(a.double() @ w.double() for a, w in zip(As, Ws))
+                    As = [torch.nn.functional.pad(a, (0, -a.shape[1] % 4)) for a in As]      # (K_s % 4 != 0: zero padding)
                 else:                     # C[M,N] += sum_s A_s[K_s,M]^T W_s[K_s,N]; M % 4 == 0 required
                     M = max(4, M // 4 * 4)
                     prior = R(M, N)
@@ -127,13 +146,17 @@ def run(seed=0, cases=120, verbose=True, routes=None):
         except Exception as e:
             bad += 1; print('EXC', kind, M, Ks, repr(e)[:200])
         finally:
-            scope.__exit__(None, None, None)
+            if scope is not None:
+                scope.__exit__(None, None, None)
         if routes:
             sha = hashlib.sha256()
             for t in result: sha.update(t.cpu().contiguous().view(torch.uint8).numpy().tobytes())
             with open(routes, 'a') as f:
-                print(it, kind, shapes, mode, sha.hexdigest(), [b - a for a, b in zip(cnt0, counters())], file=f)
+                extra = ((tile, [ops.f32_launches(k) - a for k, a in enumerate(f32_0)]),) if f32 else ()
+                print(it, kind, shapes, mode, sha.hexdigest(), [b - a for a, b in zip(cnt0, counters())], *extra, file=f)
     ops.set_h3_mode(1)
+    if f32:
+        ops.set_tile_override(-1)
     if verbose:
         print('cases done, bad =', bad, 'large / skinny split-f16 launches', ops._lib.load().isc_h3_launches(),
               ops._lib.load().isc_h3s_launches())
@@ -142,4 +165,5 @@ def run(seed=0, cases=120, verbose=True, routes=None):
 
 if __name__ == '__main__':
     sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 0, int(sys.argv[2]) if len(sys.argv) > 2 else 120,
-                      routes=sys.argv[3] if len(sys.argv) > 3 else None) else 0)
+                      routes=sys.argv[3] if len(sys.argv) > 3 else None,
+                      engine=sys.argv[4] if len(sys.argv) > 4 else 'split_f16') else 0)
