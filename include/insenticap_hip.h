@@ -83,6 +83,17 @@ long long isc_h3s_launches(void);
  * split-K reduce launch of any epilogue (linear, LSTM, vocabulary; the reduce behind a K-split of the split-f16
  * kernels included).  Any other kind returns -1.  A call turned away on the host counts nowhere. */
 long long isc_f32_launches(int kind);
+/* Launches of the split-f16 GEMM kernels since the library was loaded, by kernel instantiation (process-wide,
+ * read-only; host counters incremented at the launch sites; test hook: the one way to tell which split-f16 kernel a
+ * launch took).  kind 3 g + f = a large tile of geometry g (0 / 1 / 2 = gemm_h3_kernel 128 rows / gemm_h3x_kernel 256
+ * rows / gemm_h3m_kernel 64 rows) whose activations are all planes (f = 0), some fp32 rows (f = 1), or f16 rows
+ * (f = 2: gemm_h3_f16a_kernel); 9 / 10 / 11 = gemm_h3s_kernel 32 x 32 on four waves / 32 x 32 on eight waves / 64 x 64
+ * (linear and LSTM epilogue); 12 / 13 = its vocabulary form, 32 x 128 on four / eight waves; 14 / 15 = gemm_h3v_kernel
+ * on planes / on fp32 rows; 16 = a launch of h3_split_kernel (plain or transposing, any number of jobs, a weights
+ * refresh included).  The epilogue is fixed by the entry point and has no kind.  Any other kind returns -1.
+ * isc_h3_launches / isc_h3x_launches / isc_h3s_launches / isc_h3_f16a_launches keep their meaning (per entry-point
+ * launch, by path). */
+long long isc_h3_kernel_launches(int kind);
 /* Weights scope of the split-f16 path.  Between _begin and _end the caller guarantees that no weight matrix passed
  * to the forward entry points changes (a roll-out's decode loop): each weight operand is then split into its planes
  * once, into `buf` (device memory, 256-byte aligned; 64 MB holds the decoder's matrices), and later launches with

@@ -174,6 +174,7 @@ SIGNATURES = {
     'isc_h3x_launches': (C.c_longlong, []),
     'isc_h3s_launches': (C.c_longlong, []),
     'isc_f32_launches': (C.c_longlong, [C.c_int]),
+    'isc_h3_kernel_launches': (C.c_longlong, [C.c_int]),
     'isc_h3_weights_begin': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     'isc_h3_weights_end': (C.c_int, [C.c_void_p]),
     'isc_h3_weights_suspend': (C.c_int, [C.c_void_p]),

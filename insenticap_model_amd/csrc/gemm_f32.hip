@@ -2608,6 +2608,17 @@ static void finish_tiling(DevLaunch &L, int tile) {
 // isc_set_h3_mode: 0 = off, 1 = auto, 2 = large kernels whenever the shapes allow, 3 / 4 = skinny kernel (32 / 64 tiles)
 static std::atomic<int> g_h3_mode{1};
 static std::atomic<long long> g_h3_launches{0}, g_h3x_launches{0}, g_h3_f16a_launches{0};
+// isc_h3_kernel_launches(kind): launches of the split-f16 kernels so far, by instantiation (a failed launch counts too;
+// the epilogue is the entry point's, so it has no kind).  3 g + f = a large tile of geometry g (0 / 1 / 2 = 128 / 256 /
+// 64 rows) reading its activations as planes (f = 0), fp32 rows (1) or f16 rows (2); 9 / 10 / 11 = gemm_h3s_kernel 32 x
+// 32 on four waves, on eight, 64 x 64; 12 / 13 = its vocabulary form 32 x 128 on four / eight waves; 14 / 15 =
+// gemm_h3v_kernel on planes / on fp32 rows; 16 = an h3_split_kernel launch (plain or transposing, any number of jobs).
+enum { H3_KIND_TILE = 0, H3_KIND_S32 = 9, H3_KIND_S32_W8 = 10, H3_KIND_S64 = 11, H3_KIND_SV = 12, H3_KIND_SV_W8 = 13,
+       H3_KIND_V = 14, H3_KIND_V_F32 = 15, H3_KIND_SPLIT = 16, H3_KINDS = 17 };
+static std::atomic<long long> g_h3_kernel_launches[H3_KINDS];
+extern "C" long long isc_h3_kernel_launches(int kind) {
+    return kind >= 0 && kind < H3_KINDS ? g_h3_kernel_launches[kind].load() : -1;
+}
 extern "C" long long isc_h3_launches(void) { return g_h3_launches.load(); }
 extern "C" long long isc_h3_f16a_launches(void) { return g_h3_f16a_launches.load(); }
 extern "C" long long isc_h3x_launches(void) { return g_h3x_launches.load(); }
@@ -2747,6 +2758,7 @@ static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
     static_assert(EPI == EPI_LINEAR || !std::is_same_v<G, H3Tile64>, "the 64-row kernel has the linear epilogue only");
     constexpr size_t lds = G::LDS_BYTES;
     constexpr auto planes = h3_tile_kernel<G, EPI, false>(), f32_rows = h3_tile_kernel<G, EPI, true>();
+    constexpr int kind = H3_KIND_TILE + 3 * (std::is_same_v<G, H3Tile128> ? 0 : (std::is_same_v<G, H3Tile256> ? 1 : 2));
     static std::atomic<bool> attr_set{false}, attr16_set{false};           // (above 64 KB: one workgroup per CU)
     if (int rc = lds_attr_once(attr_set, lds, planes, f32_rows)) return rc;
     if (h3_any_f16(L)) {
@@ -2754,6 +2766,7 @@ static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
             constexpr auto f16_rows = &gemm_h3_f16a_kernel<G>;
             if (int rc = lds_attr_once(attr16_set, lds, f16_rows)) return rc;
             hipLaunchKernelGGL(f16_rows, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
+            ++g_h3_kernel_launches[kind + 2];
             ISC_LAUNCH_CHECK();
             ++g_h3_f16a_launches;
             return ISC_OK;
@@ -2761,8 +2774,10 @@ static int launch_h3_tile(const DevLaunch &L, hipStream_t st) {
             return ISC_E_SHAPE;
         }
     }
-    const auto kernel = h3_any_f32(L) ? f32_rows : planes;
+    const bool rows32 = h3_any_f32(L);
+    const auto kernel = rows32 ? f32_rows : planes;
     hipLaunchKernelGGL(kernel, dim3(L.total_tiles), dim3(G::THREADS), lds, st, L);
+    ++g_h3_kernel_launches[kind + (rows32 ? 1 : 0)];
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -2894,6 +2909,7 @@ extern "C" int isc_h3_weights_refresh(void *stream) {
             blocks += e.transposed ? ((e.rows + 63) / 64) * (k0 >> 5) : (int)(((long long)e.rows * (k0 >> 3) + 255) / 256);
         }
         hipLaunchKernelGGL(h3_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S);
+        ++g_h3_kernel_launches[H3_KIND_SPLIT];
         ISC_LAUNCH_CHECK();
     }
     return ISC_OK;
@@ -2987,6 +3003,7 @@ struct H3Planner {
     int launch(hipStream_t st) {
         if (!S.njobs) return ISC_OK;
         hipLaunchKernelGGL(h3_split_kernel, dim3(blocks), dim3(256), 0, st, S);
+        ++g_h3_kernel_launches[H3_KIND_SPLIT];
         ISC_LAUNCH_CHECK();
         return ISC_OK;
     }
@@ -3105,6 +3122,8 @@ static int launch_h3s(const DevLaunch &L, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
     if (int rc = lds_attr_once(attr_set, lds, &gemm_h3s_kernel<EPI, T, NW>)) return rc;
     hipLaunchKernelGGL((gemm_h3s_kernel<EPI, T, NW>), dim3(L.total_tiles), dim3(64 * NW), lds, st, L);
+    ++g_h3_kernel_launches[EPI == EPI_VOCAB ? (NW == 8 ? H3_KIND_SV_W8 : H3_KIND_SV)
+                                            : (T == 2 ? H3_KIND_S64 : (NW == 8 ? H3_KIND_S32_W8 : H3_KIND_S32))];
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }
@@ -3198,8 +3217,10 @@ static int launch_h3s_t(const DevLaunch &L, int T, hipStream_t st) {
             if (int rc = lds_attr_once(attr_set, lds, &gemm_h3v_kernel<true>,
                                        &gemm_h3v_kernel<false>))
                 return rc;
-            if (h3_any_f32(L)) hipLaunchKernelGGL((gemm_h3v_kernel<true>), dim3(L.total_tiles), dim3(256), lds, st, L);
+            const bool rows32 = h3_any_f32(L);
+            if (rows32) hipLaunchKernelGGL((gemm_h3v_kernel<true>), dim3(L.total_tiles), dim3(256), lds, st, L);
             else hipLaunchKernelGGL((gemm_h3v_kernel<false>), dim3(L.total_tiles), dim3(256), lds, st, L);
+            ++g_h3_kernel_launches[rows32 ? H3_KIND_V_F32 : H3_KIND_V];
             ISC_LAUNCH_CHECK();
             return ISC_OK;
         }

@@ -481,6 +481,17 @@ def f32_launches(kind):
     return _lib.load().isc_f32_launches(int(kind))
 
 
+H3_KINDS = 17
+
+
+def h3_kernel_launches(kind):
+    """Launches of the split-f16 GEMM kernels so far, by instantiation (isc_h3_kernel_launches): 3 g + f = the large
+    tile of 128 / 256 / 64 rows (g = 0 / 1 / 2) on planes / fp32 rows / f16 rows (f = 0 / 1 / 2); 9 / 10 / 11 = the skinny
+    kernel 32 x 32 on four waves / on eight / 64 x 64; 12 / 13 = its vocabulary form on four / eight waves; 14 / 15 =
+    gemm_h3v_kernel on planes / fp32 rows; 16 = an operand-split launch; -1 for any other kind."""
+    return _lib.load().isc_h3_kernel_launches(int(kind))
+
+
 def linear_fwd(problems):
     lib = _lib.load()
     _attach_ws(problems[0], torch.cuda.current_device())

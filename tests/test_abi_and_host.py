@@ -180,6 +180,15 @@ def test_f32_launch_counter_kinds_without_a_gpu():
     assert ops.f32_launches(7) == -1 and ops.f32_launches(6) >= 0
 
 
+def test_h3_kernel_launch_counter_kinds_without_a_gpu():
+    """isc_h3_kernel_launches: kinds 0-16 exist and read 0 or more, any other kind answers -1; reading touches no device."""
+    lib = _lib.load()
+    assert lib.isc_h3_kernel_launches(-1) == -1 and lib.isc_h3_kernel_launches(17) == -1
+    assert all(lib.isc_h3_kernel_launches(k) >= 0 for k in range(17))
+    from insenticap_model_amd import ops
+    assert ops.H3_KINDS == 17 and ops.h3_kernel_launches(17) == -1 and ops.h3_kernel_launches(16) >= 0
+
+
 def make(V=64, st=synth.TINY_SETTINGS):
     return Captioner(synth.make_idx2word(V), synth.SENTIMENT_CATEGORIES, st)
 

@@ -36,7 +36,8 @@ def _restore():
 def counters():
     lib = _lib.load()
     return {'h3': lib.isc_h3_launches(), 'h3x': lib.isc_h3x_launches(), 'f16a': lib.isc_h3_f16a_launches(),
-            'conv': lib.isc_f16_convert_launches(), 'gemv': lib.isc_gemv_launches(), 'h3s': lib.isc_h3s_launches()}
+            'conv': lib.isc_f16_convert_launches(), 'gemv': lib.isc_gemv_launches(), 'h3s': lib.isc_h3s_launches(),
+            **{'kind%d' % k: ops.h3_kernel_launches(k) for k in range(ops.H3_KINDS)}}
 
 
 def moved(before):
@@ -94,6 +95,10 @@ def check_equal(x16, K, full, mode=1):
 
 # ------------------------------------------------------------------ 1. GEMM level
 GEOMS = {'256': (14336, 1), '64': (4096, 1), '128': (5000, 1), '128_forced_m1000': (1000, 2)}
+# the f16-row kind of ops.h3_kernel_launches each geometry must run (3 g + 2, g = 0 / 1 / 2 for 128 / 256 / 64 rows).  M =
+# 1000 under mode 2 is 32 tiles of 128 x 128 = 64 tiles of 64 x 128: h3_plan's half_tile rule gives it the 64-row tile,
+# not the 128-row one its name promises (the 128-row tile is M = 5000's: 160 tiles, 316 of 64 rows = two rounds)
+GEOM_KIND = {'256': 5, '64': 8, '128': 2, '128_forced_m1000': 8}
 
 
 @pytest.mark.parametrize('full', [False, True], ids=['plain', 'relu_bias_mask_pre'])
@@ -107,6 +112,8 @@ def test_native_geometries(geom, K, full):
         return
     assert d['f16a'] == 1 and d['h3'] == 1 and d['conv'] == 0 and d['gemv'] == 0 and d['h3s'] == 0, d
     assert d['h3x'] == (1 if geom == '256' else 0), d
+    kinds = {k: v for k, v in d.items() if k.startswith('kind') and v}
+    assert kinds == {'kind%d' % GEOM_KIND[geom]: 1, 'kind16': 1}, kinds      # the tile's f16-row form + one weight split
 
 
 @pytest.mark.parametrize('geom', ['256', '64', '128'])

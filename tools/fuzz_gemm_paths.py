@@ -12,7 +12,8 @@ always drew: its seeds keep their cases.
 
 With a third argument every case appends one line to that file - kind, shapes, mode, the SHA-256 of the output tensors'
 bytes and the deltas of the five launch counters (engine='f32': the override and the seven isc_f32_launches kinds as
-well): two builds route and compute alike when their files are identical.
+well), then the deltas of the 17 isc_h3_kernel_launches kinds (which split-f16 instantiation ran): two builds route and
+compute alike when their files are identical.
 """
 import hashlib
 import os
@@ -57,6 +58,7 @@ def run(seed=0, cases=120, verbose=True, routes=None, engine='split_f16'):
             scope.__enter__()
         cnt0, shapes, result = counters(), None, []
         f32_0 = [ops.f32_launches(k) for k in range(7)]
+        h3k_0 = [ops.h3_kernel_launches(k) for k in range(ops.H3_KINDS)]
         try:
             if kind in ('linear', 'linear3'):
                 nprob = 1 if kind == 'linear' else random.randint(2, 3)
@@ -153,7 +155,8 @@ def run(seed=0, cases=120, verbose=True, routes=None, engine='split_f16'):
             for t in result: sha.update(t.cpu().contiguous().view(torch.uint8).numpy().tobytes())
             with open(routes, 'a') as f:
                 extra = ((tile, [ops.f32_launches(k) - a for k, a in enumerate(f32_0)]),) if f32 else ()
-                print(it, kind, shapes, mode, sha.hexdigest(), [b - a for a, b in zip(cnt0, counters())], *extra, file=f)
+                h3k = [ops.h3_kernel_launches(k) - a for k, a in enumerate(h3k_0)]
+                print(it, kind, shapes, mode, sha.hexdigest(), [b - a for a, b in zip(cnt0, counters())], *extra, h3k, file=f)
     ops.set_h3_mode(1)
     if f32:
         ops.set_tile_override(-1)
