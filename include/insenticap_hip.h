@@ -943,6 +943,70 @@ int64_t isc_sent_cls_workspace_bytes(int B, int L, int W, int H);
 int isc_sent_cls_fwd(const isc_sent_cls_problem *prob_host, void *stream);
 long long isc_sent_cls_launches(void);    /* kernels enqueued by isc_sent_cls_fwd so far (measurement / test hook) */
 
+/* The frozen image-sentiment detector, forward in eval mode (sentiment_detector.py:30-60; called by decoder.py:83 for the
+ * image labels of an RL iteration and by decoder.py:182-192 in front of a beam search):
+ *   x = conv_{n-1}( ... conv_0(features) ... ), 3x3, padding 1, cross-correlation, channels C -> C/2 -> C/4 ..., NO
+ *   non-linearity between the convolutions;  r = relu(x);  m[b,j,p] = bs[j] + r[b,p,:] . Ws[j,:]  (the 1x1 conv);
+ *   z = FC_{f-1}( ... FC_0(mean_p m) ... )  (k x k layers, no activation between them);  prob = softmax(z);
+ *   maps[b,p] = sum_j prob_j m[b,j,p];  scores[b] = max_j prob_j;  labels[b] = the first arg-max, or neu_idx when
+ *   scores[b] < threshold (compared in fp32).
+ * feats [B,h,w,C] channels-last as the region grid is stored, contiguous, fp32 or (feats_f16 = 1) _Float16 - read as
+ * they are: no im2col buffer, no padded copy, no up-cast copy.  packed: the conv weights as isc_senti_det_pack wrote
+ * them.  conv_b[i] [C >> (i+1)]; senti_w [k, C >> n_convs], senti_b [k]; fc_w[l] [k,k] row-major (out, in), fc_b[l] [k].
+ * The convolutions are implicit GEMMs on the split-f16 engine (row (b h + y) w + x, contraction over 9 taps x Cin,
+ * tap-major; three v_mfma_f32_16x16x32_f16 terms, the 2^-11 weight applied once): operand domain |x| < 65504.  A tap
+ * outside the image's own grid reads a zeroed line of the workspace - exact zeros, whatever the neighbouring image holds;
+ * every output row of image b depends on image b alone.  f16 features are their own hi plane: the result equals the call
+ * on the up-cast values bit for bit.
+ * Route per conv layer, chosen on the host from the tile count (64 x 128 tiles): one workgroup per tile with bias (and
+ * ReLU behind the last layer) in the kernel, or - few tiles - the contraction split over `ksplit` workgroups per tile, raw
+ * partial tiles to slabs of the workspace and a reduce kernel that sums them in ascending order and adds the bias.
+ * ksplit: 0 = auto, n >= 1 forces n (clamped to the layer's 9 Cin / 32 chunks).  No atomics anywhere: two calls give the
+ * same bits.  A non-finite logit raises the numerics status word non-finite vocabulary logits raise
+ * (ISC_STATUS_NONFINITE_STATS) and its label is neu_idx.
+ * One memset node + n_convs .. 2 n_convs + 1 launches on `stream`; no allocation, no host read: capturable.
+ * Shapes: every conv's Cin = C >> i a multiple of 32, 1 <= n_convs <= 4, 0 <= n_fcs <= 4, 1 <= k <= 8, 0 <= neu_idx < k,
+ * 1 <= h w <= ISC_SENTI_DET_MAX_HW (the k maps of an image stay in LDS: 8 x 1024 floats), B h w <= 2^22: anything else
+ * ISC_E_SHAPE; a workspace under isc_senti_det_workspace_bytes(B, h, w, C, n_convs, ksplit) ISC_E_WORKSPACE; feats, packed,
+ * workspace, conv_out or a conv bias not 16-byte aligned ISC_E_ALIGN - all before any launch, nothing is written then.
+ * conv_out (optional, [B h w, C >> n_convs]): the post-ReLU activations, for tests. */
+#define ISC_SENTI_DET_MAX_CONVS 4
+#define ISC_SENTI_DET_MAX_FCS 4
+#define ISC_SENTI_DET_MAX_HW 1024
+/* isc_senti_det_launches(kind): launches so far, per kind (host-atomic, read-only; -1 for an unknown kind) */
+#define ISC_SENTI_DET_KIND_DIRECT 0     /* conv, one workgroup per tile */
+#define ISC_SENTI_DET_KIND_SPLIT 1      /* conv, contraction split over workgroups */
+#define ISC_SENTI_DET_KIND_REDUCE 2     /* slab reduce behind a split conv */
+#define ISC_SENTI_DET_KIND_TAIL 3       /* 1x1 conv, pooling, FCs, softmax, decision */
+#define ISC_SENTI_DET_KIND_PACK 4       /* weight pack, one per conv layer */
+#define ISC_SENTI_DET_KIND_F16 5        /* conv launches (of either route) that read _Float16 rows natively */
+#define ISC_SENTI_DET_KINDS 6
+typedef struct {
+    const void *feats;
+    int32_t feats_f16, B, h, w, C, n_convs, n_fcs, k, neu_idx, ksplit;
+    float threshold;
+    int32_t _pad;
+    const void *packed;
+    const float *conv_b[ISC_SENTI_DET_MAX_CONVS];
+    const float *senti_w, *senti_b;
+    const float *fc_w[ISC_SENTI_DET_MAX_FCS], *fc_b[ISC_SENTI_DET_MAX_FCS];
+    void *workspace;
+    int64_t workspace_bytes;
+    float *logits, *maps;
+    int64_t *labels;
+    float *scores;
+    float *conv_out;
+} isc_senti_det_problem;
+/* bytes of the packed weights: per conv layer i the hi/lo planes (layout: isc_seg.A_hi) of [C >> (i+1), 9 (C >> i)] with
+ * k = (ky 3 + kx) Cin + ci, layer after layer; 0 for a shape the library refuses */
+int64_t isc_senti_det_pack_bytes(int C, int n_convs);
+/* conv_w_host: HOST array of n_convs device pointers [Cout, Cin, 3, 3] fp32 contiguous; one launch per layer.  The
+ * weights are frozen: once per weight version. */
+int isc_senti_det_pack(const float *const *conv_w_host, int C, int n_convs, void *packed, void *stream);
+int64_t isc_senti_det_workspace_bytes(int B, int h, int w, int C, int n_convs, int ksplit);
+int isc_senti_det_fwd(const isc_senti_det_problem *prob_host, void *stream);
+long long isc_senti_det_launches(int kind);
+
 /* Power-of-two gradient scale for a backward sweep whose contractions run on the split-f16 engine: out4[0..1] = { S, 1/S },
  * S = 2^k with max |x| over the given tensors (HOST arrays of device pointers / element counts, <= ISC_SCALE_SRC_MAX)
  * brought into [2^-4, 2^-3); S = 1 when they are all zero.  out4[2..3] are state words of the multi-workgroup reduction:

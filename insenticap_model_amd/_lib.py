@@ -161,6 +161,21 @@ class SentClsProblem(C.Structure):
                    C.c_void_p) + [('workspace_bytes', C.c_int64)] + _f('logits weights pred reward feats', C.c_void_p))
 
 
+SENTI_DET_MAX_CONVS = SENTI_DET_MAX_FCS = 4
+SENTI_DET_MAX_HW = 1024
+SENTI_DET_KINDS = ('direct', 'split', 'reduce', 'tail', 'pack', 'f16')      # isc_senti_det_launches(kind index)
+
+
+class SentiDetProblem(C.Structure):
+    """isc_senti_det_problem: the frozen image-sentiment detector's forward (csrc/senti_det.hip)."""
+    _fields_ = ([('feats', C.c_void_p)] + _f('feats_f16 B h w C n_convs n_fcs k neu_idx ksplit', C.c_int32) +
+                [('threshold', C.c_float), ('_pad', C.c_int32), ('packed', C.c_void_p),
+                 ('conv_b', C.c_void_p * SENTI_DET_MAX_CONVS)] + _f('senti_w senti_b', C.c_void_p) +
+                [('fc_w', C.c_void_p * SENTI_DET_MAX_FCS), ('fc_b', C.c_void_p * SENTI_DET_MAX_FCS),
+                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64)] +
+                _f('logits maps labels scores conv_out', C.c_void_p))
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -286,6 +301,11 @@ SIGNATURES = {
     'isc_sent_cls_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'isc_sent_cls_fwd': (C.c_int, [C.POINTER(SentClsProblem), C.c_void_p]),
     'isc_sent_cls_launches': (C.c_longlong, []),
+    'isc_senti_det_pack_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'isc_senti_det_pack': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'isc_senti_det_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_senti_det_fwd': (C.c_int, [C.POINTER(SentiDetProblem), C.c_void_p]),
+    'isc_senti_det_launches': (C.c_longlong, [C.c_int]),
     'isc_grad_scale': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
     'isc_splitk_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'isc_h3_weights_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),

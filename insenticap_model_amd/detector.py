@@ -93,6 +93,22 @@ class Detector(nn.Module):
     def native_sentence_classifier(self, on):
         self.sent_senti_cls.enable_native(on)
 
+    @property
+    def native_sentiment_detector(self):
+        """True: the frozen image-sentiment detector runs on the library's kernels (helper_nets.SentimentDetector.native:
+        implicit-GEMM convolutions on the split-f16 engine) and reads float16 features as they are - the image labels of an
+        iteration and the label in front of `sample`'s beam search; default False: stock torch ops on an fp32 copy."""
+        return bool(self.senti_detector.native)
+
+    @native_sentiment_detector.setter
+    def native_sentiment_detector(self, on):
+        self.senti_detector.enable_native(on)
+
+    def _detector_input(self, feats):
+        """What the image detector is handed: with its native forward on, the features as they are (float16 rows are read
+        natively; should the call fall to the torch code - exact-fp32 engine - the module up-casts them itself)."""
+        return feats if self.senti_detector.native else _helper_input(feats)
+
     def enable_data_parallel(self, group=None, broadcast=True):
         """Data-parallel RL training over the ranks of `group` (default process group; backend nccl = RCCL over xGMI,
         gloo in tests).  The reference is single-device; under DP every rank runs `forward` on ITS shard of the fact /
@@ -369,6 +385,11 @@ class Detector(nn.Module):
                 cap._warn_out_of_domain('non-finite values in a roll-out')
                 del stats_it[:]
                 with ops.exact_fp32_engine():
+                    if self.senti_detector.native and (data_type == 'fact' or not training):
+                        # the flagged batch's image labels came from the split-f16 convolutions (a non-finite logit
+                        # reads `neutral`): recomputed here, on the torch path, they also replace what the label
+                        # cache took from that batch
+                        senti_labels = self._image_sentiments(fns, att_feats, refresh=True)
                     run_iteration(True, lambda k, v: stats_it.append((k, v)))
             for k, v in stats_it:
                 add(k, v)
@@ -390,17 +411,18 @@ class Detector(nn.Module):
         that reuses names, features edited in place - or construct with cache_image_sentiments = False."""
         self._senti_cache, self._senti_cache_key = {}, None
 
-    def _image_sentiments(self, fns, att_feats):
+    def _image_sentiments(self, fns, att_feats, refresh=False):
+        """refresh: compute the labels anew and overwrite the cached ones (no cache hit is taken)."""
         if not self.cache_image_sentiments:
-            return self.senti_detector.sample(_helper_input(att_feats), self.senti_threshold)[0].detach()
+            return self.senti_detector.sample(self._detector_input(att_feats), self.senti_threshold)[0].detach()
         key = (self.senti_threshold, tuple(att_feats.shape[1:]), att_feats.dtype) + \
             tuple((q.data_ptr(), q._version) for q in self.senti_detector.parameters())
         if key != self._senti_cache_key:                 # weights reloaded / threshold changed
             self._senti_cache, self._senti_cache_key = {}, key
         cache = self._senti_cache
-        if all(fn in cache for fn in fns):
+        if not refresh and all(fn in cache for fn in fns):
             return ops.upload([cache[fn] for fn in fns], torch.int64, att_feats.device)
-        labels = self.senti_detector.sample(_helper_input(att_feats), self.senti_threshold)[0].detach()
+        labels = self.senti_detector.sample(self._detector_input(att_feats), self.senti_threshold)[0].detach()
         for fn, lab in zip(fns, labels.tolist()):
             cache[fn] = lab
         return labels
@@ -411,7 +433,7 @@ class Detector(nn.Module):
         att_feats = att_feats.unsqueeze(0)
         # the label stays on the device until the search is queued: the category name (a host read) is looked up behind the
         # search's own read-back instead of draining the device between the two (tools/eval_loop_probe.py)
-        senti_label, _, _ = self.senti_detector.sample_device(_helper_input(att_feats), self.senti_threshold)
+        senti_label, _, _ = self.senti_detector.sample_device(self._detector_input(att_feats), self.senti_threshold)
         captions, _ = self.captioner.sample(fc_feats, att_feats, sentis_tensor, senti_label, beam_size,
                                             decoding_constraint, self.max_seq_len)
         return captions, self.senti_detector.names(senti_label)

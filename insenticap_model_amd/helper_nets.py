@@ -6,7 +6,8 @@ self_critical/utils.py:120-151), their dense conv / LSTM work goes to MIOpen / r
 stock torch ops, and only their *outputs* (sentiment labels, per-token reward weights) enter the
 hand-written kernels.  Parameter names and shapes equal the reference's, so its checkpoints load
 (train_rl.py:42-53,88-97).  The sentence classifier has an opt-in native forward on the library's own kernels
-(`enable_native`, include/insenticap_hip.h: isc_sent_cls_fwd); off by default.
+(`enable_native`, include/insenticap_hip.h: isc_sent_cls_fwd), the image detector one on the library's implicit-GEMM
+convolution (isc_senti_det_fwd); both off by default.
 
 * SentimentDetector            /root/reference/models/sentiment_detector.py:5-64
 * SentenceSentimentClassifier  /root/reference/models/sent_senti_cls.py:6-72
@@ -19,6 +20,8 @@ class SentimentDetector(nn.Module):
     """Image-level sentiment from the [B,h,w,F] feature grid: two 3x3 convs (F -> F/2 -> F/4, no
     non-linearity in between), dropout, ReLU, a 1x1 conv to one map per sentiment, global average
     pooling and `sentiment_fcs_num` small linear layers."""
+    native = False          # (class default: an instance unpickled from before the switch existed reads it)
+    _native_pack = None
 
     def __init__(self, sentiment_categories, settings):
         super().__init__()
@@ -35,8 +38,55 @@ class SentimentDetector(nn.Module):
         self.senti_conv = nn.Conv2d(ch, k, 1)
         self.global_pool = nn.AdaptiveAvgPool2d(1)
         self.output = nn.Sequential(*[nn.Linear(k, k) for _ in range(settings['sentiment_fcs_num'])])
+        # Opt-in: the eval-mode forward on the library's own kernels (isc_senti_det_fwd: the 3x3 convolutions as implicit
+        # GEMMs on the split-f16 engine over the channels-last grid as it is stored - fp32 or float16 - and one tail
+        # kernel per image) instead of stock torch ops (permute, vendor-library fp32 convolutions, a dozen small
+        # launches).  enable_native() / `native = True`.
+        self.native = False
+        self._native_pack = None        # (key, packed conv weights): rebuilt when a parameter's (data_ptr, _version) moves
+
+    def enable_native(self, on=True):
+        self.native = bool(on)
+        return self
+
+    def native_params(self):
+        """The parameters in state_dict order: (weight, bias) of every 3x3 conv, of senti_conv and of every FC layer."""
+        mods = [m for m in self.convs if isinstance(m, nn.Conv2d)] + [self.senti_conv] + list(self.output)
+        return [t for m in mods for t in (m.weight, m.bias)]
+
+    def native_active(self, features):
+        """Whether forward(features) takes the native path now: the flag is on, eval mode (no dropout), the tensors live
+        on the ROCm device, nothing asks for a gradient of a parameter, and the split-f16 engine is in use (mode 0 /
+        `ops.exact_fp32_engine()` - the engine that serves features beyond |x| < 65504 - runs the torch code, as do
+        train mode, CPU tensors and the detector's own training)."""
+        if not self.native or self.training or not features.is_cuda:
+            return False
+        params = self.native_params()
+        if params[0].device != features.device or features.dtype not in (torch.float32, torch.float16):
+            return False
+        if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in params)):
+            return False
+        from . import ops
+        return ops.h3_mode() != 0
+
+    def forward_native(self, features, threshold=0, ksplit=0):
+        """The native forward in full: -> (logits [B,k], sentiment map [B,h,w], labels [B] int64 - neu_idx where the
+        largest probability is under `threshold` -, largest probabilities [B]).  features [B,h,w,F] fp32 or float16."""
+        from . import ops
+        params = [p.detach() for p in self.native_params()]
+        key = tuple((q.data_ptr(), q._version) for q in params)
+        if self._native_pack is None or self._native_pack[0] != key:
+            n_convs = sum(1 for m in self.convs if isinstance(m, nn.Conv2d))
+            self._native_pack = (key, ops.senti_det_pack(params[0:2 * n_convs:2]))
+        with torch.no_grad():
+            return ops.senti_det_fwd(params, features.contiguous(), threshold, self.neu_idx,
+                                     packed=self._native_pack[1], ksplit=ksplit)
 
     def forward(self, features):
+        if self.native_active(features):
+            return self.forward_native(features)[:2]
+        if features.dtype != self.senti_conv.weight.dtype:
+            features = features.to(self.senti_conv.weight.dtype)
         x = self.convs(features.permute(0, 3, 1, 2))
         maps = self.senti_conv(x)                                   # [B,k,h,w]
         logits = self.output(maps.mean(dim=(2, 3)))                 # GAP + FCs
@@ -50,6 +100,9 @@ class SentimentDetector(nn.Module):
         nothing is read back, so the caller can queue its next step (the beam search takes the labels as a tensor) before
         the host looks at them (`names`)."""
         self.eval()
+        if self.native_active(features):
+            _, maps, labels, scores = self.forward_native(features, senti_threshold)
+            return labels, maps, scores
         logits, maps = self.forward(features)
         scores, labels = logits.softmax(dim=-1).max(dim=-1)
         labels = torch.where(scores < senti_threshold, torch.full_like(labels, self.neu_idx), labels)

@@ -1012,6 +1012,111 @@ def sent_cls_fwd(params, tokens, lens_i32, labels=None, pad_to=None, want_feats=
     return (logits, weights, pred, reward) + ((feats,) if want_feats else ())
 
 
+_SENTI_DET_WS = {}          # (device index, stream, B, h, w, C, n_convs, ksplit) -> workspace of isc_senti_det_fwd
+
+
+def senti_det_launches(kind=None):
+    """Launches of the image-sentiment detector's kernels so far: a dict over _lib.SENTI_DET_KINDS ('direct', 'split',
+    'reduce', 'tail', 'pack', 'f16' = conv launches that read float16 rows natively), or one kind's count."""
+    lib = _lib.load()
+    if kind is not None:
+        return lib.isc_senti_det_launches(_lib.SENTI_DET_KINDS.index(kind))
+    return {name: lib.isc_senti_det_launches(i) for i, name in enumerate(_lib.SENTI_DET_KINDS)}
+
+
+def _senti_det_split_params(params):
+    """params: the module's tensors in state_dict order - (weight, bias) of every 3x3 conv, of the 1x1 senti_conv and of
+    every FC layer -> (conv weights, conv biases, senti_w, senti_b, fc weights, fc biases)."""
+    params = list(params)
+    assert len(params) >= 4 and len(params) % 2 == 0, 'weight / bias pairs: convs, senti_conv, fcs'
+    n_convs = 0
+    while 2 * n_convs < len(params) and params[2 * n_convs].dim() == 4 and tuple(params[2 * n_convs].shape[2:]) == (3, 3):
+        n_convs += 1
+    assert n_convs >= 1 and len(params) >= 2 * n_convs + 2
+    conv_w, conv_b = params[0:2 * n_convs:2], params[1:2 * n_convs:2]
+    senti_w, senti_b = params[2 * n_convs], params[2 * n_convs + 1]
+    fc_w, fc_b = params[2 * n_convs + 2::2], params[2 * n_convs + 3::2]
+    return conv_w, conv_b, senti_w, senti_b, fc_w, fc_b
+
+
+def senti_det_pack(conv_weights):
+    """The detector's conv weights ([Cout, Cin, 3, 3] fp32, layer after layer) as the split-f16 planes isc_senti_det_fwd
+    reads (isc_senti_det_pack: tap-major K = 9 Cin, one launch per layer) -> a uint8 tensor.  The weights are frozen: pack
+    once per weight version."""
+    lib = _lib.load()
+    conv_weights = list(conv_weights)
+    require_device(*conv_weights)
+    Cf, n = conv_weights[0].shape[1], len(conv_weights)
+    for i, t in enumerate(conv_weights):
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'conv weights: contiguous fp32'
+        if tuple(t.shape) != ((Cf >> i) // 2, Cf >> i, 3, 3):
+            raise _lib.HipLibraryError('isc_senti_det_pack failed: ISC_E_SHAPE (conv %d is %s)' % (i, tuple(t.shape)))
+    nbytes = int(lib.isc_senti_det_pack_bytes(Cf, n))
+    packed = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=conv_weights[0].device)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in conv_weights])
+    check(lib.isc_senti_det_pack(ptrs, Cf, n, packed.data_ptr(), stream()), 'isc_senti_det_pack')
+    return packed
+
+
+def senti_det_fwd(params, feats, threshold, neu_idx, *, packed=None, ksplit=0, out=None, want_conv_out=False,
+                  workspace=None):
+    """The frozen image-sentiment detector's forward (isc_senti_det_fwd): `params` = the module's tensors in state_dict
+    order ((weight, bias) of every 3x3 conv, of senti_conv and of every FC layer), feats [B,h,w,C] contiguous, fp32 or
+    float16 (read natively).  packed: senti_det_pack(conv weights) - built here when None.  ksplit: 0 = the library
+    chooses each conv layer's route, n >= 1 forces n workgroups per tile.  -> (logits [B,k], maps [B,h,w], labels [B]
+    int64, scores [B][, conv_out [B*h*w, C >> n_convs]]).  `out` = (logits, maps, labels, scores) to write into.  The
+    workspace is kept per (device, stream, geometry) except inside a graph capture (hand `workspace`, or a fresh one is
+    drawn from the capture's pool).  A shape the library does not take raises (ISC_E_SHAPE); nothing is launched or
+    written then."""
+    lib = _lib.load()
+    conv_w, conv_b, senti_w, senti_b, fc_w, fc_b = _senti_det_split_params(params)
+    require_device(feats, *params)
+    register_status_words(feats.device)                 # (a non-finite logit flags the numerics status)
+    assert feats.dim() == 4 and feats.is_contiguous() and feats.dtype in (torch.float32, torch.float16)
+    for t in list(params):
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'detector parameters: contiguous fp32'
+    B, h, w, Cf = feats.shape
+    n_convs, n_fcs, k = len(conv_w), len(fc_w), senti_w.shape[0]
+    dev = feats.device
+    if n_convs > _lib.SENTI_DET_MAX_CONVS or n_fcs > _lib.SENTI_DET_MAX_FCS or conv_w[0].shape[1] != Cf or \
+            senti_w.numel() != k * (Cf >> n_convs):
+        raise _lib.HipLibraryError('isc_senti_det_fwd failed: ISC_E_SHAPE (unsupported size)')
+    CL = Cf >> n_convs
+    if out is None:
+        out = (torch.empty(B, k, dtype=torch.float32, device=dev), torch.empty(B, h, w, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.float32, device=dev))
+    logits, maps, labels, scores = out
+    assert logits.shape == (B, k) and maps.shape == (B, h, w) and labels.shape == (B,) and scores.shape == (B,)
+    assert labels.dtype == torch.int64 and all(t.is_contiguous() for t in out)
+    need = int(lib.isc_senti_det_workspace_bytes(B, h, w, Cf, n_convs, int(ksplit)))   # (0: refused - said below)
+    if need and packed is None:
+        packed = senti_det_pack(conv_w)
+    if workspace is None:
+        if torch.cuda.is_current_stream_capturing():
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        else:
+            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, B, h, w, Cf, n_convs, int(ksplit))
+            workspace = _SENTI_DET_WS.get(key)
+            if workspace is None:
+                workspace = _SENTI_DET_WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    conv_out = torch.empty(B * h * w, CL, dtype=torch.float32, device=dev) if want_conv_out else None
+    p = _lib.SentiDetProblem()
+    p.feats, p.feats_f16 = feats.data_ptr(), int(feats.dtype == torch.float16)
+    p.B, p.h, p.w, p.C, p.n_convs, p.n_fcs, p.k = B, h, w, Cf, n_convs, n_fcs, k
+    p.neu_idx, p.ksplit, p.threshold = int(neu_idx), int(ksplit), float(threshold)
+    p.packed = packed.data_ptr() if packed is not None else workspace.data_ptr()   # (refused shapes: never read)
+    for i, t in enumerate(conv_b):
+        p.conv_b[i] = t.data_ptr()
+    p.senti_w, p.senti_b = senti_w.data_ptr(), senti_b.data_ptr()
+    for i, (tw, tb) in enumerate(zip(fc_w, fc_b)):
+        p.fc_w[i], p.fc_b[i] = tw.data_ptr(), tb.data_ptr()
+    p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    p.logits, p.maps, p.labels, p.scores = logits.data_ptr(), maps.data_ptr(), labels.data_ptr(), scores.data_ptr()
+    p.conv_out = ptr(conv_out)
+    check(lib.isc_senti_det_fwd(C.byref(p), stream()), 'isc_senti_det_fwd')
+    return (logits, maps, labels, scores) + ((conv_out,) if want_conv_out else ())
+
+
 __all__ = [n for n in dir() if n.endswith('_fwd') or n.endswith('_problem')] + [
     'RolloutStep', 'rollout_finalize', 'rollout_finalize_filtered', 'beam_topk', 'logsoftmax_apply', 'require_device']
 
