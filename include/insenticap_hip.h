@@ -643,6 +643,12 @@ int isc_set_h3v(int on);
  * 2 = for forward launches as well (tests: a forward launch otherwise keeps one summation order at every batch size),
  * 0 = never.  Returns the previous value. */
 int isc_set_h3_ksplit(int on);
+/* Tile geometry of a vocabulary launch (isc_vocab_fwd / isc_step_fwd) once the large split-f16 kernels have it: 0
+ * (default) = auto, which is the 128-row tile at every size (the 256-row tile the other epilogues take from 224 tiles on
+ * measures 3-7 % slower at [16384 x 10000 x 512]: its statistics epilogue is not overlapped by a second workgroup),
+ * 128 / 256 = that geometry at any tile count (tests, A/B runs).  A row's pmax / psum / pidx and logits are the same bits
+ * under either geometry.  Any other value changes nothing.  Returns the previous value. */
+int isc_set_h3_vocab_tile(int rows);
 
 /* Top-k + candidate merge of one beam step in ONE launch (captioner.py:390-411), from the tile statistics and tile
  * candidates isc_rows_step_fwd left: per row the log-softmax normaliser is folded from (pmax, psum), the row's top-`beam`

@@ -216,6 +216,7 @@ SIGNATURES = {
     'isc_set_rows_scan_regions': (C.c_int, [C.c_int]),
     'isc_set_h3v': (C.c_int, [C.c_int]),
     'isc_set_h3_ksplit': (C.c_int, [C.c_int]),
+    'isc_set_h3_vocab_tile': (C.c_int, [C.c_int]),
     'isc_copy_multi': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     'isc_rows_launches': (C.c_longlong, []),
     'isc_beam_select': (C.c_int, [C.POINTER(BeamSelectArgs), C.c_void_p]),

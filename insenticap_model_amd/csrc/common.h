@@ -281,19 +281,19 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += isc_dpp<ISC_DPP_HALF_MIRROR>(v);
     return v + isc_dpp<ISC_DPP_MIRROR>(v);
 }
-// (value, index) arg-max over each 16-lane row; ties resolve to the smaller index
-__device__ __forceinline__ void row16_argmax(float &v, int &i) {
-#define ISC_ARGMAX_STEP(OV, OI)                                        \
-    {                                                                  \
-        const float ov = (OV);                                         \
-        const int oi = (OI);                                           \
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }         \
-    }
-    ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_XOR1>(v), isc_dpp<ISC_DPP_XOR1>(i))
-    ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_XOR2>(v), isc_dpp<ISC_DPP_XOR2>(i))
-    ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_HALF_MIRROR>(v), isc_dpp<ISC_DPP_HALF_MIRROR>(i))
-    ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_MIRROR>(v), isc_dpp<ISC_DPP_MIRROR>(i))
-#undef ISC_ARGMAX_STEP
+// all-reduce over each 16-lane row / each 32-lane half with any commutative, associative combine op(a, b) of T = float
+// or int (max, min, or ...): the DPP operand folds into the VALU instruction, one instruction per step
+template <class T, class Op>
+__device__ __forceinline__ T row16_reduce(T v, Op op) {
+    v = op(v, isc_dpp<ISC_DPP_XOR1>(v));
+    v = op(v, isc_dpp<ISC_DPP_XOR2>(v));
+    v = op(v, isc_dpp<ISC_DPP_HALF_MIRROR>(v));
+    return op(v, isc_dpp<ISC_DPP_MIRROR>(v));
+}
+template <class T, class Op>
+__device__ __forceinline__ T half_reduce(T v, Op op) {
+    v = row16_reduce(v, op);
+    return op(v, isc_swz16(v));
 }
 
 // 64-lane butterfly reductions (wavefront = 64 on CDNA4).

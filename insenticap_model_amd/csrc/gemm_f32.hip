@@ -166,7 +166,7 @@ __device__ __forceinline__ void map_tile(const DevLaunch &L, int &pi, int &tm, i
 // ---- epilogues, shared by the tile shapes ---------------------------------------------------------
 // Where the accumulators of a wave's 32-row fragment sit, for the two MFMA shapes in use.  A lane holds NR rows x NC
 // column blocks of CW columns; element (e, j) is tile row frow0 + row(e, lane), tile column fcol0 + CW j + col(lane).
-// The lanes that share a row (equal row(e, .)) reduce over it with row_sum / row_argmax.
+// The lanes that share a row (equal row(e, .)) reduce over it with row_sum / row_reduce.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // v_mfma_f32_32x32x*: f32x16 acc[NC]; one register index is one output row per half-wave, and the row's 32 NC columns
 // sit on the 32 lanes of that half - reductions are 4 DPP steps inside the 16-lane rows + one swizzle across them.
@@ -179,7 +179,8 @@ struct Frag32 {
     template <int NC>
     static __device__ __forceinline__ void set(f32x16 (&acc)[NC], int e, int j, float v) { acc[j][e] = v; }
     static __device__ __forceinline__ float row_sum(float v) { return half_sum(v); }
-    static __device__ __forceinline__ void row_argmax(float &v, int &i) { half_argmax(v, i); }
+    template <class T, class Op>
+    static __device__ __forceinline__ T row_reduce(T v, Op op) { return half_reduce(v, op); }
 };
 // v_mfma_f32_16x16x32_f16 (the large split-f16 tiles): f32x4 acc[2][NC], 2 row blocks x NC column blocks of 16 x 16; a
 // row's 16 NC columns sit on the 16 lanes of ONE DPP row - reductions are four DPP steps, no swizzle.
@@ -192,39 +193,52 @@ struct Frag16 {
     template <int NC>
     static __device__ __forceinline__ void set(f32x4 (&acc)[2][NC], int e, int j, float v) { acc[e >> 2][j][e & 3] = v; }
     static __device__ __forceinline__ float row_sum(float v) { return row16_sum(v); }
-    static __device__ __forceinline__ void row_argmax(float &v, int &i) { row16_argmax(v, i); }
+    template <class T, class Op>
+    static __device__ __forceinline__ T row_reduce(T v, Op op) { return row16_reduce(v, op); }
 };
 
 // Vocabulary epilogue of one fragment (layout F, NC column blocks), straight from the registers (no LDS round trip).
 // Per row: max / arg-max / sum exp(x - max) over the wave's CW * NC columns.  frow0 = tile-relative first row of the
 // fragment, fcol0 = tile-relative first column.  WN == 1 (the wave spans the 128-column tile) writes the tile
 // statistics directly, otherwise they go to smx/ssm/six[wn][BM] for the cross-wave combine.
-template <class F, int NC, int WN, int BM, class Acc>
-__device__ __forceinline__ void epi_vocab_frag(const DevProb &P, Acc &acc, int frow0, int fcol0, int wn, int lane,
-                                               int row0, int col0, int tn, float *smem) {
-    constexpr int NR = F::NR;
+// Straight-line code but for the guards of the stores.  EDGE = false: every column of the fragment is inside N, and the
+// column-validity selects (cok) fold away - only the last column tile of a launch pays them.
+// The arg-max is the one of `if (x > m) { m = x; i = column; }` over ascending columns: the smallest column among
+// the `==`-equal maxima, never a NaN, and the bits of THAT element (a row whose maxima are +0 and -0 reports the sign
+// of the first).  In a lane it is that chain, as selects; across the lanes of a row it is three integer reductions -
+// the maximum of the lanes' maxima as ordered keys, the smallest index among the lanes that hold it, the bits of the
+// lane that has this index (every other lane contributes 0; in a row of -inf / NaN alone every lane holds -inf and the
+// index 2^31 - 1) - of one DPP-operand instruction per step, where a (value, index) butterfly compares and selects
+// three times per step.  (Integer, because fmaxf on a lane exchange's result first quiets both operands.)
+template <bool EDGE, class F, int NC, int WN, int BM, class Acc>
+__device__ __forceinline__ void epi_vocab_frag_cols(const DevProb &P, Acc &acc, int frow0, int fcol0, int wn, int lane,
+                                                    int row0, int col0, int tn, float *smem) {
+    constexpr int NR = F::NR, NONE = 0x7fffffff;
     const int M = P.M, N = P.N, gn0 = col0 + fcol0 + F::col(lane);
     float bv[NC];
     bool cok[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-        cok[j] = gn0 + j * F::CW < N;
-        bv[j] = cok[j] ? P.bias0[gn0 + j * F::CW] : 0.f;
+        cok[j] = !EDGE || gn0 + j * F::CW < N;
+        bv[j] = P.bias0[cok[j] ? gn0 + j * F::CW : N - 1];                   // (a padded column's logit is -inf below)
     }
-    // Phased over the fragment's rows, every phase straight-line code: the dependent reduction chains of the rows
-    // interleave instead of running one after the other between per-row branches.
+    // Phased over the fragment's rows: the dependent reduction chains of the rows interleave.
     float mx[NR], sm[NR];
     int ix[NR];
 #pragma unroll
     for (int e = 0; e < NR; ++e) {
-        mx[e] = -INFINITY;
-        ix[e] = 0x7fffffff;
+        float m = -INFINITY;
+        int i = NONE;
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             const float x = cok[j] ? F::get(acc, e, j) + bv[j] : -INFINITY;
             F::set(acc, e, j, x);                                            // acc now holds the logits
-            if (x > mx[e]) { mx[e] = x; ix[e] = gn0 + j * F::CW; }           // j ascending => smaller column wins ties
+            const bool gt = x > m;                                           // j ascending => smaller column wins ties
+            m = gt ? x : m;
+            i = gt ? gn0 + j * F::CW : i;
         }
+        mx[e] = m;
+        ix[e] = i;
     }
     if (P.C) {
 #pragma unroll
@@ -238,8 +252,22 @@ __device__ __forceinline__ void epi_vocab_frag(const DevProb &P, Acc &acc, int f
             }
         }
     }
+    {
+        // a lane's maximum (never a NaN) as the int that orders as the float does; -0 counts as +0, as `==` has it
+        const auto key = [](float v) {
+            const int b = __float_as_int(v + 0.f);
+            return b ^ ((b >> 31) & 0x7fffffff);
+        };
+        const auto imax_ = [](int a, int b) { return a > b ? a : b; };
+        const auto imin_ = [](int a, int b) { return a < b ? a : b; };
+        const auto or_ = [](int a, int b) { return a | b; };
 #pragma unroll
-    for (int e = 0; e < NR; ++e) F::row_argmax(mx[e], ix[e]);
+        for (int e = 0; e < NR; ++e) {
+            const int mine = ix[e], own = key(mx[e]), top = F::row_reduce(own, imax_);
+            ix[e] = F::row_reduce(own == top ? mine : NONE, imin_);
+            mx[e] = __int_as_float(F::row_reduce(mine == ix[e] ? __float_as_int(mx[e]) : 0, or_));
+        }
+    }
 #pragma unroll
     for (int e = 0; e < NR; ++e) {
         sm[e] = 0.f;
@@ -268,6 +296,15 @@ __device__ __forceinline__ void epi_vocab_frag(const DevProb &P, Acc &acc, int f
             }
         }
     }
+}
+
+template <class F, int NC, int WN, int BM, class Acc>
+__device__ __forceinline__ void epi_vocab_frag(const DevProb &P, Acc &acc, int frow0, int fcol0, int wn, int lane,
+                                               int row0, int col0, int tn, float *smem) {
+    if (col0 + fcol0 + F::CW * NC <= P.N)                                     // (uniform over the wave)
+        epi_vocab_frag_cols<false, F, NC, WN, BM>(P, acc, frow0, fcol0, wn, lane, row0, col0, tn, smem);
+    else
+        epi_vocab_frag_cols<true, F, NC, WN, BM>(P, acc, frow0, fcol0, wn, lane, row0, col0, tn, smem);
 }
 
 // accumulator fragment -> Cs[BM][LDC] (row-major tile image in LDS)
@@ -2696,6 +2733,14 @@ static int gemv_run(DevLaunch &L, int kmax, hipStream_t st) {
 // (tests / A-B runs: 0 keeps long contractions on few large tiles in one slice of K)
 static std::atomic<int> g_h3_ksplit{1};
 extern "C" int isc_set_h3_ksplit(int on) { return g_h3_ksplit.exchange(on < 0 ? 0 : (on > 2 ? 2 : on)); }
+// Tile geometry of a vocabulary launch on the large split-f16 kernels: 0 = auto (launch_h3_big: 128 rows, which measures
+// faster), 128 / 256 = that many rows whatever the tile count (tests / A-B runs; a row's statistics are the same bits
+// either way).  Any other value changes nothing.  Returns the previous value.
+static std::atomic<int> g_h3_vocab_tile{0};
+extern "C" int isc_set_h3_vocab_tile(int rows) {
+    if (rows == 0 || rows == 128 || rows == 256) return g_h3_vocab_tile.exchange(rows);
+    return g_h3_vocab_tile.load();
+}
 
 // The reduce launch behind a K-split launch, by epilogue: sums the slabs in fixed order and finishes the outputs.
 // (every split - the fp32 32-row tile's, the skinny and the large split-f16 kernels' - writes linear-epilogue slabs)
@@ -2928,13 +2973,18 @@ static const H3WEntry *h3w_find(const H3WScope *sc, const DevProb &p, int transp
 }
 
 // 256-row tiles when they fill the chip, else the 128-row kernel.  The vocabulary projection stays on the 128-row
-// kernel: its epilogue (per-row softmax statistics, ~3k VALU instructions per wave) is as long as its 16-chunk main
-// loop, and only a second, out-of-phase workgroup on the CU overlaps the two (174 us on the 256-row tile vs 162 us;
-// a persistent form of the 256-row kernel that put the next tile's first two chunks in flight before the epilogue
-// measured 173 us: what is exposed is the epilogue's own VALU time, 8-10 us per tile, not the workgroup turnover).
+// kernel unless isc_set_h3_vocab_tile(256) sends it to the other: a one-workgroup-per-CU kernel runs the statistics
+// epilogue of its eight waves with the matrix pipe idle, where a second, out-of-phase workgroup on the CU overlaps it
+// with the main loop.  Measured at the headline shape [16384 x 10000 x 512], five alternating runs of the benchmark:
+// 128 rows 456-459 us per launch, 256 rows 472-489 us (with the branchy epilogue of before, ~1300 VALU + 340 SALU
+// instructions per wave against ~860 + 40 now: 128 rows 477-483 us; [4096 x 9984 x 512] in the lab then 162 us
+// against 174 us, and 173 us for a persistent 256-row form with the next tile's first two chunks in flight before the
+// epilogue - what is exposed is the epilogue's own VALU time, not the workgroup turnover).
 template <int EPI>
 static int launch_h3_big(DevLaunch &L, hipStream_t st) {
-    if (EPI != EPI_VOCAB && count_tiles(L, 256, 128) >= 224) {        // (round 3: 160 - the three h-projections on this kernel - measured the same)
+    bool rows256 = count_tiles(L, 256, 128) >= 224;                   // (round 3: 160 - the three h-projections on this kernel - measured the same)
+    if (EPI == EPI_VOCAB) rows256 = g_h3_vocab_tile.load() == 256;    // 0 (auto) = 128 rows: see above
+    if (rows256) {
         ++g_h3x_launches;
         finish_tiling(L, 3);
         return launch_h3_tile<H3Tile256, EPI>(L, st);

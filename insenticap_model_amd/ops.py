@@ -632,6 +632,15 @@ def set_h3v(on):
     return _lib.load().isc_set_h3v(int(on))
 
 
+def set_h3_vocab_tile(rows):
+    """Tile geometry of the classifier launches of the large split-f16 kernels (isc_set_h3_vocab_tile): 0 = auto (128
+    rows), 128 / 256 = that many rows per tile at any tile count.  Returns the previous value."""
+    rows = int(rows)
+    if rows not in (0, 128, 256):
+        raise ValueError('set_h3_vocab_tile: 0 (auto), 128 or 256, got %r' % rows)
+    return _lib.load().isc_set_h3_vocab_tile(rows)
+
+
 def rows_step_supported(plan):
     return bool(_lib.load().isc_rows_step_supported(C.byref(plan)))
 
