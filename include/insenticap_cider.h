@@ -43,6 +43,35 @@ int isc_cider_score(const isc_cider *h, const int64_t *hyp, int64_t n_hyp, int64
                     int64_t hyp_stride, const int64_t *ref_tokens, const int64_t *ref_cap_off,
                     const int64_t *ref_img_off, double *scores_out, int n_threads);
 
+/* ---- What the device scorer (isc_cider_dev_score, include/insenticap_hip.h) reads, prepared here.
+ * The n-gram key, its hash and the 16-byte slot {uint64 key, double log_df} are defined once, in
+ * csrc/cider_key.h: field j (16 bits) of a key holds id_j + 1, unused fields hold 0, key 0 = empty
+ * slot.  Every id must lie in [0, 65534]: where one does not, the functions below return -3. */
+
+/* log(number of images), the maximal order n and sigma of the scorer.  0, or -1 on a null pointer. */
+int isc_cider_params(const isc_cider *h, double *ref_len, int *n, double *sigma);
+
+/* The document frequencies as an open-addressing array with linear probing: home slot
+ * isc_cider_hash(key) & (capacity - 1), log_df = log(max(1, df)) (the `d` of counts2vec).
+ * isc_cider_table_capacity: the smallest power of two >= max(16, 2 x isc_cider_num_ngrams).
+ * isc_cider_table_fill writes `capacity` slots; any power of two above the number of n-grams is
+ * taken (tests fill a tighter table).  0, -1 null pointer, -2 bad capacity, -3 id out of range. */
+int64_t isc_cider_table_capacity(const isc_cider *h);
+int isc_cider_table_fill(const isc_cider *h, void *slots, int64_t capacity);
+
+/* Cooked captions: for each of n_caps captions (flattened as above) its distinct n-grams in the
+ * scorer's first-occurrence order - all 1-grams by position, then the 2-grams, ... - as keys[] and
+ * the tf-idf vals[] of counts2vec, back to back over the captions; ord_off[5 c + o] = index of
+ * caption c's first entry of order o + 1, ord_off[5 c + 4] = one past its last; norms[4 c + o]
+ * and length[c] as counts2vec forms them - the values the host scorer uses, bit for bit.
+ * isc_cider_cook_size returns the number of entries, isc_cider_cook_fill fills and returns it;
+ * negative: -1 null pointer, -2 more than 2^31 - 1 entries, -3 id out of range. */
+int64_t isc_cider_cook_size(const isc_cider *h, const int64_t *tokens, const int64_t *cap_off,
+                            int64_t n_caps);
+int64_t isc_cider_cook_fill(const isc_cider *h, const int64_t *tokens, const int64_t *cap_off,
+                            int64_t n_caps, uint64_t *keys, double *vals, int32_t *ord_off,
+                            double *norms, double *length);
+
 #ifdef __cplusplus
 }
 #endif

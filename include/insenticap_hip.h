@@ -875,6 +875,31 @@ int isc_reward_loss_bwd(const float *seq_masks, const float *reward, int B, int 
 int isc_group_reward(const double *scores, int I, int n, const float *cls_reward, double cls_flag, int T,
                      float *reward, double *stats4, void *stream);
 
+/* CIDEr-D of N hypotheses on the device: scores[r] = what isc_cider_score (include/insenticap_cider.h) gives for row r -
+ * the mean over the references of the row's image, x 10 - fp64 throughout.  All pointers are device memory.
+ *   hyp [N, T] int64, contiguous: the raw roll-out rows (a leading sos_id is dropped, the row is cut at its first eos_id,
+ *     eos_id is appended: L <= T + 1 words); row r belongs to image r / row_div (1: one row per image; n: the grouped
+ *     roll-out's n rows per image).  Ids in [0, 65534] (csrc/cider_key.h: 16-bit key fields) - an id is never an index,
+ *     so a larger one reads nothing out of bounds, it only aliases another id.
+ *   table [capacity] 16-byte slots {uint64 key, double log(max(1, df))}, key 0 = empty, capacity a power of two, home
+ *     slot isc_cider_hash(key) & (capacity - 1), linear probing (isc_cider_table_fill).  A lookup makes at most
+ *     `capacity` probes: a table without an empty slot answers "absent", it cannot spin.
+ *   the batch's cooked references (isc_cider_cook_fill) as CSR arrays: image i owns captions img_cap_off[i] ..
+ *     img_cap_off[i + 1] (n_img + 1 entries, every image at least one caption - the caller's check, as the host scorer's
+ *     -2), caption c owns the entries ord_off[5 c] .. ord_off[5 c + 4] of ref_keys / ref_vals (its k-grams of order o + 1
+ *     start at ord_off[5 c + o]), ref_norms [4 c + o], ref_length [c].
+ *   n, sigma, ref_len: isc_cider_params.
+ * One wave64 per hypothesis, one lane per position, four hypotheses per workgroup; no workspace, no LDS, no atomics;
+ * every sum runs in the host scorer's order (first-occurrence order within an order, references ascending), so two
+ * launches give the same bits and only exp, sqrt and the division can differ from the host's.  One launch, no host
+ * read: capturable.
+ * N < 1, T outside [1, 63], row_div < 1, n outside [1, 4], a capacity that is no power of two >= 2, or fewer than
+ * ceil(N / row_div) images: ISC_E_SHAPE, nothing is launched or written. */
+int isc_cider_dev_score(const int64_t *hyp, int64_t N, int T, int row_div, const void *table, int64_t capacity,
+                        const int32_t *img_cap_off, int64_t n_img, const int32_t *ord_off, const double *ref_norms,
+                        const double *ref_length, const uint64_t *ref_keys, const double *ref_vals, int n, double sigma,
+                        double ref_len, int64_t sos_id, int64_t eos_id, double *scores, void *stream);
+
 /* Log-softmax backward with the criteria's gradient handed over SPARSE: XECriterion (captioner.py:427-440) and the
  * REINFORCE gather (captioner.py:336) touch one column per (caption, step) row, so their d log-prob is `coef[m]` at
  * column `ids[m]` - up to ISC_SPARSE_MAX such (ids, coef) pairs (HOST arrays of device pointers to [M] vectors, rows

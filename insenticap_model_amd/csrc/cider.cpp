@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/insenticap_cider.h"
+#include "cider_key.h"
 
 namespace {
 
@@ -221,4 +222,89 @@ extern "C" int isc_cider_score(const isc_cider *h, const int64_t *hyp, int64_t n
         for (auto &t : th) t.join();
     }
     return 0;
+}
+
+// ------------------------------------------------------------------ exports for the device scorer (csrc/cider_dev.hip)
+// The device scores a hypothesis from two things the host prepares with the functions above: the document-frequency
+// table as an open-addressing array of (key, log df) slots, and the references "cooked" - their distinct n-grams in
+// first-occurrence order with the tf-idf values, norms and length counts2vec forms.  Keys and hash: cider_key.h.
+static bool key_of(const NGram &g, uint64_t *key) {
+    for (int j = 0; j < g.n; ++j)
+        if (g.w[j] < 0 || g.w[j] > ISC_CIDER_MAX_ID) return false;
+    *key = isc_cider_key(g.w, g.n);
+    return true;
+}
+
+extern "C" int isc_cider_params(const isc_cider *h, double *ref_len, int *n, double *sigma) {
+    if (!h || !ref_len || !n || !sigma) return -1;
+    *ref_len = h->ref_len; *n = h->n; *sigma = h->sigma;
+    return 0;
+}
+
+extern "C" int64_t isc_cider_table_capacity(const isc_cider *h) {
+    if (!h) return -1;
+    int64_t cap = 16;
+    while (cap < 2 * (int64_t)h->df.size()) cap <<= 1;
+    return cap;
+}
+
+extern "C" int isc_cider_table_fill(const isc_cider *h, void *slots_out, int64_t capacity) {
+    isc_cider_slot *slots = (isc_cider_slot *)slots_out;
+    if (!h || !slots) return -1;
+    if (capacity < 2 || (capacity & (capacity - 1)) || capacity <= (int64_t)h->df.size()) return -2;
+    const uint64_t mask = (uint64_t)capacity - 1;
+    for (int64_t i = 0; i < capacity; ++i) slots[i].key = 0, slots[i].log_df = 0.0;
+    for (const auto &kv : h->df) {
+        uint64_t key;
+        if (!key_of(kv.first, &key)) return -3;
+        uint64_t s = isc_cider_hash(key) & mask;
+        while (slots[s].key) s = (s + 1) & mask;          // (an empty slot exists: capacity > number of n-grams)
+        slots[s].key = key;
+        slots[s].log_df = std::log(std::fmax(1.0, kv.second));
+    }
+    return 0;
+}
+
+// One pass over `n_caps` captions; with keys == nullptr only the number of entries is counted.
+static int64_t cook(const isc_cider *h, const int64_t *tokens, const int64_t *cap_off, int64_t n_caps, uint64_t *keys,
+                    double *vals, int32_t *ord_off, double *norms, double *length) {
+    Scratch S;
+    int64_t at = 0;
+    for (int64_t c = 0; c < n_caps; ++c) {
+        normalise(tokens + cap_off[c], cap_off[c + 1] - cap_off[c], h->sos, h->eos, S.words);
+        precook(S.words, h->n, S.ref);
+        const int64_t m = (int64_t)S.ref.keys.size();
+        if (at + m > 0x7fffffffLL) return -2;
+        if (keys) {
+            h->counts2vec(S.ref, S.vr);
+            int32_t *off = ord_off + 5 * c;
+            int order = 0;                                // precook lists all 1-grams, then all 2-grams, ...
+            off[0] = (int32_t)at;
+            for (int64_t i = 0; i < m; ++i) {
+                if (!key_of(S.ref.keys[i], keys + at + i)) return -3;
+                while (order < S.ref.keys[i].n - 1) off[++order] = (int32_t)(at + i);
+                vals[at + i] = S.vr.val[i];
+            }
+            while (order < 4) off[++order] = (int32_t)(at + m);
+            for (int o = 0; o < 4; ++o) norms[4 * c + o] = S.vr.norm[o];
+            length[c] = S.vr.length;
+        } else {
+            uint64_t key;
+            for (int64_t i = 0; i < m; ++i)
+                if (!key_of(S.ref.keys[i], &key)) return -3;
+        }
+        at += m;
+    }
+    return at;
+}
+
+extern "C" int64_t isc_cider_cook_size(const isc_cider *h, const int64_t *tokens, const int64_t *cap_off, int64_t n_caps) {
+    if (!h || !tokens || !cap_off || n_caps < 0) return -1;
+    return cook(h, tokens, cap_off, n_caps, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int64_t isc_cider_cook_fill(const isc_cider *h, const int64_t *tokens, const int64_t *cap_off, int64_t n_caps,
+                                       uint64_t *keys, double *vals, int32_t *ord_off, double *norms, double *length) {
+    if (!h || !tokens || !cap_off || n_caps < 0 || !keys || !vals || !ord_off || !norms || !length) return -1;
+    return cook(h, tokens, cap_off, n_caps, keys, vals, ord_off, norms, length);
 }

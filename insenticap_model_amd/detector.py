@@ -5,8 +5,9 @@ and `sample(...)`.
 One RL iteration = sampled roll-out (with REINFORCE gradients) + greedy roll-out (baseline) +
 CIDEr-D and classifier rewards + XE pass (ss_prob 0.5) + seq2seq pass (ss_prob 0.25) + backward +
 clamp(0.1) + Adam (decoder.py:65-167).  The decoder work runs on the HIP kernels through
-`Captioner`; CIDEr-D runs in the native host library; the two frozen helper nets are stock
-PyTorch-ROCm modules (helper_nets.py).
+`Captioner`; CIDEr-D runs in the native host library (or, `device_cider = True`, on the device in the
+eager iterations: rewards.DeviceCiderD); the two frozen helper nets are stock PyTorch-ROCm modules
+(helper_nets.py).
 
 `rl_samples_per_image = n` > 1 (opt-in): n sampled captions per image from one grouped differentiable roll-out, the
 baseline of a sample = the mean CIDEr-D of the image's other n - 1 samples (no greedy roll-out), the reward formed on
@@ -23,8 +24,8 @@ from .helper_nets import SentenceSentimentClassifier, SentimentDetector
 from .optim import clip_gradient
 from .train import run_on_side_stream
 from .ops import OutOfDomain
-from .rewards import (RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward,
-                      group_self_critical_scores)
+from .rewards import (CIDER_DEV_MAX_T, RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward,
+                      get_self_critical_reward_device, group_self_critical_scores)
 
 
 def _helper_input(feats):
@@ -72,6 +73,41 @@ class Detector(nn.Module):
         # repeated), no greedy roll-out, the reward built on the device from the uploaded scores (isc_group_reward).
         # Such iterations run the eager sequence; evaluation keeps the n = 1 path; not built under a process group.
         self.rl_samples_per_image = 1
+        # True (opt-in): the iterations that run the eager sequence - evaluation, train_graphs = False, rollout_constraints,
+        # rl_samples_per_image > 1, the exact-engine retry - take the fact reward from the device CIDEr-D scorer
+        # (rewards.DeviceCiderD, isc_cider_dev_score): the token matrices are not copied to the host and the host scorer
+        # is not called; grouped iterations hand the device scores straight to isc_group_reward.  The device twin of
+        # `ciderd_scorer` is built on first use and rebuilt when set_ciderd_scorer replaces the host scorer; a vocabulary
+        # above 65535 ids or max_seq_len > 63 warns once and keeps the host scorer.  Graph-served iterations
+        # (train_graph.RLTrainGraph) are untouched: they keep the host scorer, whose time they already hide under the
+        # greedy roll-out and the XE graphs.
+        self.device_cider = False
+        self._cider_dev, self._cider_dev_warned = None, False
+
+    def _device_ciderd(self, device, T):
+        """The device twin of `ciderd_scorer` for rows of T tokens, or None: the flag is off, or this vocabulary / length
+        is outside what the device scorer takes (warned once; the host scorer serves)."""
+        if not self.device_cider or device.type != 'cuda':
+            return None
+        host = self.ciderd_scorer
+        twin = self._cider_dev
+        if twin is None or twin[0] is not host or twin[1] != device:
+            try:
+                twin = (host, device, host.to_device(device, self.captioner.vocab_size))
+            except ValueError as e:
+                twin = (host, device, None)
+                self._warn_device_cider(str(e))
+            self._cider_dev = twin
+        if twin[2] is not None and T > CIDER_DEV_MAX_T:
+            self._warn_device_cider('rows of %d tokens (the device scorer takes %d)' % (T, CIDER_DEV_MAX_T))
+            return None
+        return twin[2]
+
+    def _warn_device_cider(self, why):
+        if not self._cider_dev_warned:
+            import warnings
+            warnings.warn('device_cider: %s - the host CIDEr-D scorer is used' % why)
+            self._cider_dev_warned = True
 
     @property
     def rl_samples_per_image(self):
@@ -275,13 +311,22 @@ class Detector(nn.Module):
                 # now, enqueue the XE / seq2seq forward passes, and only then wait: the host scores the captions
                 # while the device works through the two unrolls.  The order of the captioner calls - hence of
                 # every random draw - is the reference's; only host-side waiting moved.
-                host_sample = torch.empty(sample_captions.shape, dtype=sample_captions.dtype).pin_memory()
-                if not grouped:
-                    host_greedy = torch.empty(greedy_captions.shape, dtype=greedy_captions.dtype).pin_memory()
+                # device_cider: CIDEr-D runs on the device instead (rewards.DeviceCiderD) - the token matrices stay where
+                # they are; the batch's cooked references depend on no device result and are uploaded now, behind the
+                # roll-outs already queued.  ('senti' has no CIDEr-D term: with the flag on nothing reads host tokens.)
+                dev_cider = self._device_ciderd(device, sample_captions.shape[1]) if data_type == 'fact' else None
+                host_tokens = dev_cider is None and not (self.device_cider and data_type != 'fact')
+                if dev_cider is not None:
+                    ref_pack = dev_cider.pack_refs([ground_truth[fn] for fn in fns], keys=list(fns))
+                if host_tokens:
+                    host_sample = torch.empty(sample_captions.shape, dtype=sample_captions.dtype).pin_memory()
+                    if not grouped:
+                        host_greedy = torch.empty(greedy_captions.shape, dtype=greedy_captions.dtype).pin_memory()
                 host_lens = torch.empty(seq_masks.shape[0], dtype=torch.int32).pin_memory()
-                host_sample.copy_(sample_captions, non_blocking=True)
-                if not grouped:
-                    host_greedy.copy_(greedy_captions, non_blocking=True)
+                if host_tokens:
+                    host_sample.copy_(sample_captions, non_blocking=True)
+                    if not grouped:
+                        host_greedy.copy_(greedy_captions, non_blocking=True)
                 host_lens.copy_(seq_masks.sum(dim=-1).type(torch.int32), non_blocking=True)
                 copied = torch.cuda.Event()
                 copied.record()
@@ -338,7 +383,9 @@ class Detector(nn.Module):
                     # the I*n float64 CIDEr-D scores are all that is uploaded ('senti': zeros - the classifier term
                     # alone, as in the reference); baseline, advantage, the sum with the classifier term and the four
                     # logged means are formed on the device: isc_group_reward, two launches
-                    if data_type == 'fact':
+                    if dev_cider is not None:            # (scored where the rows are: nothing is uploaded)
+                        scores = dev_cider.score(sample_captions, ref_pack, row_div=n_rl)
+                    elif data_type == 'fact':
                         scores = ops.upload(torch.from_numpy(group_self_critical_scores(
                             host_sample.numpy(), fns, ground_truth, self.ciderd_scorer, n_rl)), torch.float64, device)
                     else:
@@ -349,6 +396,9 @@ class Detector(nn.Module):
                     put('fact_reward', stats4[1])            # the mean advantage: 0 up to rounding by construction
                     put('cls_reward', stats4[2])
                     put('all_rewards', stats4[3])
+                elif dev_cider is not None:
+                    fact_reward = get_self_critical_reward_device(sample_captions, greedy_captions, ref_pack, dev_cider)
+                    put('fact_reward', share(fact_reward[:, 0].mean(), w_rows))
                 elif data_type == 'fact':
                     fact_reward = get_self_critical_reward(
                         host_sample.numpy(), host_greedy.numpy(), fns, ground_truth, cap.sos_id, cap.eos_id,

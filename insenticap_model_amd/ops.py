@@ -1293,6 +1293,34 @@ def group_reward(scores, n, cls_reward, cls_flag, T, reward=None, stats4=None):
     return reward, stats4
 
 
+def cider_dev_score(hyps, row_div, table, img_cap_off, ord_off, ref_norms, ref_length, ref_keys, ref_vals, n, sigma,
+                    ref_len, sos_id, eos_id, out=None):
+    """isc_cider_dev_score: CIDEr-D of the raw roll-out rows `hyps` int64 [N, T] on the device, row r against the cooked
+    references of image r // row_div -> float64 [N].  table int64 [capacity, 2] (the 16-byte slots), img_cap_off int32
+    [I + 1], ord_off int32 [C, 5], ref_norms float64 [C, 4], ref_length float64 [C], ref_keys int64 [E] (the keys' bits),
+    ref_vals float64 [E] - rewards.DeviceCiderD builds them.  T > 63 raises (ISC_E_SHAPE); nothing is written then."""
+    require_device(hyps, table, img_cap_off, ord_off, ref_norms, ref_length, ref_keys, ref_vals, out)
+    assert hyps.dtype == torch.int64 and hyps.dim() == 2 and hyps.is_contiguous()
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 2 and table.is_contiguous()
+    assert img_cap_off.dtype == torch.int32 and img_cap_off.dim() == 1 and img_cap_off.is_contiguous()
+    C_ = ref_length.numel()
+    assert ord_off.dtype == torch.int32 and tuple(ord_off.shape) == (C_, 5) and ord_off.is_contiguous()
+    assert ref_norms.dtype == torch.float64 and tuple(ref_norms.shape) == (C_, 4) and ref_norms.is_contiguous()
+    assert ref_length.dtype == torch.float64 and ref_length.is_contiguous()
+    assert ref_keys.dtype == torch.int64 and ref_vals.dtype == torch.float64 and ref_keys.shape == ref_vals.shape
+    assert ref_keys.dim() == 1 and ref_keys.is_contiguous() and ref_vals.is_contiguous()
+    N, T = hyps.shape
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=hyps.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == N
+    check(_lib.load().isc_cider_dev_score(hyps.data_ptr(), N, T, int(row_div), table.data_ptr(), table.shape[0],
+                                          img_cap_off.data_ptr(), img_cap_off.numel() - 1, ord_off.data_ptr(),
+                                          ref_norms.data_ptr(), ref_length.data_ptr(), ref_keys.data_ptr(),
+                                          ref_vals.data_ptr(), int(n), float(sigma), float(ref_len), int(sos_id),
+                                          int(eos_id), out.data_ptr(), stream()), 'isc_cider_dev_score')
+    return out
+
+
 def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=None):
     lib = _lib.load()
     M, H = c.shape

@@ -6,6 +6,8 @@
   (include/insenticap_cider.h) instead of the pure-Python scorer (~1,240 hypotheses/s/core there,
   the first wall of the RL step once decoding is fast: SURVEY 8(a-19)).
 * `get_cls_reward` (utils.py:120-151) - sentence-sentiment-classifier reward.
+* `DeviceCiderD` / `get_self_critical_reward_device` - the same CIDEr-D scores formed on the device
+  (isc_cider_dev_score) from the host library's table and cooked references; opt-in (Detector.device_cider).
 """
 import ctypes as C
 import os
@@ -50,6 +52,17 @@ def _load_cider():
     lib.isc_cider_score.restype = C.c_int
     lib.isc_cider_score.argtypes = [C.c_void_p, i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p,
                                     C.POINTER(C.c_double), C.c_int]
+    # what the device scorer reads (DeviceCiderD)
+    lib.isc_cider_params.restype = C.c_int
+    lib.isc_cider_params.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    lib.isc_cider_table_capacity.restype = C.c_int64
+    lib.isc_cider_table_capacity.argtypes = [C.c_void_p]
+    lib.isc_cider_table_fill.restype = C.c_int
+    lib.isc_cider_table_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.isc_cider_cook_size.restype = C.c_int64
+    lib.isc_cider_cook_size.argtypes = [C.c_void_p, i64p, i64p, C.c_int64]
+    lib.isc_cider_cook_fill.restype = C.c_int64
+    lib.isc_cider_cook_fill.argtypes = [C.c_void_p, i64p, i64p, C.c_int64] + [C.c_void_p] * 5
     _cider = lib
     return lib
 
@@ -138,6 +151,142 @@ class CiderD:
             raise RuntimeError('isc_cider_score failed (%d)' % rc)
         return out
 
+    # ---- what the device scorer reads (DeviceCiderD; csrc/cider_key.h defines the key, the hash and the slot)
+    def device_params(self):
+        """(ref_len = log(#images), n, sigma) of the scorer."""
+        ref_len, n, sigma = C.c_double(), C.c_int(), C.c_double()
+        if self._lib.isc_cider_params(self._h, C.byref(ref_len), C.byref(n), C.byref(sigma)) != 0:
+            raise RuntimeError('isc_cider_params failed')
+        return ref_len.value, n.value, sigma.value
+
+    def device_table(self, capacity=None):
+        """The document frequencies as an open-addressing array (linear probing) of CIDER_SLOT records: key, log(max(1,
+        df)); key 0 = empty.  `capacity`: a power of two above num_ngrams, default the production size (>= 2 x num_ngrams).
+        ValueError when an n-gram holds an id above 65534 (a key field is 16 bits)."""
+        cap = int(capacity) if capacity is not None else self._lib.isc_cider_table_capacity(self._h)
+        tab = np.empty(cap, dtype=CIDER_SLOT)
+        rc = self._lib.isc_cider_table_fill(self._h, tab.ctypes.data, cap)
+        if rc == -3:
+            raise ValueError('the device CIDEr-D table needs every token id <= %d' % CIDER_MAX_ID)
+        if rc != 0:
+            raise RuntimeError('isc_cider_table_fill failed (%d)' % rc)
+        return tab
+
+    def cook_refs(self, captions):
+        """The captions of ONE list cooked for the device: (keys uint64 [E], vals float64 [E], ord_off int32 [C, 5], norms
+        float64 [C, 4], length float64 [C]) - per caption its distinct n-grams in the scorer's first-occurrence order, grouped
+        by order, with counts2vec's tf-idf values, norms and length (the host scorer's own numbers, bit for bit)."""
+        toks, cap_off, _ = _flatten([captions])
+        n_caps = len(cap_off) - 1
+        E = self._lib.isc_cider_cook_size(self._h, _p(toks), _p(cap_off), n_caps)
+        if E == -3:
+            raise ValueError('the device CIDEr-D scorer needs every token id <= %d' % CIDER_MAX_ID)
+        if E < 0:
+            raise RuntimeError('isc_cider_cook_size failed (%d)' % E)
+        keys, vals = np.empty(E, dtype=np.uint64), np.empty(E, dtype=np.float64)
+        ord_off = np.empty((n_caps, 5), dtype=np.int32)
+        norms, length = np.empty((n_caps, 4), dtype=np.float64), np.empty(n_caps, dtype=np.float64)
+        got = self._lib.isc_cider_cook_fill(self._h, _p(toks), _p(cap_off), n_caps, keys.ctypes.data, vals.ctypes.data,
+                                            ord_off.ctypes.data, norms.ctypes.data, length.ctypes.data)
+        if got != E:
+            raise RuntimeError('isc_cider_cook_fill failed (%d)' % got)
+        return keys, vals, ord_off, norms, length
+
+    def to_device(self, device, vocab_size):
+        """The device twin of this scorer (DeviceCiderD): the table is uploaded once.  ValueError when vocab_size > 65535."""
+        return DeviceCiderD(self, device, vocab_size)
+
+
+CIDER_SLOT = np.dtype([('key', '<u8'), ('log_df', '<f8')])      # isc_cider_slot (csrc/cider_key.h): 16 bytes
+CIDER_MAX_ID = 65534                                             # ISC_CIDER_MAX_ID: a key field holds id + 1 in 16 bits
+CIDER_DEV_MAX_T = 63                                             # isc_cider_dev_score: one lane per word, L <= T + 1 <= 64
+
+
+class CiderRefPack:
+    """The cooked references of one batch on the device (DeviceCiderD.pack_refs): views into ONE uploaded buffer."""
+    __slots__ = ('n_img', 'buffer', 'img_cap_off', 'ord_off', 'norms', 'length', 'keys', 'vals')
+
+
+class DeviceCiderD:
+    """CIDEr-D on the device (isc_cider_dev_score): the twin of a host `CiderD`, whose table and cooked references it reads.
+    One wave per hypothesis, the host scorer's order of sums: scores agree with CiderD.score_arrays to the last bits of
+    exp / sqrt / division (tests: 1e-12)."""
+
+    def __init__(self, host, device, vocab_size):
+        if int(vocab_size) > CIDER_MAX_ID + 1:
+            raise ValueError('the device CIDEr-D scorer packs an id into 16 bits: vocab_size <= %d, got %d'
+                             % (CIDER_MAX_ID + 1, vocab_size))
+        self.host, self.device = host, torch.device(device)
+        self.ref_len, self.n, self.sigma = host.device_params()
+        tab = host.device_table()
+        self.table = torch.from_numpy(tab.view(np.int64).reshape(-1, 2)).to(self.device)      # [capacity, 2], once
+        self._cache = {}
+
+    def pack_refs(self, ref_caption_lists, keys=None):
+        """The batch's references cooked (per image, cached by `keys` - image ids - as CiderD.flatten_refs caches),
+        concatenated and uploaded as one buffer through pinned memory, non-blocking.  Depends on no device result: it can be
+        issued while a roll-out is still running.  An image without references raises, as the host scorer does."""
+        cooked = []
+        for i, caps in enumerate(ref_caption_lists):
+            k = None if keys is None else keys[i]
+            c = None if k is None else self._cache.get(k)
+            if c is None:
+                if len(caps) == 0:
+                    raise RuntimeError('CIDEr-D: image %d of the batch has no reference caption' % i)
+                c = self.host.cook_refs(caps)
+                if k is not None:
+                    self._cache[k] = c
+            cooked.append(c)
+        n_img = len(cooked)
+        caps_per = np.asarray([len(c[4]) for c in cooked], dtype=np.int64)
+        ents_per = np.asarray([len(c[0]) for c in cooked], dtype=np.int64)
+        n_cap, n_ent = int(caps_per.sum()), int(ents_per.sum())
+        if n_ent > 0x7fffffff:
+            raise RuntimeError('CIDEr-D: more than 2^31 - 1 reference n-grams in one batch')
+        ent_base = np.concatenate([[0], np.cumsum(ents_per)[:-1]])
+        # one pinned buffer, every region 8-byte aligned: keys, vals, norms, length | ord_off, img_cap_off (int32)
+        sizes = [8 * n_ent, 8 * n_ent, 32 * n_cap, 8 * n_cap, (20 * n_cap + 7) // 8 * 8, (4 * (n_img + 1) + 7) // 8 * 8]
+        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+        host = torch.empty(offs[-1], dtype=torch.uint8)
+        if self.device.type == 'cuda':
+            host = host.pin_memory()
+        raw = host.numpy()
+
+        def region(j, dtype, count):
+            return raw[offs[j]:offs[j] + count * np.dtype(dtype).itemsize].view(dtype)
+        np.concatenate([c[0] for c in cooked], out=region(0, np.uint64, n_ent))
+        np.concatenate([c[1] for c in cooked], out=region(1, np.float64, n_ent))
+        np.concatenate([c[3] for c in cooked], out=region(2, np.float64, 4 * n_cap).reshape(n_cap, 4))
+        np.concatenate([c[4] for c in cooked], out=region(3, np.float64, n_cap))
+        ord_off = region(4, np.int32, 5 * n_cap).reshape(n_cap, 5)
+        np.concatenate([c[2] for c in cooked], out=ord_off)
+        ord_off += np.repeat(ent_base, caps_per).astype(np.int32)[:, None]
+        img_cap = region(5, np.int32, n_img + 1)
+        img_cap[0] = 0
+        np.cumsum(caps_per, out=img_cap[1:])
+        dev = host.to(self.device, non_blocking=True)
+
+        def view(j, dtype, count, size):
+            return dev[offs[j]:offs[j] + count * size].view(dtype)
+        p = CiderRefPack()
+        p.n_img, p.buffer = n_img, dev
+        p.keys, p.vals = view(0, torch.int64, n_ent, 8), view(1, torch.float64, n_ent, 8)
+        p.norms, p.length = view(2, torch.float64, 4 * n_cap, 8).view(n_cap, 4), view(3, torch.float64, n_cap, 8)
+        p.ord_off = view(4, torch.int32, 5 * n_cap, 4).view(n_cap, 5)
+        p.img_cap_off = view(5, torch.int32, n_img + 1, 4)
+        return p
+
+    def score(self, hyps, pack, row_div=1, out=None):
+        """hyps: int64 [N, T] raw roll-out rows on the device, row r of image r // row_div of `pack` -> float64 [N] on the
+        device.  T > 63 raises (the caller keeps the host scorer for such rows)."""
+        from . import ops
+        if hyps.shape[0] != pack.n_img * int(row_div):
+            raise ValueError('CIDEr-D: %d rows for %d images x %d rows per image' % (hyps.shape[0], pack.n_img, row_div))
+        hyps = hyps if hyps.is_contiguous() else hyps.contiguous()
+        return ops.cider_dev_score(hyps, row_div, self.table, pack.img_cap_off, pack.ord_off, pack.norms, pack.length,
+                                   pack.keys, pack.vals, self.n, self.sigma, self.ref_len, self.host.sos, self.host.eos,
+                                   out=out)
+
 
 def get_ciderd_scorer(split_captions, sos_token, eos_token):
     """utils.py:38-53: `split_captions` = {split: {fn: [[ids], ...]}}; document frequencies over all images."""
@@ -170,6 +319,17 @@ def get_self_critical_reward(sample_captions, greedy_captions, fns, ground_truth
     flat = scorer.flatten_refs([ground_truth[fn] for fn in fns], keys=list(fns))
     scores = scorer.score_arrays(sample_captions, None, flat) - scorer.score_arrays(greedy_captions, None, flat)
     return np.repeat(scores[:, np.newaxis], sample_captions.shape[1], 1)
+
+
+def get_self_critical_reward_device(sample_captions, greedy_captions, pack, dev_scorer):
+    """get_self_critical_reward on the device: token matrices [B, T] on the device, `pack` = dev_scorer.pack_refs(...) of
+    the batch -> float32 [B, T] on the device: (CIDEr-D(sample) - CIDEr-D(greedy)) in fp64, rounded to float32, repeated
+    over T - the host form followed by `.astype('float32')`."""
+    if not isinstance(dev_scorer, DeviceCiderD):
+        raise Exception('do not support this scorer: %s' % type(dev_scorer))
+    assert sample_captions.shape == greedy_captions.shape
+    scores = dev_scorer.score(sample_captions, pack) - dev_scorer.score(greedy_captions, pack)
+    return scores.to(torch.float32).unsqueeze(1).repeat(1, sample_captions.shape[1])
 
 
 def _check_group(n, rows, images=None):
