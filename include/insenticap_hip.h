@@ -366,7 +366,8 @@ long long isc_rollout_finalize_launches(void);   /* launches so far (tests: isc_
  * sampling_logprobs (optional, [B,T]) receives log(w_token / kept mass).  Everything else - seq, seq_masks, <EOS>, the
  * `alive` counters, raw_tokens, xt_next - as isc_rollout_finalize with sample_u (required here, as are the logits;
  * `forced` must be null).  One launch, no host read; integer (fixed-point) mass sums: bit-repeatable.
- * temperature must be finite and > 0, top_k >= 0, top_p > 0: otherwise ISC_E_SHAPE before any launch. */
+ * temperature must be finite and > 0, top_k >= 0, top_p > 0: otherwise ISC_E_SHAPE before any launch.  With xt_next set,
+ * emb / xt_next / xt_add not 16-byte aligned -> ISC_E_ALIGN before any launch, as isc_rollout_finalize. */
 typedef struct {
     float temperature;
     int32_t top_k;
@@ -389,7 +390,8 @@ int isc_rollout_finalize_filtered(const isc_rollout_step *s_host, const isc_samp
  * struct; min_len alone once t >= min_len) is served by the two entry points above, bit for bit.
  * Before any launch: a null struct -> ISC_E_NULL; n_ban outside [0, 8], an id outside [0, V), min_len outside [0, T],
  * `forced` together with any constraint, V <= n_ban + 2 (no allowed id left), n_tile != ceil(V / 128) -> ISC_E_SHAPE;
- * logits missing (every constrained form reads them) -> ISC_E_NULL. */
+ * logits missing (every constrained form reads them) -> ISC_E_NULL; with xt_next set, emb / xt_next / xt_add not 16-byte
+ * aligned -> ISC_E_ALIGN, as isc_rollout_finalize. */
 typedef struct {
     int64_t ban_ids[8];
     int32_t n_ban;

@@ -279,10 +279,7 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
             rs.t, rs.logits = t, out[:, t].data_ptr()
             rs.part_max, rs.part_sum, rs.part_idx = S.pm[t].data_ptr(), S.ps[t].data_ptr(), S.pi[t].data_ptr()
             rs.xt_next = S.xt[t + 1].data_ptr() if t + 1 < T else None
-            if tokens_in.get('cons') is not None:     # (token constraints: the draw runs over the allowed ids)
-                ops.rollout_finalize_constrained(rs, tokens_in['cons'])
-            else:
-                ops.rollout_finalize(rs)
+            ops.rollout_finalize_step(rs, tokens_in.get('cons'))     # (constraints: the draw runs over the allowed ids)
             if t + 1 < T:
                 S.tok[t + 1].copy_(seq[:, t])         # it * unfinished, written by this finalize
     _keep_mask(cap, S, L, [masks])

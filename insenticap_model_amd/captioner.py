@@ -1314,14 +1314,7 @@ class Captioner(nn.Module):
                 rs.t = t
                 rs.unfinished = unf[t].data_ptr() if fuse else unfinished.data_ptr()
                 rs.xt_next = None if use_tab else xt[nxt].data_ptr()
-                if cons is not None:
-                    ops.rollout_finalize_constrained(
-                        rs, cons, (filt['temperature'], filt['top_k'], filt['top_p']) if filtered or slp is not None
-                        else None, slp)
-                elif filtered:
-                    ops.rollout_finalize_filtered(rs, filt['temperature'], filt['top_k'], filt['top_p'], slp)
-                else:
-                    ops.rollout_finalize(rs)
+                ops.rollout_finalize_step(rs, cons, filt, slp)
         ops.TIMER.armed = False
         if filt is not None and filt['want_slp']:
             # (default controls: the sampled distribution IS the model's)

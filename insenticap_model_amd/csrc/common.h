@@ -237,7 +237,27 @@ __device__ __forceinline__ void half_argmax(float &v, int &i) {
     ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_HALF_MIRROR>(v), isc_dpp<ISC_DPP_HALF_MIRROR>(i))
     ISC_ARGMAX_STEP(isc_dpp<ISC_DPP_MIRROR>(v), isc_dpp<ISC_DPP_MIRROR>(i))
     ISC_ARGMAX_STEP(isc_swz16(v), isc_swz16(i))
+}
+// The cross-half steps that finish a half reduction, and the whole-wave reductions: every lane gets the result.  The tie
+// rule of the arg-max (the larger value, then the smaller index) is written here and in ISC_ARGMAX_STEP only.
+__device__ __forceinline__ void cross_argmax(float &v, int &i) {
+    ISC_ARGMAX_STEP(__shfl_xor(v, 32, 64), __shfl_xor(i, 32, 64))
+}
 #undef ISC_ARGMAX_STEP
+__device__ __forceinline__ float cross_sum(float v) { return v + __shfl_xor(v, 32, 64); }
+__device__ __forceinline__ void full_argmax(float &v, int &i) {
+    half_argmax(v, i);
+    cross_argmax(v, i);
+}
+__device__ __forceinline__ float full_sum(float v) { return cross_sum(half_sum(v)); }
+
+// What a decode step's finalize does with the chosen token `it` of a row: a finished row feeds <PAD> (id 0: the
+// reference's `it * unfinished`) and the row stays unfinished until it feeds <EOS>.  Returns the next `unfinished`.
+// (Tok: the caller's own integer type - a 32-bit index is selected as one and widened afterwards)
+template <class Tok>
+__device__ __forceinline__ int finalize_advance(int unf, Tok it, long long eos, long long &itm) {
+    itm = unf ? it : 0;
+    return unf && (itm != eos);
 }
 
 // A row's tile statistics folded by one wave (the body of pointwise.hip's fold_row_stats; rows.hip folds with it as well):
@@ -255,16 +275,10 @@ __device__ __forceinline__ bool fold_row_stats_impl(const float *pmax, const flo
         if (v > mx || (v == mx && id < ix)) { mx = v; ix = id; }
     }
     // lane exchanges inside 32-lane halves by DPP, one cross-half swap (same order: value, then the smaller index)
-    half_argmax(mx, ix);
-    {
-        const float ov = __shfl_xor(mx, 32, 64);
-        const int oi = __shfl_xor(ix, 32, 64);
-        if (ov > mx || (ov == mx && oi < ix)) { mx = ov; ix = oi; }
-    }
+    full_argmax(mx, ix);
     float s = 0.f;
     for (int i = lane; i < n_tile; i += 64) s += psum[i] * expf(pmax[i] - mx);
-    s = half_sum(s);
-    S = s + __shfl_xor(s, 32, 64);
+    S = full_sum(s);
     gmax = mx;
     // a row whose maxima are all NaN never satisfied `v > mx`: its index is still the sentinel, and a consumer would
     // gather an embedding row 2^31 rows past the table.  Such a row decodes <PAD> (id 0) and is flagged.

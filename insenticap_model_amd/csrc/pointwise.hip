@@ -287,7 +287,6 @@ struct DevRollout {
     int64_t *raw_tokens;
     const float *emb, *xt_add;
     float *xt_next;
-    int rows_per_wave;
 };
 
 // Inverse-CDF sampling from softmax over one row, in vocabulary order, by one wavefront.  Two levels: the
@@ -350,18 +349,44 @@ __device__ __forceinline__ int sample_two_level(const float *x, float shift, flo
                               [](int) { return false; }, n_tile, V, target, lane);
 }
 
-#define ISC_FIN_ROWS_PER_WAVE 4
-// One wavefront per row, 4 rows per wave, 16 rows per workgroup; the count of still-unfinished rows
-// is reduced inside the workgroup so that the `alive` counter sees one atomic per 16 rows (4096
-// same-address atomics used to dominate this kernel).
-__device__ __forceinline__ int rollout_finalize_row(const DevRollout &R, int b, int lane) {
+// The commit stage of a decode step, the one place where every form of the finalize writes what the step decided: the
+// NT threads that worked on row b hand in its chosen token `it`, its log-probability `lp` (thread 0's counts) and the
+// row's `unfinished` flag as it was read before the step.  Thread 0 stores seq / seq_masks / seq_logprobs / raw_tokens /
+// unfinished, all NT threads stream xt_next = relu(emb[fed token]) (+ xt_add) as float4s.  Returns the row's next flag.
+template <int NT>
+__device__ __forceinline__ int finalize_commit(const DevRollout &R, int b, long long it, float lp, int unf, int tid) {
+    long long itm;
+    const int u2 = finalize_advance(unf, it, R.eos_id, itm);
+    if (tid == 0) {
+        const long long o = (long long)b * R.T + R.t;
+        R.seq_masks[o] = (float)unf;
+        R.seq[o] = itm;
+        R.seq_logprobs[o] = lp;
+        if (R.raw_tokens) R.raw_tokens[o] = it;
+        R.unfinished[b] = u2;
+    }
+    if (R.xt_next) {
+        const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
+        const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
+        float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
+        for (int i = tid; i < (R.W >> 2); i += NT) {
+            float4 v = src[i];
+            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
+            dst[i] = v;
+        }
+    }
+    return u2;
+}
+
+// The plain choice of row b by one wavefront: the forced token, a draw against sample_u, or the arg-max, and the
+// model's log-probability of it.  Stores nothing.
+__device__ __forceinline__ void rollout_choose_row(const DevRollout &R, int b, int lane, long long &it, float &lp) {
     float gmax, S;
     int gidx;
     fold_row_stats(R.part_max + (long long)b * R.n_tile, R.part_sum + (long long)b * R.n_tile,
                    R.part_idx + (long long)b * R.n_tile, R.n_tile, lane, gmax, gidx, S);
     const float logS = logf(S);
-    long long it;
-    float lp;
     if (R.forced) {
         it = R.forced[(long long)b * R.T + R.t];
         lp = (R.logits[(long long)b * R.ld_logits + it] - gmax) - logS;
@@ -376,68 +401,6 @@ __device__ __forceinline__ int rollout_finalize_row(const DevRollout &R, int b, 
     } else {
         it = gidx;
         lp = -logS;  // log_softmax at the arg-max: (x_max - x_max) - log S
-    }
-    const int u = R.unfinished[b];
-    const long long itm = u ? it : 0;  // finished rows feed <PAD> (id 0): `it * unfinished`
-    const int u2 = u && (itm != R.eos_id);
-    if (lane == 0) {
-        const long long o = (long long)b * R.T + R.t;
-        R.seq_masks[o] = (float)u;
-        R.seq[o] = itm;
-        R.seq_logprobs[o] = lp;
-        if (R.raw_tokens) R.raw_tokens[o] = it;
-        R.unfinished[b] = u2;
-    }
-    if (R.xt_next) {
-        const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
-        const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
-        float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
-        for (int i = lane; i < (R.W >> 2); i += 64) {
-            float4 v = src[i];
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-            dst[i] = v;
-        }
-    }
-    return u2;
-}
-
-__global__ __launch_bounds__(256) void rollout_finalize_kernel(const DevRollout R) {
-    __shared__ int cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // the reference `break`s once no row is unfinished (captioner.py:343-344): later steps
-    // leave seq / seq_logprobs / seq_masks at their zero initialisation
-    if (R.alive[R.t] == 0) return;          // block-uniform
-    int alive = 0;
-    for (int i = 0; i < R.rows_per_wave; ++i) {
-        const int b = (blockIdx.x * 4 + wave) * R.rows_per_wave + i;
-        if (b < R.B) alive += rollout_finalize_row(R, b, lane);
-    }
-    if (lane == 0) cnt[wave] = alive;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        if (tot) atomicAdd(&R.alive[R.t + 1], tot);
-    }
-}
-
-// Many rows: sixteen waves per workgroup, ONE row per wave (every row's dependent chain - two strided sweeps, a dozen
-// cross-lane steps, logf, stores - runs at the same time as all the others) and still one `alive` atomic per 16 rows.
-// (Round 3: the four-rows-per-wave form of rounds 1-2 walked its rows one after the other: 16.8 us at B = 4096.)
-__global__ __launch_bounds__(1024) void rollout_finalize_wide_kernel(const DevRollout R) {
-    __shared__ int cnt[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (R.alive[R.t] == 0) return;          // block-uniform
-    const int b = blockIdx.x * 16 + wave;
-    int alive = 0;
-    if (b < R.B) alive = rollout_finalize_row(R, b, lane);
-    if (lane == 0) cnt[wave] = alive;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) tot += cnt[w];
-        if (tot) atomicAdd(&R.alive[R.t + 1], tot);
     }
 }
 
@@ -468,7 +431,10 @@ __device__ __forceinline__ bool con_banned(const int (&ids)[ISC_CON_MAX], int i)
     return hit;
 }
 
-__device__ __forceinline__ int rollout_finalize_con_row(const DevRollout &R, const DevCons &C, int b, int lane) {
+// The constrained choice of row b by one wavefront: the arg-max, or a draw against sample_u, over the allowed ids, and
+// the model's log-probability of it.  Stores nothing.
+__device__ __forceinline__ void rollout_choose_con_row(const DevRollout &R, const DevCons &C, int b, int lane,
+                                                       long long &it, float &lp) {
     const float *pm = R.part_max + (long long)b * R.n_tile, *ps = R.part_sum + (long long)b * R.n_tile;
     const int *pi = R.part_idx + (long long)b * R.n_tile;
     const float *x = R.logits + (long long)b * R.ld_logits;
@@ -494,16 +460,9 @@ __device__ __forceinline__ int rollout_finalize_con_row(const DevRollout &R, con
         int ix = 0x7fffffff;
         if (ok0) { mx = x0; ix = i0; }
         if (ok1 && (x1 > mx || ix == 0x7fffffff)) { mx = x1; ix = i1; }       // (equal values: i0 < i1 stays)
-        half_argmax(mx, ix);
-        {
-            const float ov = __shfl_xor(mx, 32, 64);
-            const int oi = __shfl_xor(ix, 32, 64);
-            if (ov > mx || (ov == mx && oi < ix)) { mx = ov; ix = oi; }
-        }
+        full_argmax(mx, ix);
         if (ix != 0x7fffffff) {             // (uniform) else: every column of the tile is banned - it contributes nothing
-            float s = half_sum((ok0 ? expf(x0 - mx) : 0.f) + (ok1 ? expf(x1 - mx) : 0.f));
-            s += __shfl_xor(s, 32, 64);
-            cm[k] = mx; cs[k] = s; ci[k] = ix;
+            cm[k] = mx; cs[k] = full_sum((ok0 ? expf(x0 - mx) : 0.f) + (ok1 ? expf(x1 - mx) : 0.f)); ci[k] = ix;
         }
     }
     auto tile = [&](int j, float &m, float &s, int &id) __attribute__((always_inline)) {
@@ -521,22 +480,16 @@ __device__ __forceinline__ int rollout_finalize_con_row(const DevRollout &R, con
         tile(j, m, s, id);
         if (m > amax || (m == amax && id < aidx)) { amax = m; aidx = id; }
     }
-    half_argmax(amax, aidx);
-    {
-        const float ov = __shfl_xor(amax, 32, 64);
-        const int oi = __shfl_xor(aidx, 32, 64);
-        if (ov > amax || (ov == amax && oi < aidx)) { amax = ov; aidx = oi; }
-    }
+    full_argmax(amax, aidx);
     for (int j = lane; j < R.n_tile; j += 64) {
         float m, s;
         int id;
         tile(j, m, s, id);
         if (s > 0.f) A += s * expf(m - amax);
     }
-    A = half_sum(A);
-    A += __shfl_xor(A, 32, 64);
+    A = full_sum(A);
     if (aidx == 0x7fffffff) aidx = gidx;    // (a non-finite row: flagged by the fold above)
-    long long it = aidx;                    // arg-max over the allowed ids, ties to the smaller id
+    it = aidx;                              // arg-max over the allowed ids, ties to the smaller id
     if (R.sample_u) {
         const int pick = sample_two_level_t(
             x, amax, 1.0f,
@@ -545,41 +498,30 @@ __device__ __forceinline__ int rollout_finalize_con_row(const DevRollout &R, con
             R.sample_u[(long long)b * R.T + R.t] * A, lane);
         if (pick >= 0) it = pick;           // (else: target == A after rounding)
     }
-    const float lp = (x[it] - gmax) - logf(S);
-    const int u = R.unfinished[b];
-    const long long itm = u ? it : 0;       // the step's outputs: as rollout_finalize_row writes them
-    const int u2 = u && (itm != R.eos_id);
-    if (lane == 0) {
-        const long long o = (long long)b * R.T + R.t;
-        R.seq_masks[o] = (float)u;
-        R.seq[o] = itm;
-        R.seq_logprobs[o] = lp;
-        if (R.raw_tokens) R.raw_tokens[o] = it;
-        R.unfinished[b] = u2;
-    }
-    if (R.xt_next) {
-        const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
-        const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
-        float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
-        for (int i = lane; i < (R.W >> 2); i += 64) {
-            float4 v = src[i];
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-            dst[i] = v;
-        }
-    }
-    return u2;
+    lp = (x[it] - gmax) - logf(S);
 }
 
-// the two launch shapes of the plain finalize (WAVES = 4: up to 1024 rows, 16: the wide one), one row per wave
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void rollout_finalize_con_kernel(const DevRollout R, const DevCons C) {
+// The launch skeleton of the wave-per-row finalize, plain or constrained (CON): ONE row per wave - every row's dependent
+// chain (two strided sweeps, a dozen cross-lane steps, logf, stores) runs at the same time as all the others - and the
+// count of still-unfinished rows reduced inside the workgroup, so that the `alive` counter sees one atomic per WAVES rows
+// (one per row, 4096 same-address atomics used to dominate this kernel).  Two launch shapes: WAVES = 4 up to 1024 rows,
+// 16 (the wide one) beyond.
+template <int WAVES, bool CON>
+__device__ __forceinline__ void rollout_finalize_body(const DevRollout &R, const DevCons &C) {
     __shared__ int cnt[WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the reference `break`s once no row is unfinished (captioner.py:343-344): later steps
+    // leave seq / seq_logprobs / seq_masks at their zero initialisation
     if (R.alive[R.t] == 0) return;          // block-uniform
     const int b = blockIdx.x * WAVES + wave;
     int alive = 0;
-    if (b < R.B) alive = rollout_finalize_con_row(R, C, b, lane);
+    if (b < R.B) {
+        long long it;
+        float lp;
+        if (CON) rollout_choose_con_row(R, C, b, lane, it, lp);
+        else rollout_choose_row(R, b, lane, it, lp);
+        alive = finalize_commit<64>(R, b, it, lp, R.unfinished[b], lane);
+    }
     if (lane == 0) cnt[wave] = alive;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -588,6 +530,19 @@ __global__ __launch_bounds__(WAVES * 64) void rollout_finalize_con_kernel(const 
         for (int w = 0; w < WAVES; ++w) tot += cnt[w];
         if (tot) atomicAdd(&R.alive[R.t + 1], tot);
     }
+}
+
+__global__ __launch_bounds__(256) void rollout_finalize_kernel(const DevRollout R) {
+    rollout_finalize_body<4, false>(R, DevCons());
+}
+
+__global__ __launch_bounds__(1024) void rollout_finalize_wide_kernel(const DevRollout R) {
+    rollout_finalize_body<16, false>(R, DevCons());
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void rollout_finalize_con_kernel(const DevRollout R, const DevCons C) {
+    rollout_finalize_body<WAVES, true>(R, C);
 }
 
 static std::atomic<long long> g_finalize_launches{0};
@@ -601,21 +556,27 @@ static DevRollout dev_rollout(const isc_rollout_step *s) {
     R.eos_id = s->eos_id; R.seq = s->seq; R.seq_logprobs = s->seq_logprobs; R.seq_masks = s->seq_masks;
     R.unfinished = s->unfinished; R.alive = s->alive; R.raw_tokens = s->raw_tokens;
     R.emb = s->emb; R.xt_add = s->xt_add; R.xt_next = s->xt_next;
-    R.rows_per_wave = 1;
     return R;
 }
 
-extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
-    if (!s) return ISC_E_NULL;
-    if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
+// What every finalize entry asks of its (non-null) isc_rollout_step, refused in the order the entries have always used: a
+// missing pointer (ISC_E_NULL), then a size (ISC_E_SHAPE), then alignment (ISC_E_ALIGN).  `own_null` / `own_shape`: the
+// calling entry's own conditions of the first two kinds, so that they keep their place in that order.
+static int rollout_step_check(const isc_rollout_step *s, bool own_null, bool own_shape) {
+    if (own_null || !s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
         !s->unfinished || !s->alive || !s->emb)
         return ISC_E_NULL;
-    if ((s->forced || s->sample_u) && !s->logits) return ISC_E_NULL;
-    if (s->B <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3)) return ISC_E_SHAPE;
-    // xt_next = relu(emb[token]) (+ xt_add) moves float4s (rollout_finalize_row)
+    if (own_shape || s->B <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3)) return ISC_E_SHAPE;
+    // xt_next = relu(emb[token]) (+ xt_add) moves float4s (finalize_commit)
     if (s->xt_next && (!isc_aligned16(s->emb) || !isc_aligned16(s->xt_next) || (s->xt_add && !isc_aligned16(s->xt_add))))
         return ISC_E_ALIGN;
-    // one row per wavefront; many rows: 16 waves per workgroup, so that the `alive` counter sees one atomic per 16 rows
+    return ISC_OK;
+}
+
+// (any n_tile: the few-row path keeps its statistics per rows_stats_tile(V) <= 64 columns; greedy reads no logits)
+extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
+    if (!s) return ISC_E_NULL;
+    if (const int rc = rollout_step_check(s, (s->forced || s->sample_u) && !s->logits, false)) return rc;
     const DevRollout R = dev_rollout(s);
     if (s->B > 1024)
         hipLaunchKernelGGL(rollout_finalize_wide_kernel, dim3((s->B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, R);
@@ -924,32 +885,17 @@ __device__ __forceinline__ void rollout_finalize_filtered_body(const DevRollout 
         __syncthreads();
         const int pk = shi[3];
         const long long it = pk < 0 ? gidx : pk;                    // (a row without any mass: non-finite, flagged)
-        // ---- the step's outputs, as rollout_finalize_row writes them
-        const long long itm = unf ? it : 0;
-        const int u2 = unf && (itm != R.eos_id);
+        // ---- the step's outputs (thread 0 alone holds the log-probabilities: it is the one that stores them)
+        float lp = 0.f;
         if (tid == 0) {
             const float xi = xs_[it];
-            const long long o = (long long)b * R.T + R.t;
-            R.seq_masks[o] = (float)unf;
-            R.seq[o] = itm;
-            R.seq_logprobs[o] = (xi - lp_max) - logf(S);             // the MODEL's log-probability of the token
+            lp = (xi - lp_max) - logf(S);                            // the MODEL's log-probability of the token
             if (F.slp)
-                F.slp[o] = (float)(((double)xi - (double)gmax) / (double)F.tau - log((double)Wk * (1.0 / 4294967296.0)));
-            if (R.raw_tokens) R.raw_tokens[o] = it;
-            R.unfinished[b] = u2;
-            alive += u2;
+                F.slp[(long long)b * R.T + R.t] =
+                    (float)(((double)xi - (double)gmax) / (double)F.tau - log((double)Wk * (1.0 / 4294967296.0)));
         }
-        if (R.xt_next) {
-            const float4 *src = reinterpret_cast<const float4 *>(R.emb + itm * R.W);
-            const float4 *ad = R.xt_add ? reinterpret_cast<const float4 *>(R.xt_add + (long long)b * R.W) : nullptr;
-            float4 *dst = reinterpret_cast<float4 *>(R.xt_next + (long long)b * R.W);
-            for (int i = tid; i < (R.W >> 2); i += 256) {
-                float4 v = src[i];
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-                if (ad) { const float4 a = ad[i]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-                dst[i] = v;
-            }
-        }
+        const int u2 = finalize_commit<256>(R, b, it, lp, unf, tid);
+        if (tid == 0) alive += u2;
         __syncthreads();                    // the row in LDS and the scratch words are the next row's
     }
     if (tid == 0 && alive) atomicAdd(&R.alive[R.t + 1], alive);
@@ -964,28 +910,31 @@ __global__ __launch_bounds__(256) void rollout_finalize_filtered_con_kernel(cons
     rollout_finalize_filtered_body<true>(R, F, C);
 }
 
+static bool flt_params_ok(const isc_sample_filter *f) {
+    return f->temperature > 0.f && f->temperature <= 3.0e38f && f->top_k >= 0 && f->top_p > 0.f;     // NaN fails
+}
+
+// the filtered launch: a workgroup per row up to ISC_FLT_MAX_GRID, the staged row (if it is staged) as dynamic LDS
+static dim3 flt_grid(const isc_rollout_step *s) { return dim3(s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID); }
+static size_t flt_lds(const isc_rollout_step *s) {
+    return s->V <= ISC_FLT_STAGE_MAX ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0;
+}
+
 static DevFilter dev_filter(const isc_rollout_step *s, const isc_sample_filter *f) {
     DevFilter F;
     F.c_exp = (float)(1.4426950408889634 / (double)f->temperature);
     F.tau = f->temperature; F.top_k = f->top_k; F.top_p = f->top_p; F.slp = f->sampling_logprobs;
-    F.staged = s->V <= ISC_FLT_STAGE_MAX;
+    F.staged = flt_lds(s) != 0;
     return F;
 }
 
 extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, void *stream) {
     if (!s || !f) return ISC_E_NULL;
-    if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
-        !s->unfinished || !s->alive || !s->emb || !s->logits || !s->sample_u)
-        return ISC_E_NULL;
-    if (!(f->temperature > 0.f) || !(f->temperature <= 3.0e38f) || f->top_k < 0 || !(f->top_p > 0.f)) return ISC_E_SHAPE;
-    if (s->B <= 0 || s->V <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3) || s->n_tile <= 0 ||
-        s->ld_logits < s->V || s->forced)
-        return ISC_E_SHAPE;
-    const DevRollout R = dev_rollout(s);
-    const DevFilter F = dev_filter(s, f);
-    const int grid = s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID;
-    hipLaunchKernelGGL(rollout_finalize_filtered_kernel, dim3(grid), dim3(256),
-                       F.staged ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0, (hipStream_t)stream, R, F);
+    if (const int rc = rollout_step_check(s, !s->logits || !s->sample_u,
+                                          !flt_params_ok(f) || s->V <= 0 || s->n_tile <= 0 || s->ld_logits < s->V || s->forced))
+        return rc;
+    hipLaunchKernelGGL(rollout_finalize_filtered_kernel, flt_grid(s), dim3(256), flt_lds(s), (hipStream_t)stream,
+                       dev_rollout(s), dev_filter(s, f));
     ISC_LAUNCH_CHECK();
     ++g_finalize_launches;
     return ISC_OK;
@@ -1015,22 +964,14 @@ extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const
     C.no_repeat = c->no_repeat != 0; C.first_id = (int)c->first_id;
     if (n == 0 && !C.no_repeat) return f ? isc_rollout_finalize_filtered(s, f, stream) : isc_rollout_finalize(s, stream);
     for (; n < ISC_CON_MAX - 1; ++n) C.ban[n] = -1;
-    if (!s->part_max || !s->part_sum || !s->part_idx || !s->seq || !s->seq_logprobs || !s->seq_masks ||
-        !s->unfinished || !s->alive || !s->emb || (f && !s->sample_u))
-        return ISC_E_NULL;
-    if (f && (!(f->temperature > 0.f) || !(f->temperature <= 3.0e38f) || f->top_k < 0 || !(f->top_p > 0.f)))
-        return ISC_E_SHAPE;
-    if (s->B <= 0 || s->V <= 0 || s->T <= 0 || s->t < 0 || s->t >= s->T || (s->W & 3) || s->n_tile != (s->V + 127) / 128 ||
-        s->ld_logits < s->V)
-        return ISC_E_SHAPE;
-    if (s->xt_next && (!isc_aligned16(s->emb) || !isc_aligned16(s->xt_next) || (s->xt_add && !isc_aligned16(s->xt_add))))
-        return ISC_E_ALIGN;
+    if (const int rc = rollout_step_check(s, f && !s->sample_u,
+                                          (f && !flt_params_ok(f)) || s->V <= 0 || s->n_tile != (s->V + 127) / 128 ||
+                                              s->ld_logits < s->V))
+        return rc;
     const DevRollout R = dev_rollout(s);
     if (f) {
-        const DevFilter F = dev_filter(s, f);
-        const int grid = s->B < ISC_FLT_MAX_GRID ? s->B : ISC_FLT_MAX_GRID;
-        hipLaunchKernelGGL(rollout_finalize_filtered_con_kernel, dim3(grid), dim3(256),
-                           F.staged ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0, (hipStream_t)stream, R, F, C);
+        hipLaunchKernelGGL(rollout_finalize_filtered_con_kernel, flt_grid(s), dim3(256), flt_lds(s), (hipStream_t)stream, R,
+                           dev_filter(s, f), C);
     } else if (s->B > 1024) {
         hipLaunchKernelGGL(rollout_finalize_con_kernel<16>, dim3((s->B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, R, C);
     } else {
@@ -1503,7 +1444,7 @@ RSTAMP_SETTER(isc_pw_set_stamp)
 #endif
 // Wave-wide maximum / sum that never leave the VALU: four DPP steps leave every 16-lane row holding its reduction, the
 // four row values then meet through row_bcast15 / row_bcast31 (maximum) or four v_readlane (sum: the association of
-// half_sum + the cross-half add, so the normaliser keeps its bits).  The ds_swizzle / ds_bpermute steps these replace are
+// common.h's full_sum, so the normaliser keeps its bits).  The ds_swizzle / ds_bpermute steps these replace are
 // LDS round trips (~100+ cycles each) - in a kernel that is ONE dependent chain they were a third of its time.
 __device__ __forceinline__ float sel_wave_fmax(float v) {               // -> the wave's maximum, wave-uniform (NaNs are dropped)
     // v_max_f32 with the DPP operand folded in (the compiler keeps v_mov_dpp + a canonicalising v_max + v_max per step);
@@ -1518,7 +1459,7 @@ __device__ __forceinline__ float sel_wave_fmax(float v) {               // -> th
                  "s_nop 1" : "+v"(v));
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
-__device__ __forceinline__ float sel_wave_sum(float v) {                // == half_sum(v) + the other half's, bit for bit
+__device__ __forceinline__ float sel_wave_sum(float v) {                // == full_sum(v), bit for bit
     v += isc_dpp<ISC_DPP_XOR1>(v);
     v += isc_dpp<ISC_DPP_XOR2>(v);
     v += isc_dpp<ISC_DPP_HALF_MIRROR>(v);

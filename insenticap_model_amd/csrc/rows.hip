@@ -329,11 +329,7 @@ __global__ __launch_bounds__(768) void rows_lstm_kernel(const RLstmArgs a) {
 #pragma unroll
             for (int r = 0; r < MR; ++r) half_argmax(mx[r], ix[r]);
 #pragma unroll
-            for (int r = 0; r < MR; ++r) {
-                const float ov = __shfl_xor(mx[r], 32, 64);
-                const int oi = __shfl_xor(ix[r], 32, 64);
-                if (ov > mx[r] || (ov == mx[r] && oi < ix[r])) { mx[r] = ov; ix[r] = oi; }
-            }
+            for (int r = 0; r < MR; ++r) cross_argmax(mx[r], ix[r]);
 #pragma unroll
             for (int r = 0; r < MR; ++r) {
                 float s = 0.f;
@@ -343,15 +339,15 @@ __global__ __launch_bounds__(768) void rows_lstm_kernel(const RLstmArgs a) {
                 sm[r] = half_sum(s);
             }
 #pragma unroll
-            for (int r = 0; r < MR; ++r) sm[r] += __shfl_xor(sm[r], 32, 64);
+            for (int r = 0; r < MR; ++r) sm[r] = cross_sum(sm[r]);
             const bool writer = blockIdx.x == 0 && lane == 0 && alive_t != 0;    // (alive == 0: the reference has left its loop)
 #pragma unroll
             for (int r = 0; r < MR; ++r) {
                 if (r < M) {                                 // (uniform)
                     if (lane == 0 && !(fabsf(mx[r]) <= 3.0e38f && sm[r] <= 3.0e38f)) isc_flag_rows(ISC_STATUS_WORD_STATS);
                     const int gidx = ix[r] == 0x7fffffff ? 0 : ix[r];
-                    const long long itm = un[r] ? gidx : 0;  // finished rows feed <PAD> (id 0): `it * unfinished`
-                    const int u2 = un[r] && (itm != F.eos);
+                    long long itm;
+                    const int u2 = finalize_advance(un[r], gidx, F.eos, itm);
                     alive_next += u2;
                     my_tok = m == r ? (int)itm : my_tok;
                     if (writer) {
@@ -376,8 +372,8 @@ __global__ __launch_bounds__(768) void rows_lstm_kernel(const RLstmArgs a) {
                     if (fold_row_stats_impl(F.pmax + so, F.psum + so, F.pidx + so, F.n_tile, lane, gmax, gidx, S) && lane == 0)
                         isc_flag_rows(ISC_STATUS_WORD_STATS);
                     const int u = F.unf_in[r];
-                    const long long itm = u ? gidx : 0;
-                    const int u2 = u && (itm != F.eos);
+                    long long itm;
+                    const int u2 = finalize_advance(u, gidx, F.eos, itm);
                     alive_next += u2;
                     my_tok = m == r ? (int)itm : my_tok;
                     if (writer) {
@@ -760,14 +756,8 @@ __global__ __launch_bounds__(768) void rows_vocab_kernel(const RVocabArgs a) {
         }
         float mx = x;
         int ix = c;
-        half_argmax(mx, ix);                                // ties: the lower column
-        {
-            const float ov = __shfl_xor(mx, 32, 64);
-            const int oi = __shfl_xor(ix, 32, 64);
-            if (ov > mx || (ov == mx && oi < ix)) { mx = ov; ix = oi; }
-        }
-        float sm = half_sum(c < tw ? __expf(x - mx) : 0.f);
-        sm += __shfl_xor(sm, 32, 64);
+        full_argmax(mx, ix);                                // ties: the lower column
+        const float sm = full_sum(c < tw ? __expf(x - mx) : 0.f);
         if (lane == 0) {
             const long long o = (long long)m * a.n_tile + tile;
             a.pmax[o] = mx;

@@ -908,6 +908,22 @@ def rollout_finalize_constrained(step, cons, filt=None, sampling_logprobs=None):
               4.0 * step.B * ((step.V if f is not None else 0) + 3 * step.n_tile + 2 * step.W))
 
 
+def rollout_finalize_step(step, cons=None, filt=None, sampling_logprobs=None):
+    """One decode step's finalize in whichever of the three forms above it takes.  cons: decode_constraints or None;
+    filt: the sampling controls (a mapping with 'temperature', 'top_k', 'top_p' and 'filtered' = any of them is on) or
+    None.  Under constraints the sampled distribution is the restricted one, so a wanted `sampling_logprobs` sends the
+    controls along even when they are the defaults."""
+    filtered = filt is not None and filt['filtered']
+    controls = None if filt is None else (filt['temperature'], filt['top_k'], filt['top_p'])
+    if cons is not None:
+        rollout_finalize_constrained(step, cons, controls if filtered or sampling_logprobs is not None else None,
+                                     sampling_logprobs)
+    elif filtered:
+        rollout_finalize_filtered(step, *controls, sampling_logprobs)
+    else:
+        rollout_finalize(step)
+
+
 def sched_sample(logp, part_max, part_sum, part_idx, u_select, u_draw, ss_prob, base_ids, out_ids, raw=False):
     """out_ids[b] = u_select[b] < ss_prob ? draw from exp(logp[b]) : base_ids[b]  (base_ids may be a strided column).
     raw: `logp` holds the row's raw logits (isc_sched_sample_raw)."""

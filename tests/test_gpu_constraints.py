@@ -16,7 +16,7 @@ from _constraint_ref import T, setup
 from insenticap_model_amd import Captioner, _lib, ops, synth
 from insenticap_model_amd.rewards import RewardCriterion
 from oracle import captioner_oracle as O
-from test_gpu_sample_filter import Rows
+from test_gpu_sample_filter import Rows, assert_xt_next, xt_next_case
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +50,7 @@ class CRows(Rows):
         st.forced, st.sample_u, st.eos_id = ops.ptr(forced), (None if greedy else self.uu.data_ptr()), self.eos_id
         st.seq, st.seq_logprobs, st.seq_masks = self.seq.data_ptr(), self.lp.data_ptr(), self.mk.data_ptr()
         st.unfinished, st.alive, st.raw_tokens = self.unf.data_ptr(), self.alive.data_ptr(), self.raw.data_ptr()
-        st.emb, st.xt_add, st.xt_next = self.emb.data_ptr(), None, None
+        st.emb, st.xt_add, st.xt_next = self.emb.data_ptr(), ops.ptr(self.add), ops.ptr(self.xt)
         if not call:
             return st
         ops.rollout_finalize_constrained(st, cons, filt, self.slp if filt is not None else None)
@@ -204,6 +204,22 @@ def test_constrained_finalize_against_fp64(V, B, mode):
     assert (seq2[ended] == 0).all() and (mk2[ended] == 0).all() and (mk2[~ended] == 1).all()
     assert (seq2[~ended] == tok2[~ended]).all() and (tok2[~ended] != tok[~ended]).all()
     assert okg[tok2[~ended]].all()
+
+
+# (B, W, xt_add) per form: the wide row is the second trip of the form's own float4 loop - 64 lanes or 256 threads a row
+XT_GEOMS = [(B, 4, True, m) for B in (6, 1030) for m in ('greedy', 'sample', 'filtered')] + \
+    [(6, 260, False, 'greedy'), (6, 260, False, 'sample'), (6, 1028, False, 'filtered')]
+
+
+@pytest.mark.parametrize('B,W,xt_add,mode', XT_GEOMS)
+def test_constrained_finalize_writes_xt_next(B, W, xt_add, mode):
+    """The commit stage behind the constrained choices: 64 lanes per row (greedy, sample; B = 1030 is the sixteen-wave
+    kernel with six rows in its last block) or 256 threads (filtered; B = 1030 is a workgroup's second row trip)."""
+    rows, u = xt_next_case(CRows, B, W, xt_add, eos_id=EOS)
+    rows.cstep(1, u, ops.decode_constraints([0, 1, 3], False, 0, 0), FILT if mode == 'filtered' else None, mode == 'greedy')
+    assert_xt_next(rows)
+    assert not np.isin(rows.raw[:, 1].cpu().numpy(), [0, 1, 3]).any()
+    assert int(rows.alive[2]) == int(rows.unf.sum())
 
 
 def test_dead_step_refusals_and_the_all_zero_struct():

@@ -580,6 +580,53 @@ def test_rollout_finalize_refuses_misaligned_pointers():
     assert rc_of(emb, add, xt) == (0, False)
 
 
+@pytest.mark.parametrize('entry', ['filtered', 'constrained', 'constrained_filtered'])
+def test_filtered_and_constrained_finalize_refuse_misaligned_pointers(entry):
+    """The same refusal at the other two entry points: their kernels move emb, xt_add and xt_next as float4 through the
+    same commit stage.  One of the three placed one float into its storage returns ISC_E_ALIGN, every output keeps its
+    sentinel and the launch counter does not move - nothing is launched.  The aligned call is accepted."""
+    lib = _lib.load()
+    c = _roll_inputs(6, 130)
+    B, V, W, T, t = 6, 130, 4, ROLL_T, ROLL_t
+    pm, ps, pi = [d(s) for s in c['stats']]
+    g = gen(5)
+    emb, add, x_d, u_d = d(rn(g, V, W)), d(rn(g, B, W)), d(c['x']), d(c['u'])
+    emb_off, add_off, xt_off = off_by_one_float(emb), off_by_one_float(add), off_by_one_float(sent(B, W))
+    f = _lib.SampleFilter()
+    f.temperature, f.top_k, f.top_p = 0.8, 50, 0.9
+    cons = ops.decode_constraints([0, 1, 3], False, 0, 0)
+
+    def rc_of(emb_, add_, xt_):
+        seq, raw, lp, mk = sent(B, T, dtype=torch.int64), sent(B, T, dtype=torch.int64), sent(B, T), sent(B, T)
+        slp = sent(B, T)
+        unf = d(c['unf'].clone())
+        alive = torch.tensor([ISENT, int(c['unf'].sum()), 0, ISENT], dtype=torch.int32, device=DEV)
+        st = _lib.RolloutStep()
+        st.B, st.V, st.T, st.t, st.n_tile, st.W = B, V, T, t, pm.shape[1], W
+        st.part_max, st.part_sum, st.part_idx = pm.data_ptr(), ps.data_ptr(), pi.data_ptr()
+        st.logits, st.ld_logits, st.sample_u, st.eos_id = x_d.data_ptr(), V, u_d.data_ptr(), c['eos']
+        st.seq, st.seq_logprobs, st.seq_masks = seq.data_ptr(), lp.data_ptr(), mk.data_ptr()
+        st.unfinished, st.alive, st.raw_tokens = unf.data_ptr(), alive.data_ptr(), raw.data_ptr()
+        st.emb, st.xt_add, st.xt_next = emb_.data_ptr(), ops.ptr(add_), ops.ptr(xt_)
+        f.sampling_logprobs = slp.data_ptr()
+        n0 = lib.isc_rollout_finalize_launches()
+        if entry == 'filtered':
+            rc = lib.isc_rollout_finalize_filtered(C.byref(st), C.byref(f), ops.stream())
+        else:
+            rc = lib.isc_rollout_finalize_constrained(C.byref(st), C.byref(f) if entry == 'constrained_filtered' else None,
+                                                      C.byref(cons), ops.stream())
+        torch.cuda.synchronize()
+        untouched = (all(bool((o == ISENT).all()) for o in (seq, raw))
+                     and all(bool((o == SENT).all()) for o in (lp, mk, slp, xt_))
+                     and torch.equal(unf.cpu(), c['unf']) and int(alive[2]) == 0)
+        return rc, untouched, lib.isc_rollout_finalize_launches() - n0
+    xt = sent(B, W)
+    assert rc_of(emb_off, add, xt) == (E_ALIGN, True, 0)
+    assert rc_of(emb, add_off, xt) == (E_ALIGN, True, 0)
+    assert rc_of(emb, add, xt_off) == (E_ALIGN, True, 0)
+    assert rc_of(emb, add, xt) == (0, False, 1)
+
+
 # ------------------------------------------------------------------------------------------------ scheduled sampling
 @pytest.mark.parametrize('ss_prob', [0.0, 1.0, 0.4])
 @pytest.mark.parametrize('V', [300, 8321])

@@ -14,6 +14,7 @@ from insenticap_model_amd import Captioner, _lib, ops, synth
 pytestmark = pytest.mark.gpu
 
 LP_TOL = 2e-5
+XT_SENTINEL = -12345.0
 PARAMS = [(1.0, 0, 0.9), (0.7, 0, 0.95), (1.5, 0, 0.5), (1.3, 50, 0.9), (2.0, 640, 0.99), (1.0, 5, 1.0), (0.8, 0, 1.0)]
 
 
@@ -25,12 +26,13 @@ def dev():
 class Rows:
     """Logits on the device WITH the tile statistics that describe them (the identity trick of
     tests/test_gpu_sampling.py::_sample: the vocabulary kernel with h = I and W^T = logits), and the buffers of one
-    roll-out of T steps over them."""
+    roll-out of T steps over them.  xt: the step also writes xt_next [B, W] = relu(emb[fed token]) (+ xt_add when
+    `xt_add`) from a random embedding table; one more row of sentinels lies behind xt_next."""
 
-    def __init__(self, logits, T=1, eos_id=2):
+    def __init__(self, logits, T=1, eos_id=2, W=32, xt=False, xt_add=False):
         D = dev()
         B, V = logits.shape
-        self.B, self.V, self.T, self.W = B, V, T, 32
+        self.B, self.V, self.T, self.W = B, V, T, W
         nt = (V + 127) // 128
         self.pm, self.ps = torch.empty(B, nt, device=D), torch.empty(B, nt, device=D)
         self.pi = torch.empty(B, nt, device=D, dtype=torch.int32)
@@ -47,7 +49,10 @@ class Rows:
         self.unf = torch.ones(B, dtype=torch.int32, device=D)
         self.alive = torch.zeros(T + 1, dtype=torch.int32, device=D)
         self.alive[0] = B
-        self.emb = torch.zeros(V, self.W, device=D)
+        g = torch.Generator().manual_seed(V + W)
+        self.emb = torch.randn(V, W, generator=g).to(D) if xt else torch.zeros(V, W, device=D)
+        self.add = torch.randn(B, W, generator=g).to(D) if xt and xt_add else None
+        self.xt = torch.full((B + 1, W), XT_SENTINEL, device=D) if xt else None
         self.eos_id = eos_id
         self.x = self.out.cpu().double().numpy()
 
@@ -60,7 +65,7 @@ class Rows:
         st.forced, st.sample_u, st.eos_id = None, self.uu.data_ptr(), self.eos_id
         st.seq, st.seq_logprobs, st.seq_masks = self.seq.data_ptr(), self.lp.data_ptr(), self.mk.data_ptr()
         st.unfinished, st.alive, st.raw_tokens = self.unf.data_ptr(), self.alive.data_ptr(), self.raw.data_ptr()
-        st.emb, st.xt_add, st.xt_next = self.emb.data_ptr(), None, None
+        st.emb, st.xt_add, st.xt_next = self.emb.data_ptr(), ops.ptr(self.add), ops.ptr(self.xt)
         ops.rollout_finalize_filtered(st, tau, k, p, self.slp)
         torch.cuda.synchronize()
 
@@ -71,6 +76,52 @@ class Rows:
         self.alive[0:1].fill_(self.B)
         self.step(0, u, tau, k, p)
         return self.raw[:, 0].cpu().numpy(), self.lp[:, 0].cpu().numpy(), self.slp[:, 0].cpu().numpy()
+
+
+def xt_next_case(cls, B, W, xt_add, V=130, T=3, eos_id=2):
+    """Rows (or a subclass) for one step t = 1 of T = 3 that writes xt_next: random logits, row 1 finished, every [B, T]
+    output filled with a sentinel."""
+    g = torch.Generator().manual_seed(B * 3 + W)
+    rows = cls(4.0 * torch.randn(B, V, generator=g), T=T, eos_id=eos_id, W=W, xt=True, xt_add=xt_add)
+    rows.alive[0:2].fill_(B)
+    rows.unf[1] = 0
+    rows.seq.fill_(-7)
+    rows.raw.fill_(-7)
+    for o in (rows.lp, rows.mk, rows.slp):
+        o.fill_(XT_SENTINEL)
+    return rows, torch.rand(B, T, generator=g)
+
+
+def assert_xt_next(rows, t=1):
+    """xt_next = relu(emb[seq[:, t]]) (+ xt_add) under torch.equal: one max and at most one IEEE add in float32, nothing
+    to round differently.  The finished row 1 feeds <PAD>, whose embedding row is what it gets; the row behind xt_next and
+    the other columns of the [B, T] outputs keep their sentinels."""
+    B = rows.B
+    seq = rows.seq.cpu()
+    assert int(seq[1, t]) == 0 and float(rows.mk[1, t]) == 0.0 and int(rows.unf[1]) == 0
+    assert bool(((seq[:, t] >= 0) & (seq[:, t] < rows.V)).all())
+    live = torch.ones(B, dtype=torch.bool)
+    live[1] = False
+    assert torch.equal(seq[live, t], rows.raw.cpu()[live, t]) and bool((rows.mk.cpu()[live, t] == 1.0).all())
+    want = rows.emb.cpu()[seq[:, t]].clamp_min(0.0)
+    assert bool((want[1] > 0).any())                    # (<PAD>'s row is not all zero: a skipped row would show)
+    if rows.add is not None:
+        want = want + rows.add.cpu()
+    assert torch.equal(rows.xt[:B].cpu(), want)
+    assert bool((rows.xt[B] == XT_SENTINEL).all())
+    others = [c for c in range(rows.T) if c != t]
+    assert bool((rows.seq[:, others] == -7).all()) and bool((rows.raw[:, others] == -7).all())
+    assert all(bool((o[:, others] == XT_SENTINEL).all()) for o in (rows.lp, rows.mk))
+
+
+@pytest.mark.parametrize('B,W,xt_add', [(6, 4, True), (1030, 4, True), (6, 1028, False)])
+def test_filtered_finalize_writes_xt_next(B, W, xt_add):
+    """The commit stage behind the filtered selection, 256 threads per row: B = 1030 is a workgroup's second row trip
+    (768 workgroups), W = 1028 the second trip of the 256-thread float4 loop (257 float4s per row)."""
+    rows, u = xt_next_case(Rows, B, W, xt_add)
+    rows.step(1, u, 0.8, 50, 0.9)
+    assert_xt_next(rows)
+    assert int(rows.alive[2]) == int(rows.unf.sum())
 
 
 _ROWS = {}
