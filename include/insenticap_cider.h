@@ -72,6 +72,40 @@ int64_t isc_cider_cook_fill(const isc_cider *h, const int64_t *tokens, const int
                             int64_t n_caps, uint64_t *keys, double *vals, int32_t *ord_off,
                             double *norms, double *length);
 
+/* ---- BLEU, the reference's other self-critical scorer (self_critical/bleu/bleu.py, bleu_scorer.py).
+ * It keeps no document frequencies, hence no handle.  Rows and references are normalised as above
+ * (_array_to_str); per row the integer statistics of cook_refs / cook_test (bleu_scorer.py:38-86):
+ *   testlen; reflen = the "closest" reference length, min((abs(l - testlen), l)) - a tie takes the
+ *   shorter; guess[k] = max(0, testlen - k); correct[k] = sum over the row's distinct (k+1)-grams of
+ *   min(count in the row, max over the image's references of the count in that reference);
+ * and the four per-sentence scores in compute_score's order of operations (bleu_scorer.py:233-242):
+ * the running product of (correct + 1e-15) / (guess + 1e-9), ** (1 / (k + 1)), and, where
+ * ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1, *= exp(1 - 1 / ratio).  fp64, no contraction.
+ *   hyp: n_hyp rows of T ids, row r at hyp + r * hyp_stride, belongs to image r / row_div;
+ *   the references flattened as for isc_cider_score, n_imgs images (ref_img_off has n_imgs + 1);
+ *   scores4 [n_hyp, 4] = BLEU-1 .. BLEU-4; stats [n_hyp, 10] int32 = testlen, reflen, guess[0..3],
+ *   correct[0..3], or NULL.
+ * Up to n_threads threads, each image's references cooked once; the result does not depend on the
+ * thread count.  0, -1 null pointer, -2 an image (that owns a row) without references, -4 bad shape
+ * (n_hyp < 1, row_div < 1, fewer than ceil(n_hyp / row_div) images). */
+int isc_bleu_score(const int64_t *hyp, int64_t n_hyp, int64_t T, int64_t hyp_stride,
+                   const int64_t *ref_tokens, const int64_t *ref_cap_off, const int64_t *ref_img_off,
+                   int64_t n_imgs, int64_t row_div, int64_t sos_id, int64_t eos_id, int n_threads,
+                   double *scores4, int32_t *stats);
+
+/* ONE image's references (n_caps captions, flattened as above) cooked for the device scorer
+ * (isc_bleu_dev_score): the distinct n-grams over all of them as csrc/cider_key.h keys with their
+ * largest count in one reference, grouped by order - within an order: references ascending, first
+ * occurrence within a reference - ent_off[o] = first entry of order o + 1, ent_off[4] = the number of
+ * entries; ref_lens[c] = words of caption c after normalisation.  isc_bleu_cook_size returns the
+ * number of entries, isc_bleu_cook_fill fills and returns it; negative: -1 null pointer, -2 more than
+ * 2^31 - 1 entries, -3 id out of [0, 65534]. */
+int64_t isc_bleu_cook_size(const int64_t *tokens, const int64_t *cap_off, int64_t n_caps,
+                           int64_t sos_id, int64_t eos_id);
+int64_t isc_bleu_cook_fill(const int64_t *tokens, const int64_t *cap_off, int64_t n_caps,
+                           int64_t sos_id, int64_t eos_id, uint64_t *keys, int32_t *counts,
+                           int32_t *ent_off, int32_t *ref_lens);
+
 #ifdef __cplusplus
 }
 #endif

@@ -902,6 +902,28 @@ int isc_cider_dev_score(const int64_t *hyp, int64_t N, int T, int row_div, const
                         const double *ref_length, const uint64_t *ref_keys, const double *ref_vals, int n, double sigma,
                         double ref_len, int64_t sos_id, int64_t eos_id, double *scores, void *stream);
 
+/* BLEU of N hypotheses on the device: what isc_bleu_score (include/insenticap_cider.h) gives for row r - the integer
+ * statistics exactly, the four scores in the order of operations of bleu_scorer.py:233-242, fp64 without contraction.
+ * All pointers are device memory.
+ *   hyp [N, T] int64, contiguous, normalised as isc_cider_dev_score normalises (L <= T + 1 words); row r belongs to image
+ *     r / row_div.  Ids in [0, 65534]; an id is never an index, so a larger one reads nothing out of bounds.
+ *   the batch's cooked references (isc_bleu_cook_fill, one image after the other): image i owns the entries
+ *     img_ent_off[5 i] .. img_ent_off[5 i + 4] of ref_keys (csrc/cider_key.h keys) / ref_counts (the largest count of the
+ *     n-gram in one of the image's references), its (o + 1)-grams start at img_ent_off[5 i + o]; and the captions
+ *     img_cap_off[i] .. img_cap_off[i + 1] of ref_lens (words of each reference; n_img + 1 offsets, every image at least
+ *     one caption - the caller's check).
+ *   order 1..4: scores [N] = BLEU-order (4: the reference's reward, scores[3]); order 0: scores [N, 4].
+ *   stats [N, 10] int32 = testlen, reflen, guess[0..3], correct[0..3], or NULL.
+ * One wave64 per hypothesis, one lane per word, four hypotheses per workgroup; no workspace, no LDS, no atomics; the
+ * statistics are integer sums, the float tail is wave-uniform: two launches give the same bits, and order k gives the
+ * bits of column k - 1 of order 0.  One launch, no host read: capturable.
+ * N < 1, T outside [1, 63], row_div < 1, order outside [0, 4], or fewer than ceil(N / row_div) images: ISC_E_SHAPE,
+ * nothing is launched or written. */
+int isc_bleu_dev_score(const int64_t *hyp, int64_t N, int T, int row_div, const int32_t *img_ent_off,
+                       const uint64_t *ref_keys, const int32_t *ref_counts, const int32_t *img_cap_off,
+                       const int32_t *ref_lens, int64_t n_img, int order, int64_t sos_id, int64_t eos_id, double *scores,
+                       int32_t *stats, void *stream);
+
 /* Log-softmax backward with the criteria's gradient handed over SPARSE: XECriterion (captioner.py:427-440) and the
  * REINFORCE gather (captioner.py:336) touch one column per (caption, step) row, so their d log-prob is `coef[m]` at
  * column `ids[m]` - up to ISC_SPARSE_MAX such (ids, coef) pairs (HOST arrays of device pointers to [M] vectors, rows

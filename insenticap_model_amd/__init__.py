@@ -15,7 +15,8 @@ from .detector import Detector  # noqa: F401,E402
 from .optim import FusedClampAdam, clip_gradient  # noqa: F401,E402
 from .rewards import RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward  # noqa: F401,E402
 from .rewards import get_group_self_critical_reward, group_self_critical_scores  # noqa: F401,E402
+from .rewards import Bleu, DeviceBleu, get_bleu_scorer  # noqa: F401,E402
 
 __all__ = ['Captioner', 'XECriterion', 'Detector', 'FusedClampAdam', 'clip_gradient', 'RewardCriterion',
            'get_ciderd_scorer', 'get_self_critical_reward', 'get_cls_reward', 'get_group_self_critical_reward',
-           'group_self_critical_scores']
+           'group_self_critical_scores', 'Bleu', 'DeviceBleu', 'get_bleu_scorer']

@@ -308,3 +308,161 @@ extern "C" int64_t isc_cider_cook_fill(const isc_cider *h, const int64_t *tokens
     if (!h || !tokens || !cap_off || n_caps < 0 || !keys || !vals || !ord_off || !norms || !length) return -1;
     return cook(h, tokens, cap_off, n_caps, keys, vals, ord_off, norms, length);
 }
+
+// ------------------------------------------------------------------------------------------------------------- BLEU
+// The reference's other self-critical scorer (self_critical/bleu/bleu_scorer.py), on the same normalised rows.  Its
+// statistics are integers - testlen, the "closest" reference length, guess[k] = max(0, testlen - k) and correct[k] =
+// the sum over the row's distinct (k+1)-grams of min(count in the row, max over the references of the count there)
+// (cook_refs / cook_test, :38-86) - and the four scores follow compute_score's order of operations (:233-242).
+namespace {
+
+// The distinct n-grams over ALL references of one image with their largest count in one reference (cook_refs'
+// `maxcounts`), in insertion order: references ascending, within one the order of precook; and the reference lengths.
+struct RefMax {
+    std::vector<NGram> keys;
+    std::vector<int32_t> count;
+    std::vector<int32_t> lens;
+    LocalIndex index;
+};
+
+struct BleuScratch {
+    std::vector<int64_t> words;
+    Cooked one;
+    RefMax ref;
+};
+
+static void cook_image(BleuScratch &S, const int64_t *tokens, const int64_t *cap_off, int64_t c0, int64_t c1,
+                       int64_t sos, int64_t eos) {
+    RefMax &R = S.ref;
+    R.keys.clear();
+    R.count.clear();
+    R.lens.clear();
+    size_t total = 0;
+    for (int64_t c = c0; c < c1; ++c) total += (size_t)(cap_off[c + 1] - cap_off[c]) + 1;
+    R.index.reset(4 * total);
+    for (int64_t c = c0; c < c1; ++c) {
+        normalise(tokens + cap_off[c], cap_off[c + 1] - cap_off[c], sos, eos, S.words);
+        precook(S.words, 4, S.one);
+        R.lens.push_back((int32_t)S.words.size());
+        for (size_t i = 0; i < S.one.keys.size(); ++i) {
+            const int32_t cnt = (int32_t)S.one.tf[i];
+            const int at = R.index.find(R.keys, S.one.keys[i], (int)R.keys.size());
+            if (at < 0) {
+                R.keys.push_back(S.one.keys[i]);
+                R.count.push_back(cnt);
+            } else if (cnt > R.count[at]) {
+                R.count[at] = cnt;
+            }
+        }
+    }
+}
+
+// stats10: testlen, reflen, guess[0..3], correct[0..3]
+static void bleu_stats(BleuScratch &S, const int64_t *hyp, int64_t T, int64_t sos, int64_t eos, int32_t *st) {
+    normalise(hyp, T, sos, eos, S.words);
+    precook(S.words, 4, S.one);
+    const int32_t testlen = (int32_t)S.words.size();
+    int32_t best_d = 0, reflen = 0;
+    for (size_t c = 0; c < S.ref.lens.size(); ++c) {      // min((abs(l - testlen), l)): a tie takes the shorter
+        const int32_t l = S.ref.lens[c], d = l > testlen ? l - testlen : testlen - l;
+        if (c == 0 || d < best_d || (d == best_d && l < reflen)) best_d = d, reflen = l;
+    }
+    st[0] = testlen;
+    st[1] = reflen;
+    for (int k = 0; k < 4; ++k) st[2 + k] = testlen - k > 0 ? testlen - k : 0, st[6 + k] = 0;
+    for (size_t i = 0; i < S.one.keys.size(); ++i) {
+        const int at = S.ref.index.find(S.ref.keys, S.one.keys[i], -1);
+        if (at < 0) continue;
+        const int32_t cnt = (int32_t)S.one.tf[i];
+        st[6 + S.one.keys[i].n - 1] += cnt < S.ref.count[at] ? cnt : S.ref.count[at];
+    }
+}
+
+// bleu_scorer.py:233-242 on one row's statistics
+static void bleu_scores(const int32_t *st, double *out4) {
+    const double small = 1e-9, tiny = 1e-15;
+    double bleu = 1.0;
+    for (int k = 0; k < 4; ++k) {
+        bleu *= ((double)st[6 + k] + tiny) / ((double)st[2 + k] + small);
+        out4[k] = std::pow(bleu, 1.0 / (double)(k + 1));
+    }
+    const double ratio = ((double)st[0] + tiny) / ((double)st[1] + small);
+    if (ratio < 1) {
+        const double pen = std::exp(1 - 1 / ratio);
+        for (int k = 0; k < 4; ++k) out4[k] *= pen;
+    }
+}
+
+}  // namespace
+
+extern "C" int isc_bleu_score(const int64_t *hyp, int64_t n_hyp, int64_t T, int64_t hyp_stride,
+                              const int64_t *ref_tokens, const int64_t *ref_cap_off, const int64_t *ref_img_off,
+                              int64_t n_imgs, int64_t row_div, int64_t sos_id, int64_t eos_id, int n_threads,
+                              double *scores4, int32_t *stats) {
+    if (!hyp || !ref_tokens || !ref_cap_off || !ref_img_off || !scores4) return -1;
+    if (n_hyp < 1 || T < 0 || row_div < 1 || n_imgs < 1 || (n_hyp - 1) / row_div >= n_imgs) return -4;
+    const int64_t used = (n_hyp - 1) / row_div + 1;      // images that own a row
+    for (int64_t i = 0; i < used; ++i)
+        if (ref_img_off[i + 1] <= ref_img_off[i]) return -2;
+    if (n_threads < 1) n_threads = 1;
+    if ((int64_t)n_threads > used) n_threads = (int)used;
+    auto work = [&](int tid) {      // an image's references are cooked once for its row_div rows
+        BleuScratch S;
+        int32_t st[10];
+        for (int64_t i = tid; i < used; i += n_threads) {
+            cook_image(S, ref_tokens, ref_cap_off, ref_img_off[i], ref_img_off[i + 1], sos_id, eos_id);
+            const int64_t r1 = std::min(n_hyp, (i + 1) * row_div);
+            for (int64_t r = i * row_div; r < r1; ++r) {
+                bleu_stats(S, hyp + r * hyp_stride, T, sos_id, eos_id, st);
+                bleu_scores(st, scores4 + 4 * r);
+                if (stats) std::memcpy(stats + 10 * r, st, sizeof(st));
+            }
+        }
+    };
+    if (n_threads == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
+        for (auto &t : th) t.join();
+    }
+    return 0;
+}
+
+// One image's references cooked for the device (csrc/bleu_dev.hip): with keys == nullptr only the entries are counted.
+static int64_t bleu_cook(const int64_t *tokens, const int64_t *cap_off, int64_t n_caps, int64_t sos, int64_t eos,
+                         uint64_t *keys, int32_t *counts, int32_t *ent_off, int32_t *ref_lens) {
+    BleuScratch S;
+    cook_image(S, tokens, cap_off, 0, n_caps, sos, eos);
+    const int64_t m = (int64_t)S.ref.keys.size();
+    if (m > 0x7fffffffLL) return -2;
+    int64_t at = 0;
+    for (int o = 0; o < 4; ++o) {                             // grouped by order, insertion order within one
+        if (keys) ent_off[o] = (int32_t)at;
+        for (int64_t i = 0; i < m; ++i) {
+            if (S.ref.keys[i].n != o + 1) continue;
+            uint64_t key;
+            if (!key_of(S.ref.keys[i], &key)) return -3;
+            if (keys) keys[at] = key, counts[at] = S.ref.count[i];
+            ++at;
+        }
+    }
+    if (keys) {
+        ent_off[4] = (int32_t)at;
+        for (int64_t c = 0; c < n_caps; ++c) ref_lens[c] = S.ref.lens[c];
+    }
+    return at;
+}
+
+extern "C" int64_t isc_bleu_cook_size(const int64_t *tokens, const int64_t *cap_off, int64_t n_caps, int64_t sos_id,
+                                      int64_t eos_id) {
+    if (!tokens || !cap_off || n_caps < 0) return -1;
+    return bleu_cook(tokens, cap_off, n_caps, sos_id, eos_id, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int64_t isc_bleu_cook_fill(const int64_t *tokens, const int64_t *cap_off, int64_t n_caps, int64_t sos_id,
+                                      int64_t eos_id, uint64_t *keys, int32_t *counts, int32_t *ent_off,
+                                      int32_t *ref_lens) {
+    if (!tokens || !cap_off || n_caps < 0 || !keys || !counts || !ent_off || !ref_lens) return -1;
+    return bleu_cook(tokens, cap_off, n_caps, sos_id, eos_id, keys, counts, ent_off, ref_lens);
+}

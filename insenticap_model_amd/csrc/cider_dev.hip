@@ -9,12 +9,7 @@
 
 #define CIDER_WAVES 4      // hypotheses per workgroup
 
-// Value of `v` in lane j, j wave-uniform.
-__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int j) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-    return ((uint64_t)hi << 32) | lo;
-}
+// Value of `v` in lane j, j wave-uniform (lane_u64: cider_key.h).
 __device__ __forceinline__ double lane_f64(double v, int j) {
     return __longlong_as_double((long long)lane_u64((uint64_t)__double_as_longlong(v), j));
 }

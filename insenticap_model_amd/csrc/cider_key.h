@@ -37,6 +37,15 @@ ISC_CIDER_HD uint64_t isc_cider_hash(uint64_t key) {
     return key;
 }
 
+#if defined(__HIPCC__)
+/* Value of `v` in lane j of the wave, j wave-uniform (the device scorers hand keys round with it). */
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return ((uint64_t)hi << 32) | lo;
+}
+#endif
+
 /* One slot of the document-frequency table: 16 bytes.  key == 0: empty. */
 typedef struct {
     uint64_t key;

@@ -24,8 +24,8 @@ from .helper_nets import SentenceSentimentClassifier, SentimentDetector
 from .optim import clip_gradient
 from .train import run_on_side_stream
 from .ops import OutOfDomain
-from .rewards import (CIDER_DEV_MAX_T, RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward,
-                      get_self_critical_reward_device, group_self_critical_scores)
+from .rewards import (CIDER_DEV_MAX_T, Bleu, RewardCriterion, get_bleu_scorer, get_ciderd_scorer, get_cls_reward,
+                      get_self_critical_reward, get_self_critical_reward_device, group_self_critical_scores)
 
 
 def _helper_input(feats):
@@ -78,7 +78,8 @@ class Detector(nn.Module):
         # (rewards.DeviceCiderD, isc_cider_dev_score): the token matrices are not copied to the host and the host scorer
         # is not called; grouped iterations hand the device scores straight to isc_group_reward.  The device twin of
         # `ciderd_scorer` is built on first use and rebuilt when set_ciderd_scorer replaces the host scorer; a vocabulary
-        # above 65535 ids or max_seq_len > 63 warns once and keeps the host scorer.  Graph-served iterations
+        # above 65535 ids or max_seq_len > 63 warns once and keeps the host scorer.  With set_bleu_scorer the twin is a
+        # rewards.DeviceBleu (isc_bleu_dev_score), everything else alike.  Graph-served iterations
         # (train_graph.RLTrainGraph) are untouched: they keep the host scorer, whose time they already hide under the
         # greedy roll-out and the XE graphs.
         self.device_cider = False
@@ -106,7 +107,8 @@ class Detector(nn.Module):
     def _warn_device_cider(self, why):
         if not self._cider_dev_warned:
             import warnings
-            warnings.warn('device_cider: %s - the host CIDEr-D scorer is used' % why)
+            which = 'BLEU' if isinstance(self.ciderd_scorer, Bleu) else 'CIDEr-D'
+            warnings.warn('device_cider: %s - the host %s scorer is used' % (why, which))
             self._cider_dev_warned = True
 
     @property
@@ -165,6 +167,12 @@ class Detector(nn.Module):
 
     def set_ciderd_scorer(self, captions):
         self.ciderd_scorer = get_ciderd_scorer(captions, self.captioner.sos_id, self.captioner.eos_id)
+
+    def set_bleu_scorer(self, order=4):
+        """BLEU-`order` per sentence as the fact reward and metric instead of CIDEr-D (the reference's reward function
+        takes either scorer through the same argument: utils.py:73-79, order 4 = its scores[3]).  The scorer is stored in
+        `ciderd_scorer`, the attribute keeps its name; with device_cider on its device twin (rewards.DeviceBleu) is built."""
+        self.ciderd_scorer = get_bleu_scorer(self.captioner.sos_id, self.captioner.eos_id, order)
 
     def set_sentiment_words(self, sentiment_words):
         self.sentiment_words = sentiment_words

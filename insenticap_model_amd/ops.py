@@ -1337,6 +1337,36 @@ def cider_dev_score(hyps, row_div, table, img_cap_off, ord_off, ref_norms, ref_l
     return out
 
 
+def bleu_dev_score(hyps, row_div, img_ent_off, ref_keys, ref_counts, img_cap_off, ref_lens, order, sos_id, eos_id,
+                   out=None, stats=None):
+    """isc_bleu_dev_score: BLEU of the raw roll-out rows `hyps` int64 [N, T] on the device, row r against the cooked
+    references of image r // row_div -> float64 [N] = BLEU-`order` (order 1..4) or [N, 4] (order 0).  img_ent_off int32
+    [I, 5], ref_keys int64 [E] (the keys' bits), ref_counts int32 [E], img_cap_off int32 [I + 1], ref_lens int32 [C] -
+    rewards.DeviceBleu builds them.  `stats`: int32 [N, 10] to fill, or None.  T > 63 raises (ISC_E_SHAPE); nothing is
+    written then."""
+    require_device(hyps, img_ent_off, ref_keys, ref_counts, img_cap_off, ref_lens, out, stats)
+    assert hyps.dtype == torch.int64 and hyps.dim() == 2 and hyps.is_contiguous()
+    n_img = img_cap_off.numel() - 1
+    assert img_cap_off.dtype == torch.int32 and img_cap_off.dim() == 1 and img_cap_off.is_contiguous()
+    assert img_ent_off.dtype == torch.int32 and tuple(img_ent_off.shape) == (n_img, 5) and img_ent_off.is_contiguous()
+    assert ref_keys.dtype == torch.int64 and ref_counts.dtype == torch.int32 and ref_keys.shape == ref_counts.shape
+    assert ref_keys.dim() == 1 and ref_keys.is_contiguous() and ref_counts.is_contiguous()
+    assert ref_lens.dtype == torch.int32 and ref_lens.dim() == 1 and ref_lens.is_contiguous()
+    N, T = hyps.shape
+    order = int(order)
+    cols = 4 if order == 0 else 1
+    if out is None:
+        out = torch.empty((N, 4) if order == 0 else (N,), dtype=torch.float64, device=hyps.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == N * cols
+    if stats is not None:
+        assert stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() == N * 10
+    check(_lib.load().isc_bleu_dev_score(hyps.data_ptr(), N, T, int(row_div), img_ent_off.data_ptr(), ref_keys.data_ptr(),
+                                         ref_counts.data_ptr(), img_cap_off.data_ptr(), ref_lens.data_ptr(), n_img, order,
+                                         int(sos_id), int(eos_id), out.data_ptr(), ptr(stats), stream()),
+          'isc_bleu_dev_score')
+    return out
+
+
 def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=None):
     lib = _lib.load()
     M, H = c.shape

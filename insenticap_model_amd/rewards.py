@@ -8,8 +8,12 @@
 * `get_cls_reward` (utils.py:120-151) - sentence-sentiment-classifier reward.
 * `DeviceCiderD` / `get_self_critical_reward_device` - the same CIDEr-D scores formed on the device
   (isc_cider_dev_score) from the host library's table and cooked references; opt-in (Detector.device_cider).
+* `Bleu` / `DeviceBleu` / `get_bleu_scorer` - the reference's other scorer (utils.py:75-77: the per-sentence BLEU-4 list
+  of self_critical/bleu) in the same library and on the device (isc_bleu_dev_score); every reward function above takes
+  either scorer, CIDEr-D stays the default.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -63,6 +67,14 @@ def _load_cider():
     lib.isc_cider_cook_size.argtypes = [C.c_void_p, i64p, i64p, C.c_int64]
     lib.isc_cider_cook_fill.restype = C.c_int64
     lib.isc_cider_cook_fill.argtypes = [C.c_void_p, i64p, i64p, C.c_int64] + [C.c_void_p] * 5
+    i32p = C.POINTER(C.c_int32)
+    lib.isc_bleu_score.restype = C.c_int
+    lib.isc_bleu_score.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_int64, C.c_int64,
+                                   C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), i32p]
+    lib.isc_bleu_cook_size.restype = C.c_int64
+    lib.isc_bleu_cook_size.argtypes = [i64p, i64p, C.c_int64, C.c_int64, C.c_int64]
+    lib.isc_bleu_cook_fill.restype = C.c_int64
+    lib.isc_bleu_cook_fill.argtypes = [i64p, i64p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
     _cider = lib
     return lib
 
@@ -83,6 +95,34 @@ def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
+def _default_threads():
+    """Up to 16 scoring threads, of this process's share of the host's cores (one process per GPU: LOCAL_WORLD_SIZE ranks of
+    a launcher share them - eight ranks x 16 threads on a 64-core host would only queue behind each other)."""
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    try:
+        local_ranks = max(1, int(os.environ.get('LOCAL_WORLD_SIZE', '1')))
+    except ValueError:
+        local_ranks = 1
+    return max(1, min(16, cores // local_ranks))
+
+
+def _flatten_cached(cache, ref_caption_lists, keys):
+    """_flatten with the per-image conversion kept in `cache` under the image ids `keys`."""
+    toks, lens, counts = [], [], []
+    for k, caps in zip(keys, ref_caption_lists):
+        c = cache.get(k)
+        if c is None:
+            c = (np.asarray([int(x) for cap in caps for x in cap], dtype=np.int64),
+                 np.asarray([len(cap) for cap in caps], dtype=np.int64))
+            cache[k] = c
+        toks.append(c[0])
+        lens.append(c[1])
+        counts.append(len(c[1]))
+    cap_off = np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64)
+    img_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return np.concatenate(toks), cap_off, img_off
+
+
 class CiderD:
     """Native CIDEr-D scorer; plays the role of the reference's `CiderD(refs=...)` object
     (ciderD.py:16-48) for `get_self_critical_reward`."""
@@ -96,14 +136,7 @@ class CiderD:
                                        n, sigma)
         if not self._h:
             raise RuntimeError('isc_cider_create failed')
-        # up to 16 scoring threads, of this process's share of the host's cores (one process per GPU: LOCAL_WORLD_SIZE ranks of
-        # a launcher share them - eight ranks x 16 threads on a 64-core host would only queue behind each other)
-        cores = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
-        try:
-            local_ranks = max(1, int(os.environ.get('LOCAL_WORLD_SIZE', '1')))
-        except ValueError:
-            local_ranks = 1
-        self.n_threads = n_threads or max(1, min(16, cores // local_ranks))
+        self.n_threads = n_threads or _default_threads()
         self._gt_cache = {}
 
     def __del__(self):
@@ -124,19 +157,7 @@ class CiderD:
         the per-image conversion is cached across calls (the ground truth of an image never changes)."""
         if keys is None:
             return _flatten(ref_caption_lists)
-        toks, lens, counts = [], [], []
-        for k, caps in zip(keys, ref_caption_lists):
-            c = self._gt_cache.get(k)
-            if c is None:
-                c = (np.asarray([int(x) for cap in caps for x in cap], dtype=np.int64),
-                     np.asarray([len(cap) for cap in caps], dtype=np.int64))
-                self._gt_cache[k] = c
-            toks.append(c[0])
-            lens.append(c[1])
-            counts.append(len(c[1]))
-        cap_off = np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64)
-        img_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        return np.concatenate(toks), cap_off, img_off
+        return _flatten_cached(self._gt_cache, ref_caption_lists, keys)
 
     def score_arrays(self, hyps, ref_caption_lists, flat=None):
         """hyps: int64 [N,T] raw roll-out rows; ref_caption_lists[i]: list of id lists (or `flat` = a
@@ -288,6 +309,215 @@ class DeviceCiderD:
                                    out=out)
 
 
+def _bleu_corpus(stats, n=4):
+    """The corpus figures of bleu_scorer.py:247-259 from the summed integer statistics, in Python floats."""
+    small, tiny = 1e-9, 1e-15
+    tot = [int(x) for x in np.asarray(stats, dtype=np.int64).reshape(-1, 10).sum(axis=0)]
+    testlen, reflen, guess, correct = tot[0], tot[1], tot[2:6], tot[6:10]
+    bleus, bleu = [], 1.
+    for k in range(n):
+        bleu *= float(correct[k] + tiny) / (guess[k] + small)
+        bleus.append(bleu ** (1. / (k + 1)))
+    ratio = (testlen + tiny) / (reflen + small)
+    if ratio < 1:
+        for k in range(n):
+            bleus[k] *= math.exp(1 - 1 / ratio)
+    return bleus
+
+
+class Bleu:
+    """Native BLEU scorer; plays the role of the reference's `Bleu(n)` object (self_critical/bleu/bleu.py) for
+    `get_self_critical_reward`, whose reward is the per-sentence BLEU-4 list (utils.py:75-77) - here BLEU-`order`.  It
+    keeps no document frequencies, hence takes no corpus.  Rows and references are normalised as the CIDEr-D scorer
+    normalises them (utils._array_to_str)."""
+
+    def __init__(self, sos_token, eos_token, n=4, order=4, n_threads=None):
+        if not 1 <= int(n) <= 4 or not 1 <= int(order) <= int(n):
+            raise ValueError('BLEU: 1 <= order <= n <= 4, got n = %r, order = %r' % (n, order))
+        self._lib = _load_cider()
+        self.sos, self.eos = int(sos_token), int(eos_token)
+        self.n, self.order = int(n), int(order)
+        self.n_threads = n_threads or _default_threads()
+        self._gt_cache = {}
+
+    def flatten_refs(self, ref_caption_lists, keys=None):
+        """As CiderD.flatten_refs: with `keys` (image ids) the per-image conversion is cached across calls."""
+        if keys is None:
+            return _flatten(ref_caption_lists)
+        return _flatten_cached(self._gt_cache, ref_caption_lists, keys)
+
+    def _score(self, hyps, ref_caption_lists, flat, row_div, want_stats):
+        hyps = np.ascontiguousarray(hyps, dtype=np.int64)
+        toks, cap_off, img_off = flat if flat is not None else _flatten(ref_caption_lists)
+        N = hyps.shape[0]
+        out = np.empty((N, 4), dtype=np.float64)
+        stats = np.empty((N, 10), dtype=np.int32) if want_stats else None
+        rc = self._lib.isc_bleu_score(_p(hyps), N, hyps.shape[1], hyps.shape[1], _p(toks), _p(cap_off), _p(img_off),
+                                      len(img_off) - 1, int(row_div), self.sos, self.eos, self.n_threads,
+                                      out.ctypes.data_as(C.POINTER(C.c_double)),
+                                      stats.ctypes.data_as(C.POINTER(C.c_int32)) if want_stats else None)
+        if rc != 0:
+            raise RuntimeError('isc_bleu_score failed (%d)' % rc)
+        return out, stats
+
+    def score4(self, hyps, ref_caption_lists, flat=None, row_div=1):
+        """hyps: int64 [N,T] raw roll-out rows, row r against ref_caption_lists[r // row_div] (or `flat` = a flatten_refs()
+        result) -> float64 [N,4]: the per-sentence BLEU-1 .. BLEU-4."""
+        return self._score(hyps, ref_caption_lists, flat, row_div, False)[0]
+
+    def score_arrays(self, hyps, ref_caption_lists, flat=None, row_div=1):
+        """-> float64 [N]: BLEU-`order` (order 4 = the reference's reward, scores[3])."""
+        return np.ascontiguousarray(self.score4(hyps, ref_caption_lists, flat, row_div)[:, self.order - 1])
+
+    def stats(self, hyps, ref_caption_lists, flat=None, row_div=1):
+        """-> int32 [N,10]: testlen, reflen, guess[0..3], correct[0..3] (bleu_scorer.py:63-86, option 'closest')."""
+        return self._score(hyps, ref_caption_lists, flat, row_div, True)[1]
+
+    def compute_score(self, gts, res):
+        """The reference wrapper's call (bleu.py:24-59): gts = {image_id: [reference strings]}, res = [{'image_id': id,
+        'caption': [string]}] -> (corpus BLEU-1..n, n per-sentence lists).  The strings are what utils._array_to_str
+        writes - ids joined by blanks, <EOS> last and nowhere else, no leading <SOS>; anything else raises ValueError."""
+        def ids(text):
+            try:
+                w = [int(x) for x in text.split()]
+            except ValueError:
+                w = None
+            if not w or w[-1] != self.eos or self.eos in w[:-1] or w[0] == self.sos:
+                raise ValueError('BLEU: %r is no normalised caption (ids, <EOS> = %d last)' % (text, self.eos))
+            return w
+        rows, refs = [], []
+        for item in res:
+            hypo, ref = item['caption'], gts[item['image_id']]
+            assert type(hypo) is list and len(hypo) == 1 and type(ref) is list and len(ref) >= 1
+            rows.append(ids(hypo[0]))
+            refs.append([ids(r) for r in ref])
+        hyps = np.full((len(rows), max(len(w) for w in rows)), self.eos, dtype=np.int64)
+        for i, w in enumerate(rows):
+            hyps[i, :len(w)] = w
+        scores, stats = self._score(hyps, refs, None, 1, True)
+        return _bleu_corpus(stats, self.n), [scores[:, k].tolist() for k in range(self.n)]
+
+    def method(self):
+        return 'Bleu'
+
+    def cook_refs(self, captions):
+        """The references of ONE image cooked for the device: (keys uint64 [E], counts int32 [E], ent_off int32 [5], lens
+        int32 [C]) - the distinct n-grams over all captions with their largest count in one caption, grouped by order
+        (within an order: captions ascending, first occurrence within a caption), and the normalised lengths."""
+        toks, cap_off, _ = _flatten([captions])
+        n_caps = len(cap_off) - 1
+        E = self._lib.isc_bleu_cook_size(_p(toks), _p(cap_off), n_caps, self.sos, self.eos)
+        if E == -3:
+            raise ValueError('the device BLEU scorer needs every token id <= %d' % CIDER_MAX_ID)
+        if E < 0:
+            raise RuntimeError('isc_bleu_cook_size failed (%d)' % E)
+        keys, counts = np.empty(E, dtype=np.uint64), np.empty(E, dtype=np.int32)
+        ent_off, lens = np.empty(5, dtype=np.int32), np.empty(n_caps, dtype=np.int32)
+        got = self._lib.isc_bleu_cook_fill(_p(toks), _p(cap_off), n_caps, self.sos, self.eos, keys.ctypes.data,
+                                           counts.ctypes.data, ent_off.ctypes.data, lens.ctypes.data)
+        if got != E:
+            raise RuntimeError('isc_bleu_cook_fill failed (%d)' % got)
+        return keys, counts, ent_off, lens
+
+    def to_device(self, device, vocab_size):
+        """The device twin of this scorer (DeviceBleu).  ValueError when vocab_size > 65535."""
+        return DeviceBleu(self, device, vocab_size)
+
+
+class BleuRefPack:
+    """The cooked references of one batch on the device (DeviceBleu.pack_refs): views into ONE uploaded buffer."""
+    __slots__ = ('n_img', 'buffer', 'keys', 'counts', 'ent_off', 'img_cap_off', 'lens')
+
+
+class DeviceBleu:
+    """BLEU on the device (isc_bleu_dev_score): the twin of a host `Bleu`, whose cooked references it reads.  One wave per
+    hypothesis; the integer statistics are the host's exactly, the scores agree to the last bits of pow / exp / division
+    (tests: 1e-12 relative)."""
+
+    def __init__(self, host, device, vocab_size):
+        if int(vocab_size) > CIDER_MAX_ID + 1:
+            raise ValueError('the device BLEU scorer packs an id into 16 bits: vocab_size <= %d, got %d'
+                             % (CIDER_MAX_ID + 1, vocab_size))
+        self.host, self.device = host, torch.device(device)
+        self._cache = {}
+
+    def pack_refs(self, ref_caption_lists, keys=None):
+        """The batch's references cooked (per image, cached by `keys` - image ids), concatenated and uploaded as one buffer
+        through pinned memory, non-blocking, as DeviceCiderD.pack_refs does.  An image without references raises."""
+        cooked = []
+        for i, caps in enumerate(ref_caption_lists):
+            k = None if keys is None else keys[i]
+            c = None if k is None else self._cache.get(k)
+            if c is None:
+                if len(caps) == 0:
+                    raise RuntimeError('BLEU: image %d of the batch has no reference caption' % i)
+                c = self.host.cook_refs(caps)
+                if k is not None:
+                    self._cache[k] = c
+            cooked.append(c)
+        n_img = len(cooked)
+        ents_per = np.asarray([len(c[0]) for c in cooked], dtype=np.int64)
+        caps_per = np.asarray([len(c[3]) for c in cooked], dtype=np.int64)
+        n_ent, n_cap = int(ents_per.sum()), int(caps_per.sum())
+        if n_ent > 0x7fffffff:
+            raise RuntimeError('BLEU: more than 2^31 - 1 reference n-grams in one batch')
+        ent_base = np.concatenate([[0], np.cumsum(ents_per)[:-1]])
+        # one pinned buffer, every region 8-byte aligned: keys | counts, ent_off, img_cap_off, lens (int32)
+
+        def pad8(b):
+            return (b + 7) // 8 * 8
+        sizes = [8 * n_ent, pad8(4 * n_ent), pad8(20 * n_img), pad8(4 * (n_img + 1)), pad8(4 * n_cap)]
+        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+        host = torch.empty(offs[-1], dtype=torch.uint8)
+        if self.device.type == 'cuda':
+            host = host.pin_memory()
+        raw = host.numpy()
+
+        def region(j, dtype, count):
+            return raw[offs[j]:offs[j] + count * np.dtype(dtype).itemsize].view(dtype)
+        np.concatenate([c[0] for c in cooked], out=region(0, np.uint64, n_ent))
+        np.concatenate([c[1] for c in cooked], out=region(1, np.int32, n_ent))
+        ent_off = region(2, np.int32, 5 * n_img).reshape(n_img, 5)
+        np.stack([c[2] for c in cooked], out=ent_off)
+        ent_off += ent_base.astype(np.int32)[:, None]
+        img_cap = region(3, np.int32, n_img + 1)
+        img_cap[0] = 0
+        np.cumsum(caps_per, out=img_cap[1:])
+        np.concatenate([c[3] for c in cooked], out=region(4, np.int32, n_cap))
+        dev = host.to(self.device, non_blocking=True)
+
+        def view(j, dtype, count, size):
+            return dev[offs[j]:offs[j] + count * size].view(dtype)
+        p = BleuRefPack()
+        p.n_img, p.buffer = n_img, dev
+        p.keys, p.counts = view(0, torch.int64, n_ent, 8), view(1, torch.int32, n_ent, 4)
+        p.ent_off = view(2, torch.int32, 5 * n_img, 4).view(n_img, 5)
+        p.img_cap_off, p.lens = view(3, torch.int32, n_img + 1, 4), view(4, torch.int32, n_cap, 4)
+        return p
+
+    def _launch(self, hyps, pack, row_div, order, out, stats=None):
+        from . import ops
+        if hyps.shape[0] != pack.n_img * int(row_div):
+            raise ValueError('BLEU: %d rows for %d images x %d rows per image' % (hyps.shape[0], pack.n_img, row_div))
+        hyps = hyps if hyps.is_contiguous() else hyps.contiguous()
+        return ops.bleu_dev_score(hyps, row_div, pack.ent_off, pack.keys, pack.counts, pack.img_cap_off, pack.lens, order,
+                                  self.host.sos, self.host.eos, out=out, stats=stats)
+
+    def score(self, hyps, pack, row_div=1, out=None):
+        """hyps: int64 [N, T] raw roll-out rows on the device, row r of image r // row_div of `pack` -> float64 [N] on the
+        device: BLEU-`order` of the host scorer.  T > 63 raises (the caller keeps the host scorer for such rows)."""
+        return self._launch(hyps, pack, row_div, self.host.order, out)
+
+    def score4(self, hyps, pack, row_div=1, out=None, stats=None):
+        """-> float64 [N, 4] on the device; `stats`: an int32 [N, 10] tensor to fill with the integer statistics."""
+        return self._launch(hyps, pack, row_div, 0, out, stats)
+
+
+def get_bleu_scorer(sos_token, eos_token, order=4):
+    """The BLEU twin of get_ciderd_scorer: the reference builds `Bleu()` and reads scores[3] (utils.py:75-77)."""
+    return Bleu(sos_token, eos_token, order=order)
+
+
 def get_ciderd_scorer(split_captions, sos_token, eos_token):
     """utils.py:38-53: `split_captions` = {split: {fn: [[ids], ...]}}; document frequencies over all images."""
     captions = {}
@@ -297,9 +527,10 @@ def get_ciderd_scorer(split_captions, sos_token, eos_token):
 
 
 def self_critical_scores(captions, fns, ground_truth, scorer):
-    """CIDEr-D of one token matrix [B,T] (host ndarray) against the images' references -> float64 [B]: one half of
-    get_self_critical_reward, for callers that score the sampled captions while the device still decodes the greedy ones."""
-    if not isinstance(scorer, CiderD):
+    """CIDEr-D (with a `Bleu`: BLEU-`order`) of one token matrix [B,T] (host ndarray) against the images' references ->
+    float64 [B]: one half of get_self_critical_reward, for callers that score the sampled captions while the device still
+    decodes the greedy ones."""
+    if not isinstance(scorer, (CiderD, Bleu)):
         raise Exception('do not support this scorer: %s' % type(scorer))
     assert captions.shape[0] == len(fns)
     flat = scorer.flatten_refs([ground_truth[fn] for fn in fns], keys=list(fns))
@@ -307,14 +538,15 @@ def self_critical_scores(captions, fns, ground_truth, scorer):
 
 
 def get_self_critical_reward(sample_captions, greedy_captions, fns, ground_truth, sos_token, eos_token, scorer):
-    """utils.py:56-83: CIDEr-D(sample) - CIDEr-D(greedy), repeated over T -> float64 ndarray [B,T]."""
+    """utils.py:56-83: CIDEr-D(sample) - CIDEr-D(greedy), repeated over T -> float64 ndarray [B,T]; with a `Bleu` the
+    scores are its per-sentence BLEU-`order` (utils.py:75-77)."""
     batch_size = len(fns)
     if torch.is_tensor(sample_captions):
         sample_captions = sample_captions.cpu().numpy()
     if torch.is_tensor(greedy_captions):
         greedy_captions = greedy_captions.cpu().numpy()
     assert sample_captions.shape[0] == greedy_captions.shape[0] == batch_size
-    if not isinstance(scorer, CiderD):
+    if not isinstance(scorer, (CiderD, Bleu)):
         raise Exception('do not support this scorer: %s' % type(scorer))
     flat = scorer.flatten_refs([ground_truth[fn] for fn in fns], keys=list(fns))
     scores = scorer.score_arrays(sample_captions, None, flat) - scorer.score_arrays(greedy_captions, None, flat)
@@ -325,7 +557,7 @@ def get_self_critical_reward_device(sample_captions, greedy_captions, pack, dev_
     """get_self_critical_reward on the device: token matrices [B, T] on the device, `pack` = dev_scorer.pack_refs(...) of
     the batch -> float32 [B, T] on the device: (CIDEr-D(sample) - CIDEr-D(greedy)) in fp64, rounded to float32, repeated
     over T - the host form followed by `.astype('float32')`."""
-    if not isinstance(dev_scorer, DeviceCiderD):
+    if not isinstance(dev_scorer, (DeviceCiderD, DeviceBleu)):
         raise Exception('do not support this scorer: %s' % type(dev_scorer))
     assert sample_captions.shape == greedy_captions.shape
     scores = dev_scorer.score(sample_captions, pack) - dev_scorer.score(greedy_captions, pack)
