@@ -1062,6 +1062,87 @@ int64_t isc_senti_det_workspace_bytes(int B, int h, int w, int C, int n_convs, i
 int isc_senti_det_fwd(const isc_senti_det_problem *prob_host, void *stream);
 long long isc_senti_det_launches(int kind);
 
+/* The concept detector (concept_detector.py; train_cpt.py, detect_concepts.py, test_cpt.py) - csrc/concept.hip.  One
+ * wave64 per row, no atomics, every sum in a fixed order (two calls give the same bits), no allocation and no host read:
+ * capturable.
+ *
+ * isc_concept_head: logits [B, C] fp32 (leading dimension ld >= C; C any positive number) ->
+ *   probs  [B, C]   sigmoid(logits)                                   (contiguous; optional)
+ *   idx    [B, num] int64: the `num` best concepts of a row, best first   (optional)
+ *   scores [B, num] their probabilities                               (optional)
+ *   words  [B, num] int64 = concept_word[idx] through the [C] int64 table of vocabulary ids (optional; needs the table)
+ *   hits [B], n_true [B] int32 with a 0/1 target matrix [B, C] (uint8, or int64 with targets_i64 != 0): n_true = the
+ *     row's targets that are set, hits = how many of the picked concepts are set - numerator and denominators of the
+ *     precision / recall loop of train_cpt.py:113-122 (the picks are distinct: a set intersection).  Optional.
+ * ORDER: the larger LOGIT first; on equal logits the lower index first; -0.0 equals +0.0; +-inf are ordinary values; a
+ * NaN ranks below every number (lower index first among NaNs) and raises ISC_STATUS_NONFINITE_STATS.  The reference
+ * sorts the fp32 probabilities with an unstable sort (concept_detector.py:28); sigmoid is monotone, so this is the
+ * reference's answer wherever that is defined, and a fixed one where probabilities saturate or tie.
+ * num outside [1, ISC_CONCEPT_MAX_NUM] or > C, B < 1, C < 1, ld < C: ISC_E_SHAPE, nothing is launched.
+ *
+ * isc_concept_loss: MultiLabelClsLoss (concept_detector.py:44-58) from the LOGITS:
+ *   out3 = { -mean(t log s(z)), -mean((1 - t) log(1 - s(z))), their sum }  over all B C elements, evaluated as
+ *   t softplus(-z) and (1 - t) softplus(z), softplus(x) = max(x, 0) + log1p(exp(-|x|)): finite for every finite z (the
+ *   reference's result.log() of a saturated fp32 sigmoid gives inf or NaN there).  Elements in fp32, sums in fp64: per-row
+ *   wave sums (lane l: columns l, l + 64, ... ascending, then the butterfly) into the workspace, then one wave over the
+ *   rows in the same fixed order.  dz (optional, [B, C] contiguous) = (s(z) - t) g / (B C), written in the same pass.
+ *   targets [B, C] contiguous, uint8 or (targets_i64 != 0) int64 - any non-zero value is 1; both give the same bits.
+ *   workspace: isc_concept_loss_workspace_bytes(B) bytes, 8-byte aligned.  Two launches.
+ *
+ * isc_senti_words_from_concepts: preprocess.py:288-301 on the device.  idx [B, num] int64 concept indices (leading
+ * dimension idx_ld; an index outside [0, C) contributes nothing), a CSR table off [C + 1] int32, word [nnz] int64
+ * (vocabulary ids), score [nnz] float64.  Per image the entries of its concepts are taken in concept order, then list
+ * order; the scores are summed per word in float64 in that order (the host's bits); the words are ordered by sum,
+ * descending, exactly equal sums in first-occurrence order (Python's stable sort over the dict's insertion order); the
+ * first n_out <= ISC_SENTI_WORDS_MAX_OUT ids go to out [B, n_out] int64, the rest - all of it for an image without an
+ * entry - is pad_id.  One wave per image, candidates in LDS.  CAP: an image may stage num * max_list <=
+ * ISC_SENTI_WORDS_CAP candidates, max_list = the longest list of the table as isc_senti_words_pack_check (host
+ * offsets) reports it: a larger product is ISC_E_SHAPE there and here, nothing is launched - never a silent cut. */
+#define ISC_CONCEPT_MAX_NUM 16
+#define ISC_SENTI_WORDS_CAP 1024
+#define ISC_SENTI_WORDS_MAX_OUT 20
+int isc_concept_head(const float *logits, int64_t ld, int B, int C, int num, float *probs, int64_t *idx, float *scores,
+                     const int64_t *concept_word, int64_t *words, const void *targets, int targets_i64, int32_t *hits,
+                     int32_t *n_true, void *stream);
+int64_t isc_concept_loss_workspace_bytes(int B);
+int isc_concept_loss(const float *logits, int64_t ld, int B, int C, const void *targets, int targets_i64, float g,
+                     void *workspace, int64_t workspace_bytes, float *out3, float *dz, void *stream);
+int isc_senti_words_cap(void);
+int isc_senti_words_pack_check(const int32_t *off_host, int C, int num, int *max_list_out);
+int isc_senti_words_from_concepts(const int64_t *idx, int64_t idx_ld, int B, int num, int C, const int32_t *off,
+                                  const int64_t *word, const double *score, int max_list, int n_out, int64_t pad_id,
+                                  int64_t *out, void *stream);
+
+/* The concept detector's eval forward (concept_detector.py:10-18,24-30): h1 = relu(feats W0^T + b0); h2 = relu(h1 W2^T +
+ * b2); logits = h2 W5^T + b5; then isc_concept_head - FOUR library launches (besides the optional conversion below): three isc_linear_fwd (whose dispatch they
+ * inherit: the few-row route, the split-f16 routes, the exact engine under isc_set_h3_mode(0)) and the head.
+ * feats [B, F] fp32 or (feats_f16 = 1) _Float16 with leading dimension feats_ld in elements: float16 rows are read
+ * natively where isc_linear_f16_native says so, else converted once (isc_f16_to_f32) into the workspace.  W0 [H, F],
+ * W2 [H, H], W5 [C, H] contiguous fp32 as the state_dict stores them.  Outputs as isc_concept_head's (all optional);
+ * logits [B, C] optional (16-byte aligned).  splitk_ws: optional workspace handed to the linear launches.
+ * F % 32 == 0, H % 32 == 0 (isc_linear_fwd contracts in 32-deep chunks), C >= 1, 1 <= num <= min(C,
+ * ISC_CONCEPT_MAX_NUM), feats_ld >= F: anything else ISC_E_SHAPE; feats not 16-byte aligned or feats_ld % 4 != 0
+ * ISC_E_ALIGN; a workspace under isc_concept_workspace_bytes(B, F, H, C) ISC_E_WORKSPACE - all before any launch. */
+typedef struct {
+    const void *feats;
+    int64_t feats_ld;
+    int32_t feats_f16, B, F, H, C, num;
+    const float *w0, *b0, *w2, *b2, *w5, *b5;
+    const int64_t *concept_word;
+    void *workspace;
+    int64_t workspace_bytes;
+    float *splitk_ws;
+    int64_t splitk_ws_floats;
+    float *logits, *probs;
+    int64_t *idx;
+    float *scores;
+    int64_t *words;
+} isc_concept_problem;
+int64_t isc_concept_workspace_bytes(int B, int F, int H, int C);
+int isc_concept_fwd(const isc_concept_problem *prob_host, void *stream);
+long long isc_concept_launches(void);     /* library launches enqueued by isc_concept_fwd so far: four per call besides the
+                                           * optional isc_f16_to_f32 conversion, which has its own counter (test hook) */
+
 /* Power-of-two gradient scale for a backward sweep whose contractions run on the split-f16 engine: out4[0..1] = { S, 1/S },
  * S = 2^k with max |x| over the given tensors (HOST arrays of device pointers / element counts, <= ISC_SCALE_SRC_MAX)
  * brought into [2^-4, 2^-3); S = 1 when they are all zero.  out4[2..3] are state words of the multi-workgroup reduction:

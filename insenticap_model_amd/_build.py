@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libinsenticap_hip.so')
 SOURCES = ['gemm_f32.hip', 'attention.hip', 'pointwise.hip', 'backward.hip', 'step.hip', 'rows.hip', 'sent_cls.hip',
-           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip']
+           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'concept.hip']
 CIDER_KEY_H = os.path.join(CSRC, 'cider_key.h')      # the n-gram key: read by cider_dev.hip, bleu_dev.hip AND cider.cpp
 HEADERS = [os.path.join(CSRC, 'common.h'),
            os.path.join(os.path.dirname(HERE), 'include', 'insenticap_hip.h'), CIDER_KEY_H]

@@ -176,6 +176,19 @@ class SentiDetProblem(C.Structure):
                 _f('logits maps labels scores conv_out', C.c_void_p))
 
 
+CONCEPT_MAX_NUM = 16
+SENTI_WORDS_CAP = 1024
+SENTI_WORDS_MAX_OUT = 20
+
+
+class ConceptProblem(C.Structure):
+    """isc_concept_problem: the concept detector's eval forward (csrc/concept.hip)."""
+    _fields_ = ([('feats', C.c_void_p), ('feats_ld', C.c_int64)] + _f('feats_f16 B F H C num', C.c_int32) +
+                _f('w0 b0 w2 b2 w5 b5 concept_word workspace', C.c_void_p) + [('workspace_bytes', C.c_int64),
+                ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)] +
+                _f('logits probs idx scores words', C.c_void_p))
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -313,6 +326,18 @@ SIGNATURES = {
     'isc_senti_det_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'isc_senti_det_fwd': (C.c_int, [C.POINTER(SentiDetProblem), C.c_void_p]),
     'isc_senti_det_launches': (C.c_longlong, [C.c_int]),
+    'isc_concept_head': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_concept_loss_workspace_bytes': (C.c_int64, [C.c_int]),
+    'isc_concept_loss': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_senti_words_cap': (C.c_int, []),
+    'isc_senti_words_pack_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    'isc_senti_words_from_concepts': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    'isc_concept_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_concept_fwd': (C.c_int, [C.POINTER(ConceptProblem), C.c_void_p]),
+    'isc_concept_launches': (C.c_longlong, []),
     'isc_grad_scale': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
     'isc_splitk_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'isc_h3_weights_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),

@@ -74,3 +74,35 @@ def write_results(result_dir, epoch, results):
         json.dump(results, f)
     with open(os.path.join(result_dir, 'result_%d.txt' % epoch), 'w') as f:
         f.write(''.join(r['caption'] + '\n' for r in results))
+
+
+def save_concept_checkpoint(directory, epoch, model, optimizer, settings, idx2concept, dataset_name, train_loss=0.0,
+                            val_loss=0.0):
+    """The concept detector's checkpoint as train_cpt.py:140-150 writes it: {epoch, model, optimizer, settings,
+    idx2concept, dataset_name} under model_<epoch>_<train loss>_<val loss>_<time>.pth."""
+    chk = {'epoch': epoch, 'model': model.state_dict(), 'optimizer': optimizer.state_dict(), 'settings': settings,
+           'idx2concept': idx2concept, 'dataset_name': dataset_name}
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, 'model_%d_%.4f_%.4f_%s.pth' % (epoch, train_loss, val_loss,
+                                                                  time.strftime('%m%d-%H%M')))
+    torch.save(chk, path)
+    return path
+
+
+def load_concept_checkpoint(path, model=None, optimizer=None, **expected):
+    """Resume as train_cpt.py:34-47 does (`expected`: settings / idx2concept / dataset_name must equal the file's), or -
+    model=None - build the detector from the file as detect_concepts.py:15-23 / test_cpt.py:11-19 do.
+    Returns (model, epoch, lr); lr is None without an optimizer."""
+    chk = torch.load(path, map_location=lambda s, l: s, weights_only=False)
+    for key in ('settings', 'idx2concept', 'dataset_name'):
+        if key in expected and expected[key] != chk[key]:
+            raise AssertionError('%s and resume model %s are different' % (key, key))
+    if model is None:
+        from .helper_nets import ConceptDetector
+        model = ConceptDetector(chk['idx2concept'], chk['settings'])
+    model.load_state_dict(chk['model'])
+    lr = None
+    if optimizer is not None and 'optimizer' in chk:
+        optimizer.load_state_dict(chk['optimizer'])
+        lr = optimizer.param_groups[0]['lr']
+    return model, chk['epoch'], lr

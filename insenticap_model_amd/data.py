@@ -11,6 +11,9 @@
   image) is replaced by one memory-mapped `[N, ...]` fp32 array + a name index, so a batch is a row gather.  The
   reference's own `.h5` feature files are taken as they are where h5py exists (`H5FeatureStore`: a path ending in
   .h5 / .hdf5 handed to a Dataset class; opened once per process) and converted once with `FeatureStore.from_h5`.
+* `ConceptDataset` / `concept_collate_fn` / `get_concept_dataloader` (dataloader.py:111-115,230-245,338-345), `tag_concepts`
+  (what detect_concepts.py writes) and `SentimentWordTable` (preprocess.py:280-302 on the host and on the device): the
+  concept pre-stage, at the end of this file.
 * `DevicePrefetcher` - pinned host staging + asynchronous H2D copies on a side HIP stream, one batch
   ahead of the consumer: at >10k captions/s the 303 KB of fp32 region features per caption
   (~3 GB/s and more) must overlap with decoding instead of serialising in front of it.
@@ -585,3 +588,121 @@ class DevicePrefetcher:
             except StopIteration:
                 nxt = None
             yield cur
+
+
+# ---------------------------------------------------------------------------- concept detector (dataloader.py:111-115,230-245,338-345)
+def concept_collate_fn(dataset):
+    """The reference's 'concept' collate (dataloader.py:111-115): items (fn, fc [F], 0/1 vector [C]) -> (fns, fc_feats
+    [B, F] fp32 - float16 when every item is -, targets [B, C] int64).  (create_collate_fn keeps the decoder path's four
+    names; this one stands beside it.)"""
+    fns, fcs, cpts = zip(*dataset)
+    return fns, _feats(fcs), torch.from_numpy(np.asarray(cpts).astype(np.int64))
+
+
+class ConceptDataset(torch.utils.data.Dataset):
+    """dataloader.py:230-245: item = (fn, fc [F], int16 vector [num_cpts] with ones at the image's concept indices)."""
+
+    def __init__(self, fc_feats, img_concepts, num_cpts):
+        self.fc_feats = _store(fc_feats)
+        self.concepts = list(img_concepts.items())
+        self.num_cpts = num_cpts
+
+    def __getitem__(self, index):
+        fn, cpts_idx = self.concepts[index]
+        cpts = np.zeros(self.num_cpts, dtype=np.int16)
+        cpts[cpts_idx] = 1
+        return fn, _item(self.fc_feats[fn]), cpts
+
+    def __len__(self):
+        return len(self.concepts)
+
+
+def get_concept_dataloader(fc_feats, img_concepts, num_cpts, batch_size, num_workers=0, shuffle=True):
+    """dataloader.py:338-345."""
+    return _loader(ConceptDataset(fc_feats, img_concepts, num_cpts), batch_size, num_workers, shuffle, concept_collate_fn)
+
+
+class SentimentWordTable:
+    """The sentiment words of an image from its detected concepts (preprocess.py:280-302): per word the scores of the
+    concepts' (word, score) lists are summed, the words sorted by sum (descending, stable), 20 kept.
+
+    Built from the `sentiment_detector.json` mapping {concept: [[word, score], ...]} and `word2idx` (a word the
+    vocabulary lacks raises KeyError, as train_rl.py:129 does).  `lookup` is the host form over concept NAMES; `forward`
+    is the device kernel (isc_senti_words_from_concepts) over concept INDICES [B, num] - it needs `idx2concept`, the
+    detector's index -> name list.  The kernel stages at most ops.SENTI_WORDS_CAP = 1024 candidates per image:
+    `num_concepts` x the longest list above that raises ValueError here, at build time - never a silent cut."""
+    KEEP = 20               # preprocess.py:301
+
+    def __init__(self, sentiment_detector, word2idx, idx2concept=None, num_concepts=5):
+        self.lists = {c: [(int(word2idx[w]), float(s)) for w, s in pairs] for c, pairs in sentiment_detector.items()}
+        self.idx2concept = list(idx2concept) if idx2concept is not None else None
+        self.num_concepts = int(num_concepts)
+        self._csr, self._dev = None, {}
+        if self.idx2concept is not None:
+            off, word, score = [0], [], []
+            for c in self.idx2concept:
+                for w, s in self.lists.get(c, ()):
+                    word.append(w)
+                    score.append(s)
+                off.append(len(word))
+            from . import ops
+            self.max_list = ops.senti_words_pack_check(off, self.num_concepts)      # ValueError beyond the cap
+            self._csr = (torch.tensor(off, dtype=torch.int32), torch.tensor(word, dtype=torch.int64),
+                         torch.tensor(score, dtype=torch.float64))
+
+    def lookup(self, concept_lists):
+        """[[concept name, ...] per image] -> [[vocabulary id, ...] per image], at most 20 each, best first: the pure-Python
+        host form (get_img_det_sentiments followed by train_rl.py:129)."""
+        out = []
+        for concepts in concept_lists:
+            sentis = []
+            for con in concepts:
+                sentis.extend(self.lists.get(con, []))
+            if sentis:
+                tmp = {}
+                for w, s in sentis:
+                    tmp[w] = tmp.get(w, 0.0) + s
+                sentis = sorted(tmp.items(), key=lambda p: p[1], reverse=True)
+                sentis = [w for w, _ in sentis]
+            out.append(sentis[:self.KEEP])
+        return out
+
+    def lookup_tensor(self, concept_lists, n_out=10, pad_id=0):
+        """`lookup` as the collates hand it on: int64 [B, n_out], filled with pad_id."""
+        return _pad_rows(self.lookup(concept_lists), n_out, pad_id)
+
+    def _on(self, device):
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            t = self._dev[device] = tuple(x.to(device) for x in self._csr)
+        return t
+
+    def forward(self, idx, n_out=10, pad_id=0):
+        """idx [B, num] int64 concept indices on the device -> int64 [B, n_out] vocabulary ids there; no host read."""
+        if self._csr is None:
+            raise ValueError('SentimentWordTable.forward needs idx2concept (the detector\'s index -> name list)')
+        from . import ops
+        if idx.shape[1] > self.num_concepts:
+            ops.senti_words_pack_check(self._csr[0].tolist(), idx.shape[1])
+            self.num_concepts = idx.shape[1]
+        off, word, score = self._on(idx.device)
+        return ops.senti_words_from_concepts(idx, off, word, score, self.max_list, n_out, pad_id)
+
+    __call__ = forward
+
+
+def tag_concepts(model, fc_store, num, batch=100, fns=None):
+    """detect_concepts.py:32-43: {fn: [concept words, best first]} for every image of `fc_store` (any fn -> fc array
+    mapping with keys(), or a path - see the Dataset classes), `batch` images per forward, ONE read-back per batch."""
+    store = _store(fc_store)
+    fns = list(store.keys()) if fns is None else list(fns)
+    device = next(model.parameters()).device
+    out = {}
+    for i in range(0, len(fns), batch):
+        cur = fns[i:i + batch]
+        feats = _feats([_item(store[fn]) for fn in cur])
+        feats = feats.to(device) if isinstance(feats, RowGather) else feats.to(device, non_blocking=True)
+        _, concepts, _ = model.sample(feats, num)
+        out.update(zip(cur, concepts))
+    return out

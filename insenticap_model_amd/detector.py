@@ -180,6 +180,38 @@ class Detector(nn.Module):
     def set_lms(self, lms):
         self.lms = lms
 
+    def set_concept_detector(self, cd, senti_table=None, num_concepts=5, num_sentiments=10):
+        """Gives the detector the pre-stage it lacked: a helper_nets.ConceptDetector (after `set_vocabulary`) and,
+        optionally, a data.SentimentWordTable built with the detector's idx2concept.  With it, `tag` produces the
+        cpts_tensor / sentis_tensor of images never seen before, `sample` derives the sentiment words of its image and
+        `forward` tags a batch whose cpts_tensor / sentis_tensor is None.  The concept detector is frozen here and is NOT
+        a registered submodule: state_dict and the RL checkpoint layout stay the reference's."""
+        if cd is not None and cd._concept_word is None:
+            raise ValueError('set_concept_detector: call ConceptDetector.set_vocabulary(word2idx) first')
+        if senti_table is not None and senti_table.idx2concept is None:
+            raise ValueError('set_concept_detector: the SentimentWordTable needs idx2concept')
+        if cd is not None:
+            cd.eval()
+        self.__dict__['concept_detector'] = cd
+        self.__dict__['senti_table'] = senti_table
+        self.__dict__['num_concepts'], self.__dict__['num_sentiments'] = int(num_concepts), int(num_sentiments)
+        return self
+
+    @torch.no_grad()
+    def tag(self, fc_feats):
+        """fc_feats [B, F] on the device -> (cpts_tensor [B, num_concepts] int64 vocabulary ids of the detected concepts,
+        sentis_tensor [B, num_sentiments] int64 ids of their sentiment words - None without a table), on the device,
+        nothing read back: what the loaders take from img_det_concepts.json / img_det_sentiments.json."""
+        cd = self.__dict__.get('concept_detector')
+        if cd is None:
+            raise ValueError('Detector.tag needs set_concept_detector')
+        if next(cd.parameters()).device != fc_feats.device:
+            cd.to(fc_feats.device)
+        idx, _, words = cd.sample_device(fc_feats, self.num_concepts)
+        table = self.__dict__.get('senti_table')
+        sentis = table.forward(idx, self.num_sentiments, self.pad_id) if table is not None else None
+        return words, sentis
+
     def forward(self, data, data_type, training):
         """data = (caption loader[, seq2seq loader]); data_type 'fact' | 'senti'. Returns the dict of
         loss sums divided by len(data) - the tuple length, as the reference does (decoder.py:178-179)."""
@@ -244,6 +276,14 @@ class Detector(nn.Module):
             fc_feats, att_feats = ops.to_device(fc_feats, device), ops.to_device(att_feats, device)
             # (ops.to_device: through pinned memory, non-blocking - `x.to(device)` from pageable memory holds the host until the
             # stream gets there, i.e. until the previous iteration has finished)
+            if cpts_tensor is None or sentis_tensor is None:
+                # an untagged batch: concepts and sentiment words from the concept detector, on the device, ahead of the
+                # iteration (graph-served or eager: both take the tensors as inputs, as before)
+                t_cpts, t_sentis = self.tag(fc_feats)
+                if sentis_tensor is None and t_sentis is None:
+                    raise ValueError('Detector.forward: the batch carries no sentis_tensor and no SentimentWordTable is set')
+                cpts_tensor = t_cpts if cpts_tensor is None else cpts_tensor
+                sentis_tensor = t_sentis if sentis_tensor is None else sentis_tensor
             cpts_tensor, sentis_tensor = ops.to_device(cpts_tensor, device), ops.to_device(sentis_tensor, device)
             del item
 
@@ -485,9 +525,15 @@ class Detector(nn.Module):
             cache[fn] = lab
         return labels
 
-    def sample(self, fc_feats, att_feats, sentis_tensor, beam_size=3, decoding_constraint=1):
-        """One image: detect its sentiment, then beam search (decoder.py:182-192)."""
+    def sample(self, fc_feats, att_feats, sentis_tensor=None, beam_size=3, decoding_constraint=1):
+        """One image: detect its sentiment, then beam search (decoder.py:182-192).  sentis_tensor=None: the image's
+        sentiment words are derived on the device from its detected concepts (set_concept_detector with a table) and the
+        search is queued behind them without a host read; without a table ValueError."""
         self.eval()
+        if sentis_tensor is None:
+            if self.__dict__.get('concept_detector') is None or self.__dict__.get('senti_table') is None:
+                raise ValueError('Detector.sample: sentis_tensor=None needs set_concept_detector with a SentimentWordTable')
+            sentis_tensor = self.tag(fc_feats.reshape(1, -1))[1]
         att_feats = att_feats.unsqueeze(0)
         # the label stays on the device until the search is queued: the category name (a host read) is looked up behind the
         # search's own read-back instead of draining the device between the two (tools/eval_loop_probe.py)

@@ -1,4 +1,5 @@
-"""The two frozen helper networks of the RL step, restated as plain PyTorch-ROCm modules.
+"""The two frozen helper networks of the RL step, restated as plain PyTorch-ROCm modules, and the concept detector of the
+pre-stage (ConceptDetector below: its eval forward runs on the library's kernels by default, isc_concept_fwd).
 
 They are harness dependencies of the hot path, not part of it:
 `Detector` only ever runs them in eval mode without gradients (decoder.py:31-32,83,133-136 and
@@ -11,6 +12,7 @@ convolution (isc_senti_det_fwd); both off by default.
 
 * SentimentDetector            /root/reference/models/sentiment_detector.py:5-64
 * SentenceSentimentClassifier  /root/reference/models/sent_senti_cls.py:6-72
+* ConceptDetector, MultiLabelClsLoss  /root/reference/models/concept_detector.py:5-58
 """
 import torch
 import torch.nn as nn
@@ -224,3 +226,143 @@ class SentenceSentimentClassifier(nn.Module):
 
     def get_optim_and_crit(self, lr, weight_decay=0):
         return torch.optim.Adam(self.parameters(), lr=lr, weight_decay=weight_decay), nn.CrossEntropyLoss()
+
+
+class MultiLabelClsLoss(nn.Module):
+    """The concept detector's criterion (what concept_detector.py:44-58 computes): binary cross-entropy on PROBABILITIES
+    p [B, C] against 0/1 targets, as the sum of two separately averaged halves - the set targets' -log p and the unset
+    ones' -log(1 - p), each averaged over the concepts and then over the rows (in that order, so the fp32 bits are the
+    reference's).  Plain torch, for drop-in callers, the CPU path and the native path's comparison; the native training
+    step (train.concept_train_step) computes the same loss from the logits in the stable softplus form
+    (isc_concept_loss), which stays finite where the log of a saturated sigmoid does not."""
+
+    def forward(self, probs, target):
+        t = target.to(probs.dtype)
+        row_mean = lambda x: x.mean(dim=-1).mean(dim=-1)
+        return -row_mean(t * probs.log()) + -row_mean((1 - t) * (1 - probs).log())
+
+
+class ConceptDetector(nn.Module):
+    """The concept detector (concept_detector.py:5-41): fc features -> Linear + ReLU -> Linear + ReLU -> Dropout ->
+    Linear -> Sigmoid over the concept vocabulary.  `output` keeps the reference's indices (Linear at 0, 2, 5; Dropout
+    at 4), so its state_dict loads by name.
+
+    Native path (isc_concept_fwd: three isc_linear_fwd launches and the head kernel) - ON by default whenever eligible,
+    see native_active.  `enable_native(False)` gives the stock torch ops, which remain the CPU path and the probe's
+    comparison.
+
+    Top-`num` order of the native path: larger logit first, lower index on equal logits, NaN last; the torch path sorts
+    the probabilities (stable, descending), which agrees wherever the probabilities are distinct."""
+    native = True
+
+    def __init__(self, idx2concept, settings):
+        super().__init__()
+        self.idx2concept = idx2concept
+        F, H = settings['fc_feat_dim'], settings['concept_mid_him']
+        self.output = nn.Sequential(nn.Linear(F, H), nn.ReLU(), nn.Linear(H, H), nn.ReLU(),
+                                    nn.Dropout(settings['dropout_p']), nn.Linear(H, len(idx2concept)), nn.Sigmoid())
+        self.native = True
+        self._concept_word = None           # [C] int64 vocabulary ids (set_vocabulary), on the host
+        self._concept_word_dev = {}         # device -> the same table there
+
+    # ---- tables
+    def set_vocabulary(self, word2idx):
+        """Builds the concept -> vocabulary id table (`words` of sample_device, the captioner's cpts_tensor).  A concept
+        that the vocabulary lacks raises KeyError, as train_rl.py:122 does."""
+        self._concept_word = torch.tensor([word2idx[c] for c in self.idx2concept], dtype=torch.int64)
+        self._concept_word_dev = {}
+        return self
+
+    def concept_word(self, device):
+        """The table on `device`, or None before set_vocabulary."""
+        if self._concept_word is None:
+            return None
+        device = torch.device(device)
+        t = self._concept_word_dev.get(device)
+        if t is None:
+            t = self._concept_word_dev[device] = self._concept_word.to(device)
+        return t
+
+    # ---- native switch
+    def enable_native(self, on=True):
+        self.native = bool(on)
+        return self
+
+    def native_params(self):
+        o = self.output
+        return [o[0].weight, o[0].bias, o[2].weight, o[2].bias, o[5].weight, o[5].bias]
+
+    def native_active(self, features):
+        """Whether forward / sample / sample_device take the native path now: the flag is on, eval mode (no dropout), the
+        tensors live on the ROCm device, the features are a [B, F] fp32 or float16 matrix, nothing asks for a gradient,
+        and isc_linear_fwd can take the three layers - it contracts in 32-deep chunks, so fc_feat_dim % 32 == 0 and
+        concept_mid_him % 32 == 0 (the number of concepts may be anything; feature rows that are not 16-byte aligned
+        or whose row stride is not a multiple of 4 elements are copied first).  Both GEMM engines serve it (split-f16
+        and, under ops.set_h3_mode(0), exact fp32).  Everything else - train mode, CPU tensors, the detector's own
+        autograd training, other widths - runs the torch ops."""
+        if not self.native or self.training or not torch.is_tensor(features) or not features.is_cuda:
+            return False
+        params = self.native_params()
+        if params[0].device != features.device or features.dim() != 2 or \
+                features.dtype not in (torch.float32, torch.float16) or params[0].dtype != torch.float32:
+            return False
+        if torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in params)):
+            return False
+        from . import ops
+        return ops.concept_shape_ok(params[0].shape[1], params[0].shape[0])
+
+    def _native(self, features, num, want_probs, want_topk=True):
+        from . import ops
+        if features.stride(1) != 1 or features.stride(0) % 4 or features.data_ptr() % 16:
+            features = features.contiguous()
+        with torch.no_grad():
+            return ops.concept_fwd([p.detach() for p in self.native_params()], features, num,
+                                   concept_word=self.concept_word(features.device), want_probs=want_probs,
+                                   want_topk=want_topk)
+
+    # ---- the reference's surface
+    def forward(self, features):
+        """features [B, F] -> probabilities [B, C]."""
+        if self.native_active(features):
+            return self._native(features, 1, True, want_topk=False)['probs']
+        if features.dtype != self.output[0].weight.dtype:
+            features = features.to(self.output[0].weight.dtype)
+        return self.output(features)
+
+    def _sample_torch(self, features, num):
+        from . import ops
+        C_ = len(self.idx2concept)
+        num = ops._check_num(num, C_)
+        if features.dtype != self.output[0].weight.dtype:
+            features = features.to(self.output[0].weight.dtype)
+        out = self.output(features)
+        scores, idx = out.sort(dim=-1, descending=True, stable=True)
+        return out, idx[:, :num].contiguous(), scores[:, :num].contiguous()
+
+    @torch.no_grad()
+    def sample_device(self, features, num):
+        """-> (idx [B, num] int64, scores [B, num], words [B, num] int64 vocabulary ids - None before set_vocabulary), all
+        on the features' device; nothing is read back.  num outside [1, min(16, C)] raises ValueError."""
+        self.eval()
+        if self.native_active(features):
+            r = self._native(features, num, False)
+            return r['idx'], r['scores'], r.get('words')
+        _, idx, scores = self._sample_torch(features, num)
+        table = self.concept_word(features.device)
+        return idx, scores, table[idx] if table is not None else None
+
+    @torch.no_grad()
+    def sample(self, features, num):
+        """-> (probabilities [B, C], concept names per row (best first), scores [B, num]): the reference's triple
+        (concept_detector.py:24-37), with ONE read-back for the names instead of one `.item()` per element."""
+        self.eval()
+        if self.native_active(features):
+            r = self._native(features, num, True)
+            out, idx, scores = r['probs'], r['idx'], r['scores']
+        else:
+            out, idx, scores = self._sample_torch(features, num)
+        return out, [[self.idx2concept[i] for i in row] for row in idx.tolist()], scores
+
+    def get_optim_criterion(self, lr, weight_decay=0):
+        from .optim import FusedClampAdam
+        return FusedClampAdam(self.parameters(), lr=lr, weight_decay=weight_decay), MultiLabelClsLoss()

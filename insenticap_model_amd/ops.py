@@ -1685,3 +1685,164 @@ def clamp_adam(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight
         return
     check(lib.isc_clamp_adam(mk(params), mk(grads), mk(exp_avg), mk(exp_avg_sq), numel, n, lr, beta1, beta2,
                              eps, weight_decay, clip, step, stream()), 'isc_clamp_adam')
+
+
+# ---------------------------------------------------------------------------- concept detector (csrc/concept.hip)
+CONCEPT_MAX_NUM = _lib.CONCEPT_MAX_NUM
+SENTI_WORDS_CAP = _lib.SENTI_WORDS_CAP
+SENTI_WORDS_MAX_OUT = _lib.SENTI_WORDS_MAX_OUT
+_CONCEPT_WS = {}            # (device index, stream) -> workspace of isc_concept_fwd, grown when a call needs more
+
+
+def _check_num(num, C_):
+    """The head's shape limits as a ValueError (the library answers ISC_E_SHAPE and launches nothing)."""
+    if isinstance(num, bool) or not hasattr(num, '__index__') or not 1 <= int(num) <= min(CONCEPT_MAX_NUM, C_):
+        raise ValueError('num must be an integer in [1, min(%d, C = %d)], got %r' % (CONCEPT_MAX_NUM, C_, num))
+    return int(num)
+
+
+def _targets(targets, B, C_):
+    assert targets.dtype in (torch.uint8, torch.int64), 'targets: uint8 or int64'
+    assert targets.is_contiguous() and tuple(targets.shape) == (B, C_)
+    return targets.data_ptr(), int(targets.dtype == torch.int64)
+
+
+def concept_head(logits, num, concept_word=None, targets=None, want=('probs', 'idx', 'scores', 'words', 'hits')):
+    """isc_concept_head on logits [B, C] fp32 (unit column stride, any row stride): -> dict with the outputs named in
+    `want` - probs [B, C], idx [B, num] int64, scores [B, num], words [B, num] int64 (needs `concept_word` [C] int64),
+    hits / n_true [B] int32 (need `targets` [B, C] uint8 or int64).  Larger logit first, lower index on ties, NaN last.
+    num outside [1, min(16, C)] raises ValueError."""
+    require_device(logits, concept_word, targets)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B, C_ = logits.shape
+    num = _check_num(num, C_)
+    dev = logits.device
+    out = {}
+    if 'probs' in want:
+        out['probs'] = torch.empty(B, C_, dtype=torch.float32, device=dev)
+    if 'idx' in want:
+        out['idx'] = torch.empty(B, num, dtype=torch.int64, device=dev)
+    if 'scores' in want:
+        out['scores'] = torch.empty(B, num, dtype=torch.float32, device=dev)
+    if 'words' in want and concept_word is not None:
+        assert concept_word.dtype == torch.int64 and concept_word.is_contiguous() and concept_word.numel() == C_
+        out['words'] = torch.empty(B, num, dtype=torch.int64, device=dev)
+    tp, t64 = (None, 0)
+    if 'hits' in want and targets is not None:
+        tp, t64 = _targets(targets, B, C_)
+        out['hits'] = torch.empty(B, dtype=torch.int32, device=dev)
+        out['n_true'] = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.load().isc_concept_head(logits.data_ptr(), logits.stride(0), B, C_, num, ptr(out.get('probs')),
+                                       ptr(out.get('idx')), ptr(out.get('scores')), ptr(concept_word),
+                                       ptr(out.get('words')), tp, t64, ptr(out.get('hits')), ptr(out.get('n_true')),
+                                       stream()), 'isc_concept_head')
+    return out
+
+
+def concept_loss(logits, targets, g=1.0, want_dz=False):
+    """isc_concept_loss: MultiLabelClsLoss from the logits [B, C] (stable softplus form) -> (out3 = {term of the set
+    targets, term of the unset ones, loss} fp32 on the device, dz [B, C] = (sigmoid(z) - t) g / (B C) or None)."""
+    require_device(logits, targets)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B, C_ = logits.shape
+    tp, t64 = _targets(targets, B, C_)
+    dev = logits.device
+    ws = torch.empty(2 * B, dtype=torch.float64, device=dev)
+    out3 = torch.empty(3, dtype=torch.float32, device=dev)
+    dz = torch.empty(B, C_, dtype=torch.float32, device=dev) if want_dz else None
+    check(_lib.load().isc_concept_loss(logits.data_ptr(), logits.stride(0), B, C_, tp, t64, float(g), ws.data_ptr(),
+                                       ws.numel() * 8, out3.data_ptr(), ptr(dz), stream()), 'isc_concept_loss')
+    return out3, dz
+
+
+def senti_words_pack_check(off, num):
+    """The longest list of a CSR offset array (host ints, [C + 1]); ValueError when `num` concepts of that length
+    exceed the kernel's cap of SENTI_WORDS_CAP candidates per image (never a silent cut)."""
+    n = len(off) - 1
+    arr = (C.c_int32 * (n + 1))(*[int(x) for x in off])
+    longest = C.c_int(0)
+    rc = _lib.load().isc_senti_words_pack_check(arr, n, int(num), C.byref(longest))
+    if rc != 0:
+        raise ValueError('sentiment-word table: %d concepts x the longest list (%d entries) exceed the device cap of %d '
+                         'candidates per image' % (num, longest.value, SENTI_WORDS_CAP))
+    return longest.value
+
+
+def senti_words_from_concepts(idx, off, word, score, max_list, n_out, pad_id, out=None):
+    """isc_senti_words_from_concepts: idx [B, num] int64 concept indices, CSR table off int32 [C + 1] / word int64 [nnz] /
+    score float64 [nnz] on the device -> int64 [B, n_out] vocabulary ids of the image's sentiment words, padded."""
+    require_device(idx, off, word, score, out)
+    assert idx.dtype == torch.int64 and idx.dim() == 2 and idx.stride(1) == 1
+    assert off.dtype == torch.int32 and off.is_contiguous() and word.dtype == torch.int64 and word.is_contiguous()
+    assert score.dtype == torch.float64 and score.is_contiguous() and word.numel() == score.numel()
+    B, num = idx.shape
+    if not 1 <= int(n_out) <= SENTI_WORDS_MAX_OUT:
+        raise ValueError('n_out must be in [1, %d], got %r' % (SENTI_WORDS_MAX_OUT, n_out))
+    if not 1 <= num <= CONCEPT_MAX_NUM or num * int(max_list) > SENTI_WORDS_CAP:
+        raise ValueError('%d concepts x lists of up to %d entries exceed the device cap of %d candidates per image'
+                         % (num, max_list, SENTI_WORDS_CAP))
+    if out is None:
+        out = torch.empty(B, int(n_out), dtype=torch.int64, device=idx.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (B, int(n_out))
+    check(_lib.load().isc_senti_words_from_concepts(idx.data_ptr(), idx.stride(0), B, num, off.numel() - 1,
+                                                    off.data_ptr(), ptr(word) if word.numel() else None,
+                                                    ptr(score) if score.numel() else None, int(max_list), int(n_out),
+                                                    int(pad_id), out.data_ptr(), stream()),
+          'isc_senti_words_from_concepts')
+    return out
+
+
+def concept_launches():
+    return _lib.load().isc_concept_launches()
+
+
+def concept_shape_ok(F, H):
+    """What isc_linear_fwd asks of the concept MLP's contraction lengths: multiples of 32 (its 32-deep chunks)."""
+    return F >= 32 and H >= 32 and F % 32 == 0 and H % 32 == 0
+
+
+def concept_fwd(params, feats, num, concept_word=None, want_probs=True, want_logits=False, want_topk=True):
+    """isc_concept_fwd: the concept detector's eval forward.  params = (W0 [H,F], b0, W2 [H,H], b2, W5 [C,H], b5)
+    contiguous fp32; feats [B, F] fp32 or float16 (unit column stride).  -> dict(idx, scores[, probs][, words][, logits]);
+    want_topk=False: probabilities / logits only (the head then selects nothing)."""
+    lib = _lib.load()
+    require_device(feats, concept_word, *params)
+    for t in params:
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'concept detector parameters: contiguous fp32'
+    assert feats.dim() == 2 and feats.stride(1) == 1 and feats.dtype in (torch.float32, torch.float16)
+    B, F = feats.shape
+    H, C_ = params[0].shape[0], params[4].shape[0]
+    assert params[0].shape == (H, F) and params[2].shape == (H, H) and params[4].shape == (C_, H)
+    num = _check_num(num, C_)
+    dev = feats.device
+    need = max(int(lib.isc_concept_workspace_bytes(B, F, H, C_)), 16)
+    if torch.cuda.is_current_stream_capturing():
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    else:                       # one per (device, stream): calls on a stream run one after another
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        workspace = _CONCEPT_WS.get(key)
+        if workspace is None or workspace.numel() < need:
+            workspace = _CONCEPT_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = {}
+    if want_topk:
+        out['idx'] = torch.empty(B, num, dtype=torch.int64, device=dev)
+        out['scores'] = torch.empty(B, num, dtype=torch.float32, device=dev)
+    if want_probs:
+        out['probs'] = torch.empty(B, C_, dtype=torch.float32, device=dev)
+    if want_logits:
+        out['logits'] = torch.empty(B, C_, dtype=torch.float32, device=dev)
+    if concept_word is not None and want_topk:
+        assert concept_word.dtype == torch.int64 and concept_word.is_contiguous() and concept_word.numel() == C_
+        out['words'] = torch.empty(B, num, dtype=torch.int64, device=dev)
+    sk = splitk_ws(dev)
+    p = _lib.ConceptProblem()
+    p.feats, p.feats_ld, p.feats_f16 = feats.data_ptr(), feats.stride(0), int(feats.dtype == torch.float16)
+    p.B, p.F, p.H, p.C, p.num = B, F, H, C_, num
+    p.w0, p.b0, p.w2, p.b2, p.w5, p.b5 = [t.data_ptr() for t in params]
+    p.concept_word = ptr(concept_word)
+    p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    p.splitk_ws, p.splitk_ws_floats = sk.data_ptr(), sk.numel()
+    p.logits, p.probs, p.idx, p.scores, p.words = (ptr(out.get('logits')), ptr(out.get('probs')), ptr(out.get('idx')),
+                                                   ptr(out.get('scores')), ptr(out.get('words')))
+    check(lib.isc_concept_fwd(C.byref(p), stream()), 'isc_concept_fwd')
+    return out

@@ -5,6 +5,8 @@ data-parallel.  Batch tuple layouts are the reference collate functions' (datalo
 The sentence-sentiment classifier that labels the factual captions (train_xe.py:155-158) is a
 frozen helper outside this path: the caller passes its arg-max as `xe_senti_labels`.
 """
+import math
+
 import torch
 
 from . import dp, ops
@@ -219,3 +221,100 @@ def xe_train_step(captioner, optim, xe_crit, da_crit, fact_batch, xe_senti_label
         vec = dp.all_reduce_(vec, group)
     xe_update(optim, grad_clip)
     return loss_dict(vec)
+
+
+# ---------------------------------------------------------------------------- concept detector (train_cpt.py:76-90)
+class _ConceptLossFn(torch.autograd.Function):
+    """Features to MultiLabelClsLoss in one node.  Forward: two isc_linear_fwd launches with ReLU (the second with the
+    dropout keep-mask in its epilogue), the logits launch, isc_concept_loss - which also leaves dz = d loss / d logits.
+    Backward: ops.gemm_bwd TN for the three dW and NN for the two dX, ops.relu_mask_bwd, ops.colsum_multi for the biases."""
+
+    @staticmethod
+    def forward(ctx, feats, targets, keep_mask, mask_scale, w0, b0, w2, b2, w5, b5):
+        B, H, C_ = feats.shape[0], w0.shape[0], w5.shape[0]
+        dev = feats.device
+        h1 = torch.empty(B, H, dtype=torch.float32, device=dev)
+        h2 = torch.empty(B, H, dtype=torch.float32, device=dev)
+        z = torch.empty(B, C_, dtype=torch.float32, device=dev)
+        ops.linear_fwd([ops.linear_problem([(feats, w0)], h1, bias0=b0, relu=True)])
+        ops.linear_fwd([ops.linear_problem([(h1, w2)], h2, bias0=b2, relu=True, keep_mask=keep_mask,
+                                           mask_scale=mask_scale)])
+        ops.linear_fwd([ops.linear_problem([(h2, w5)], z, bias0=b5)])
+        # dz is of the order 1 / (B C) - below the f16 normal range at any training size, where the split-f16 engine's
+        # planes (the dW contractions of a batch that is a multiple of 32) keep bits relative to 2^-14, not to the element.
+        # The sweep is linear in dz: it enters as dz S with S the power of two that brings S / (B C) into (2^-4, 2^-3],
+        # and the parameter gradients leave times 1 / S - both exact, so the fp32 tiles give the unscaled bits.
+        S = 2.0 ** (math.floor(math.log2(B * C_)) - 3)
+        out3, dz = ops.concept_loss(z, targets, S, want_dz=True)
+        ctx.save_for_backward(feats, h1, h2, dz, w2, w5)
+        ctx.keep_mask, ctx.mask_scale, ctx.unscale = keep_mask, mask_scale, 1.0 / S
+        ctx.terms = out3
+        return out3[2].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        feats, h1, h2, dz, w2, w5 = ctx.saved_tensors
+        B, H, C_, F = feats.shape[0], w2.shape[0], w5.shape[0], feats.shape[1]
+        dev = feats.device
+        dz = dz * g                                          # (the caller's d loss: a device scalar, 1 in the step below)
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        dw0, db0, dw2, db2, dw5, db5 = new(H, F), new(H), new(H, H), new(H), new(C_, H), new(C_)
+        dh2, dp2, dh1, dp1 = new(B, H), new(B, H), new(B, H), new(B, H)
+        ops.gemm_bwd([ops.gemm_problem([(dz, h2)], dw5, ops.TN)], ops.TN)
+        ops.gemm_bwd([ops.gemm_problem([(dz, w5)], dh2, ops.NN)], ops.NN)
+        ops.relu_mask_bwd(dh2, h2, dp2, ctx.keep_mask, ctx.mask_scale)     # (h2 = relu * mask * scale: > 0 where both let through)
+        ops.gemm_bwd([ops.gemm_problem([(dp2, h1)], dw2, ops.TN)], ops.TN)
+        ops.gemm_bwd([ops.gemm_problem([(dp2, w2)], dh1, ops.NN)], ops.NN)
+        ops.relu_mask_bwd(dh1, h1, dp1)
+        ops.gemm_bwd([ops.gemm_problem([(dp1, feats)], dw0, ops.TN)], ops.TN)
+        ops.colsum_multi([(dz, [db5], False), (dp2, [db2], False), (dp1, [db0], False)])
+        torch._foreach_mul_([dw0, db0, dw2, db2, dw5, db5], ctx.unscale)
+        return None, None, None, None, dw0, db0, dw2, db2, dw5, db5
+
+
+def concept_loss_with_grad(model, fc_feats, targets, _keep_mask=None):
+    """MultiLabelClsLoss of model(fc_feats) against the 0/1 `targets` [B, C] (uint8 or int64, as the concept collate
+    gives them) as a differentiable device scalar, on the library's kernels.  In train mode with dropout_p > 0 the
+    uint8 keep-mask [B, mid] is drawn the way the captioner draws its masks (one bernoulli_ launch on torch's
+    generator); `_keep_mask` replays a given one (tests).  Needs fc_feat_dim % 32 == concept_mid_him % 32 == 0 (the
+    forward contractions) and a number of concepts that is a multiple of 4 (the backward contractions): ValueError
+    otherwise - there is no quiet torch fallback; call model(fc_feats) with its criterion for such shapes."""
+    ops.require_device(fc_feats, targets)
+    w0, b0, w2, b2, w5, b5 = model.native_params()
+    H, F = w0.shape
+    C_ = w5.shape[0]
+    if not ops.concept_shape_ok(F, H) or C_ % 4:
+        raise ValueError('concept training step: fc_feat_dim (%d) and concept_mid_him (%d) must be multiples of 32 and '
+                         'the number of concepts (%d) a multiple of 4' % (F, H, C_))
+    if fc_feats.dtype == torch.float16:
+        fc_feats = ops.f16_to_f32(fc_feats if fc_feats.stride(1) == 1 else fc_feats.contiguous())
+    if fc_feats.stride(1) != 1 or fc_feats.stride(0) % 4 or fc_feats.data_ptr() % 16:
+        fc_feats = fc_feats.contiguous()
+    if targets.dtype not in (torch.uint8, torch.int64):
+        targets = targets.to(torch.int64)
+    targets = targets.contiguous()
+    p = model.output[4].p
+    keep, scale = None, 1.0
+    if _keep_mask is not None:
+        keep = _keep_mask.to(device=fc_feats.device, dtype=torch.uint8).reshape(fc_feats.shape[0], H).contiguous()
+        scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    elif model.training and p > 0.0:
+        keep = torch.empty(fc_feats.shape[0], H, dtype=torch.uint8, device=fc_feats.device).bernoulli_(1.0 - p)
+        scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    return _ConceptLossFn.apply(fc_feats, targets, keep, scale, w0, b0, w2, b2, w5, b5)
+
+
+def concept_train_step(model, optimizer, fc_feats, targets, grad_clip, _keep_mask=None):
+    """One training iteration of train_cpt.py:79-89 on the device: loss (concept_loss_with_grad), backward, the
+    elementwise clamp to +-grad_clip and Adam (one launch with a FusedClampAdam).  Returns the loss as a device scalar -
+    the trainer decides when to read it.  Dropout follows the module's mode, as in the reference's loop
+    (train_cpt.py:77): call model.train() first - `sample`, `sample_device` and Detector.tag leave the module in eval
+    mode, and in eval mode this step draws no mask."""
+    device = next(model.parameters()).device
+    fc_feats, targets = ops.to_device(fc_feats, device), ops.to_device(targets, device)
+    loss = concept_loss_with_grad(model, fc_feats, targets, _keep_mask)
+    optimizer.zero_grad()
+    loss.backward()
+    clip_gradient(optimizer, grad_clip)
+    optimizer.step()
+    return loss.detach()
