@@ -998,6 +998,102 @@ int64_t isc_sent_cls_workspace_bytes(int B, int L, int W, int H);
 int isc_sent_cls_fwd(const isc_sent_cls_problem *prob_host, void *stream);
 long long isc_sent_cls_launches(void);    /* kernels enqueued by isc_sent_cls_fwd so far (measurement / test hook) */
 
+/* ---- the classifier's own training (train_sent_senti_cls_rnn.py:110-126): saved-activation forward, CrossEntropyLoss,
+ * and the whole reverse sweep, on the library's kernels.  Every floating-point sum runs in one fixed order without atomics
+ * (two calls give the same bits; the only atomics are the integer counters of isc_embed_relu_bwd_ws's position index from
+ * 1024 rows on, whose segments are sorted before they are summed), allocates nothing, never reads back, and validates before the first launch (nothing is written
+ * when a call returns an error).
+ *
+ * isc_sent_cls_head_loss - the k-way head with its loss (two launches: one wave per caption, then one thread per output):
+ *   logits[b,j] = hid[b,:] . cls3_w[j,:] + cls3_b[j]   (the bits of isc_sent_cls_fwd's head);  pred = arg-max, lowest index
+ *   on ties;  loss_rows[b] = logsumexp(z) - z[label] in the max-subtracted form;  dz8[b,j] = g (softmax_j - [j == label]) / B
+ *   in a [B,8] buffer whose columns k..7 are zero;  dhid[b,:] = sum_j dz8[b,j] cls3_w[j,:] (j ascending);
+ *   loss[0] = mean of loss_rows, wrong[0] = rows with pred != label, dw3[j,:] = sum_b dz8[b,j] hid[b,:],
+ *   db3[j] = sum_b dz8[b,j] (b ascending).  hid [B,H] is the head's hidden layer after ReLU and dropout; labels [B] int64,
+ *   each in [0, k).  1 <= k <= 8, H % 4 == 0, B >= 1 (ISC_E_SHAPE); hid, cls3_w, dz8, dhid, dw3 16-byte aligned
+ *   (ISC_E_ALIGN).  g: the gradient scale (below).
+ *
+ * isc_sent_cls_pool_bwd - backward of the squeeze-excite pooling (one workgroup per caption, a wave per step), from
+ *   dfeats [B,H], the saved pre-sigmoid e2 and dropped LSTM outputs o ([L*B,H], time-major rows t*B+b), the saved token
+ *   weights [B, ldw] and lens [B] (clamped into [0, L]).  For t < len:
+ *     dw[b,t] = dfeats[b,:] . o[t,b,:];  de2[t,b,h] = (dw[b,t] / H) s (1 - s), s = sigmoid(e2[t,b,h]);
+ *     d_o[t,b,:] = weights[b,t] dfeats[b,:];
+ *   for t >= len both output rows (and dw[b,t]) are written as exact zeros whatever they held.  dw [B,L] is optional.
+ *   H % 4 == 0, 1 <= L <= 4096, ldw >= L (ISC_E_SHAPE); the five [.,H] tensors 16-byte aligned (ISC_E_ALIGN). */
+int isc_sent_cls_head_loss(const float *hid, const float *cls3_w, const float *cls3_b, const int64_t *labels, int B, int H,
+                           int k, float g, float *logits, int32_t *pred, float *loss_rows, float *dz8, float *dhid,
+                           float *dw3, float *db3, float *loss, int32_t *wrong, void *stream);
+int isc_sent_cls_pool_bwd(const float *dfeats, const float *e2, const float *o, const float *weights, int64_t ldw,
+                          const int32_t *lens, int B, int L, int H, float *de2, float *d_o, float *dw, void *stream);
+
+/* One training iteration's problem: what isc_sent_cls_train_fwd and isc_sent_cls_bwd share (the backward is called with the
+ * struct the forward was called with, gradients and workspace filled in).  Sizes, tokens, lens, the thirteen parameters and
+ * labels (required) as in isc_sent_cls_problem; H % 32 == W % 32 == 0, W <= 1024 (the embedding gradient).
+ * Dropout: three optional uint8 keep-masks - emb_keep [L*B, W] and out_keep [L*B, H] over the time-major rows t*B+b,
+ * hid_keep [B, H] - sharing mask_scale = 1 / (1 - p).  Null = no dropout at that place; with all three null the forward is
+ * the eval forward and its logits equal isc_sent_cls_fwd's bit for bit.
+ * grad_scale = S: the sweep runs on S dz and every gradient leaves times S - the caller multiplies by 1 / S.  dz is of the
+ * order 1 / B and de2 carries a further 1 / H: below the f16 normal range, where the split-f16 contractions keep bits
+ * relative to 2^-14.  S a power of two makes both scalings exact.
+ * saved (isc_sent_cls_train_saved_bytes): written by the forward, read by the backward -
+ *   x (after ReLU and emb_keep) | Xg | activated gates [L,B,4H] | c [L,B,H] | h [L,B,H] (raw: the recurrence input) |
+ *   o [L,B,H] (dropped; o = h without out_keep) | e1 | e2 | zero state | feats | hid | dz8 | dhid | loss_rows.
+ * isc_sent_cls_train_fwd: the launch sequence of isc_sent_cls_fwd (L + 7, the cells with gates_out and, under out_keep,
+ *   h_keep_mask / hdrop_out; the head GEMM with hid_keep in its epilogue; + 1 launch for emb_keep) with the head replaced
+ *   by isc_sent_cls_head_loss (2 launches): L + 8 launches, + 1 with emb_keep.
+ *   Outputs: logits [B,k], weights [B,T_out], pred [B], loss [1], wrong [1] int32, d_cls3_w [k,H], d_cls3_b [k].
+ * isc_sent_cls_bwd: the reverse sweep, one call.  Library calls enqueued (isc_sent_cls_bwd_launches counts them):
+ *     1            prepare: d_emb = 0, the token ids time-major (<PAD> behind each length), d_w_hh = 0 when L == 1
+ *     3            head hidden layer: ReLU / hid_keep mask, TN (d_cls0_w), NN (dfeats)
+ *     1            isc_sent_cls_pool_bwd
+ *     5            excitation: TN (d_ex2_w), NN, ReLU mask, TN (d_ex0_w), NN accumulating onto d_o
+ *     [out_keep]   the LSTM-output dropout mask
+ *     2 L - 1      per step t = L-1 .. 0: isc_lstm_bwd, and for t > 0 one NN  dgates[t] W_hh  for the step before
+ *     [L > 1]      d_w_hh: ONE TN over the (L-1) B rows  dgates[1:]^T h[:L-1]
+ *     4            d_w_ih (ONE TN over L B rows), dx (one NN), the embedding gradient (isc_embed_relu_bwd_ws, skip_id =
+ *                  pad_id: nn.Embedding's padding_idx), the five bias gradients (one isc_colsum_multi; d_b_ih and d_b_hh
+ *                  share a reduction)
+ *   = 2 L + 13 + [L > 1] + [out_keep].  (A call is one kernel, except: a TN / NN contraction on the split-f16 route is a
+ *   plane split plus the GEMM (TN only), isc_colsum_multi is up to two, the embedding gradient one or five.)
+ *   Rows at and behind a caption's length are exact zeros from isc_sent_cls_pool_bwd on, and isc_lstm_bwd maps zero dh /
+ *   dc_next to zeros, so the contractions over all L B rows need no masking and the tokens there change no bit.
+ *   workspace: isc_sent_cls_bwd_workspace_bytes(B, L, W, H, V).  splitk_ws (optional, 256-byte aligned): handed to the TN
+ *   contractions - the split-f16 route of isc_gemm_bwd builds its planes there; the NN contractions get none and stay on
+ *   the exact-fp32 tiles (one kernel each, also inside the step loop).
+ * Errors as isc_sent_cls_fwd, all before any launch. */
+typedef struct {
+    int32_t B, L, W, H, V, k, T_out, _pad;
+    const int64_t *tokens;
+    int64_t tokens_ld;
+    const int32_t *lens;
+    const float *emb, *w_ih, *w_hh, *b_ih, *b_hh;
+    const float *ex0_w, *ex0_b, *ex2_w, *ex2_b;
+    const float *cls0_w, *cls0_b, *cls3_w, *cls3_b;
+    const int64_t *labels;
+    const uint8_t *emb_keep, *out_keep, *hid_keep;
+    float mask_scale, grad_scale;
+    int64_t pad_id;
+    void *saved;
+    int64_t saved_bytes;
+    void *workspace;            /* isc_sent_cls_bwd only */
+    int64_t workspace_bytes;
+    float *splitk_ws;           /* isc_sent_cls_bwd only, optional */
+    int64_t splitk_ws_floats;
+    float *logits, *weights;
+    int32_t *pred;
+    float *loss;
+    int32_t *wrong;
+    /* gradients (times grad_scale): d_cls3_w / d_cls3_b are the forward's outputs, the other eleven the backward's */
+    float *d_emb, *d_w_ih, *d_w_hh, *d_b_ih, *d_b_hh;
+    float *d_ex0_w, *d_ex0_b, *d_ex2_w, *d_ex2_b;
+    float *d_cls0_w, *d_cls0_b, *d_cls3_w, *d_cls3_b;
+} isc_sent_cls_train_problem;
+int64_t isc_sent_cls_train_saved_bytes(int B, int L, int W, int H);
+int64_t isc_sent_cls_bwd_workspace_bytes(int B, int L, int W, int H, int V);
+int isc_sent_cls_train_fwd(const isc_sent_cls_train_problem *prob_host, void *stream);
+int isc_sent_cls_bwd(const isc_sent_cls_train_problem *prob_host, void *stream);
+long long isc_sent_cls_bwd_launches(void);    /* library calls enqueued by isc_sent_cls_bwd so far (test hook) */
+
 /* The frozen image-sentiment detector, forward in eval mode (sentiment_detector.py:30-60; called by decoder.py:83 for the
  * image labels of an RL iteration and by decoder.py:182-192 in front of a beam search):
  *   x = conv_{n-1}( ... conv_0(features) ... ), 3x3, padding 1, cross-correlation, channels C -> C/2 -> C/4 ..., NO

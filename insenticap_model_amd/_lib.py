@@ -161,6 +161,18 @@ class SentClsProblem(C.Structure):
                    C.c_void_p) + [('workspace_bytes', C.c_int64)] + _f('logits weights pred reward feats', C.c_void_p))
 
 
+class SentClsTrainProblem(C.Structure):
+    """isc_sent_cls_train_problem: one training iteration of the sentence-sentiment classifier (csrc/sent_cls.hip)."""
+    _fields_ = (_f('B L W H V k T_out _pad', C.c_int32) + [('tokens', C.c_void_p), ('tokens_ld', C.c_int64)] +
+                _f('lens emb w_ih w_hh b_ih b_hh ex0_w ex0_b ex2_w ex2_b cls0_w cls0_b cls3_w cls3_b labels '
+                   'emb_keep out_keep hid_keep', C.c_void_p) +
+                [('mask_scale', C.c_float), ('grad_scale', C.c_float), ('pad_id', C.c_int64), ('saved', C.c_void_p),
+                 ('saved_bytes', C.c_int64), ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                 ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)] +
+                _f('logits weights pred loss wrong d_emb d_w_ih d_w_hh d_b_ih d_b_hh d_ex0_w d_ex0_b d_ex2_w d_ex2_b '
+                   'd_cls0_w d_cls0_b d_cls3_w d_cls3_b', C.c_void_p))
+
+
 SENTI_DET_MAX_CONVS = SENTI_DET_MAX_FCS = 4
 SENTI_DET_MAX_HW = 1024
 SENTI_DET_KINDS = ('direct', 'split', 'reduce', 'tail', 'pack', 'f16')      # isc_senti_det_launches(kind index)
@@ -321,6 +333,16 @@ SIGNATURES = {
     'isc_sent_cls_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'isc_sent_cls_fwd': (C.c_int, [C.POINTER(SentClsProblem), C.c_void_p]),
     'isc_sent_cls_launches': (C.c_longlong, []),
+    'isc_sent_cls_head_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_sent_cls_pool_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_sent_cls_train_saved_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_sent_cls_bwd_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_sent_cls_train_fwd': (C.c_int, [C.POINTER(SentClsTrainProblem), C.c_void_p]),
+    'isc_sent_cls_bwd': (C.c_int, [C.POINTER(SentClsTrainProblem), C.c_void_p]),
+    'isc_sent_cls_bwd_launches': (C.c_longlong, []),
     'isc_senti_det_pack_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'isc_senti_det_pack': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'isc_senti_det_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -106,3 +106,40 @@ def load_concept_checkpoint(path, model=None, optimizer=None, **expected):
         optimizer.load_state_dict(chk['optimizer'])
         lr = optimizer.param_groups[0]['lr']
     return model, chk['epoch'], lr
+
+
+_SENT_CLS_META = ('settings', 'idx2word', 'sentiment_categories', 'dataset_name', 'corpus_type')
+
+
+def save_sent_cls_checkpoint(directory, epoch, model, optimizer, settings, idx2word, sentiment_categories, dataset_name,
+                             corpus_type, train_loss=0.0, acc_rate=0.0):
+    """The sentence-sentiment classifier's checkpoint as train_sent_senti_cls_rnn.py:178-190 writes it: {epoch, model,
+    optimizer, settings, idx2word, sentiment_categories, dataset_name, corpus_type} under
+    model_<epoch>_<train loss>_<accuracy>_<time>.pth."""
+    chk = {'epoch': epoch, 'model': model.state_dict(), 'optimizer': optimizer.state_dict(), 'settings': settings,
+           'idx2word': idx2word, 'sentiment_categories': sentiment_categories, 'dataset_name': dataset_name,
+           'corpus_type': corpus_type}
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, 'model_%d_%.4f_%.4f_%s.pth' % (epoch, train_loss, acc_rate, time.strftime('%m%d-%H%M')))
+    torch.save(chk, path)
+    return path
+
+
+def load_sent_cls_checkpoint(path, model=None, optimizer=None, **expected):
+    """Resume as train_sent_senti_cls_rnn.py:42-59 does (`expected`: settings / idx2word / sentiment_categories /
+    dataset_name / corpus_type must equal the file's - AssertionError with the reference's words otherwise, which name
+    the settings `opt.settings`), or - model=None - build the classifier from the file.  Returns (model, epoch, lr); lr is
+    None without an optimizer."""
+    chk = torch.load(path, map_location=lambda s, l: s, weights_only=False)
+    for key in _SENT_CLS_META:
+        if key in expected and expected[key] != chk[key]:
+            raise AssertionError('%s and resume model %s are different' % ('opt.settings' if key == 'settings' else key, key))
+    if model is None:
+        from .helper_nets import SentenceSentimentClassifier
+        model = SentenceSentimentClassifier(chk['idx2word'], chk['sentiment_categories'], chk['settings'])
+    model.load_state_dict(chk['model'])
+    lr = None
+    if optimizer is not None and 'optimizer' in chk:
+        optimizer.load_state_dict(chk['optimizer'])
+        lr = optimizer.param_groups[0]['lr']
+    return model, chk['epoch'], lr

@@ -192,8 +192,18 @@ def create_collate_fn(name, pad_index=0, max_seq_len=17, num_concepts=5, num_sen
         return fns, _feats(fcs), _feats(atts), _pad_rows(cpts, num_concepts, pad_index), \
             _pad_rows(sentis, num_sentiments, pad_index), torch.from_numpy(np.asarray(labels, dtype=np.int64))
 
+    def senti_sents(dataset):
+        # dataloader.py:123-134 (the sentence classifier's own training): (label, ids) pairs, longest first (stable), cut at
+        # max_seq_len, padded to the first row -> labels [B], (caps [B, lengths[0]], lengths) - the lengths are the rows'
+        # own, not minus one: the classifier reads the whole sentence
+        rows = sorted(dataset, key=lambda p: len(p[1]), reverse=True)
+        sentis, caps = zip(*rows)
+        lengths = [min(len(c), max_seq_len) for c in caps]
+        return torch.from_numpy(np.asarray(sentis, dtype=np.int64)), \
+            (_pad_rows(caps, lengths[0], pad_index, limit=max_seq_len), lengths)
+
     table = {'caption': caption if captions_per_image is None else caption_grouped, 'scs': scs, 'senti_corpus_with_sentis': scs, 'rl_fact': rl_fact,
-             'rl_senti': rl_senti}
+             'rl_senti': rl_senti, 'senti_sents': senti_sents}
     if name not in table:
         raise KeyError('collate %r is outside the decoder path (have: %s)' % (name, sorted(table)))
     return table[name]
@@ -594,7 +604,7 @@ class DevicePrefetcher:
 def concept_collate_fn(dataset):
     """The reference's 'concept' collate (dataloader.py:111-115): items (fn, fc [F], 0/1 vector [C]) -> (fns, fc_feats
     [B, F] fp32 - float16 when every item is -, targets [B, C] int64).  (create_collate_fn keeps the decoder path's four
-    names; this one stands beside it.)"""
+    names and the sentence classifier's 'senti_sents'; this one stands beside it.)"""
     fns, fcs, cpts = zip(*dataset)
     return fns, _feats(fcs), torch.from_numpy(np.asarray(cpts).astype(np.int64))
 
@@ -620,6 +630,57 @@ class ConceptDataset(torch.utils.data.Dataset):
 def get_concept_dataloader(fc_feats, img_concepts, num_cpts, batch_size, num_workers=0, shuffle=True):
     """dataloader.py:338-345."""
     return _loader(ConceptDataset(fc_feats, img_concepts, num_cpts), batch_size, num_workers, shuffle, concept_collate_fn)
+
+
+# ---------------------------------------------------------------------------- sentence classifier (dataloader.py:263-272,360-370)
+class SentiSentDataset(torch.utils.data.Dataset):
+    """dataloader.py:263-272: item = (sentiment id, the sentence's word ids as an array)."""
+
+    def __init__(self, senti_sentences):
+        self.senti_sentences = senti_sentences
+
+    def __getitem__(self, index):
+        senti, sent = self.senti_sentences[index]
+        return senti, np.array(sent)
+
+    def __len__(self):
+        return len(self.senti_sentences)
+
+
+def get_senti_sents_dataloader(senti_sentences, pad_index, max_seq_len, batch_size=80, num_workers=2, shuffle=True):
+    """dataloader.py:360-370: batches of (labels [B], (caps [B, L], lengths)) for train.sent_cls_train_step."""
+    return _loader(SentiSentDataset(senti_sentences), batch_size, num_workers, shuffle,
+                   create_collate_fn('senti_sents', pad_index=pad_index, max_seq_len=max_seq_len))
+
+
+def build_senti_sents_sets(senti_captions, word2idx, categories, val_counts=None, rng=random):
+    """train_sent_senti_cls_rnn.py:69-95: the classifier's training list and validation lists from `senti_captions`
+    {category: [[words, ...], ...]} (the first entry of every item is its word list).
+    Per category: shuffle (rng.shuffle), the first val_counts[category] sentences are the validation set (the reference
+    takes 5000 neutral and 1000 of each other category - the default), the rest train; 'positive' and 'negative' are then
+    repeated int(len(neutral) / len(own)) times - whole-number oversampling.  Words become ids by
+    `word2idx.get(w) or word2idx['<UNK>']` - so a word whose index is 0 becomes <UNK> too, as in the reference - plus <EOS>.
+    The training list is shuffled once more.  -> (train_set [[senti_id, ids], ...], val_set {category: [[senti_id, ids], ...]})."""
+    if val_counts is None:
+        val_counts = {c: 5000 if c == 'neutral' else 1000 for c in senti_captions}
+    caps = {}
+    for senti in senti_captions:                        # (the dict's order: it is the order of the rng draws)
+        caps[senti] = [c[0] for c in senti_captions[senti]]
+        rng.shuffle(caps[senti])
+    split = {'train': {}, 'val': {}}
+    for senti in ('neutral', 'positive', 'negative'):
+        split['train'][senti] = list(caps[senti][val_counts[senti]:])
+        split['val'][senti] = list(caps[senti][:val_counts[senti]])
+    for senti in ('positive', 'negative'):
+        split['train'][senti] = split['train'][senti] * int(len(split['train']['neutral']) / len(split['train'][senti]))
+    unk, eos = word2idx['<UNK>'], word2idx['<EOS>']
+    to_ids = lambda cap: [word2idx.get(w, None) or unk for w in cap] + [eos]
+    train_set, val_set = [], {}
+    for senti_id, senti in enumerate(categories):
+        train_set += [[senti_id, to_ids(cap)] for cap in split['train'][senti]]
+        val_set[senti] = [[senti_id, to_ids(cap)] for cap in split['val'][senti]]
+    rng.shuffle(train_set)
+    return train_set, val_set
 
 
 class SentimentWordTable:

@@ -161,8 +161,9 @@ class SentenceSentimentClassifier(nn.Module):
 
     def native_active(self, seqs):
         """Whether forward(seqs, ...) takes the native path now: the flag is on, the module is in eval mode (no dropout),
-        the tensors live on the ROCm device and nothing asks for a gradient of a parameter (the classifier's own
-        pre-training, train mode and CPU tensors run the torch code below)."""
+        the tensors live on the ROCm device and nothing asks for a gradient of a parameter (train mode, CPU tensors and
+        autograd through forward() run the torch code below; the classifier's training on the library's kernels is a
+        separate entry point, train.sent_cls_train_step)."""
         if not self.native or self.training or not seqs.is_cuda:
             return False
         params = self.native_params()
@@ -224,7 +225,12 @@ class SentenceSentimentClassifier(nn.Module):
         result = [int(p.argmax(-1)) for p in pred]
         return result, [self.sentiment_categories[r] for r in result], att_weights
 
-    def get_optim_and_crit(self, lr, weight_decay=0):
+    def get_optim_and_crit(self, lr, weight_decay=0, fused=False):
+        """`fused=True`: optim.FusedClampAdam (clamp + Adam in one launch) for train.sent_cls_train_step; the default is
+        the reference's torch.optim.Adam."""
+        if fused:
+            from .optim import FusedClampAdam
+            return FusedClampAdam(self.parameters(), lr=lr, weight_decay=weight_decay), nn.CrossEntropyLoss()
         return torch.optim.Adam(self.parameters(), lr=lr, weight_decay=weight_decay), nn.CrossEntropyLoss()
 
 

@@ -1037,6 +1037,118 @@ def sent_cls_fwd(params, tokens, lens_i32, labels=None, pad_to=None, want_feats=
     return (logits, weights, pred, reward) + ((feats,) if want_feats else ())
 
 
+# ---- the classifier's training (isc_sent_cls_train_fwd / isc_sent_cls_bwd and their two kernels on their own)
+SENT_CLS_GRADS = tuple('d_' + n for n in SENT_CLS_PARAMS)
+
+
+def sent_cls_bwd_launches():
+    return _lib.load().isc_sent_cls_bwd_launches()
+
+
+def sent_cls_train_shape_ok(W, H):
+    """The shapes the training entry points take: the native forward's (W % 32 == H % 32 == 0, hence H % 4) and
+    W <= 1024 (the embedding gradient's row width)."""
+    return W >= 32 and H >= 32 and W % 32 == 0 and H % 32 == 0 and W <= 1024
+
+
+def sent_cls_head_loss(hid, cls3_w, cls3_b, labels, g=1.0):
+    """isc_sent_cls_head_loss on its own: hid [B,H] (the head's hidden layer), labels [B] int64 in [0, k) -> dict of
+    logits [B,k], pred [B] int32, loss_rows [B], dz [B,8] (= g (softmax - onehot) / B, columns k..7 zero), dhid [B,H],
+    dw3 [k,H], db3 [k], loss [1], wrong [1] int32."""
+    require_device(hid, cls3_w, cls3_b, labels)
+    assert hid.dtype == torch.float32 and hid.is_contiguous() and cls3_w.is_contiguous() and cls3_b.is_contiguous()
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    B, H = hid.shape
+    k = cls3_w.shape[0]
+    dev = hid.device
+    new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+    o = dict(logits=new(B, k), pred=new(B, dt=torch.int32), loss_rows=new(B), dz=new(B, 8), dhid=new(B, H),
+             dw3=new(k, H), db3=new(k), loss=new(1), wrong=new(1, dt=torch.int32))
+    check(_lib.load().isc_sent_cls_head_loss(hid.data_ptr(), cls3_w.data_ptr(), cls3_b.data_ptr(), labels.data_ptr(), B, H,
+                                             k, float(g), *[o[n].data_ptr() for n in
+                                                            ('logits', 'pred', 'loss_rows', 'dz', 'dhid', 'dw3', 'db3',
+                                                             'loss', 'wrong')], stream()), 'isc_sent_cls_head_loss')
+    return o
+
+
+def sent_cls_pool_bwd(dfeats, e2, o, weights, lens_i32, de2=None, d_o=None, want_dw=True):
+    """isc_sent_cls_pool_bwd on its own: dfeats [B,H], e2 and o [L,B,H] (time-major), weights [B,>=L], lens [B] int32 ->
+    (de2 [L,B,H], d_o [L,B,H], dw [B,L] or None); the two outputs may be handed in (they are overwritten in full)."""
+    require_device(dfeats, e2, o, weights, lens_i32)
+    L, B, H = e2.shape
+    assert dfeats.shape == (B, H) and o.shape == (L, B, H) and weights.shape[0] == B and weights.stride(1) == 1
+    assert dfeats.is_contiguous() and e2.is_contiguous() and o.is_contiguous()
+    assert lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.shape == (B,)
+    de2 = torch.empty_like(e2) if de2 is None else de2
+    d_o = torch.empty_like(o) if d_o is None else d_o
+    assert de2.is_contiguous() and d_o.is_contiguous() and de2.shape == e2.shape and d_o.shape == o.shape
+    dw = torch.empty(B, L, dtype=torch.float32, device=e2.device) if want_dw else None
+    check(_lib.load().isc_sent_cls_pool_bwd(dfeats.data_ptr(), e2.data_ptr(), o.data_ptr(), weights.data_ptr(),
+                                            weights.stride(0), lens_i32.data_ptr(), B, L, H, de2.data_ptr(), d_o.data_ptr(),
+                                            ptr(dw), stream()), 'isc_sent_cls_pool_bwd')
+    return de2, d_o, dw
+
+
+def sent_cls_train_fwd(params, tokens, lens_i32, labels, grad_scale=1.0, keep_masks=None, mask_scale=1.0, pad_id=-1):
+    """isc_sent_cls_train_fwd: the saved-activation forward and the loss.  params / tokens / lens_i32 as sent_cls_fwd,
+    labels [B] int64; keep_masks = None or (emb_keep [L*B,W], out_keep [L*B,H], hid_keep [B,H]) uint8 over the time-major
+    rows t*B+b (any of them None).  -> a state dict: logits, weights [B,L], pred, loss [1], wrong [1] int32, the scaled
+    d_cls3_w / d_cls3_b, and what sent_cls_bwd needs (the filled problem struct and the tensors it points at)."""
+    lib = _lib.load()
+    assert len(params) == len(SENT_CLS_PARAMS)
+    require_device(tokens, lens_i32, labels, *params)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.stride(1) == 1
+    B, L = tokens.shape
+    assert lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.shape == (B,)
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)
+    for t in params:
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'classifier parameters: contiguous fp32'
+    V, W = params[0].shape
+    H = params[2].shape[1]
+    k = params[11].shape[0]
+    dev = tokens.device
+    masks = tuple(keep_masks) if keep_masks is not None else (None, None, None)
+    for m, shape in zip(masks, ((L * B, W), (L * B, H), (B, H))):
+        assert m is None or (m.dtype == torch.uint8 and m.is_contiguous() and m.shape == shape and m.device == dev)
+    new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+    st = dict(logits=new(B, k), weights=new(B, L), pred=new(B, dt=torch.int32), loss=new(1),
+              wrong=new(1, dt=torch.int32), d_cls3_w=new(k, H), d_cls3_b=new(k),
+              saved=new(max(int(lib.isc_sent_cls_train_saved_bytes(B, L, W, H)), 16), dt=torch.uint8),
+              keep=(params, tokens, lens_i32, labels, masks))
+    p = _lib.SentClsTrainProblem()
+    p.B, p.L, p.W, p.H, p.V, p.k, p.T_out = B, L, W, H, V, k, L
+    p.tokens, p.tokens_ld, p.lens, p.labels = tokens.data_ptr(), tokens.stride(0), lens_i32.data_ptr(), labels.data_ptr()
+    for name, t in zip(SENT_CLS_PARAMS, params):
+        setattr(p, name, t.data_ptr())
+    p.emb_keep, p.out_keep, p.hid_keep = (ptr(m) for m in masks)
+    p.mask_scale, p.grad_scale, p.pad_id = float(mask_scale), float(grad_scale), int(pad_id)
+    p.saved, p.saved_bytes = st['saved'].data_ptr(), st['saved'].numel()
+    for name in ('logits', 'weights', 'pred', 'loss', 'wrong', 'd_cls3_w', 'd_cls3_b'):
+        setattr(p, name, st[name].data_ptr())
+    check(lib.isc_sent_cls_train_fwd(C.byref(p), stream()), 'isc_sent_cls_train_fwd')
+    st['problem'] = p
+    return st
+
+
+def sent_cls_bwd(state):
+    """isc_sent_cls_bwd: the reverse sweep behind sent_cls_train_fwd's state -> the thirteen gradients in SENT_CLS_PARAMS
+    order, each times the forward's grad_scale (d_cls3_w / d_cls3_b are the forward's)."""
+    lib = _lib.load()
+    p = state['problem']
+    params = state['keep'][0]
+    dev = params[0].device
+    grads = [state[n] if n in state else torch.empty_like(t) for n, t in zip(SENT_CLS_GRADS, params)]
+    ws = torch.empty(max(int(lib.isc_sent_cls_bwd_workspace_bytes(p.B, p.L, p.W, p.H, p.V)), 16), dtype=torch.uint8,
+                     device=dev)
+    sk = splitk_ws(dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    p.splitk_ws, p.splitk_ws_floats = sk.data_ptr(), sk.numel()
+    for name, g in zip(SENT_CLS_GRADS, grads):
+        setattr(p, name, g.data_ptr())
+    check(lib.isc_sent_cls_bwd(C.byref(p), stream()), 'isc_sent_cls_bwd')
+    return grads
+
+
 _SENTI_DET_WS = {}          # (device index, stream, B, h, w, C, n_convs, ksplit) -> workspace of isc_senti_det_fwd
 
 

@@ -318,3 +318,117 @@ def concept_train_step(model, optimizer, fc_feats, targets, grad_clip, _keep_mas
     clip_gradient(optimizer, grad_clip)
     optimizer.step()
     return loss.detach()
+
+
+# ---------------------------------------------------------------------------- sentence classifier (train_sent_senti_cls_rnn.py:110-165)
+class _SentClsLossFn(torch.autograd.Function):
+    """Tokens to CrossEntropyLoss in one node.  Forward: ops.sent_cls_train_fwd (isc_sent_cls_train_fwd: the native
+    forward's launch sequence with every intermediate kept, then isc_sent_cls_head_loss, which also leaves dz, d hid and the
+    last layer's two gradients).  Backward: ops.sent_cls_bwd (isc_sent_cls_bwd: the whole reverse sweep in one call)."""
+
+    @staticmethod
+    def forward(ctx, tokens, lens, labels, masks, mask_scale, pad_id, *params):
+        B, H = tokens.shape[0], params[2].shape[1]
+        # dz is of the order 1 / B and the excitation's gradient carries a further 1 / H - below the f16 normal range at
+        # any training size, where the split-f16 engine's planes keep bits relative to 2^-14, not to the element.  The
+        # sweep is linear in dz (isc_lstm_bwd included): it runs on dz S with S the power of two that brings S / (B H)
+        # into (2^-4, 2^-3], and the gradients leave times 1 / S - both exact.
+        S = 2.0 ** (math.floor(math.log2(B * H)) - 3)
+        st = ops.sent_cls_train_fwd(list(params), tokens, lens, labels, grad_scale=S, keep_masks=masks,
+                                    mask_scale=mask_scale, pad_id=pad_id)
+        ctx.state, ctx.unscale = st, 1.0 / S
+        return st['loss'].reshape(()).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        # (the last layer's two gradients are the forward's own tensors: unscaled out of place, so that a second backward
+        #  through a retained graph starts from the same values; the other eleven are fresh from every sweep)
+        grads = torch._foreach_mul(ops.sent_cls_bwd(ctx.state), g * ctx.unscale)      # g: the caller's d loss, a device scalar
+        return (None,) * 6 + tuple(grads)
+
+
+def _sent_cls_inputs(seqs, lengths):
+    """(tokens [B, L] on the device, lens [B] int32 there) the way forward_native takes them: a device tensor of lengths
+    is used as it is (L = the tensor's width, no host read), host ints give L = max(lengths)."""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        return seqs, lengths.to(torch.int32).contiguous()
+    lengths = [int(x) for x in lengths]
+    return seqs[:, :max(lengths)], ops.upload(lengths, torch.int32, seqs.device)
+
+
+def sent_cls_loss_with_grad(model, seqs, lengths, labels, _keep_masks=None):
+    """nn.CrossEntropyLoss of model(seqs, lengths)[0] against `labels` [B] as a differentiable device scalar whose
+    backward() fills the thirteen .grad, on the library's kernels.  seqs [B, L] int64 on the device (every entry a valid id;
+    what stands behind a row's length changes no bit), lengths: host ints or a device tensor [B] (then nothing is read
+    back).  In train mode with dropout_p > 0 the three uint8 keep-masks - embedding [L, B, W], LSTM output [L, B, H] (both
+    time-major), head hidden layer [B, H] - are drawn the way the captioner draws its masks (bernoulli_ on torch's
+    generator); `_keep_masks` replays given ones (tests).  Shapes: the native forward's (word_emb_dim % 32 == rnn_hid_dim
+    % 32 == 0) and word_emb_dim <= 1024: ValueError otherwise - there is no quiet torch fallback; call model(seqs, lengths)
+    with its criterion for such shapes."""
+    ops.require_device(seqs, labels)
+    params = model.native_params()
+    (V, W), H = params[0].shape, params[2].shape[1]
+    if not ops.sent_cls_train_shape_ok(W, H) or not 1 <= params[11].shape[0] <= 8:
+        raise ValueError('sentence classifier training step: word_emb_dim (%d) and rnn_hid_dim (%d) must be multiples of 32, '
+                         'word_emb_dim <= 1024 and 1..8 categories (%d)' % (W, H, params[11].shape[0]))
+    if seqs.dim() != 2 or seqs.dtype != torch.int64:
+        raise ValueError('seqs must be an int64 matrix [B, L]')
+    tokens, lens = _sent_cls_inputs(seqs, lengths)
+    if tokens.stride(1) != 1:
+        tokens = tokens.contiguous()
+    B, L = tokens.shape
+    dev = tokens.device
+    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    p = model.drop.p
+    masks, scale = None, 1.0
+    shapes = ((L * B, W), (L * B, H), (B, H))
+    if _keep_masks is not None:
+        masks = tuple(None if m is None else m.to(device=dev, dtype=torch.uint8).reshape(s).contiguous()
+                      for m, s in zip(_keep_masks, shapes))
+        scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    elif model.training and p > 0.0:
+        masks = tuple(torch.empty(s, dtype=torch.uint8, device=dev).bernoulli_(1.0 - p) for s in shapes)
+        scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    return _SentClsLossFn.apply(tokens, lens, labels, masks, scale, model.pad_id, *params)
+
+
+def sent_cls_train_step(model, optimizer, seqs, lengths, labels, grad_clip):
+    """One training iteration of train_sent_senti_cls_rnn.py:118-125 on the device: loss (sent_cls_loss_with_grad),
+    backward, the elementwise clamp to +-grad_clip and Adam (one launch with a FusedClampAdam -
+    model.get_optim_and_crit(lr, fused=True) - or torch.optim.Adam).  Returns the loss as a device scalar - the trainer
+    decides when to read it.  Dropout follows the module's mode: call model.train() first (`sample` and
+    sent_cls_evaluate leave the module in eval mode, and in eval mode this step draws no mask)."""
+    device = next(model.parameters()).device
+    seqs, labels = ops.to_device(seqs, device), ops.to_device(labels, device)
+    loss = sent_cls_loss_with_grad(model, seqs, lengths, labels)
+    optimizer.zero_grad()
+    loss.backward()
+    clip_gradient(optimizer, grad_clip)
+    optimizer.step()
+    return loss.detach()
+
+
+@torch.no_grad()
+def sent_cls_evaluate(model, loaders_by_category):
+    """The validation pass of train_sent_senti_cls_rnn.py:128-165 on the native forward: `loaders_by_category` =
+    {category: iterable of (labels [B], (caps [B, L], lengths))}.  The wrong predictions are counted on the device, one
+    read-back per call.  -> {'all': {total_num, wrong_num, acc_rate}, 'by_category': {category: the same three}} with
+    acc_rate = 100 - wrong_num / total_num * 100.  Leaves the module in eval mode, as `sample` does."""
+    model.eval()
+    device = next(model.parameters()).device
+    names, totals, wrongs = [], [], []
+    for senti, loader in loaders_by_category.items():
+        total, wrong = 0, torch.zeros((), dtype=torch.int64, device=device)
+        for labels, (caps, lengths) in loader:
+            labels, caps = ops.to_device(labels, device), ops.to_device(caps, device)
+            pred = model.forward_native(caps, lengths)[2]
+            wrong += (pred.to(torch.int64) != labels).sum()
+            total += int(labels.shape[0])
+        names.append(senti)
+        totals.append(total)
+        wrongs.append(wrong)
+    counts = torch.stack(wrongs).tolist() if wrongs else []
+    rate = lambda w, t: 100 - w / t * 100
+    by = {n: {'total_num': t, 'wrong_num': int(w), 'acc_rate': rate(int(w), t)} for n, t, w in zip(names, totals, counts)}
+    t_all, w_all = sum(totals), sum(int(w) for w in counts)
+    return {'all': {'total_num': t_all, 'wrong_num': w_all, 'acc_rate': rate(w_all, t_all)}, 'by_category': by}
