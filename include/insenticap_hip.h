@@ -1158,6 +1158,82 @@ int64_t isc_senti_det_workspace_bytes(int B, int h, int w, int C, int n_convs, i
 int isc_senti_det_fwd(const isc_senti_det_problem *prob_host, void *stream);
 long long isc_senti_det_launches(int kind);
 
+/* Training the image-sentiment detector (train_senti.py:68-86): the saved-activation forward with the loss, and the whole
+ * reverse sweep in one call.  Shape domain, weights and layouts as isc_senti_det_fwd; feats fp32 [B,h,w,C].
+ * isc_senti_det_train_fwd:
+ *   packs the conv weights (they move every step: one launch per layer), runs the frozen forward's conv launches - the same
+ *   kernel, the same route choice (ksplit = 0) - without the ReLU, then  r = relu(keep x2 mask_scale)  (keep: optional
+ *   uint8 [B,h,w,C >> n_convs], channels-last; null = no dropout), the tail kernel (which also keeps the
+ *   pooled means and every FC activation) and the head loss:  loss = scale mean_b CE(logits_b, labels_b)  in the stable form
+ *   and dz = d loss / d logits.  labels [B] int64 on the device.  With keep null, logits and maps equal isc_senti_det_fwd's
+ *   bit for bit.  What the backward reads of the tail - pooled means, FC outputs, dz - and the loss come from a second
+ *   evaluation of the same maps in double, in the tail kernel itself: pooled sums, FC layers, softmax and the image's
+ *   cross-entropy term (the frozen tail's fp32 sum over up to 1024 pixels would otherwise stand, through dz and times
+ *   |pooled|, in every gradient); those logits differ from the ones handed out by a few fp32 ulp.  A label outside
+ *   [0, k) makes that image's loss term and dz NaN (torch raises there): the loss and every gradient come out NaN.
+ *   Launches: 2 n_convs + 3, + 1 per conv layer on the split route (its slab reduce).
+ * isc_senti_det_bwd (called with the struct the forward was called with, gradients and workspace filled in):
+ *     1          per image: dz back through the FCs to dpool, sum_p r[b,p,:], dr[b,:] = sum_j dpool[b,j]/(h w) Ws[j,:] and
+ *                the image's power-of-two scale (below)
+ *     1          d senti_conv, d FC weights and biases: one ordered sum over the images each; the common scale
+ *     1          dx2 = dr [x2 keep > 0] keep mask_scale, times the image's scale
+ *     per conv layer i = n_convs-1 .. 0:
+ *       1        d bias = sum_m dY[m,:], fixed order
+ *       1        d weight [Cout,Cin,3,3]: the implicit TN contraction  sum_m dY[m,co] X[pixel(m) + (ky-1,kx-1), ci]  over
+ *                the M = B h w rows on the split-f16 MFMA engine (64 x 128 output tiles, both operands staged through
+ *                LDS transposed, X read where it lies; out-of-grid taps are exact zeros)
+ *       2 [i>0]  dX = conv3x3(dY, W') with W'[ci,co,ky,kx] = W[co,ci,2-ky,2-kx]: the flipped-transposed pack and a launch of
+ *                the forward's convolution kernel (no bias, no ReLU; + 1 slab reduce on the split route)
+ *   = 4 n_convs + 1 launches (+ 1 per dX on the split route, + 1 with dx_out); n_fcs and the mask change neither count.
+ *   Scaling: dz <= scale / B and dx2 carries a further 1 / (h w) and |Ws|: far below the f16 normal range.  Every image's
+ *   dx2 is multiplied by e_b = 2^-floor(log2 max_c |dr[b,c]|) before it meets the split-f16 planes (so an image's dX rows
+ *   depend on that image alone), the contractions over m bring the rows to the common scale E = min_b e_b as they load them
+ *   and multiply by 1 / E in fp32 in their epilogue - all exact powers of two, all read from device memory.
+ *   No allocation, no host read, no atomics; every cross-image and cross-pixel sum runs in a fixed order.
+ * saved: isc_senti_det_train_saved_bytes (forward writes, backward reads); workspace (backward only):
+ * isc_senti_det_bwd_workspace_bytes.  dx_out (optional, tests): [B h w, C/2] the gradient of conv_0's output, unscaled
+ * (n_convs >= 2).  Errors as isc_senti_det_fwd (ISC_E_NULL / SHAPE / WORKSPACE / ALIGN), all before any launch. */
+typedef struct {
+    const float *feats;
+    int32_t B, h, w, C, n_convs, n_fcs, k, _pad;
+    float mask_scale, scale;
+    const float *conv_w[ISC_SENTI_DET_MAX_CONVS], *conv_b[ISC_SENTI_DET_MAX_CONVS];
+    const float *senti_w, *senti_b;
+    const float *fc_w[ISC_SENTI_DET_MAX_FCS], *fc_b[ISC_SENTI_DET_MAX_FCS];
+    const int64_t *labels;
+    const uint8_t *keep;
+    void *saved;
+    int64_t saved_bytes;
+    void *workspace;            /* isc_senti_det_bwd only */
+    int64_t workspace_bytes;
+    float *logits, *maps, *loss;
+    float *d_conv_w[ISC_SENTI_DET_MAX_CONVS], *d_conv_b[ISC_SENTI_DET_MAX_CONVS];
+    float *d_senti_w, *d_senti_b;
+    float *d_fc_w[ISC_SENTI_DET_MAX_FCS], *d_fc_b[ISC_SENTI_DET_MAX_FCS];
+    float *dx_out;
+} isc_senti_det_train_problem;
+int64_t isc_senti_det_train_saved_bytes(int B, int h, int w, int C, int n_convs, int n_fcs);
+int64_t isc_senti_det_bwd_workspace_bytes(int B, int h, int w, int C, int n_convs);
+int isc_senti_det_train_fwd(const isc_senti_det_train_problem *prob_host, void *stream);
+int isc_senti_det_bwd(const isc_senti_det_train_problem *prob_host, void *stream);
+/* launches so far (test hook; -1 for an unknown kind) */
+#define ISC_SENTI_DET_TRAIN_KIND_FWD 0      /* all launches of isc_senti_det_train_fwd */
+#define ISC_SENTI_DET_TRAIN_KIND_BWD 1      /* all launches of isc_senti_det_bwd */
+#define ISC_SENTI_DET_TRAIN_KIND_REDUCE 2   /* of either: slab reduces behind split-route convolutions */
+#define ISC_SENTI_DET_TRAIN_KINDS 3
+long long isc_senti_det_bwd_launches(int kind);
+/* The kernels of the sweep on their own (tests).
+ * isc_senti_det_dw: dw [Cout,Cin,3,3] = unscale sum_m dy[m,co] ratio[b(m)] x[pixel(m) + tap, ci];  dy [M, ldy] (ldy >=
+ *   Cout, ldy % 4 == 0), x [B,h,w,Cin]; ratio [B] and unscale [1] on the device, null = 1.  Cin % 32 == 0, Cout % 16 == 0.
+ * isc_senti_det_pack_flipped: planes of W' [Cin, 9 Cp] (Cp = Cout rounded up to 32, the padding zero) from w [Cout,Cin,3,3];
+ *   2 Cin 9 Cp halfs. */
+int isc_senti_det_dw(const float *dy, int ldy, const float *x, int B, int h, int w, int Cin, int Cout, const float *ratio,
+                     const float *unscale, float *dw, void *stream);
+int isc_senti_det_pack_flipped(const float *w, int Cout, int Cin, void *planes, void *stream);
+/* Float offsets into isc_senti_det_bwd's workspace of what its first two launches leave (tests): out6 = g [n_fcs][B][8]
+ * (d loss / d output of FC l), dpool [B][8], rsum [B, C >> n_convs] (sum_p r), dr [B, C >> n_convs], e_b [B], E / e_b [B]. */
+int isc_senti_det_bwd_tail_offsets(int B, int h, int w, int C, int n_convs, int64_t *out6);
+
 /* The concept detector (concept_detector.py; train_cpt.py, detect_concepts.py, test_cpt.py) - csrc/concept.hip.  One
  * wave64 per row, no atomics, every sum in a fixed order (two calls give the same bits), no allocation and no host read:
  * capturable.

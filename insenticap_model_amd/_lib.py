@@ -188,6 +188,25 @@ class SentiDetProblem(C.Structure):
                 _f('logits maps labels scores conv_out', C.c_void_p))
 
 
+SENTI_DET_TRAIN_KINDS = ('fwd', 'bwd', 'reduce')                          # isc_senti_det_bwd_launches(kind index)
+
+
+class SentiDetTrainProblem(C.Structure):
+    """isc_senti_det_train_problem: one training iteration of the image-sentiment detector (csrc/senti_det.hip)."""
+    _fields_ = ([('feats', C.c_void_p)] + _f('B h w C n_convs n_fcs k _pad', C.c_int32) +
+                [('mask_scale', C.c_float), ('scale', C.c_float),
+                 ('conv_w', C.c_void_p * SENTI_DET_MAX_CONVS), ('conv_b', C.c_void_p * SENTI_DET_MAX_CONVS)] +
+                _f('senti_w senti_b', C.c_void_p) +
+                [('fc_w', C.c_void_p * SENTI_DET_MAX_FCS), ('fc_b', C.c_void_p * SENTI_DET_MAX_FCS)] +
+                _f('labels keep saved', C.c_void_p) + [('saved_bytes', C.c_int64), ('workspace', C.c_void_p),
+                                                       ('workspace_bytes', C.c_int64)] +
+                _f('logits maps loss', C.c_void_p) +
+                [('d_conv_w', C.c_void_p * SENTI_DET_MAX_CONVS), ('d_conv_b', C.c_void_p * SENTI_DET_MAX_CONVS)] +
+                _f('d_senti_w d_senti_b', C.c_void_p) +
+                [('d_fc_w', C.c_void_p * SENTI_DET_MAX_FCS), ('d_fc_b', C.c_void_p * SENTI_DET_MAX_FCS),
+                 ('dx_out', C.c_void_p)])
+
+
 CONCEPT_MAX_NUM = 16
 SENTI_WORDS_CAP = 1024
 SENTI_WORDS_MAX_OUT = 20
@@ -348,6 +367,15 @@ SIGNATURES = {
     'isc_senti_det_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'isc_senti_det_fwd': (C.c_int, [C.POINTER(SentiDetProblem), C.c_void_p]),
     'isc_senti_det_launches': (C.c_longlong, [C.c_int]),
+    'isc_senti_det_train_saved_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_senti_det_bwd_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'isc_senti_det_train_fwd': (C.c_int, [C.POINTER(SentiDetTrainProblem), C.c_void_p]),
+    'isc_senti_det_bwd': (C.c_int, [C.POINTER(SentiDetTrainProblem), C.c_void_p]),
+    'isc_senti_det_bwd_launches': (C.c_longlong, [C.c_int]),
+    'isc_senti_det_dw': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_senti_det_pack_flipped': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'isc_senti_det_bwd_tail_offsets': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     'isc_concept_head': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'isc_concept_loss_workspace_bytes': (C.c_int64, [C.c_int]),

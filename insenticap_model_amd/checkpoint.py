@@ -143,3 +143,32 @@ def load_sent_cls_checkpoint(path, model=None, optimizer=None, **expected):
         optimizer.load_state_dict(chk['optimizer'])
         lr = optimizer.param_groups[0]['lr']
     return model, chk['epoch'], lr
+
+
+def save_senti_checkpoint(directory, epoch, model, optimizer, settings, sentiment_categories, train_loss=0.0, val_loss=0.0):
+    """The image-sentiment detector's checkpoint as train_senti.py:119-128 writes it: {epoch, model, optimizer, settings,
+    sentiment_categories} under model_<epoch>_<train loss>_<val loss>_<time>.pth."""
+    chk = {'epoch': epoch, 'model': model.state_dict(), 'optimizer': optimizer.state_dict(), 'settings': settings,
+           'sentiment_categories': sentiment_categories}
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, 'model_%d_%.4f_%.4f_%s.pth' % (epoch, train_loss, val_loss, time.strftime('%m%d-%H%M')))
+    torch.save(chk, path)
+    return path
+
+
+def load_senti_checkpoint(path, model=None, optimizer=None, **expected):
+    """Resume as train_senti.py:28-40 does (`expected`: settings / sentiment_categories must equal the file's), or -
+    model=None - build the detector from the file.  Returns (model, epoch, lr); lr is None without an optimizer."""
+    chk = torch.load(path, map_location=lambda s, l: s, weights_only=False)
+    for key in ('settings', 'sentiment_categories'):
+        if key in expected and expected[key] != chk[key]:
+            raise AssertionError('%s and resume model %s are different' % ('opt.settings' if key == 'settings' else key, key))
+    if model is None:
+        from .helper_nets import SentimentDetector
+        model = SentimentDetector(chk['sentiment_categories'], chk['settings'])
+    model.load_state_dict(chk['model'])
+    lr = None
+    if optimizer is not None and 'optimizer' in chk:
+        optimizer.load_state_dict(chk['optimizer'])
+        lr = optimizer.param_groups[0]['lr']
+    return model, chk['epoch'], lr

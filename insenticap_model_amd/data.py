@@ -203,7 +203,7 @@ def create_collate_fn(name, pad_index=0, max_seq_len=17, num_concepts=5, num_sen
             (_pad_rows(caps, lengths[0], pad_index, limit=max_seq_len), lengths)
 
     table = {'caption': caption if captions_per_image is None else caption_grouped, 'scs': scs, 'senti_corpus_with_sentis': scs, 'rl_fact': rl_fact,
-             'rl_senti': rl_senti, 'senti_sents': senti_sents}
+             'rl_senti': rl_senti, 'senti_sents': senti_sents, 'senti_image': senti_image_collate_fn}
     if name not in table:
         raise KeyError('collate %r is outside the decoder path (have: %s)' % (name, sorted(table)))
     return table[name]
@@ -630,6 +630,36 @@ class ConceptDataset(torch.utils.data.Dataset):
 def get_concept_dataloader(fc_feats, img_concepts, num_cpts, batch_size, num_workers=0, shuffle=True):
     """dataloader.py:338-345."""
     return _loader(ConceptDataset(fc_feats, img_concepts, num_cpts), batch_size, num_workers, shuffle, concept_collate_fn)
+
+
+# ---------------------------------------------------------------------------- image-sentiment detector (dataloader.py:117-121,248-260,349-357)
+def senti_image_collate_fn(dataset):
+    """The reference's 'senti_image' collate (dataloader.py:117-121): items (fn, att [h, w, F], label) -> (fns, att_feats
+    [B, h, w, F] fp32 - float16 when every item is, rows of a DeviceFeatureStore gathered on the device -, labels [B]
+    int64)."""
+    fns, atts, labels = zip(*dataset)
+    return fns, _feats(atts), torch.from_numpy(np.asarray(labels, dtype=np.int64))
+
+
+class SentiImageDataset(torch.utils.data.Dataset):
+    """dataloader.py:248-260: item = (fn, att [h, w, F], sentiment label index) over [(fn, label index), ...]."""
+
+    def __init__(self, senti_att_feats, img_senti_labels):
+        self.att_feats = _store(senti_att_feats)
+        self.img_senti_labels = list(img_senti_labels)
+
+    def __getitem__(self, index):
+        fn, senti_label = self.img_senti_labels[index]
+        return fn, _item(self.att_feats[fn]), senti_label
+
+    def __len__(self):
+        return len(self.img_senti_labels)
+
+
+def get_senti_image_dataloader(senti_att_feats, img_senti_labels, batch_size, num_workers=0, shuffle=True):
+    """dataloader.py:349-357, over any of the project's feature stores (or a {fn: array} mapping)."""
+    return _loader(SentiImageDataset(senti_att_feats, img_senti_labels), batch_size, num_workers, shuffle,
+                   senti_image_collate_fn)
 
 
 # ---------------------------------------------------------------------------- sentence classifier (dataloader.py:263-272,360-370)

@@ -120,7 +120,12 @@ class SentimentDetector(nn.Module):
         labels, maps, scores = self.sample_device(features, senti_threshold)
         return labels, maps, self.names(labels), scores
 
-    def get_optim_criterion(self, lr, weight_decay=0):
+    def get_optim_criterion(self, lr, weight_decay=0, fused=False):
+        """`fused=True`: optim.FusedClampAdam (clamp + Adam in one launch) for train.senti_det_train_step; the default is
+        the reference's torch.optim.Adam."""
+        if fused:
+            from .optim import FusedClampAdam
+            return FusedClampAdam(self.parameters(), lr=lr, weight_decay=weight_decay), nn.CrossEntropyLoss()
         return torch.optim.Adam(self.parameters(), lr=lr, weight_decay=weight_decay), nn.CrossEntropyLoss()
 
 

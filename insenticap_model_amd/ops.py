@@ -1254,6 +1254,143 @@ def senti_det_fwd(params, feats, threshold, neu_idx, *, packed=None, ksplit=0, o
     return (logits, maps, labels, scores) + ((conv_out,) if want_conv_out else ())
 
 
+# ---- the detector's training (isc_senti_det_train_fwd / isc_senti_det_bwd and two of its kernels on their own)
+_SENTI_DET_TRAIN_WS = {}    # (device index, stream, B, h, w, C, n_convs, n_fcs) -> (saved, backward workspace)
+
+
+def senti_det_bwd_launches(kind=None):
+    """Launches of the detector's training calls so far: a dict over _lib.SENTI_DET_TRAIN_KINDS ('fwd', 'bwd', and of
+    either 'reduce' = slab reduces behind split-route convolutions), or one kind's count."""
+    lib = _lib.load()
+    if kind is not None:
+        return lib.isc_senti_det_bwd_launches(_lib.SENTI_DET_TRAIN_KINDS.index(kind))
+    return {name: lib.isc_senti_det_bwd_launches(i) for i, name in enumerate(_lib.SENTI_DET_TRAIN_KINDS)}
+
+
+def senti_det_train_buffers(dev, B, h, w, Cf, n_convs, n_fcs):
+    """(saved, workspace) of one training iteration.  saved belongs to the iteration (the caching allocator hands it
+    out without a device call); the backward's workspace is scratch, kept per (device, stream, geometry) as
+    _SENTI_DET_WS is - except inside a graph capture (a fresh one from the capture's pool)."""
+    lib = _lib.load()
+    new = lambda n: torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+    saved = new(lib.isc_senti_det_train_saved_bytes(B, h, w, Cf, n_convs, n_fcs))
+    need = lib.isc_senti_det_bwd_workspace_bytes(B, h, w, Cf, n_convs)
+    if torch.cuda.is_current_stream_capturing():
+        return saved, new(need)
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, B, h, w, Cf, n_convs, n_fcs)
+    ws = _SENTI_DET_TRAIN_WS.get(key)
+    if ws is None:
+        ws = _SENTI_DET_TRAIN_WS[key] = new(need)
+    return saved, ws
+
+
+def senti_det_train_fwd(params, feats, labels, scale=1.0, keep=None, mask_scale=1.0, buffers=None):
+    """isc_senti_det_train_fwd: the saved-activation forward and the loss.  params as senti_det_fwd, feats [B,h,w,C] fp32
+    contiguous, labels [B] int64 on the device, keep = None or a uint8 keep-mask [B,h,w,C >> n_convs].  -> a state dict:
+    logits [B,k], maps [B,h,w], loss [1] (= scale * mean cross-entropy) and what senti_det_bwd needs."""
+    lib = _lib.load()
+    conv_w, conv_b, senti_w, senti_b, fc_w, fc_b = _senti_det_split_params(params)
+    require_device(feats, labels, *params)
+    register_status_words(feats.device)
+    assert feats.dim() == 4 and feats.is_contiguous() and feats.dtype == torch.float32
+    for t in list(params):
+        assert t.dtype == torch.float32 and t.is_contiguous(), 'detector parameters: contiguous fp32'
+    B, h, w, Cf = feats.shape
+    n_convs, n_fcs, k = len(conv_w), len(fc_w), senti_w.shape[0]
+    dev = feats.device
+    if n_convs > _lib.SENTI_DET_MAX_CONVS or n_fcs > _lib.SENTI_DET_MAX_FCS or conv_w[0].shape[1] != Cf or \
+            senti_w.numel() != k * (Cf >> n_convs):
+        raise _lib.HipLibraryError('isc_senti_det_train_fwd failed: ISC_E_SHAPE (unsupported size)')
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)
+    CL = Cf >> n_convs
+    assert keep is None or (keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == B * h * w * CL
+                            and keep.device == dev)
+    saved, workspace = buffers if buffers is not None else senti_det_train_buffers(dev, B, h, w, Cf, n_convs, n_fcs)
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    st = dict(logits=new(B, k), maps=new(B, h, w), loss=new(1), saved=saved, workspace=workspace,
+              keep=(list(params), feats, labels, keep))
+    p = _lib.SentiDetTrainProblem()
+    p.feats = feats.data_ptr()
+    p.B, p.h, p.w, p.C, p.n_convs, p.n_fcs, p.k = B, h, w, Cf, n_convs, n_fcs, k
+    p.mask_scale, p.scale = float(mask_scale), float(scale)
+    for i, (tw, tb) in enumerate(zip(conv_w, conv_b)):
+        p.conv_w[i], p.conv_b[i] = tw.data_ptr(), tb.data_ptr()
+    p.senti_w, p.senti_b = senti_w.data_ptr(), senti_b.data_ptr()
+    for i, (tw, tb) in enumerate(zip(fc_w, fc_b)):
+        p.fc_w[i], p.fc_b[i] = tw.data_ptr(), tb.data_ptr()
+    p.labels, p.keep = labels.data_ptr(), ptr(keep)
+    p.saved, p.saved_bytes = saved.data_ptr(), saved.numel()
+    p.logits, p.maps, p.loss = st['logits'].data_ptr(), st['maps'].data_ptr(), st['loss'].data_ptr()
+    check(lib.isc_senti_det_train_fwd(C.byref(p), stream()), 'isc_senti_det_train_fwd')
+    st['problem'] = p
+    return st
+
+
+def senti_det_bwd(state, want_dx=False):
+    """isc_senti_det_bwd: the reverse sweep behind senti_det_train_fwd's state -> the gradients in the order of `params`
+    [, dx [B*h*w, C/2]: the gradient of conv_0's output (tests; two convs or more)]."""
+    lib = _lib.load()
+    p = state['problem']
+    params = state['keep'][0]
+    grads = [torch.empty_like(t) for t in params]
+    conv_w, conv_b, senti_w, senti_b, fc_w, fc_b = _senti_det_split_params(grads)
+    for i, (tw, tb) in enumerate(zip(conv_w, conv_b)):
+        p.d_conv_w[i], p.d_conv_b[i] = tw.data_ptr(), tb.data_ptr()
+    p.d_senti_w, p.d_senti_b = senti_w.data_ptr(), senti_b.data_ptr()
+    for i, (tw, tb) in enumerate(zip(fc_w, fc_b)):
+        p.d_fc_w[i], p.d_fc_b[i] = tw.data_ptr(), tb.data_ptr()
+    ws = state['workspace']
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    dx = torch.empty(p.B * p.h * p.w, p.C // 2, dtype=torch.float32, device=ws.device) if want_dx else None
+    p.dx_out = ptr(dx)
+    check(lib.isc_senti_det_bwd(C.byref(p), stream()), 'isc_senti_det_bwd')
+    return grads + ([dx] if want_dx else [])
+
+
+def senti_det_bwd_tail(state):
+    """What isc_senti_det_bwd's first two launches left in the workspace of `state` (after senti_det_bwd; tests): a dict
+    of views - g [n_fcs,B,8], dpool [B,8], rsum [B,CL], dr [B,CL], eb [B], ratio [B]."""
+    p = state['problem']
+    off = (C.c_int64 * 6)()
+    check(_lib.load().isc_senti_det_bwd_tail_offsets(p.B, p.h, p.w, p.C, p.n_convs, off), 'isc_senti_det_bwd_tail_offsets')
+    ws = state['workspace'].view(torch.float32)
+    CL = p.C >> p.n_convs
+    shapes = dict(g=(p.n_fcs, p.B, 8), dpool=(p.B, 8), rsum=(p.B, CL), dr=(p.B, CL), eb=(p.B,), ratio=(p.B,))
+    out = {}
+    for o, (name, shape) in zip(off, shapes.items()):
+        n = 1
+        for d in shape:
+            n *= d
+        out[name] = ws[o:o + n].view(shape)
+    return out
+
+
+def senti_det_dw(dy, x, Cout, ratio=None, unscale=None):
+    """isc_senti_det_dw on its own: dy [B*h*w, ld >= Cout], x [B,h,w,Cin] fp32 -> dw [Cout,Cin,3,3] =
+    unscale * sum_m dy[m,co] ratio[b(m)] x[pixel(m) + tap, ci]; ratio [B] / unscale [1] device tensors or None (= 1)."""
+    require_device(dy, x)
+    assert dy.dtype == x.dtype == torch.float32 and dy.is_contiguous() and x.is_contiguous() and x.dim() == 4
+    B, h, w, Cin = x.shape
+    assert dy.shape[0] == B * h * w
+    dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
+    check(_lib.load().isc_senti_det_dw(dy.data_ptr(), dy.shape[1], x.data_ptr(), B, h, w, Cin, Cout, ptr(ratio),
+                                       ptr(unscale), dw.data_ptr(), stream()), 'isc_senti_det_dw')
+    return dw
+
+
+def senti_det_pack_flipped(w):
+    """isc_senti_det_pack_flipped: w [Cout,Cin,3,3] -> the float16 planes [Cin, 2 * 9 * Cp] (Cp = Cout rounded up to 32)
+    of W'[ci, (2-ky, 2-kx), co] = w[co, ci, ky, kx] in the plane layout of the convolution kernel."""
+    require_device(w)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
+    Cout, Cin = w.shape[:2]
+    Cp = (Cout + 31) // 32 * 32
+    planes = torch.empty(Cin, 2 * 9 * Cp, dtype=torch.float16, device=w.device)
+    check(_lib.load().isc_senti_det_pack_flipped(w.data_ptr(), Cout, Cin, planes.data_ptr(), stream()),
+          'isc_senti_det_pack_flipped')
+    return planes
+
+
 __all__ = [n for n in dir() if n.endswith('_fwd') or n.endswith('_problem')] + [
     'RolloutStep', 'rollout_finalize', 'rollout_finalize_filtered', 'beam_topk', 'logsoftmax_apply', 'require_device']
 

@@ -432,3 +432,103 @@ def sent_cls_evaluate(model, loaders_by_category):
     by = {n: {'total_num': t, 'wrong_num': int(w), 'acc_rate': rate(int(w), t)} for n, t, w in zip(names, totals, counts)}
     t_all, w_all = sum(totals), sum(int(w) for w in counts)
     return {'all': {'total_num': t_all, 'wrong_num': w_all, 'acc_rate': rate(w_all, t_all)}, 'by_category': by}
+
+
+# ---------------------------------------------------------------------------- image-sentiment detector (train_senti.py:68-108)
+class _SentiDetLossFn(torch.autograd.Function):
+    """Features to CrossEntropyLoss in one node.  Forward: ops.senti_det_train_fwd (isc_senti_det_train_fwd: the frozen
+    forward's convolution launches with every intermediate kept, the tail and the head loss, which also leaves dz).
+    Backward: ops.senti_det_bwd (isc_senti_det_bwd: the whole reverse sweep in one call; the small gradients meet the
+    split-f16 planes times a power of two the sweep itself takes from their magnitude - no constant to choose here)."""
+
+    @staticmethod
+    def forward(ctx, feats, labels, keep, mask_scale, scale, *params):
+        st = ops.senti_det_train_fwd(list(params), feats, labels, scale=scale, keep=keep, mask_scale=mask_scale)
+        ctx.state = st
+        # (the backward reads the parameters again - the flipped pack, the FC and senti_conv weights: saved as tensors, so
+        #  that an in-place update between forward and backward raises autograd's version error)
+        ctx.save_for_backward(*params)
+        return st['loss'].reshape(())           # (a fresh tensor of this call: no copy)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.saved_tensors                        # (the version check)
+        grads = torch._foreach_mul(ops.senti_det_bwd(ctx.state), g)      # g: the caller's d loss, a device scalar
+        return (None,) * 5 + tuple(grads)
+
+
+def _senti_det_feats(att_feats, device):
+    """[B, h, w, F] fp32 contiguous on the device; float16 features are converted once per batch."""
+    att_feats = ops.to_device(att_feats, device)
+    if att_feats.dtype != torch.float32:
+        att_feats = att_feats.to(torch.float32)
+    return att_feats.contiguous()
+
+
+def senti_det_loss_with_grad(model, att_feats, labels, _keep_mask=None, _scale=1.0):
+    """nn.CrossEntropyLoss of model(att_feats)[0] against `labels` [B] as a differentiable device scalar whose backward()
+    fills the .grad of every parameter, on the library's kernels.  att_feats [B, h, w, F] fp32 or float16 on the device,
+    labels a device tensor or host ints.  In train mode with dropout_p > 0 the uint8 keep-mask [B, h, w, F >> convs]
+    (channels-last) is drawn the way the captioner draws its masks (bernoulli_ on torch's generator); a label outside
+    [0, categories) makes the loss and every gradient NaN (torch raises there; here nothing is read back); `_keep_mask` replays
+    a given one and `_scale` multiplies the loss (tests).  Shapes: the native forward's (every conv's input width a multiple
+    of 32, at most four convs and four FCs, 1..8 categories, h w <= 1024): ValueError otherwise - there is no quiet torch
+    fallback; call model(att_feats) with its criterion for such shapes."""
+    params = model.native_params()
+    device = params[0].device
+    att_feats = ops.to_device(att_feats, device)                # (a data.RowGather batch is expanded here)
+    if att_feats.dim() != 4:
+        raise ValueError('att_feats must be [B, h, w, F]')
+    B, h, w, F = att_feats.shape
+    n_convs = sum(1 for m in model.convs if isinstance(m, torch.nn.Conv2d))
+    n_fcs, k = len(model.output), model.senti_conv.weight.shape[0]
+    if not ops._lib.load().isc_senti_det_train_saved_bytes(B, h, w, F, n_convs, n_fcs) or not 1 <= k <= 8 or \
+            model.convs[0].weight.shape[1] != F:
+        raise ValueError('image-sentiment training step: [%d, %d, %d, %d] features with %d convs, %d FCs and %d categories '
+                         'are outside the kernels (every conv input width a multiple of 32, h w <= 1024)'
+                         % (B, h, w, F, n_convs, n_fcs, k))
+    feats = _senti_det_feats(att_feats, device)
+    if not torch.is_tensor(labels):
+        labels = ops.upload([int(x) for x in labels], torch.int64, device)
+    labels = ops.to_device(labels, device).to(torch.int64).contiguous()
+    ops.require_device(feats, labels)
+    p = model.convs.dropout.p
+    CL = F >> n_convs
+    keep, ms = None, 1.0
+    if _keep_mask is not None:
+        keep = _keep_mask.to(device=device, dtype=torch.uint8).reshape(B, h, w, CL).contiguous()
+        ms = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    elif model.training and p > 0.0:
+        keep = torch.empty(B, h, w, CL, dtype=torch.uint8, device=device).bernoulli_(1.0 - p)
+        ms = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+    return _SentiDetLossFn.apply(feats, labels, keep, ms, float(_scale), *params)
+
+
+def senti_det_train_step(model, optimizer, att_feats, labels, grad_clip):
+    """One training iteration of train_senti.py:78-85 on the device: loss (senti_det_loss_with_grad), backward, the
+    elementwise clamp to +-grad_clip and Adam (one launch with a FusedClampAdam - model.get_optim_criterion(lr,
+    fused=True) - or torch.optim.Adam).  Returns the loss as a device scalar - the trainer decides when to read it.
+    Dropout follows the module's mode: call model.train() first (senti_det_evaluate and `sample` leave it in eval mode)."""
+    loss = senti_det_loss_with_grad(model, att_feats, labels)
+    optimizer.zero_grad()
+    loss.backward()
+    clip_gradient(optimizer, grad_clip)
+    optimizer.step()
+    return loss.detach()
+
+
+@torch.no_grad()
+def senti_det_evaluate(model, loader):
+    """The test pass of train_senti.py:100-108 through sample_device (the native forward when the module's switch is on):
+    `loader` yields (fns, att_feats, labels).  The correct predictions are counted on the device, one read-back per call.
+    -> {'corr_num', 'all_num', 'corr_rate'}.  Leaves the module in eval mode, as `sample` does."""
+    model.eval()
+    device = next(model.parameters()).device
+    corr, total = torch.zeros((), dtype=torch.int64, device=device), 0
+    for _, att_feats, labels in loader:
+        att_feats, labels = ops.to_device(att_feats, device), ops.to_device(labels, device)
+        idx = model.sample_device(att_feats)[0]
+        corr += (idx == labels.to(torch.int64)).sum()
+        total += int(labels.shape[0])
+    corr = int(corr)
+    return {'corr_num': corr, 'all_num': total, 'corr_rate': corr / total if total else 0.0}
