@@ -106,6 +106,40 @@ int64_t isc_bleu_cook_fill(const int64_t *tokens, const int64_t *cap_off, int64_
                            int64_t sos_id, int64_t eos_id, uint64_t *keys, int32_t *counts,
                            int32_t *ent_off, int32_t *ref_lens);
 
+/* ---- n-gram language models (per-sentiment ARPA models of order <= 4: the `ppl` metric and the LM reward of
+ * self_critical/utils.py:86-100).  An ARPA file is parsed in Python (rewards.read_arpa); here its n-grams arrive as
+ * csrc/cider_key.h keys - the OLDEST word in field 0 - with logp and backoff already rounded to float32 (a missing
+ * back-off weight is +0.0).  With V vocabulary words, <s>, </s>, <unk> are the ids V, V + 1, V + 2 and V + 3 is "no
+ * word" (what a token outside [0, V) becomes; no table holds it): V <= 65531.  Slot (csrc/lm_slot.h, 16 bytes):
+ * {uint64 key; float logp; float backoff}, key 0 = empty; home slot isc_cider_hash(key) & (capacity - 1), linear probing.
+ *
+ * isc_lm_table_capacity(n): the smallest power of two >= max(16, 2 n).  isc_lm_table_fill writes `capacity` slots; any
+ * power of two above n is taken (tests fill a tighter table; one slot at least stays empty).  0, -1 null pointer, -2 bad
+ * capacity, -3 a key 0, -5 a duplicate key. */
+int64_t isc_lm_table_capacity(int64_t n);
+int isc_lm_table_fill(const uint64_t *keys, const float *logp, const float *backoff, int64_t n, void *slots,
+                      int64_t capacity);
+
+/* Host scorer: the inputs and outputs of isc_lm_dev_score (include/insenticap_hip.h), all in host memory, plus n_slots,
+ * the length of the slot array.  Several models lie in ONE slot array, model l in lm_off[l] .. lm_off[l] + lm_capacity[l]
+ * with order lm_order[l]; a probe wraps inside its own model's range.  Row r (hyp + r T, normalised as isc_cider_score
+ * normalises) is scored by model labels[r] (labels == NULL: model 0):
+ *   eos_mode 0 ('word'): the <EOS> id is scored as a word, then </s>;  1 ('end'): the <EOS> becomes </s>;
+ *   the value of a word after its context (the last order - 1 words, starting at <s>): from the longest context c to the
+ *   empty one - c.w in the table: (double)logp(c.w) + acc; otherwise acc += (double)backoff(c) where c is in the table,
+ *   and the oldest word of c is dropped; acc starts at 0.0.  A word without a unigram is out of vocabulary: with
+ *   unk_as_word and an <unk> unigram it scores logp(<unk>) + acc, otherwise it is skipped (value 0.0, not in n_scored);
+ *   score[r] = the float64 sum of the values over the positions in ascending order (log10); n_scored[r], n_oov[r] (or
+ *   NULL); tok_logp [N, T + 2] (or NULL): the value per position, 0.0 where skipped and behind the sentence.
+ * A label outside [0, n_lm): score NaN, n_scored -1, n_oov 0.  Up to min(n_threads, 16) threads; the result does not
+ * depend on their number and equals the device scorer's in bits.
+ * 0, -1 null pointer, -2 a bad table description (capacity no power of two >= 2, a range outside the slot array, an order
+ * outside [1, 4]), -4 bad shape (N < 1, T < 1, n_lm < 1, V outside [1, 65531], eos_mode outside {0, 1}). */
+int isc_lm_score(const int64_t *hyp, int64_t N, int64_t T, const int64_t *labels, int n_lm, const void *slots,
+                 int64_t n_slots, const int64_t *lm_off, const int64_t *lm_capacity, const int32_t *lm_order, int V,
+                 int eos_mode, int unk_as_word, int64_t sos_id, int64_t eos_id, double *score, int32_t *n_scored,
+                 int32_t *n_oov, double *tok_logp, int n_threads);
+
 #ifdef __cplusplus
 }
 #endif

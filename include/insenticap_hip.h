@@ -924,6 +924,26 @@ int isc_bleu_dev_score(const int64_t *hyp, int64_t N, int T, int row_div, const 
                        const int32_t *ref_lens, int64_t n_img, int order, int64_t sos_id, int64_t eos_id, double *scores,
                        int32_t *stats, void *stream);
 
+/* Back-off n-gram language models on the device: what isc_lm_score (include/insenticap_cider.h, where the model, the slot
+ * and the walk are defined) gives for row r, in bits - only float32 -> float64 conversions and float64 additions in a
+ * fixed order are involved.  All pointers are device memory.
+ *   hyp [N, T] int64, contiguous, normalised as isc_cider_dev_score normalises; T <= 62 (T + 2 scored positions).  An id
+ *     outside [0, V) becomes the "no word" id: an id is never an index, so it reads nothing out of bounds.
+ *   labels [N] int64 (the model of each row) or NULL (model 0); n_lm models in ONE array of 16-byte slots (csrc/lm_slot.h):
+ *     model l owns slots[lm_off[l] .. lm_off[l] + lm_capacity[l]) (int64 [n_lm] each, the capacity a power of two with at
+ *     least one empty slot) and has order lm_order[l] (int32 [n_lm], 1 .. 4).  The caller vouches for these three arrays:
+ *     they are device memory, no host check can read them.
+ *   eos_mode 0 ('word') / 1 ('end'), unk_as_word, V <= 65531: see isc_lm_score.
+ *   score [N] float64 (log10); n_scored [N], n_oov [N] int32 or NULL; tok_logp [N, T + 2] float64 or NULL.
+ * One wave64 per row, one lane per scored position, four rows per workgroup; a lane walks at most 2 order - 1 probe
+ * chains; the row's sum runs over the lanes in ascending order.  No workspace, no LDS, no atomics.  One launch, no host
+ * read: capturable.  A label outside [0, n_lm): score NaN, n_scored -1, n_oov 0, no table is read.
+ * N < 1, T outside [1, 62], n_lm < 1, V outside [1, 65531], eos_mode outside {0, 1}: ISC_E_SHAPE, nothing is launched. */
+int isc_lm_dev_score(const int64_t *hyp, int64_t N, int T, const int64_t *labels, int n_lm, const void *slots,
+                     const int64_t *lm_off, const int64_t *lm_capacity, const int32_t *lm_order, int V, int eos_mode,
+                     int unk_as_word, int64_t sos_id, int64_t eos_id, double *score, int32_t *n_scored, int32_t *n_oov,
+                     double *tok_logp, void *stream);
+
 /* Log-softmax backward with the criteria's gradient handed over SPARSE: XECriterion (captioner.py:427-440) and the
  * REINFORCE gather (captioner.py:336) touch one column per (caption, step) row, so their d log-prob is `coef[m]` at
  * column `ids[m]` - up to ISC_SPARSE_MAX such (ids, coef) pairs (HOST arrays of device pointers to [M] vectors, rows

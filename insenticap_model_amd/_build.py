@@ -11,10 +11,11 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libinsenticap_hip.so')
 SOURCES = ['gemm_f32.hip', 'attention.hip', 'pointwise.hip', 'backward.hip', 'step.hip', 'rows.hip', 'sent_cls.hip',
-           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'concept.hip']
+           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'lm_dev.hip', 'concept.hip']
 CIDER_KEY_H = os.path.join(CSRC, 'cider_key.h')      # the n-gram key: read by cider_dev.hip, bleu_dev.hip AND cider.cpp
+LM_SLOT_H = os.path.join(CSRC, 'lm_slot.h')          # the language-model slot: read by lm_dev.hip AND lm.cpp
 HEADERS = [os.path.join(CSRC, 'common.h'),
-           os.path.join(os.path.dirname(HERE), 'include', 'insenticap_hip.h'), CIDER_KEY_H]
+           os.path.join(os.path.dirname(HERE), 'include', 'insenticap_hip.h'), CIDER_KEY_H, LM_SLOT_H]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
 
@@ -71,14 +72,14 @@ CIDER_LIB_PATH = os.path.join(LIB_DIR, 'libinsenticap_cider.so')
 
 
 def build_cider(force=False, verbose=False, _report=False):
-    """Host-side CIDEr-D / BLEU reward library (plain C++, g++; fp64 without contraction)."""
+    """Host-side CIDEr-D / BLEU reward and n-gram language-model library (plain C++, g++; fp64 without contraction)."""
     os.makedirs(LIB_DIR, exist_ok=True)
-    src = os.path.join(CSRC, 'cider.cpp')
+    srcs = [os.path.join(CSRC, 'cider.cpp'), os.path.join(CSRC, 'lm.cpp')]
     hdr = os.path.join(os.path.dirname(HERE), 'include', 'insenticap_cider.h')
     did = False
-    if force or _stale(CIDER_LIB_PATH, [src, hdr, CIDER_KEY_H]):
-        cmd = ['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-Wall', '-ffp-contract=off', src, '-o',
-               CIDER_LIB_PATH]
+    if force or _stale(CIDER_LIB_PATH, srcs + [hdr, CIDER_KEY_H, LM_SLOT_H]):
+        cmd = ['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-Wall', '-ffp-contract=off'] + srcs + \
+              ['-o', CIDER_LIB_PATH]
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)

@@ -24,8 +24,9 @@ from .helper_nets import SentenceSentimentClassifier, SentimentDetector
 from .optim import clip_gradient
 from .train import run_on_side_stream
 from .ops import OutOfDomain
-from .rewards import (CIDER_DEV_MAX_T, Bleu, RewardCriterion, get_bleu_scorer, get_ciderd_scorer, get_cls_reward,
-                      get_self_critical_reward, get_self_critical_reward_device, group_self_critical_scores)
+from .rewards import (CIDER_DEV_MAX_T, LM_DEV_MAX_T, Bleu, NgramLM, NgramLMSet, RewardCriterion, get_bleu_scorer,
+                      get_ciderd_scorer, get_cls_reward, get_lm_reward, get_lm_reward_device, get_self_critical_reward,
+                      get_self_critical_reward_device, group_self_critical_scores, lm_perplexity)
 
 
 def _helper_input(feats):
@@ -84,6 +85,15 @@ class Detector(nn.Module):
         # greedy roll-out and the XE graphs.
         self.device_cider = False
         self._cider_dev, self._cider_dev_warned = None, False
+        # The reference's dormant LM reward (decoder.py:114-118, utils.py:86-100), opt-in: with lm_flag != 0 an n = 1
+        # iteration adds lm_flag * get_lm_reward(...) to `rewards` - per row sign(score(greedy) - score(sample)) under the
+        # n-gram model of the row's sentiment label (lm_reward_form 'sign', the reference's active line) or ppl(greedy) -
+        # ppl(sample) ('ppl_diff', its commented alternative) - and logs 'lm_reward'.  Needs set_lms with the models; such
+        # iterations run the eager sequence; with device_cider on the scores are formed on the device
+        # (rewards.DeviceNgramLMSet, isc_lm_dev_score), otherwise by the host scorer.  0: nothing changes.
+        self.lm_flag = 0.0
+        self.lm_reward_form = 'sign'
+        self._lms_dev, self._lms_dev_warned = None, False
 
     def _device_ciderd(self, device, T):
         """The device twin of `ciderd_scorer` for rows of T tokens, or None: the flag is off, or this vocabulary / length
@@ -177,8 +187,60 @@ class Detector(nn.Module):
     def set_sentiment_words(self, sentiment_words):
         self.sentiment_words = sentiment_words
 
-    def set_lms(self, lms):
+    def set_lms(self, lms, eos_mode='word', unk_as_word=True):
+        """The per-sentiment n-gram language models: {sentiment label: rewards.NgramLM or the path of an ARPA file over
+        token ids (the reference's *_id.kenlm.arpa)} - labels 0 .. n - 1 - or a ready rewards.NgramLMSet.  Paths are read
+        with the captioner's vocabulary; `eos_mode` / `unk_as_word` default to what the id files and KenLM imply.  Anything
+        else is stored as it is (the reference's setter: decoder.py:52-53), and lm_flag != 0 then raises."""
+        cap = self.captioner
+        if isinstance(lms, dict) and lms and all(isinstance(v, (NgramLM, str)) or hasattr(v, '__fspath__')
+                                                 for v in lms.values()):
+            lms = NgramLMSet({k: v if isinstance(v, NgramLM) else NgramLM.from_arpa(str(v), cap.vocab_size)
+                              for k, v in lms.items()}, cap.vocab_size, eos_mode, unk_as_word)
+        if isinstance(lms, NgramLMSet):
+            if lms.sos is None:
+                lms.sos = cap.sos_id
+            if lms.eos is None:
+                lms.eos = cap.eos_id
         self.lms = lms
+        self._lms_dev = None
+
+    def _device_lms(self, device, T):
+        """The device twin of `lms` for rows of T tokens, or None: device_cider is off, or the rows are longer than the
+        device scorer takes (warned once; the host scorer serves)."""
+        if not self.device_cider or device.type != 'cuda':
+            return None
+        if T > LM_DEV_MAX_T:
+            if not self._lms_dev_warned:
+                import warnings
+                warnings.warn('device_cider: rows of %d tokens (the device LM scorer takes %d) - the host LM scorer is used'
+                              % (T, LM_DEV_MAX_T))
+                self._lms_dev_warned = True
+            return None
+        twin = self._lms_dev
+        if twin is None or twin[0] is not self.lms or twin[1] != device:
+            twin = self._lms_dev = (self.lms, device, self.lms.to_device(device))
+        return twin[2]
+
+    def caption_perplexity(self, token_rows, labels=None):
+        """The corpus perplexity of caption rows under the models of `set_lms`: token_rows int [N, T] (ndarray or tensor,
+        raw rows as the roll-outs and the result files hold them), labels [N] sentiment labels (None: model 0) ->
+        rewards.lm_perplexity's dictionary {label: {'ppl', 'ppl1', 'logprob', 'sentences', 'words', 'oovs'}}.  Device rows
+        are scored on the device where device_cider is on and they fit; the sums are taken on the host in float64."""
+        lms = self.__dict__.get('lms')
+        if not isinstance(lms, NgramLMSet):
+            raise ValueError('Detector.caption_perplexity needs set_lms with n-gram language models')
+        dev = None
+        if torch.is_tensor(token_rows) and token_rows.is_cuda:
+            dev = self._device_lms(token_rows.device, token_rows.shape[1])
+        if dev is not None:
+            lab = None if labels is None else torch.as_tensor(labels, dtype=torch.int64).to(token_rows.device)
+            score, n_scored, n_oov = (x.cpu().numpy() for x in dev.score(token_rows.to(torch.int64), lab))
+        else:
+            score, n_scored, n_oov = lms.score(token_rows, labels)
+        if torch.is_tensor(labels):
+            labels = labels.cpu().numpy()
+        return lm_perplexity(score, n_scored, n_oov, labels)
 
     def set_concept_detector(self, cd, senti_table=None, num_concepts=5, num_sentiments=10):
         """Gives the detector the pre-stage it lacked: a helper_nets.ConceptDetector (after `set_vocabulary`) and,
@@ -247,6 +309,12 @@ class Detector(nn.Module):
         # (shares are then exactly 1.0), so a one-GPU RCCL run crosses the code an 8-rank run does
         dist_on = self.dp_arena is not None and dp.distributed(self.dp_group)
         n_rl = self.rl_samples_per_image if training else 1      # (evaluation keeps the n = 1 path)
+        lm_on = self.lm_flag != 0
+        if lm_on and n_rl > 1:
+            raise ValueError('lm_flag != 0 with rl_samples_per_image=%d: the LM reward compares a sample with the greedy '
+                             'baseline, which a grouped iteration does not roll out' % n_rl)
+        if lm_on and not isinstance(self.__dict__.get('lms'), NgramLMSet):
+            raise ValueError('lm_flag != 0 needs set_lms with n-gram language models (rewards.NgramLMSet)')
         if n_rl > 1 and dist_on:
             raise ValueError('rl_samples_per_image=%d is not built for data-parallel training (a process group is '
                              'active): set it to 1' % n_rl)
@@ -294,7 +362,7 @@ class Detector(nn.Module):
                 """One iteration (models/decoder.py:69-167).  `exact`: on the exact-fp32 GEMM engine, eagerly - the retry of
                 an iteration whose roll-outs left the split-f16 operand domain (OutOfDomain is raised at the iteration's
                 own synchronisation point, before anything is updated)."""
-                if (training and self.train_graphs and not rl_kw and n_rl == 1 and device.type == 'cuda'
+                if (training and self.train_graphs and not rl_kw and n_rl == 1 and not lm_on and device.type == 'cuda'
                         and ops.TIMER.arm_step is None and ops.graphs_allowed_here() and not exact):
                     # the same iteration from HIP graphs (train_graph.RLTrainGraph): same calls in the same order
                     from .train_graph import RLTrainGraph
@@ -364,6 +432,9 @@ class Detector(nn.Module):
                 # roll-outs already queued.  ('senti' has no CIDEr-D term: with the flag on nothing reads host tokens.)
                 dev_cider = self._device_ciderd(device, sample_captions.shape[1]) if data_type == 'fact' else None
                 host_tokens = dev_cider is None and not (self.device_cider and data_type != 'fact')
+                # (the LM reward: on the device with device_cider where the rows fit, else from host tokens)
+                dev_lms = self._device_lms(device, sample_captions.shape[1]) if lm_on else None
+                host_tokens = host_tokens or (lm_on and dev_lms is None)
                 if dev_cider is not None:
                     ref_pack = dev_cider.pack_refs([ground_truth[fn] for fn in fns], keys=list(fns))
                 if host_tokens:
@@ -458,6 +529,16 @@ class Detector(nn.Module):
                 if not grouped:
                     put('cls_reward', share(cls_reward.mean(-1).mean(-1), w_rows))
                     rewards = fact_reward + self.cls_flag * cls_reward
+                    if lm_on:
+                        if dev_lms is not None:
+                            lm_reward = get_lm_reward_device(sample_captions, greedy_captions, senti_labels, dev_lms,
+                                                             self.lm_reward_form)
+                        else:
+                            lm_reward = get_lm_reward(host_sample.numpy(), host_greedy.numpy(), senti_labels, cap.sos_id,
+                                                      cap.eos_id, self.lms, self.lm_reward_form)
+                            lm_reward = ops.upload(lm_reward.astype('float32'), torch.float32, device)
+                        put('lm_reward', lm_reward[:, 0].sum())      # (a sum, as decoder.py:118 logs it)
+                        rewards = rewards + self.lm_flag * lm_reward
                     put('all_rewards', share(rewards.mean(-1).mean(-1), w_rows))
                 cap_loss = share(self.cap_rl_crit(sample_logprobs, seq_masks, rewards), w_rl)
                 put('cap_loss', cap_loss)

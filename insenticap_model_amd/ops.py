@@ -1616,6 +1616,41 @@ def bleu_dev_score(hyps, row_div, img_ent_off, ref_keys, ref_counts, img_cap_off
     return out
 
 
+def lm_dev_score(hyps, labels, slots, lm_off, lm_capacity, lm_order, vocab_size, eos_mode, unk_as_word, sos_id, eos_id,
+                 out=None, n_scored=None, n_oov=None, tok_logp=None):
+    """isc_lm_dev_score: the back-off language-model score of the raw rows `hyps` int64 [N, T] on the device, row r by
+    model labels[r] (labels None: model 0) -> (score float64 [N], n_scored int32 [N], n_oov int32 [N]).  slots int64
+    [S, 2] (the 16-byte slots), lm_off / lm_capacity int64 [n_lm], lm_order int32 [n_lm] - rewards.DeviceNgramLMSet builds
+    them.  `tok_logp`: float64 [N, T + 2] to fill, or None.  T > 62 raises (ISC_E_SHAPE); nothing is written then."""
+    require_device(hyps, labels, slots, lm_off, lm_capacity, lm_order, out, n_scored, n_oov, tok_logp)
+    assert hyps.dtype == torch.int64 and hyps.dim() == 2 and hyps.is_contiguous()
+    assert slots.dtype == torch.int64 and slots.dim() == 2 and slots.shape[1] == 2 and slots.is_contiguous()
+    n_lm = lm_off.numel()
+    assert lm_off.dtype == torch.int64 and lm_capacity.dtype == torch.int64 and lm_order.dtype == torch.int32
+    assert n_lm >= 1 and lm_capacity.numel() == n_lm and lm_order.numel() == n_lm
+    assert lm_off.is_contiguous() and lm_capacity.is_contiguous() and lm_order.is_contiguous()
+    N, T = hyps.shape
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == N
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=hyps.device)
+    if n_scored is None:
+        n_scored = torch.empty(N, dtype=torch.int32, device=hyps.device)
+    if n_oov is None:
+        n_oov = torch.empty(N, dtype=torch.int32, device=hyps.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == N
+    for x in (n_scored, n_oov):
+        assert x.dtype == torch.int32 and x.is_contiguous() and x.numel() == N
+    if tok_logp is not None:
+        assert tok_logp.dtype == torch.float64 and tok_logp.is_contiguous() and tok_logp.numel() == N * (T + 2)
+    check(_lib.load().isc_lm_dev_score(hyps.data_ptr(), N, T, ptr(labels), n_lm, slots.data_ptr(), lm_off.data_ptr(),
+                                       lm_capacity.data_ptr(), lm_order.data_ptr(), int(vocab_size), int(eos_mode),
+                                       int(bool(unk_as_word)), int(sos_id), int(eos_id), out.data_ptr(),
+                                       n_scored.data_ptr(), n_oov.data_ptr(), ptr(tok_logp), stream()),
+          'isc_lm_dev_score')
+    return out, n_scored, n_oov
+
+
 def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=None):
     lib = _lib.load()
     M, H = c.shape

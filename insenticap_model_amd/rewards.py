@@ -11,6 +11,9 @@
 * `Bleu` / `DeviceBleu` / `get_bleu_scorer` - the reference's other scorer (utils.py:75-77: the per-sentence BLEU-4 list
   of self_critical/bleu) in the same library and on the device (isc_bleu_dev_score); every reward function above takes
   either scorer, CIDEr-D stays the default.
+* `read_arpa` / `NgramLM` / `NgramLMSet` / `DeviceNgramLMSet`, `get_lm_reward` / `get_lm_reward_device`, `lm_perplexity` -
+  the per-sentiment back-off n-gram language models: the reference's dormant LM reward (utils.py:86-100) and its `ppl`
+  metric (eval_ppl.py), on the host (isc_lm_score) and on the device (isc_lm_dev_score); opt-in (Detector.lm_flag).
 """
 import ctypes as C
 import math
@@ -644,3 +647,323 @@ def get_cls_reward(sample_captions, sample_masks, greedy_captions, greedy_masks,
         return torch.nn.functional.pad(sample_scores, (0, max_len - sample_scores.shape[1]))
     sample_scores = sample_scores.cpu().numpy()
     return np.pad(sample_scores, ((0, 0), (0, max_len - sample_scores.shape[1])))
+
+
+# ------------------------------------------------------------------------------------------------ n-gram language models
+# The per-sentiment ARPA models of the reference (preprocess.py:426-466): its `ppl` metric (eval_ppl.py) and its LM reward
+# (self_critical/utils.py:86-100).  DESIGN.md "Per-sentiment n-gram language models" holds the definition; the slot, the
+# special ids and the probe are csrc/lm_slot.h; host scorer isc_lm_score (csrc/lm.cpp), device isc_lm_dev_score.
+LM_SLOT = np.dtype([('key', '<u8'), ('logp', '<f4'), ('backoff', '<f4')])      # isc_lm_slot: 16 bytes
+LM_MAX_VOCAB = CIDER_MAX_ID - 3          # <s>, </s>, <unk> = V, V + 1, V + 2 and "no word" = V + 3 must fit a key field
+LM_MAX_ORDER = 4
+LM_DEV_MAX_T = 62                        # isc_lm_dev_score: T + 2 scored positions in 64 lanes
+_LM_SPECIALS = ('<s>', '</s>', '<unk>')
+_LM_LIB_TYPED = False
+
+
+def _load_lm():
+    global _LM_LIB_TYPED
+    lib = _load_cider()
+    if not _LM_LIB_TYPED:
+        lib.isc_lm_table_capacity.restype = C.c_int64
+        lib.isc_lm_table_capacity.argtypes = [C.c_int64]
+        lib.isc_lm_table_fill.restype = C.c_int
+        lib.isc_lm_table_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        lib.isc_lm_score.restype = C.c_int
+        lib.isc_lm_score.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _LM_LIB_TYPED = True
+    return lib
+
+
+def _check_lm_vocab(vocab_size):
+    V = int(vocab_size)
+    if not 1 <= V <= LM_MAX_VOCAB:
+        raise ValueError('an n-gram language model packs an id into 16 bits and adds four ids of its own: 1 <= vocab_size '
+                         '<= %d, got %d' % (LM_MAX_VOCAB, V))
+    return V
+
+
+def read_arpa(path_or_text, vocab_size, word2idx=None):
+    """An ARPA file (a path, or its text: anything holding a newline) of order <= 4 -> {'order', 'ids': [int64 [n_k, k]
+    per order k], 'logp': [float32 [n_k]], 'backoff': [float32 [n_k]], 'dropped': n}.  Every decimal is read as a Python
+    float and rounded once to float32; a missing back-off weight is +0.0.  Words map through `word2idx` when given (the
+    word-level *_w.sri files), else as decimal ids (the *_id.kenlm.arpa files); <s>, </s>, <unk> take the ids V, V + 1,
+    V + 2.  An n-gram holding a word outside the vocabulary is dropped and counted.  ValueError: vocab_size > 65531, an
+    order above 4, a malformed line."""
+    V = _check_lm_vocab(vocab_size)
+    if '\n' in path_or_text:
+        text = path_or_text
+    else:
+        with open(path_or_text) as f:
+            text = f.read()
+    special = {w: V + j for j, w in enumerate(_LM_SPECIALS)}
+    ids, logp, backoff, dropped, k = {}, {}, {}, 0, 0
+    for no, line in enumerate(text.splitlines(), 1):
+        line = line.strip()
+        if not line or line == '\\data\\' or line.startswith('ngram '):
+            continue
+        if line == '\\end\\':
+            break
+        if line.startswith('\\'):
+            if not line.endswith('-grams:') or not line[1:-7].isdigit():
+                raise ValueError('ARPA line %d: %r' % (no, line))
+            k = int(line[1:-7])
+            if not 1 <= k <= LM_MAX_ORDER:
+                raise ValueError('ARPA: order %d (an n-gram key has %d fields)' % (k, LM_MAX_ORDER))
+            ids.setdefault(k, []), logp.setdefault(k, []), backoff.setdefault(k, [])
+            continue
+        parts = line.split()
+        if k < 1 or len(parts) not in (k + 1, k + 2):
+            raise ValueError('ARPA line %d: %r is no %d-gram entry' % (no, line, k))
+        row = []
+        for w in parts[1:k + 1]:
+            i = special.get(w)
+            if i is None:
+                i = word2idx.get(w) if word2idx is not None else (int(w) if w.isdigit() else None)
+                if i is not None and not 0 <= int(i) < V:
+                    i = None
+            if i is None:
+                break
+            row.append(int(i))
+        if len(row) < k:
+            dropped += 1
+            continue
+        ids[k].append(row)
+        logp[k].append(float(parts[0]))
+        backoff[k].append(float(parts[k + 1]) if len(parts) == k + 2 else 0.0)
+    if not ids:
+        raise ValueError('ARPA: no n-gram section')
+    order = max(ids)
+    with np.errstate(over='ignore'):
+        return {'order': order, 'dropped': dropped,
+                'ids': [np.asarray(ids.get(k, []), dtype=np.int64).reshape(-1, k) for k in range(1, order + 1)],
+                'logp': [np.asarray(logp.get(k, []), dtype=np.float64).astype(np.float32) for k in range(1, order + 1)],
+                'backoff': [np.asarray(backoff.get(k, []), dtype=np.float64).astype(np.float32)
+                            for k in range(1, order + 1)]}
+
+
+class NgramLM:
+    """One back-off model: `order`, `vocab_size`, its n-grams as csrc/cider_key.h keys (`keys` uint64 [n], the oldest
+    word in field 0) with `logp` / `backoff` float32 [n], `n_dropped` (n-grams of the file with a word outside the
+    vocabulary) and `has_unk`."""
+
+    def __init__(self, order, vocab_size, keys, logp, backoff, n_dropped=0):
+        self.order, self.vocab_size = int(order), _check_lm_vocab(vocab_size)
+        if not 1 <= self.order <= LM_MAX_ORDER:
+            raise ValueError('n-gram language model: 1 <= order <= %d, got %d' % (LM_MAX_ORDER, self.order))
+        self.keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        self.logp = np.ascontiguousarray(logp, dtype=np.float32)
+        self.backoff = np.ascontiguousarray(backoff, dtype=np.float32)
+        assert self.keys.ndim == 1 and self.keys.shape == self.logp.shape == self.backoff.shape
+        self.n_dropped = int(n_dropped)
+        self.has_unk = bool((self.keys == np.uint64(self.vocab_size + 3)).any())      # the unigram key of <unk>: id + 1
+
+    @classmethod
+    def from_arpa(cls, path_or_text, vocab_size, word2idx=None):
+        a = read_arpa(path_or_text, vocab_size, word2idx)
+        keys = []
+        for k, ids in enumerate(a['ids'], 1):
+            key = np.zeros(len(ids), dtype=np.uint64)
+            for j in range(k):
+                key |= (ids[:, j] + 1).astype(np.uint64) << np.uint64(16 * j)
+            keys.append(key)
+        return cls(a['order'], vocab_size, np.concatenate(keys), np.concatenate(a['logp']), np.concatenate(a['backoff']),
+                   a['dropped'])
+
+    def __len__(self):
+        return len(self.keys)
+
+    def table(self, capacity=None):
+        """The model as an open-addressing array of LM_SLOT records (isc_lm_table_fill).  `capacity`: a power of two above
+        the number of n-grams, default the production size (>= 2 x).  ValueError: a bad capacity, a duplicate n-gram."""
+        lib = _load_lm()
+        cap = int(capacity) if capacity is not None else lib.isc_lm_table_capacity(len(self))
+        tab = np.empty(max(cap, 0), dtype=LM_SLOT)
+        rc = lib.isc_lm_table_fill(self.keys.ctypes.data, self.logp.ctypes.data, self.backoff.ctypes.data, len(self),
+                                   tab.ctypes.data, cap)
+        if rc == -2:
+            raise ValueError('n-gram language model: capacity %d is no power of two above %d n-grams' % (cap, len(self)))
+        if rc in (-3, -5):
+            raise ValueError('n-gram language model: %s' % ('an empty n-gram' if rc == -3 else 'an n-gram occurs twice'))
+        if rc != 0:
+            raise RuntimeError('isc_lm_table_fill failed (%d)' % rc)
+        return tab
+
+
+def _eos_mode(mode):
+    if mode not in ('word', 'end'):
+        raise ValueError("eos_mode is 'word' (the <EOS> id is a word, then </s>: the id files) or 'end' (the <EOS> becomes "
+                         "</s>: the word files), got %r" % (mode,))
+    return 0 if mode == 'word' else 1
+
+
+class NgramLMSet:
+    """The models of all sentiment labels in ONE slot array: `lms_by_label` = {label: NgramLM} (labels 0 .. n - 1) or a
+    list.  `eos_mode` / `unk_as_word`: see isc_lm_score; `sos` / `eos`: the caption ids <SOS> / <EOS> that `score`
+    normalises rows with (they can also be given per call).  `capacities`: per label, a tighter table than the default."""
+
+    def __init__(self, lms_by_label, vocab_size, eos_mode='word', unk_as_word=True, sos=None, eos=None, capacities=None,
+                 n_threads=None):
+        self.vocab_size = _check_lm_vocab(vocab_size)
+        if isinstance(lms_by_label, dict):
+            if sorted(lms_by_label) != list(range(len(lms_by_label))):
+                raise ValueError('NgramLMSet: the labels must be 0 .. n - 1, got %r' % sorted(lms_by_label))
+            lms = [lms_by_label[l] for l in range(len(lms_by_label))]
+        else:
+            lms = list(lms_by_label)
+        if not lms or not all(isinstance(m, NgramLM) for m in lms):
+            raise ValueError('NgramLMSet takes at least one NgramLM per label')
+        if any(m.vocab_size != self.vocab_size for m in lms):
+            raise ValueError('NgramLMSet: every model must be loaded with vocab_size = %d' % self.vocab_size)
+        self.lms = lms
+        self.eos_mode, self._eos_mode = eos_mode, _eos_mode(eos_mode)
+        self.unk_as_word = bool(unk_as_word)
+        self.sos, self.eos = sos, eos
+        self.n_threads = n_threads or _default_threads()
+        caps = capacities if capacities is not None else [None] * len(lms)
+        caps = [caps[l] for l in range(len(lms))]
+        tabs = [m.table(c) for m, c in zip(lms, caps)]
+        self.slots = np.concatenate(tabs)
+        self.lm_capacity = np.asarray([len(t) for t in tabs], dtype=np.int64)
+        self.lm_off = np.concatenate([[0], np.cumsum(self.lm_capacity)[:-1]]).astype(np.int64)
+        self.lm_order = np.asarray([m.order for m in lms], dtype=np.int32)
+
+    def __len__(self):
+        return len(self.lms)
+
+    def _ids(self, sos, eos):
+        sos = self.sos if sos is None else sos
+        eos = self.eos if eos is None else eos
+        if sos is None or eos is None:
+            raise ValueError('NgramLMSet: the <SOS> / <EOS> ids are not set (constructor or call)')
+        return int(sos), int(eos)
+
+    def score(self, hyps, labels=None, sos=None, eos=None, tok_logp=False):
+        """hyps int64 [N, T] raw rows (ndarray or tensor), labels [N] or None (model 0) -> (score float64 [N] (log10),
+        n_scored int32 [N], n_oov int32 [N]) and, with tok_logp, the values per position float64 [N, T + 2].  The host
+        scorer (isc_lm_score), up to 16 threads."""
+        sos, eos = self._ids(sos, eos)
+        if torch.is_tensor(hyps):
+            hyps = hyps.cpu().numpy()
+        if torch.is_tensor(labels):
+            labels = labels.cpu().numpy()
+        hyps = np.ascontiguousarray(hyps, dtype=np.int64)
+        N, T = hyps.shape
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+            if labels.shape[0] != N:
+                raise ValueError('NgramLMSet.score: %d labels for %d rows' % (labels.shape[0], N))
+        score = np.empty(N, dtype=np.float64)
+        ns, no = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+        tok = np.empty((N, T + 2), dtype=np.float64) if tok_logp else None
+        if N:
+            rc = _load_lm().isc_lm_score(hyps.ctypes.data, N, T, labels.ctypes.data if labels is not None else None,
+                                         len(self.lms), self.slots.ctypes.data, len(self.slots), self.lm_off.ctypes.data,
+                                         self.lm_capacity.ctypes.data, self.lm_order.ctypes.data, self.vocab_size,
+                                         self._eos_mode, int(self.unk_as_word), sos, eos, score.ctypes.data,
+                                         ns.ctypes.data, no.ctypes.data, tok.ctypes.data if tok_logp else None,
+                                         self.n_threads)
+            if rc != 0:
+                raise RuntimeError('isc_lm_score failed (%d)' % rc)
+        return (score, ns, no, tok) if tok_logp else (score, ns, no)
+
+    def to_device(self, device):
+        """The device twin (DeviceNgramLMSet): the slot array is uploaded once."""
+        return DeviceNgramLMSet(self, device)
+
+
+class DeviceNgramLMSet:
+    """The models on the device (isc_lm_dev_score): the twin of a host `NgramLMSet`, whose slot array it holds.  One wave
+    per row; the scores equal the host scorer's in bits."""
+
+    def __init__(self, host, device):
+        self.host, self.device = host, torch.device(device)
+        self.slots = torch.from_numpy(host.slots.view(np.int64).reshape(-1, 2)).to(self.device)      # [slots, 2], once
+        self.lm_off = torch.from_numpy(host.lm_off).to(self.device)
+        self.lm_capacity = torch.from_numpy(host.lm_capacity).to(self.device)
+        self.lm_order = torch.from_numpy(host.lm_order).to(self.device)
+
+    def score(self, hyps, labels=None, out=None, tok_logp=None, n_scored=None, n_oov=None, sos=None, eos=None):
+        """hyps int64 [N, T] on the device (T <= 62), labels int64 [N] on the device or None -> (score float64 [N],
+        n_scored int32 [N], n_oov int32 [N]) on the device; `out` / `n_scored` / `n_oov`: tensors to fill; `tok_logp`: a
+        float64 [N, T + 2] tensor to fill with the values per position.  One launch, nothing read back."""
+        from . import ops
+        sos, eos = self.host._ids(sos, eos)
+        hyps = hyps if hyps.is_contiguous() else hyps.contiguous()
+        if labels is not None:
+            labels = labels if labels.is_contiguous() else labels.contiguous()
+        return ops.lm_dev_score(hyps, labels, self.slots, self.lm_off, self.lm_capacity, self.lm_order,
+                                self.host.vocab_size, self.host._eos_mode, self.host.unk_as_word, sos, eos, out=out,
+                                n_scored=n_scored, n_oov=n_oov, tok_logp=tok_logp)
+
+
+def _lm_form(form):
+    if form not in ('sign', 'ppl_diff'):
+        raise ValueError("the LM reward is 'sign' or 'ppl_diff', got %r" % (form,))
+    return form
+
+
+def get_lm_reward(sample_captions, greedy_captions, senti_labels, sos_token, eos_token, lms, form='sign'):
+    """utils.py:86-100 with `lms` an NgramLMSet -> float64 ndarray [B, T].  'sign': the reference's active line,
+    sign(score(greedy) - score(sample)); 'ppl_diff': its commented alternative, ppl(greedy) - ppl(sample) with the
+    per-sentence ppl = 10 ** (-score / n_scored).  The value is repeated over the T columns."""
+    _lm_form(form)
+    if not isinstance(lms, NgramLMSet):
+        raise Exception('do not support these language models: %s' % type(lms))
+    if torch.is_tensor(sample_captions):
+        sample_captions = sample_captions.cpu().numpy()
+    if torch.is_tensor(greedy_captions):
+        greedy_captions = greedy_captions.cpu().numpy()
+    if torch.is_tensor(senti_labels):
+        senti_labels = senti_labels.cpu().numpy()
+    assert sample_captions.shape[0] == greedy_captions.shape[0] == len(senti_labels)
+    s, s_n, _ = lms.score(sample_captions, senti_labels, sos_token, eos_token)
+    g, g_n, _ = lms.score(greedy_captions, senti_labels, sos_token, eos_token)
+    if form == 'sign':
+        scores = np.sign(g - s)
+    else:
+        with np.errstate(divide='ignore', invalid='ignore'):
+            scores = 10.0 ** (-g / g_n) - 10.0 ** (-s / s_n)
+    return np.repeat(scores[:, np.newaxis], sample_captions.shape[1], 1)
+
+
+def get_lm_reward_device(sample_captions, greedy_captions, senti_labels, dev_lms, form='sign'):
+    """get_lm_reward on the device: token matrices [B, T] and labels [B] on the device -> float32 [B, T] on the device, the
+    host form followed by `.astype('float32')`; no token is copied to the host."""
+    _lm_form(form)
+    if not isinstance(dev_lms, DeviceNgramLMSet):
+        raise Exception('do not support these language models: %s' % type(dev_lms))
+    assert sample_captions.shape == greedy_captions.shape
+    s, s_n, _ = dev_lms.score(sample_captions, senti_labels)
+    g, g_n, _ = dev_lms.score(greedy_captions, senti_labels)
+    if form == 'sign':
+        scores = torch.sign(g - s)
+    else:
+        scores = torch.pow(10.0, -g / g_n.to(torch.float64)) - torch.pow(10.0, -s / s_n.to(torch.float64))
+    return scores.to(torch.float32).unsqueeze(1).repeat(1, sample_captions.shape[1])
+
+
+def lm_perplexity(scores, n_scored, n_oov, labels, n_labels=None):
+    """The corpus figures per label from the read-back rows, summed on the host in float64 in row order:
+    {label: {'ppl': 10 ** (-sum score / sum n_scored), 'ppl1': the same without the sentence ends in the denominator
+    (sum n_scored - sentences), 'logprob', 'sentences', 'words' (= sum n_scored - sentences), 'oovs'}} - SRILM's `ppl` and
+    `ppl1`.  Rows of a label outside the set (n_scored -1) are left out.  A label without a scored position: ppl nan."""
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    n_scored, n_oov = np.asarray(n_scored).reshape(-1), np.asarray(n_oov).reshape(-1)
+    labels = np.zeros(len(scores), dtype=np.int64) if labels is None else np.asarray(labels).reshape(-1)
+    out = {}
+    for lab in (range(int(n_labels)) if n_labels is not None else sorted(set(int(x) for x in labels))):
+        total, count, sent, oov = 0.0, 0, 0, 0
+        for r in np.nonzero(labels == lab)[0]:
+            if n_scored[r] < 0:
+                continue
+            total += float(scores[r])
+            count += int(n_scored[r])
+            oov += int(n_oov[r])
+            sent += 1
+        out[lab] = {'ppl': 10.0 ** (-total / count) if count > 0 else float('nan'),
+                    'ppl1': 10.0 ** (-total / (count - sent)) if count - sent > 0 else float('nan'),
+                    'logprob': total, 'sentences': sent, 'words': count - sent, 'oovs': oov}
+    return out

@@ -532,3 +532,53 @@ def senti_det_evaluate(model, loader):
         total += int(labels.shape[0])
     corr = int(corr)
     return {'corr_num': corr, 'all_num': total, 'corr_rate': corr / total if total else 0.0}
+
+
+EVAL_PPL_SENTIS = ('positive', 'negative', 'neutral')      # eval_ppl.py:7
+
+
+def eval_ppl(captions_file_prefix, data_type, lms, word2idx=None, sentis=EVAL_PPL_SENTIS):
+    """eval_ppl.py's `compute_ppl` without SRILM: the perplexity of the result files train_rl.py:304-309 writes, per
+    sentiment, under that sentiment's n-gram model -> {sentiment: ppl}, 0 where the file is missing or nothing was scored
+    (as the reference's `except`).  `lms`: a rewards.NgramLMSet whose label l is the model of sentis[l].
+      word2idx None: the id files `<prefix>_<senti>_<data_type>.txt` (ids, the <EOS> id last), for a set loaded from the
+        *_id.kenlm.arpa files (eos_mode 'word');
+      word2idx given: the word files `..._w.txt` (words, no <EOS>), for a set loaded from the *_w.sri files through the
+        same word2idx (eos_mode 'end', unk_as_word False: SRILM's `ngram -ppl` without -unk skips unknown words).
+    ppl = 10 ** (-sum score / sum n_scored) (rewards.lm_perplexity), SRILM's `ppl=` figure; host scorer, float64 sums.  An
+    empty line is no sentence."""
+    import os
+
+    import numpy as np
+
+    from .rewards import NgramLMSet, lm_perplexity
+    if not isinstance(lms, NgramLMSet):
+        raise ValueError('eval_ppl takes a rewards.NgramLMSet')
+    if len(lms) < len(sentis):
+        raise ValueError('eval_ppl: %d sentiments, %d language models' % (len(sentis), len(lms)))
+    scores = {}
+    for label, senti in enumerate(sentis):
+        path = '%s_%s_%s%s.txt' % (captions_file_prefix, senti, data_type, '_w' if word2idx is not None else '')
+        scores[senti] = 0
+        if not os.path.exists(path):
+            continue
+        with open(path) as f:
+            lines = [ln.split() for ln in f.read().splitlines() if ln.strip()]
+        if not lines:
+            continue
+        if word2idx is not None:          # unknown words: an id no vocabulary holds; the row ends at an <EOS> no word is
+            eos, sos = -1, -3
+            rows = [[word2idx.get(w, -2) for w in ln] for ln in lines]
+        else:                             # the lines carry their <EOS> id themselves
+            eos = int(lines[0][-1]) if lms.eos is None else lms.eos
+            sos = -3 if lms.sos is None else lms.sos
+            rows = [[int(w) for w in ln] for ln in lines]
+        T = max(len(r) for r in rows)
+        hyps = np.full((len(rows), T), eos, dtype=np.int64)
+        for i, r in enumerate(rows):
+            hyps[i, :len(r)] = r
+        labels = np.full(len(rows), label, dtype=np.int64)
+        s, n_scored, n_oov = lms.score(hyps, labels, sos=sos, eos=eos)
+        ppl = lm_perplexity(s, n_scored, n_oov, labels)[label]['ppl']
+        scores[senti] = ppl if ppl == ppl else 0
+    return scores
