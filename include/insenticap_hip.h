@@ -1388,6 +1388,97 @@ int isc_clamp_adam_hyper(float *const *params_host, float *const *grads_host, fl
                          const float *hyper3_dev, double beta1, double beta2, double eps, double weight_decay,
                          double clip, void *stream);
 
+/* ---- The image encoder (csrc/encoder.hip): the reference's models/encoder.py in eval mode, from pixels to fc [B, C] and
+ * att [B, a, a, C] (C = 32 width), every batch norm folded into the convolution in front of it.  A bottleneck ResNet of
+ * layers[4] blocks at base width `width` (32 or 64: the stem keeps its weights in LDS); the reference is {3, 4, 23, 3}
+ * at 64.  Every activation is channels-last fp32 [B, h, w, C].  Status codes, never throws; every shape, alignment and
+ * workspace check in front of the first launch, nothing written on refusal; no allocation and no host read inside a call
+ * (a forward at a fixed image size is capturable); no atomics: two runs give the same bits.
+ *
+ * Convolution order (isc_encoder_pack's `convs`, isc_encoder_num_convs of them): the stem, then per block conv1, conv2,
+ * conv3 and - in the first block of a layer - the downsample.  Each entry: the weight [N, Cin, R, R] and the batch norm
+ * behind it (weight, bias, running_mean, running_var; eps = 1e-5), all fp32 on the device.  The pack computes
+ * w' = w g / sqrt(v + eps), b' = beta - mu g / sqrt(v + eps) in double, rounds once to fp32 and splits w' into the f16
+ * planes [N, 2 R R Cin], k = tap Cin + ci (the stem: fp32 [147, C0], k = (ky 7 + kx) 3 + c).  packed: 256-byte aligned.
+ *
+ * isc_encoder_fwd: image [B, H, W, 3], uint8 (image_u8 != 0: x / 255, then (x - mean) / std of the reference's
+ * preprocess, as the stem's taps load) or fp32 already normalised; H, W >= 3 (below, the ceil-mode pool has no output),
+ * B Ho Wo <= 2^22, B <= 65535, 1 <= att_size <= 64: else ISC_E_SHAPE.  ksplit: 0 = every convolution's route by the cost
+ * rule (per image: independent of B), n >= 1 = n workgroups per tile forced (capped at the chunk count); workspace at least
+ * isc_encoder_workspace_bytes_ksplit(..., ksplit) (== isc_encoder_workspace_bytes for ksplit 0), packed_bytes at least
+ * isc_encoder_pack_bytes: else ISC_E_WORKSPACE.  fc_f16 / att_f16: optional float16 copies (round to nearest even). */
+#define ISC_ENCODER_KIND_STEM 0
+#define ISC_ENCODER_KIND_POOL 1
+#define ISC_ENCODER_KIND_DIRECT 2   /* convolution, one workgroup per tile */
+#define ISC_ENCODER_KIND_SPLIT 3    /* convolution, contraction split over workgroups */
+#define ISC_ENCODER_KIND_REDUCE 4   /* slab reduce behind a split convolution */
+#define ISC_ENCODER_KIND_TAIL 5
+#define ISC_ENCODER_KIND_PACK 6     /* weight pack, one per convolution */
+#define ISC_ENCODER_KIND_R1 7       /* convolution launches (of either route) of the 1x1 form */
+#define ISC_ENCODER_KIND_R3 8       /* ... of the 3x3 form */
+#define ISC_ENCODER_KINDS 9
+long long isc_encoder_launches(int kind);
+
+typedef struct {
+    const float *w, *gamma, *beta, *mean, *var;
+} isc_encoder_conv_params;
+
+typedef struct {
+    const void *image;
+    int image_u8, B, H, W;
+    int layers[4];
+    int width, att_size, ksplit, _pad;
+    const void *packed;
+    int64_t packed_bytes;
+    void *workspace;
+    int64_t workspace_bytes;
+    float *fc, *att;
+    void *fc_f16, *att_f16;
+} isc_encoder_problem;
+
+int isc_encoder_num_convs(const int *layers4, int width);                  /* 0: refused */
+int64_t isc_encoder_pack_bytes(const int *layers4, int width);             /* 0: refused */
+int isc_encoder_pack(const isc_encoder_conv_params *convs_host, int n_convs, const int *layers4, int width, void *packed,
+                     void *stream);
+int64_t isc_encoder_workspace_bytes(int B, int H, int W, const int *layers4, int width);
+int64_t isc_encoder_workspace_bytes_ksplit(int B, int H, int W, const int *layers4, int width, int ksplit);
+int isc_encoder_final_grid(int H, int W, int *hf, int *wf);                 /* the layer-4 grid of an H x W image */
+int isc_encoder_fwd(const isc_encoder_problem *prob_host, void *stream);
+
+/* The parts on their own (tests).
+ * isc_conv_pack: planes of one convolution, R in {1, 3}; gamma null: no fold, `bias` not written.
+ * isc_conv_fwd: out [B ho wo, N] = (relu)(conv(x) + bias[n] (+ residual[m, n])); x [B, h, w, Cin]; R = 1: stride 1 or
+ *   2, ho = (h - 1) / stride + 1; R = 3: stride 1, pad 1.  Cin % 32 == 0, N % 16 == 0, B h w <= 2^22.
+ * isc_encoder_stem_pack / isc_encoder_stem: wk [147, C0], C0 in {32, 64}; out [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C0].
+ * isc_encoder_maxpool: 3x3 / 2, pad 0, ceil mode: out [B, (h - 2) / 2 + 1, (w - 2) / 2 + 1, C]; h, w >= 2, C % 4 == 0.
+ * isc_encoder_tail: fc [B, C] = mean over w, then over h; att [B, a, a, C] = adaptive average pool.
+ * Alignment: x, planes, bias, residual, workspace and out of isc_conv_fwd, `out` of the stem and both tensors of the
+ * max-pool 16 bytes (vector accesses); wk, bias and fp32 pixels of the stem, x / fc / att of the tail 4 bytes, the float16
+ * copies 2 bytes (scalar accesses): else ISC_E_ALIGN.  Order of the checks in every call: null pointers, shape,
+ * workspace size, alignment - a call wrong in two ways gets the first of these codes.
+ * The route of a convolution (ksplit 0) is chosen from ONE image's rows h_out w_out, never from B: an image gets the
+ * same bits in a batch as alone. */
+typedef struct {
+    const float *x;
+    int B, h, w, Cin, N, R, stride, relu, ksplit, _pad;
+    const void *planes;
+    const float *bias, *residual;
+    void *workspace;
+    int64_t workspace_bytes;
+    float *out;
+} isc_conv_problem;
+int isc_conv_pack(const float *w, const float *gamma, const float *beta, const float *mean, const float *var, int N,
+                  int Cin, int R, void *planes, float *bias, void *stream);
+int64_t isc_conv_workspace_bytes(int B, int h, int w, int Cin, int N, int R, int stride, int ksplit);
+int isc_conv_fwd(const isc_conv_problem *prob_host, void *stream);
+int isc_encoder_stem_pack(const float *w, const float *gamma, const float *beta, const float *mean, const float *var,
+                          int C0, float *wk, float *bias, void *stream);
+int isc_encoder_stem(const void *img, int img_u8, int B, int H, int W, int C0, const float *wk, const float *bias,
+                     float *out, void *stream);
+int isc_encoder_maxpool(const float *x, int B, int h, int w, int C, float *out, void *stream);
+int isc_encoder_tail(const float *x, int B, int h, int w, int C, int att_size, float *fc, float *att, void *fc_f16,
+                     void *att_f16, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .captioner import Captioner, XECriterion  # noqa: F401,E402
 from .detector import Detector  # noqa: F401,E402
 from .optim import FusedClampAdam, clip_gradient  # noqa: F401,E402
 from .helper_nets import ConceptDetector, MultiLabelClsLoss  # noqa: F401,E402
+from .encoder import Encoder  # noqa: F401,E402
 from .data import SentimentWordTable, tag_concepts  # noqa: F401,E402
 from .train import concept_train_step  # noqa: F401,E402
 from .rewards import RewardCriterion, get_ciderd_scorer, get_cls_reward, get_self_critical_reward  # noqa: F401,E402
@@ -25,4 +26,4 @@ __all__ = ['Captioner', 'XECriterion', 'Detector', 'FusedClampAdam', 'clip_gradi
            'get_ciderd_scorer', 'get_self_critical_reward', 'get_cls_reward', 'get_group_self_critical_reward',
            'group_self_critical_scores', 'Bleu', 'DeviceBleu', 'get_bleu_scorer', 'ConceptDetector', 'MultiLabelClsLoss',
            'SentimentWordTable', 'tag_concepts', 'concept_train_step', 'NgramLM', 'NgramLMSet', 'DeviceNgramLMSet',
-           'get_lm_reward', 'get_lm_reward_device', 'lm_perplexity']
+           'get_lm_reward', 'get_lm_reward_device', 'lm_perplexity', 'Encoder']

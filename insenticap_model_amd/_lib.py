@@ -220,6 +220,28 @@ class ConceptProblem(C.Structure):
                 _f('logits probs idx scores words', C.c_void_p))
 
 
+ENCODER_KINDS = ('stem', 'pool', 'direct', 'split', 'reduce', 'tail', 'pack', 'r1', 'r3')     # isc_encoder_launches(kind index)
+
+
+class EncoderConvParams(C.Structure):
+    """isc_encoder_conv_params: one convolution's weight and the batch norm behind it (csrc/encoder.hip)."""
+    _fields_ = _f('w gamma beta mean var', C.c_void_p)
+
+
+class EncoderProblem(C.Structure):
+    """isc_encoder_problem: the image encoder's forward, pixels -> fc, att (csrc/encoder.hip)."""
+    _fields_ = ([('image', C.c_void_p)] + _f('image_u8 B H W', C.c_int32) + [('layers', C.c_int32 * 4)] +
+                _f('width att_size ksplit _pad', C.c_int32) +
+                [('packed', C.c_void_p), ('packed_bytes', C.c_int64), ('workspace', C.c_void_p),
+                 ('workspace_bytes', C.c_int64)] + _f('fc att fc_f16 att_f16', C.c_void_p))
+
+
+class ConvProblem(C.Structure):
+    """isc_conv_problem: one 1x1 / 3x3 convolution of the encoder on its own (csrc/encoder.hip)."""
+    _fields_ = ([('x', C.c_void_p)] + _f('B h w Cin N R stride relu ksplit _pad', C.c_int32) +
+                _f('planes bias residual workspace', C.c_void_p) + [('workspace_bytes', C.c_int64), ('out', C.c_void_p)])
+
+
 # name -> (restype, argtypes); every symbol include/insenticap_hip.h declares
 SIGNATURES = {
     'isc_abi_version': (C.c_int, []),
@@ -392,6 +414,24 @@ SIGNATURES = {
     'isc_concept_fwd': (C.c_int, [C.POINTER(ConceptProblem), C.c_void_p]),
     'isc_concept_launches': (C.c_longlong, []),
     'isc_grad_scale': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
+    'isc_encoder_launches': (C.c_longlong, [C.c_int]),
+    'isc_encoder_num_convs': (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    'isc_encoder_pack_bytes': (C.c_int64, [C.POINTER(C.c_int), C.c_int]),
+    'isc_encoder_pack': (C.c_int, [C.POINTER(EncoderConvParams), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    'isc_encoder_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    'isc_encoder_workspace_bytes_ksplit': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    'isc_encoder_final_grid': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'isc_encoder_fwd': (C.c_int, [C.POINTER(EncoderProblem), C.c_void_p]),
+    'isc_conv_pack': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_conv_workspace_bytes': (C.c_int64, [C.c_int] * 8),
+    'isc_conv_fwd': (C.c_int, [C.POINTER(ConvProblem), C.c_void_p]),
+    'isc_encoder_stem_pack': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_encoder_stem': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    'isc_encoder_maxpool': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'isc_encoder_tail': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     'isc_splitk_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
     'isc_h3_weights_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),
     'isc_status': (C.c_int, [C.c_int]),

@@ -797,3 +797,63 @@ def tag_concepts(model, fc_store, num, batch=100, fns=None):
         _, concepts, _ = model.sample(feats, num)
         out.update(zip(cur, concepts))
     return out
+
+
+def _image_items(images):
+    """(name, uint8 array) pairs as they are; paths are decoded with PIL (RGBA and palette images become RGB, grey stays
+    two-dimensional)."""
+    for item in images:
+        if isinstance(item, (str, os.PathLike)):
+            from PIL import Image
+            with Image.open(item) as im:
+                if im.mode not in ('L', 'RGB'):
+                    im = im.convert('RGB')
+                yield os.path.basename(os.fspath(item)), np.asarray(im)
+        else:
+            name, array = item
+            yield name, np.asarray(array)
+
+
+def extract_features(encoder, images, out_dir, dtype=np.float32, att_size=14):
+    """preprocess.py:23-46 (`extract_imgs_feat`) for this package: every image through `encoder` (encoder.Encoder, on
+    whatever device it lives) into the two stores the datasets read - `<out_dir>/feats_fc.npy` [N, C] and
+    `<out_dir>/feats_att.npy` [N, a, a, C] with their `.index.json` (FeatureStore), float32 or float16.  `images`: a
+    sized collection (its len() gives N) of (name, uint8 array [H, W] / [H, W, 3] / [H, W, 4]) or of image paths; it may
+    produce its items lazily.  Each image's features go straight into the memory-mapped files, as the reference writes
+    per image: the host never holds more than one image's features.  Returns the two paths."""
+    import json
+    dtype = _feature_dtype(dtype)
+    try:
+        n = len(images)
+    except TypeError:
+        raise TypeError('extract_features: `images` must have a len() (the stores are allocated up front); pass a list '
+                        'of paths or a sized dataset, not a generator')
+    os.makedirs(out_dir, exist_ok=True)
+    paths = (os.path.join(out_dir, 'feats_fc.npy'), os.path.join(out_dir, 'feats_att.npy'))
+    names, maps = [], None
+    encoder.eval()
+    with torch.no_grad():
+        for name, array in _image_items(images):
+            if array.ndim == 3 and array.shape[-1] == 4:
+                array = array[:, :, :3]
+            if array.dtype != np.uint8:
+                raise ValueError('extract_features: image %r is %s, not uint8' % (name, array.dtype))
+            out = encoder.encode_uint8(array, att_size, want_f16=dtype == np.float16)
+            feats = [t.cpu().numpy() for t in (out[2:] if dtype == np.float16 else out[:2])]
+            if maps is None:                    # the first image gives the shapes
+                maps = [np.lib.format.open_memmap(p, mode='w+', dtype=dtype, shape=(n,) + f.shape)
+                        for p, f in zip(paths, feats)]
+            if len(names) >= n:
+                raise ValueError('extract_features: `images` produced more than its len() = %d items' % n)
+            for m, f in zip(maps, feats):
+                m[len(names)] = f
+            names.append(name)
+    if len(names) != n or len(set(names)) != n:
+        raise ValueError('extract_features: %d items with %d distinct names from a collection of len() %d'
+                         % (len(names), len(set(names)), n))
+    for m, p in zip(maps or (), paths):
+        m.flush()
+        with open(p + '.index.json', 'w') as f:
+            json.dump({fn: i for i, fn in enumerate(names)}, f)
+    del maps
+    return paths

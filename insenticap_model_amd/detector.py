@@ -622,3 +622,23 @@ class Detector(nn.Module):
         captions, _ = self.captioner.sample(fc_feats, att_feats, sentis_tensor, senti_label, beam_size,
                                             decoding_constraint, self.max_seq_len)
         return captions, self.senti_detector.names(senti_label)
+
+    def set_encoder(self, enc):
+        """The image encoder (encoder.Encoder) behind sample_image; kept outside the module tree, as the concept detector
+        is: the encoder is frozen and has its own checkpoint."""
+        self.__dict__['encoder'] = enc
+        return self
+
+    def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14):
+        """One image from its pixels: uint8 [H, W, 3] / [H, W] as decoded (the normalisation is fused into the encoder's
+        first kernel) or a `preprocess`ed fp32 tensor [3, H, W] -> encoder -> sample(fc, att).  The sentiment words come
+        from the concept detector (set_concept_detector with a table); no host read between the encoder and the search."""
+        enc = self.__dict__.get('encoder')
+        if enc is None:
+            raise ValueError('Detector.sample_image needs set_encoder')
+        with torch.no_grad():
+            if torch.is_tensor(image) and image.is_floating_point():
+                fc, att = enc(image.to(enc.resnet.conv1.weight.device), att_size)
+            else:
+                fc, att = enc.encode_uint8(image, att_size)
+        return self.sample(fc, att, None, beam_size, decoding_constraint)

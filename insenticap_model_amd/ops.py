@@ -2130,3 +2130,190 @@ def concept_fwd(params, feats, num, concept_word=None, want_probs=True, want_log
                                                    ptr(out.get('scores')), ptr(out.get('words')))
     check(lib.isc_concept_fwd(C.byref(p), stream()), 'isc_concept_fwd')
     return out
+
+
+# ---- the image encoder (csrc/encoder.hip): isc_encoder_* and its parts on their own
+_ENCODER_WS = {}            # (device index, stream) -> workspace of isc_encoder_fwd, grown when a call needs more
+
+
+def _grown_workspace(cache, key, need, device):
+    """ONE uint8 workspace per key, replaced by a larger one when a call needs more (the old one is dropped): the cache
+    holds the largest need seen, whatever the number of distinct geometries - image sizes are unbounded."""
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        cache.pop(key, None)                # (freed before the larger one is drawn)
+        ws = None
+        ws = cache[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def encoder_launches(kind=None):
+    """Launches of the encoder's kernels so far: a dict over _lib.ENCODER_KINDS ('stem', 'pool', 'direct', 'split',
+    'reduce', 'tail', 'pack'; 'r1' / 'r3' = convolution launches of the 1x1 / 3x3 form, either route), or one kind's."""
+    lib = _lib.load()
+    if kind is not None:
+        return lib.isc_encoder_launches(_lib.ENCODER_KINDS.index(kind))
+    return {name: lib.isc_encoder_launches(i) for i, name in enumerate(_lib.ENCODER_KINDS)}
+
+
+def _f32c(*tensors):
+    for t in tensors:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), 'contiguous fp32'
+
+
+def _layers4(layers):
+    layers = tuple(int(n) for n in layers)
+    assert len(layers) == 4, 'four layer block counts'
+    return layers, (C.c_int * 4)(*layers)
+
+
+def encoder_pack(convs, layers, width):
+    """convs: [(weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)] in the library's order (the stem, then per
+    block conv1, conv2, conv3 and the first block's downsample) -> the packed uint8 buffer isc_encoder_fwd reads (batch
+    norms folded in double, weights split into f16 planes).  Pack once per weight version."""
+    lib = _lib.load()
+    layers, l4 = _layers4(layers)
+    convs = [tuple(c) for c in convs]
+    for c in convs:
+        require_device(*c)
+        _f32c(*c)
+    nbytes = int(lib.isc_encoder_pack_bytes(l4, int(width)))
+    if not nbytes or len(convs) != lib.isc_encoder_num_convs(l4, int(width)):
+        raise _lib.HipLibraryError('isc_encoder_pack failed: ISC_E_SHAPE (layers %s, width %s, %d convolutions)'
+                                   % (layers, width, len(convs)))
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=convs[0][0].device)
+    arr = (_lib.EncoderConvParams * len(convs))()
+    for a, c in zip(arr, convs):
+        a.w, a.gamma, a.beta, a.mean, a.var = [t.data_ptr() for t in c]
+    check(lib.isc_encoder_pack(arr, len(convs), l4, int(width), packed.data_ptr(), stream()), 'isc_encoder_pack')
+    return packed
+
+
+def encoder_final_grid(H, W):
+    """(h, w) of the layer-4 grid of an H x W image; raises for an image the encoder refuses."""
+    h, w = C.c_int(), C.c_int()
+    check(_lib.load().isc_encoder_final_grid(int(H), int(W), C.byref(h), C.byref(w)), 'isc_encoder_final_grid')
+    return h.value, w.value
+
+
+def encoder_fwd(packed, image, layers, width, att_size=14, *, ksplit=0, want_f16=False, workspace=None):
+    """isc_encoder_fwd: image [B, H, W, 3] contiguous, uint8 (normalised as the stem loads it) or fp32 (already
+    normalised) -> (fc [B, C], att [B, a, a, C]) fp32 [, fc, att float16].  One workspace is kept per (device, stream)
+    and grown when a call needs more, except inside a graph capture (hand `workspace`, or a fresh one is drawn from the capture's pool).  A shape
+    the library does not take raises (ISC_E_SHAPE); nothing is launched or written then."""
+    lib = _lib.load()
+    require_device(packed, image)
+    assert image.dim() == 4 and image.shape[3] == 3 and image.is_contiguous() and \
+        image.dtype in (torch.uint8, torch.float32), 'image: contiguous [B, H, W, 3] uint8 or fp32'
+    layers, l4 = _layers4(layers)
+    B, H, W = (int(n) for n in image.shape[:3])
+    dev, a, width = image.device, int(att_size), int(width)
+    need = int(lib.isc_encoder_workspace_bytes_ksplit(B, H, W, l4, width, int(ksplit)))       # (0: refused - said below)
+    Cf = 32 * width
+    if workspace is None:
+        if torch.cuda.is_current_stream_capturing():
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        else:
+            workspace = _grown_workspace(_ENCODER_WS, (dev.index, torch.cuda.current_stream(dev).cuda_stream), need, dev)
+    a_ok = max(min(a, 64), 1)
+    fc = torch.empty(B, Cf, dtype=torch.float32, device=dev)
+    att = torch.empty(B, a_ok, a_ok, Cf, dtype=torch.float32, device=dev)
+    fc16 = torch.empty(B, Cf, dtype=torch.float16, device=dev) if want_f16 else None
+    att16 = torch.empty(B, a_ok, a_ok, Cf, dtype=torch.float16, device=dev) if want_f16 else None
+    p = _lib.EncoderProblem()
+    p.image, p.image_u8, p.B, p.H, p.W = image.data_ptr(), int(image.dtype == torch.uint8), B, H, W
+    for i, n in enumerate(layers):
+        p.layers[i] = n
+    p.width, p.att_size, p.ksplit = width, a, int(ksplit)
+    p.packed, p.packed_bytes = packed.data_ptr(), packed.numel()
+    p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() if need else 0     # (refused: never read)
+    p.fc, p.att, p.fc_f16, p.att_f16 = fc.data_ptr(), att.data_ptr(), ptr(fc16), ptr(att16)
+    check(lib.isc_encoder_fwd(C.byref(p), stream()), 'isc_encoder_fwd')
+    return (fc, att) + ((fc16, att16) if want_f16 else ())
+
+
+def conv_pack(w, bn=None):
+    """isc_conv_pack: w [N, Cin, R, R] (R 1 or 3) -> (planes uint8, bias [N] or None); bn = (weight, bias, running_mean,
+    running_var) folds the batch norm, None packs w as it is."""
+    require_device(w)
+    _f32c(w, *(bn or ()))
+    N, Cin, R = w.shape[0], w.shape[1], w.shape[2]
+    planes = torch.empty(max(4 * N * R * R * Cin, 16), dtype=torch.uint8, device=w.device)
+    bias = torch.empty(N, dtype=torch.float32, device=w.device) if bn is not None else None
+    g = [t.data_ptr() for t in bn] if bn is not None else [None] * 4
+    check(_lib.load().isc_conv_pack(w.data_ptr(), *g, N, Cin, R, planes.data_ptr(), ptr(bias), stream()), 'isc_conv_pack')
+    return planes, bias
+
+
+def conv_fwd(x, planes, bias, N, R, stride=1, residual=None, relu=False, ksplit=0, out=None, workspace=None):
+    """isc_conv_fwd: x [B, h, w, Cin] fp32 channels-last -> out [B, ho, wo, N] = (relu)(conv + bias (+ residual))."""
+    lib = _lib.load()
+    require_device(x, planes, bias, residual)
+    _f32c(x, bias, residual)
+    B, h, w, Cin = (int(n) for n in x.shape)
+    ho, wo = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if stride == 2 else (h, w)
+    if out is None:
+        out = torch.empty(B, ho, wo, N, dtype=torch.float32, device=x.device)
+    need = int(lib.isc_conv_workspace_bytes(B, h, w, Cin, int(N), int(R), int(stride), int(ksplit)))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    p = _lib.ConvProblem()
+    p.x, p.B, p.h, p.w, p.Cin, p.N, p.R, p.stride = x.data_ptr(), B, h, w, Cin, int(N), int(R), int(stride)
+    p.relu, p.ksplit = int(bool(relu)), int(ksplit)
+    p.planes, p.bias, p.residual = planes.data_ptr(), bias.data_ptr(), ptr(residual)
+    p.workspace, p.workspace_bytes, p.out = workspace.data_ptr(), workspace.numel(), out.data_ptr()
+    check(lib.isc_conv_fwd(C.byref(p), stream()), 'isc_conv_fwd')
+    return out
+
+
+def encoder_stem_pack(w, bn=None):
+    """isc_encoder_stem_pack: w [C0, 3, 7, 7] -> (wk [147, C0], bias [C0] or None)."""
+    require_device(w)
+    _f32c(w, *(bn or ()))
+    C0 = w.shape[0]
+    wk = torch.empty(147, C0, dtype=torch.float32, device=w.device)
+    bias = torch.empty(C0, dtype=torch.float32, device=w.device) if bn is not None else None
+    g = [t.data_ptr() for t in bn] if bn is not None else [None] * 4
+    check(_lib.load().isc_encoder_stem_pack(w.data_ptr(), *g, C0, wk.data_ptr(), ptr(bias), stream()),
+          'isc_encoder_stem_pack')
+    return wk, bias
+
+
+def encoder_stem(image, wk, bias, out=None):
+    """isc_encoder_stem: image [B, H, W, 3] uint8 or fp32 -> relu(conv7x7/2 + bias) [B, Ho, Wo, C0]."""
+    require_device(image, wk, bias)
+    _f32c(wk, bias)
+    assert image.is_contiguous() and image.dtype in (torch.uint8, torch.float32)
+    B, H, W = (int(n) for n in image.shape[:3])
+    C0 = wk.shape[1]
+    if out is None:
+        out = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C0, dtype=torch.float32, device=image.device)
+    check(_lib.load().isc_encoder_stem(image.data_ptr(), int(image.dtype == torch.uint8), B, H, W, C0, wk.data_ptr(),
+                                       bias.data_ptr(), out.data_ptr(), stream()), 'isc_encoder_stem')
+    return out
+
+
+def encoder_maxpool(x, out=None):
+    """isc_encoder_maxpool: x [B, h, w, C] -> [B, ho, wo, C], 3x3 / 2, pad 0, ceil mode."""
+    require_device(x)
+    _f32c(x)
+    B, h, w, Cc = (int(n) for n in x.shape)
+    if out is None:
+        out = torch.empty(B, max((h - 2) // 2 + 1, 1), max((w - 2) // 2 + 1, 1), Cc, dtype=torch.float32, device=x.device)
+    check(_lib.load().isc_encoder_maxpool(x.data_ptr(), B, h, w, Cc, out.data_ptr(), stream()), 'isc_encoder_maxpool')
+    return out
+
+
+def encoder_tail(x, att_size, want_f16=False):
+    """isc_encoder_tail: x [B, h, w, C] -> (fc [B, C], att [B, a, a, C]) [, float16 copies]."""
+    require_device(x)
+    _f32c(x)
+    B, h, w, Cc = (int(n) for n in x.shape)
+    a = int(att_size)
+    fc = torch.empty(B, Cc, dtype=torch.float32, device=x.device)
+    att = torch.empty(B, a, a, Cc, dtype=torch.float32, device=x.device)
+    fc16 = torch.empty(B, Cc, dtype=torch.float16, device=x.device) if want_f16 else None
+    att16 = torch.empty(B, a, a, Cc, dtype=torch.float16, device=x.device) if want_f16 else None
+    check(_lib.load().isc_encoder_tail(x.data_ptr(), B, h, w, Cc, a, fc.data_ptr(), att.data_ptr(), ptr(fc16), ptr(att16),
+                                       stream()), 'isc_encoder_tail')
+    return (fc, att) + ((fc16, att16) if want_f16 else ())
