@@ -402,6 +402,24 @@ typedef struct {
 int isc_rollout_finalize_constrained(const isc_rollout_step *s_host, const isc_sample_filter *f_host /* may be NULL */,
                                      const isc_decode_constraints *c_host, void *stream);
 
+/* isc_rollout_finalize_filtered (c NULL) or isc_rollout_finalize_constrained with f given - the same kernels, the same
+ * choice, the same outputs bit for bit - that additionally keeps, per (b, t) of a step that runs, what the backward of
+ * sampling_logprobs reads (isc_logsoftmax_bwd_raw_filtered): kstar = the boundary rank key K* (the kept set is
+ * { key <= K* } minus the banned ids), gmax = the largest allowed logit, logz = log(kept mass) (the term of
+ * sampling_logprobs), ban (optional, [B,T,10]) = the row's banned ids at a constrained step, -1 for unused slots.  A step
+ * behind the early break (alive[t] == 0) and an unconstrained step's ban entries are not written: the caller zero-fills
+ * kstar / gmax / logz (and sampling_logprobs) and fills ban with -1 up front.  s, f, sv or one of kstar / gmax / logz
+ * NULL -> ISC_E_NULL; everything else as the entry it forwards to. */
+typedef struct {
+    int64_t *kstar;              /* [B,T] */
+    float *gmax;                 /* [B,T] */
+    float *logz;                 /* [B,T] */
+    int32_t *ban;                /* optional [B,T,10] */
+} isc_filter_saved;
+int isc_rollout_finalize_saved(const isc_rollout_step *s_host, const isc_sample_filter *f_host,
+                               const isc_decode_constraints *c_host /* may be NULL */, const isc_filter_saved *sv_host,
+                               void *stream);
+
 /* Scheduled sampling of the teacher-forced unrolls (captioner.py:219-228): out_ids[b] = u_select[b] < ss_prob
  * ? a draw from exp(logp[b,:]) (inverse CDF with uniform u_draw[b], vocabulary order) : base_ids[b*stride].
  * logp = the previous step's normalised output, part_* = that step's tile statistics from isc_vocab_fwd. */
@@ -978,6 +996,25 @@ int isc_logsoftmax_bwd_raw(const float *raw, int64_t ld_b, int64_t ld_t, int B, 
                            const float *part_sum, int step_rows, const int64_t *const *ids_host,
                            const float *const *coef_host, int n_sparse, const float *scale, float *dlogits, int64_t ld_out,
                            int out_step_rows, void *stream);
+
+/* isc_logsoftmax_bwd_raw plus the gradient of the SAMPLED distribution's log-probability (filtered sampling:
+ * isc_rollout_finalize_saved), in one launch and one pass over the raw logits.  Per row (b,t), with c = flt_coef[b,t],
+ * K = { v : rank key(x_v, v) <= kstar[b,t] } minus the row's ban[b,t,0..10) ids (-1: unused slot; ban NULL: none) and
+ * q_v = exp((x_v - gmax[b,t]) * inv_tau - logz[b,t]) (clamped to 1):
+ *     d logits[t*out_step_rows + b, v] = (the n_sparse model pairs' term of isc_logsoftmax_bwd_raw)
+ *                                        + scale * c * inv_tau * ([v == flt_tok[b,t]] - [v in K] * q_v).
+ * The two terms are rounded separately and then added: in bits, isc_logsoftmax_bwd_raw's result plus the result of this
+ * call with n_sparse = 0.  n_sparse may be 0 (part_max / part_sum may then be NULL).  A row whose coefficients are all
+ * zero is written as zeros without reading its logits; columns outside K other than flt_tok get exactly 0; pad columns
+ * [V, ld_out) are zero.  flt_tok / kstar int64 [B,T], flt_coef / gmax / logz fp32 [B,T], ban int32 [B,T,10].
+ * A missing pointer -> ISC_E_NULL, sizes (and inv_tau not finite and > 0, n_sparse outside [0, ISC_SPARSE_MAX]) ->
+ * ISC_E_SHAPE, before any launch.  No atomics: bit-repeatable; no host read: capturable. */
+int isc_logsoftmax_bwd_raw_filtered(const float *raw, int64_t ld_b, int64_t ld_t, int B, int T, int V,
+                                    const float *part_max, const float *part_sum, int step_rows,
+                                    const int64_t *const *ids_host, const float *const *coef_host, int n_sparse,
+                                    const int64_t *flt_tok, const float *flt_coef, float inv_tau, const int64_t *kstar,
+                                    const float *gmax, const float *logz, const int32_t *ban, const float *scale,
+                                    float *dlogits, int64_t ld_out, int out_step_rows, void *stream);
 
 /* The frozen sentence-sentiment classifier of the RL rewards, forward in eval mode (sent_senti_cls.py:38-56; called by
  * self_critical/utils.py:120-151 for the classifier reward and by decoder.py:133-136 for the XE sentiment labels):

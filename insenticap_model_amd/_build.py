@@ -14,8 +14,9 @@ SOURCES = ['gemm_f32.hip', 'attention.hip', 'pointwise.hip', 'backward.hip', 'st
            'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'lm_dev.hip', 'concept.hip', 'encoder.hip']
 CIDER_KEY_H = os.path.join(CSRC, 'cider_key.h')      # the n-gram key: read by cider_dev.hip, bleu_dev.hip AND cider.cpp
 LM_SLOT_H = os.path.join(CSRC, 'lm_slot.h')          # the language-model slot: read by lm_dev.hip AND lm.cpp
+FLT_KEY_H = os.path.join(CSRC, 'flt_key.h')          # the filtered sampling's rank key: pointwise.hip AND backward.hip
 HEADERS = [os.path.join(CSRC, 'common.h'),
-           os.path.join(os.path.dirname(HERE), 'include', 'insenticap_hip.h'), CIDER_KEY_H, LM_SLOT_H]
+           os.path.join(os.path.dirname(HERE), 'include', 'insenticap_hip.h'), CIDER_KEY_H, LM_SLOT_H, FLT_KEY_H]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
 

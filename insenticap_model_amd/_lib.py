@@ -148,6 +148,11 @@ class SampleFilter(C.Structure):
                 ('sampling_logprobs', C.c_void_p)]
 
 
+class FilterSaved(C.Structure):
+    """isc_filter_saved: what isc_rollout_finalize_saved keeps for the backward of the sampling log-probabilities."""
+    _fields_ = [('kstar', C.c_void_p), ('gmax', C.c_void_p), ('logz', C.c_void_p), ('ban', C.c_void_p)]
+
+
 class DecodeConstraints(C.Structure):
     """isc_decode_constraints: the banned ids of isc_rollout_finalize_constrained."""
     _fields_ = [('ban_ids', C.c_int64 * 8), ('n_ban', C.c_int32), ('no_repeat', C.c_int32), ('first_id', C.c_int64),
@@ -374,6 +379,13 @@ SIGNATURES = {
     'isc_logsoftmax_bwd_raw': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'isc_logsoftmax_bwd_raw_filtered': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                                  C.c_void_p]),
+    'isc_rollout_finalize_saved': (C.c_int, [C.POINTER(RolloutStep), C.POINTER(SampleFilter),
+                                             C.POINTER(DecodeConstraints), C.POINTER(FilterSaved), C.c_void_p]),
     'isc_sent_cls_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'isc_sent_cls_fwd': (C.c_int, [C.POINTER(SentClsProblem), C.c_void_p]),
     'isc_sent_cls_launches': (C.c_longlong, []),

@@ -253,6 +253,12 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     L = S.L = _Rows([(0, B, T)], counts)
     extra = [((B, T), torch.int64), ((B, T), torch.float32), ((B, T), torch.float32), ((B, T), torch.int64),
              ((T + 1,), torch.int32)] if sampling else []
+    flt = tokens_in.get('flt') if sampling else None
+    if flt is not None:
+        # filtered draws (temperature / top_k / top_p, or constraints with the sampling log-probs wanted): the sampling
+        # log-probs and what their backward reads - K*, the largest allowed logit, log Z - per (b, t); zero behind the
+        # early break (the finalize returns before writing)
+        extra += [((B, T), torch.float32), ((B, T), torch.int64), ((B, T), torch.float32), ((B, T), torch.float32)]
     extra = _forward_buffers(cap, S, L, [P], _has_keep(cap, [masks]), False, extra)
     step_cls = sampling or sched                  # a draw reads each step's raw logits: the classifier runs per step
     out = None if (lazy is not None and not step_cls) else cap._new(B, T, V)   # (lazy, tokens known: raw logits only)
@@ -261,7 +267,13 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
     after = None
     if sampling:
         from ._lib import RolloutStep
-        seq, seq_lp, seq_masks, raw, alive = extra
+        seq, seq_lp, seq_masks, raw, alive = extra[:5]
+        slp = saved = None
+        if flt is not None:
+            slp = extra[5]
+            saved = dict(zip(('kstar', 'gmax', 'logz'), extra[6:9]))
+            if tokens_in.get('cons') is not None:       # the row's banned ids, -1: unused (an unconstrained step writes none)
+                saved['ban'] = torch.full((B, T, 10), -1, dtype=torch.int32, device=cap._dev)
         unfinished = torch.ones(B, dtype=torch.int32, device=cap._dev)
         alive[0:1].fill_(B)                     # a fill kernel (a scalar assignment would be a pageable H2D copy)
         forced, sample_u = tokens_in.get('forced'), tokens_in.get('u')
@@ -279,7 +291,8 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
             rs.t, rs.logits = t, out[:, t].data_ptr()
             rs.part_max, rs.part_sum, rs.part_idx = S.pm[t].data_ptr(), S.ps[t].data_ptr(), S.pi[t].data_ptr()
             rs.xt_next = S.xt[t + 1].data_ptr() if t + 1 < T else None
-            ops.rollout_finalize_step(rs, tokens_in.get('cons'))     # (constraints: the draw runs over the allowed ids)
+            # (constraints: the draw runs over the allowed ids)
+            ops.rollout_finalize_step(rs, tokens_in.get('cons'), flt, slp, saved)
             if t + 1 < T:
                 S.tok[t + 1].copy_(seq[:, t])         # it * unfinished, written by this finalize
     _keep_mask(cap, S, L, [masks])
@@ -300,8 +313,11 @@ def _train_forward(cap, mode, fc, att, cpt_words, senti_words, tokens_in, senti_
             S.lazy = (out, out.stride(0), out.stride(1))      # raw logits [B,T,V]: row (b,t) at b*T*V + t*V
         else:
             ops.logsoftmax_apply_steps(out, S.pm, S.ps)       # in place: [B,T,V] raw logits -> log-probs
+    S.flt = None
     if sampling:
         S.sample = (seq, seq_masks, raw, alive)
+        if flt is not None:
+            S.flt = dict(saved, slp=slp, inv_tau=1.0 / flt['temperature'])
     cap._set_weights(S.aC, S.aS, S.bG, T)
     S.pi = None                             # (the tile statistics: only the lazy forms' backward reads them)
     if S.lazy is None:
@@ -479,10 +495,15 @@ def _step_bwd_plan(cap, p, Pc, Ps):
     return bp
 
 
-def _dlogits(lazy, d, logp, sparse, out, B, T, V, step_rows, scale):
+def _dlogits(lazy, d, logp, sparse, out, B, T, V, step_rows, scale, flt=None):
     """d logits of one call's B x T positions into `out`, time-major at step_rows rows per step: the softmax term from
-    the log-probs logp, or - lazy = (raw, ld_b, ld_t, part_max, part_sum) - from the raw logits and their statistics."""
-    if lazy is not None:
+    the log-probs logp, or - lazy = (raw, ld_b, ld_t, part_max, part_sum) - from the raw logits and their statistics.
+    flt (lazy only): the filtered term - the gradient of the sampled distribution's log-probability - in the same pass."""
+    if flt is not None:
+        raw, ld_b, ld_t, pm, ps = lazy
+        ops.logsoftmax_bwd_raw_filtered(raw, ld_b, ld_t, B, T, V, pm, ps, step_rows, list(sparse), flt, out, scale=scale,
+                                        out_step_rows=step_rows)
+    elif lazy is not None:
         raw, ld_b, ld_t, pm, ps = lazy
         ops.logsoftmax_bwd_raw(raw, ld_b, ld_t, B, T, V, pm, ps, step_rows, list(sparse), out, scale=scale,
                                out_step_rows=step_rows)
@@ -788,11 +809,13 @@ def _group_sum(x, n):
 
 
 # ------------------------------------------------------------------------------ backward
-def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
+def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=(), flt=None):
     """Returns {param name: gradient}.  The gradient of the log-probs arrives as `dlogp` [B,T,V] (contiguous; None when
     every consumer handed its part over sparse) plus `sparse` = [(ids [B,T] int64, coef [B,T] fp32)]: coef at column ids
     of each row (XELossFn / GatherLogpFn below).  Optional gradients of the `fc_feats` (pre-dropout) and `cpt_feats`
-    attributes.  Gradient scale and outputs: _Grads."""
+    attributes.  flt: the filtered term of a sampled roll-out under sampling controls (DecodeFn.backward) - (tok, coef) of
+    the SAMPLING log-probabilities and what the forward saved for them; it enters d logits in the same launch.
+    Gradient scale and outputs: _Grads."""
     p, P, B, T, L = S.p, S.P, S.B, S.T, S.L
     E, A, H, _, V = _dims(cap)
     new, zeros = cap._new, cap._zeros
@@ -811,7 +834,8 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
     # [offs[t], offs[t] + counts[t]) - the contractions over all rows behind the sweep (both LSTM cells' dW groups, dxt,
     # the bias sums) see N rows, no gather
     D = _sweep_buffers(cap, g, S, L, L.short, B, 0 if pk is None else pk['Np'])
-    scale, (d_fc_feats, d_cpt_feats) = g.scale(D.gs_z, [c for _, c in sparse], (d_fc_feats, d_cpt_feats), [dlogp])
+    scale, (d_fc_feats, d_cpt_feats) = g.scale(D.gs_z, [c for _, c in sparse] + ([flt['coef']] if flt else []),
+                                               (d_fc_feats, d_cpt_feats), [dlogp])
     if pk is not None:
         # ragged, packed classifier block (see _train_forward): d logits over the N rows inside their captions
         N = pk['N']
@@ -823,11 +847,11 @@ def _backward(cap, S, dlogp, d_fc_feats, d_cpt_feats, sparse=()):
                 dlogits[N:].zero_()
         else:
             dlogits.zero_()
-    elif dlogp is None and not sparse:
+    elif dlogp is None and not sparse and flt is None:
         dlogits.zero_()
     else:                       # (lazy: the log-probs were never formed - softmax from raw logits + stats)
         lazy = getattr(S, 'lazy', None)
-        _dlogits(lazy and (*lazy, S.pm, S.ps), dlogp, S.logp, sparse, dlogits, B, T, V, B, scale)
+        _dlogits(lazy and (*lazy, S.pm, S.ps), dlogp, S.logp, sparse, dlogits, B, T, V, B, scale, flt)
     hdrop_tb = (S.hdrop if S.hdrop is not None else S.h2[1:]).reshape(TB, H) if pk is None else pk['hs']
     dhd = _classifier_bwd(cap, g, dlogits, hdrop_tb)
     if pk is not None:          # d h_lang back in [T,B] order, zero behind the captions' ends
@@ -927,20 +951,28 @@ class DecodeFn(torch.autograd.Function):
         outs = [logp, cap.cpt_feats]
         if mode != 'seq2seq':
             outs.append(cap.fc_feats)
+        if S.flt is not None:               # the sampling log-probs [B,T]: a differentiable output of their own
+            outs.append(S.flt.pop('slp'))
         # the attribute tensors alias internal buffers: hand autograd distinct objects
         return tuple(o if i == 0 else o.clone() for i, o in enumerate(outs))
 
     @staticmethod
-    def backward(ctx, dlogp, d_cpt, d_fc=None):
+    def backward(ctx, dlogp, d_cpt, d_fc=None, d_slp=None):
         cap, S = ctx.cap, ctx.S
         sparse, ctx._isc_sparse = ctx._isc_sparse, []
         with torch.no_grad():
+            flt = None
+            if d_slp is not None:
+                # d log q(drawn token) [B,T], one coefficient per row like the model's below - times `live`: behind the
+                # early break the output is the constant zero.  No [B,T,V] tensor: the decode node's d logits kernel
+                # rebuilds the kept set from what the forward saved (isc_logsoftmax_bwd_raw_filtered)
+                flt = dict(S.flt, tok=S.lazy_ids, coef=(d_slp * S.lazy_live).contiguous())
             if getattr(S, 'lazy', None) is not None or getattr(S, 'packed', None) is not None:
                 # dlogp is d log p(id) [B,T]: one column per row
                 if dlogp is not None:
                     coef = dlogp.contiguous() if S.lazy_live is None else (dlogp * S.lazy_live).contiguous()
                     sparse, dlogp = [(S.lazy_ids, coef)], None
-            G = _backward(cap, S, dlogp.contiguous() if dlogp is not None else None, d_fc, d_cpt, sparse)
+            G = _backward(cap, S, dlogp.contiguous() if dlogp is not None else None, d_fc, d_cpt, sparse, flt)
         grads = tuple(G.get(n) for n in ctx.names)
         ctx.S = None
         return (None,) * 12 + grads
@@ -969,14 +1001,20 @@ def xe_with_grad(cap, mode, fc, att, cpt_words, senti_words, captions, senti_lab
     return logp
 
 
-def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks, cons=None, group=1):
+def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, replay, masks, cons=None, group=1,
+                      filt=None):
     """Sampled roll-out with REINFORCE gradients (captioner.py:290-349, sample_max=0, train mode): one unroll
     that samples each next token on the device and keeps the activations for the backward pass; the returned
     log-probs are log p(drawn token), zero after the reference's early `break`.
     cons: forward_rl's token constraints (an isc_decode_constraints struct) - they decide which token is drawn; the
     log-probability, and so the gradient, stays the model's own of that token.
     group = n > 1 (forward_rl captions_per_image): the inputs hold one entry per image, the draws (`replay`, the
-    uniforms) and the returned tensors n rows per image, row i*n + j = draw j of image i."""
+    uniforms) and the returned tensors n rows per image, row i*n + j = draw j of image i.
+    filt: forward_rl's sampling controls (Captioner._sample_filter).  When they change the sampled distribution
+    (temperature / top_k / top_p on, or constraints with the sampling log-probs wanted) the draws come from the filtered
+    finalize, which keeps what the backward needs, and the sampling log-probabilities log q(drawn token) are a second
+    differentiable output - the on-policy REINFORCE gradient of a filtered roll-out is that of log q, not of the
+    model's log p.  With `want_slp` they are returned as the fourth tensor (default controls: the model's own)."""
     fc, att = cap._f32(fc), cap._f32(att)          # (as xe_with_grad: fp32 once, in front of the prologue)
     names = [n for n, q in cap.named_parameters() if q.requires_grad]
     params = [q for _, q in cap.named_parameters() if q.requires_grad]
@@ -987,8 +1025,18 @@ def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, rep
         if group > 1 and tuple(draws['forced'].shape) != (B, T):
             raise ValueError('_replay must hold the draws of every row, [%d, %d], got %r'
                              % (B, T, tuple(draws['forced'].shape)))
+    elif filt is not None and filt['uniforms'] is not None:
+        u = filt['uniforms']
+        if not torch.is_tensor(u) or u.dtype != torch.float32 or tuple(u.shape) != (B, T):
+            raise ValueError('_uniforms must be a float32 tensor of shape [B, T] = [%d, %d]' % (B, T))
+        draws['u'] = u.to(cap._dev).contiguous()
+    elif filt is not None and filt['generator'] is not None:
+        draws['u'] = torch.rand(B, T, device=cap._dev, generator=filt['generator'])
     else:
         draws['u'] = torch.rand(B, T, device=cap._dev)
+    want_slp = filt is not None and filt['want_slp']
+    if filt is not None and (filt['filtered'] or (cons is not None and want_slp)):
+        draws['flt'] = filt
     was = cap.training
     # the roll-out's [B,T,V] log-probs are never an API output (captioner.py:336 keeps log p(drawn token) only): the
     # decode node returns that column - already times `live` - from the raw logits (lazy = True; DecodeFn.backward)
@@ -999,6 +1047,8 @@ def rollout_with_grad(cap, fc, att, cpt_words, senti_words, senti_labels, T, rep
     cap.cpt_feats, cap.fc_feats = outs[1], outs[2]
     seq, seq_masks, raw, alive = cap._last_sample
     cap._last_sample = None
+    if want_slp:       # (default controls: the sampled distribution IS the model's)
+        return seq, lp, seq_masks, outs[3] if 'flt' in draws else lp.clone()
     return seq, lp, seq_masks
 
 

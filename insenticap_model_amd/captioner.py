@@ -869,7 +869,16 @@ class Captioner(nn.Module):
         and `generator` for the uniforms; `_uniforms` [B,T] float32 replaces the drawn uniforms (tests, the counterpart of
         `_replay`).  `seq_logprobs` stays the MODEL's log-probability of the drawn token; `return_sampling_logprobs=True`
         appends a fourth tensor, the log-probability under the distribution that was sampled.  With the default controls
-        the call is today's plain multinomial roll-out, bit for bit.  The sampling controls are inference-only.
+        the call is today's plain multinomial roll-out, bit for bit.
+        With gradients enabled (the differentiable sampled roll-out) the controls, `generator`, `_uniforms` and
+        `return_sampling_logprobs` apply as well, and the sampling log-probabilities are differentiable: their gradient is
+        d log q(token) / d logits = (1 / temperature) ([v == token] - [v kept] q_v), formed by the decode node's d logits
+        kernel (isc_logsoftmax_bwd_raw_filtered) from what the forward kept per step.  A token drawn from the filtered
+        distribution q is on-policy for q, not for the model's p: REINFORCE under sampling controls takes its loss on
+        the sampling log-probs (`Detector.rollout_sampling` does); `seq_logprobs` stays differentiable as the model's.
+        With `top_k=1` the gradient of the sampling log-probs is exactly zero.  A filtered call with gradients that does
+        NOT ask for the sampling log-probs stays a `ValueError` (without them filtered sampling is inference-only): the
+        model's `seq_logprobs` alone would invite the off-policy loss.
         `captions_per_image=n` > 1 draws n captions per image without repeating the image: the five inputs hold one
         entry per image, [I, ...]; everything step-invariant (embedded regions, their projection, the att-LSTM's hoisted
         term) is computed and kept once per image, and the decode runs on I*n rows that share it (the scan loads a
@@ -889,7 +898,7 @@ class Captioner(nn.Module):
         explicit `_masks`, or with dropout off, the call is the function of the same call on the repeated inputs with
         each per-image mask repeated; in training mode the per-image masks are DRAWN once per image, where the repeated
         form draws one per copy (the one deliberate difference, as in `forward_xe`).  The uniforms are
-        torch.rand(I*n, T); temperature / top_k / top_p stay inference-only.
+        torch.rand(I*n, T) (or `generator`'s / `_uniforms`); temperature / top_k / top_p apply as with n = 1.
         Token constraints - the beam search's rules (`sample_batch`, captioner.py:394-399), all off by default: under
         `suppress_special` a live row never chooses <PAD>, <SOS> or <UNK> (as there: only when pad_id != eos_id), under
         `decoding_constraint=1` never the token it was just fed (seq[b, t-1]; <SOS> at t = 0), and never <EOS> while
@@ -897,8 +906,9 @@ class Captioner(nn.Module):
         id: greedy under the first two rules is `sample_batch(beam_size=1)`); a sampled draw runs over the allowed ids
         only - ban, then temperature, top-k, top-p.  `seq_logprobs` stays the MODEL's log_softmax(x)[token] over the full
         row (what the beam's scores sum); the sampling log-probs are those of the restricted distribution.  They combine
-        with the sampling controls, `captions_per_image` and the differentiable sampled roll-out (the gradient is that
-        of the model's log-probability of the drawn token); `_replay` excludes them.  The token is chosen on the device
+        with the sampling controls, `captions_per_image` and the differentiable sampled roll-out (`seq_logprobs`' gradient
+        is that of the model's log-probability of the drawn token, the sampling log-probs' that of the restricted
+        distribution's); `_replay` excludes them.  The token is chosen on the device
         (isc_rollout_finalize_constrained), still without a host read.  A constrained greedy roll-out materialises each
         step's [B, V] logits (the plain one decides on the tile statistics alone), and a constrained call stays on the
         general kernels, served eagerly: no few-row step, no fused finalize, no roll-out graph (follow-ups)."""
@@ -913,21 +923,26 @@ class Captioner(nn.Module):
                              'sampled roll-outs only (sample_max=0)')
         if _replay is not None and (filtered or return_sampling_logprobs or _uniforms is not None):
             raise ValueError('_replay forces the tokens: it excludes the sampling controls')
-        if filtered and self._needs_grad():
-            raise ValueError('filtered sampling (temperature / top_k / top_p) is inference-only for now: call it under '
-                             'torch.no_grad() (the backward through 1 / temperature is not built)')
+        if filtered and self._needs_grad() and not return_sampling_logprobs:
+            # the tokens come from the filtered distribution q: weighting them with the gradient of the model's
+            # seq_logprobs is REINFORCE for neither policy, so a differentiable filtered call has to ask for log q
+            raise ValueError('filtered sampling (temperature / top_k / top_p) without return_sampling_logprobs=True is '
+                             'inference-only: with gradients enabled the on-policy term is the sampling log-probability '
+                             '- pass return_sampling_logprobs=True and take the loss on the fourth tensor, or call under '
+                             'torch.no_grad()')
         if not sample_max and not self._needs_grad() and _replay is None and (
                 filtered or return_sampling_logprobs or _uniforms is not None or generator is not None):
             filt = self._sample_filter(temperature, top_k, top_p, generator, _uniforms, return_sampling_logprobs)
             out = self._rollout(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0, None,
                                 _masks, filt, group=n_cap, cons=cons)
             return out[:3] + ((filt['slp'],) if return_sampling_logprobs else ())
-        if return_sampling_logprobs or _uniforms is not None or generator is not None:
-            raise ValueError('generator / return_sampling_logprobs / _uniforms are not available with gradients enabled')
         if not sample_max and self._needs_grad():
             from .autograd import rollout_with_grad
+            filt = None
+            if filtered or return_sampling_logprobs or _uniforms is not None or generator is not None:
+                filt = self._sample_filter(temperature, top_k, top_p, generator, _uniforms, return_sampling_logprobs)
             return rollout_with_grad(self, fc_feats, att_feats, cpt_words, senti_words, senti_labels,
-                                     max_seq_len, _replay, _masks, cons, group=n_cap)
+                                     max_seq_len, _replay, _masks, cons, group=n_cap, filt=filt)
         if (sample_max and cons is None and self.__dict__.get('_rollout_graphs') is not None and not self._needs_grad()
                 and not self.training and _replay is None and _masks is None and ops.TIMER.arm_step is None
                 and fc_feats.shape[0] <= self.ROLLOUT_GRAPH_MAX_ROWS and ops.graphs_allowed_here()

@@ -3,6 +3,7 @@
 // (train_xe.py:19-23 / captioner.py:422-423).  All contractions run on the MFMA GEMM
 // (isc_gemm_bwd); this file holds the HBM-bound pointwise / scan parts.
 #include "common.h"
+#include "flt_key.h"
 
 // ------------------------------------------------------------------ log-softmax backward
 // dlogits[m,:] = dlogp[m,:] - exp(logp[m,:]) * sum_v dlogp[m,v];  columns V..ld_out-1 are zeroed
@@ -206,6 +207,150 @@ extern "C" int isc_logsoftmax_bwd_raw(const float *raw, int64_t ld_b, int64_t ld
         hipLaunchKernelGGL(logsoftmax_bwd_raw_kernel<false>, dim3((unsigned)(B * T)), dim3(256), 0, (hipStream_t)stream, raw,
                            (long long)ld_b, (long long)ld_t, B, T, V, part_max, part_sum, (V + 127) / 128, step_rows, sp,
                            scale, dlogits, (long long)ld_out, out_step_rows);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
+// The same pass with the gradient of the SAMPLED distribution's log-probability added (self-critical RL under
+// temperature / top-k / top-p: the on-policy REINFORCE gradient is that of log q(token), q = the filtered distribution
+// the token was drawn from).  The forward (pointwise.hip: rollout_finalize_filtered_body, isc_rollout_finalize_saved)
+// kept per row the boundary key K*, the largest allowed logit g, log Z of the kept mass and the banned ids; with
+// c = coef * (1 / tau):
+//   F[v] = scale * c * ( [v == tok] - [key(x_v, v) <= K*, v not banned] * q_v ),   q_v = exp2((x_v - g) log2(e) / tau) / Z.
+// 1 / Z is one expf per ROW; q is clamped to 1 (it is a probability: with one id kept, q - 1 is rounding alone and the
+// row must be exactly zero).  The model term A (logsoftmax_bwd_raw_kernel's expression) and F are rounded apart and then
+// added without contraction: the bits of A's launch plus the bits of F's.  The banned ids - at most ISC_CON_MAX per row -
+// are not tested per element: their columns are rewritten behind a barrier, by one thread each.
+struct FilteredDlogp {
+    const int64_t *tok, *kstar;
+    const float *coef, *gmax, *logz;
+    const int32_t *ban;
+    float inv_tau, c_exp;
+};
+
+template <bool VEC4>
+__global__ __launch_bounds__(256) void logsoftmax_bwd_raw_filtered_kernel(const float *raw, long long ld_b, long long ld_t,
+                                                                          int B, int T, int V, const float *pmax,
+                                                                          const float *psum, int n_tile, int step_rows,
+                                                                          SparseDlogp sp, FilteredDlogp ft,
+                                                                          const float *scale, float *dlogits,
+                                                                          long long ld_out, int out_step_rows) {
+    __shared__ float sh[2];
+    const int mi = blockIdx.x, tid = threadIdx.x;
+    const int b = mi / T, t = mi - b * T;
+    const long long ms = (long long)t * step_rows + b;
+    float tot = 0.f;
+    long long id[ISC_SPARSE_MAX];
+    float cf[ISC_SPARSE_MAX];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < ISC_SPARSE_MAX; ++j) {
+        id[j] = -1; cf[j] = 0.f;
+        if (j < sp.n) { id[j] = sp.ids[j][mi]; cf[j] = sp.coef[j][mi]; tot += cf[j]; any = any || cf[j] != 0.f; }
+    }
+    const float cF = ft.coef[mi];
+    const bool flt = cF != 0.f;
+    float *o = dlogits + ((long long)t * out_step_rows + b) * ld_out;
+    if (!any && !flt) {
+        // (block-uniform) nothing enters this position - behind <EOS> or the early break: zeros, its logits unread
+        if (VEC4) {
+            for (int i = tid * 4; i < ld_out; i += 1024) *reinterpret_cast<float4 *>(o + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (int i = tid; i < ld_out; i += 256) o[i] = 0.f;
+        }
+        return;
+    }
+    if (any && tid < 64) {
+        float gm, S;
+        int gi;
+        fold_row_stats_impl(pmax + ms * n_tile, psum + ms * n_tile, nullptr, n_tile, tid, gm, gi, S);
+        if (tid == 0) { sh[0] = gm; sh[1] = logf(S); }
+    }
+    __syncthreads();
+    const float gmax = any ? sh[0] : 0.f, logS = any ? sh[1] : 0.f;
+    const float sc = scale ? scale[0] : 1.f;
+    // the row's filtered scalars (uniform loads)
+    const long long tokF = flt ? ft.tok[mi] : -1;
+    const isc_u64 Kst = flt ? (isc_u64)ft.kstar[mi] : 0ull;
+    const float gF = flt ? ft.gmax[mi] : 0.f, invZ = flt ? expf(-ft.logz[mi]) : 0.f, cw = cF * ft.inv_tau;
+    const float *y = raw + (long long)b * ld_b + (long long)t * ld_t;
+    auto model = [&](int i, float yi) __attribute__((always_inline)) {
+        float v = 0.f;
+#pragma unroll
+        for (int j = 0; j < ISC_SPARSE_MAX; ++j)
+            if ((long long)i == id[j]) v += cf[j];
+        return (v - expf((yi - gmax) - logS) * tot) * sc;
+    };
+    auto one = [&](int i, float yi, bool allowed) __attribute__((always_inline)) {
+        const float A = any ? model(i, yi) : 0.f;
+        float F = 0.f;
+        if (flt) {
+            float q = 0.f;
+            if (allowed && flt_key(yi, i) <= Kst) q = fminf(__builtin_amdgcn_exp2f((yi - gF) * ft.c_exp) * invZ, 1.f);
+            F = (((long long)i == tokF ? 1.f : 0.f) - q) * cw * sc;
+        }
+        float r;
+        {
+#pragma clang fp contract(off)
+            r = A + F;
+        }
+        return r;
+    };
+    if (VEC4) {
+        for (int i = tid * 4; i < ld_out; i += 1024) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < V) {
+                const float4 yv = *reinterpret_cast<const float4 *>(y + i);
+                v.x = one(i, yv.x, true); v.y = one(i + 1, yv.y, true); v.z = one(i + 2, yv.z, true);
+                v.w = one(i + 3, yv.w, true);
+            }
+            *reinterpret_cast<float4 *>(o + i) = v;
+        }
+    } else {
+        for (int i = tid; i < ld_out; i += 256) o[i] = i < V ? one(i, y[i], true) : 0.f;
+    }
+    if (flt && ft.ban) {                    // (block-uniform)
+        __syncthreads();                    // the row is written: a banned column is now rewritten as outside K
+        if (tid < ISC_CON_MAX) {
+            const int v = ft.ban[(long long)mi * ISC_CON_MAX + tid];
+            if (v >= 0 && v < V) o[v] = one(v, y[v], false);
+        }
+    }
+}
+
+extern "C" int isc_logsoftmax_bwd_raw_filtered(const float *raw, int64_t ld_b, int64_t ld_t, int B, int T, int V,
+                                               const float *part_max, const float *part_sum, int step_rows,
+                                               const int64_t *const *ids_host, const float *const *coef_host, int n_sparse,
+                                               const int64_t *flt_tok, const float *flt_coef, float inv_tau,
+                                               const int64_t *kstar, const float *gmax, const float *logz,
+                                               const int32_t *ban, const float *scale, float *dlogits, int64_t ld_out,
+                                               int out_step_rows, void *stream) {
+    if (!raw || !dlogits || !flt_tok || !flt_coef || !kstar || !gmax || !logz) return ISC_E_NULL;
+    if (n_sparse > 0 && (!part_max || !part_sum)) return ISC_E_NULL;
+    if (B <= 0 || T <= 0 || V <= 0 || ld_out < V || (long long)B * T > 2147483647LL) return ISC_E_SHAPE;
+    if (n_sparse < 0 || n_sparse > ISC_SPARSE_MAX || !(inv_tau > 0.f && inv_tau <= 3.0e38f)) return ISC_E_SHAPE;
+    if (step_rows == 0) step_rows = B;
+    if (out_step_rows == 0) out_step_rows = B;
+    if (step_rows < B || out_step_rows < B) return ISC_E_SHAPE;
+    SparseDlogp sp = {};
+    sp.n = n_sparse;
+    for (int j = 0; j < n_sparse; ++j) {
+        if (!ids_host || !coef_host || !ids_host[j] || !coef_host[j]) return ISC_E_NULL;
+        sp.ids[j] = ids_host[j]; sp.coef[j] = coef_host[j];
+    }
+    FilteredDlogp ft;
+    ft.tok = flt_tok; ft.kstar = kstar; ft.coef = flt_coef; ft.gmax = gmax; ft.logz = logz; ft.ban = ban;
+    ft.inv_tau = inv_tau; ft.c_exp = (float)(1.4426950408889634 * (double)inv_tau);
+    const bool vec4 = (V & 3) == 0 && (ld_out & 3) == 0 && (ld_b & 3) == 0 && (ld_t & 3) == 0 && isc_aligned16(raw) &&
+                      isc_aligned16(dlogits);
+    if (vec4)
+        hipLaunchKernelGGL(logsoftmax_bwd_raw_filtered_kernel<true>, dim3((unsigned)(B * T)), dim3(256), 0,
+                           (hipStream_t)stream, raw, (long long)ld_b, (long long)ld_t, B, T, V, part_max, part_sum,
+                           (V + 127) / 128, step_rows, sp, ft, scale, dlogits, (long long)ld_out, out_step_rows);
+    else
+        hipLaunchKernelGGL(logsoftmax_bwd_raw_filtered_kernel<false>, dim3((unsigned)(B * T)), dim3(256), 0,
+                           (hipStream_t)stream, raw, (long long)ld_b, (long long)ld_t, B, T, V, part_max, part_sum,
+                           (V + 127) / 128, step_rows, sp, ft, scale, dlogits, (long long)ld_out, out_step_rows);
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }

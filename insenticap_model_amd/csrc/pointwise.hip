@@ -4,6 +4,7 @@
 #include <cstddef>
 
 #include "common.h"
+#include "flt_key.h"
 
 // ------------------------------------------------------------------ embeddings
 // TM (isc_sent_cls_fwd, sent_cls.hip): the ids are a [B, L] matrix read TIME-MAJOR - output row r = t * tm_B + b takes
@@ -411,7 +412,6 @@ __device__ __forceinline__ void rollout_choose_row(const DevRollout &R, int b, i
 // cancel to noise under a dominant banned token: the (max, arg-max, sum-exp) of every 128-column tile that holds a banned
 // id - at most ISC_CON_MAX tiles - are recomputed over its allowed columns, and the fold and the two-level draw run on the
 // corrected statistics.  A tile without an allowed column has maximum -inf and mass 0.
-#define ISC_CON_MAX 10
 struct DevCons {
     int ban[ISC_CON_MAX - 1];
     int no_repeat, first_id;
@@ -602,7 +602,6 @@ extern "C" int isc_rollout_finalize(const isc_rollout_step *s, void *stream) {
 // The draw is the inverse CDF over the kept set in vocabulary order, against u * (kept mass), in the same integers.
 // One 256-thread workgroup per row, the row staged in LDS once (V <= ISC_FLT_STAGE_MAX; longer rows are re-read from
 // L2); a workgroup walks rows blockIdx.x, + gridDim.x, ... so that `alive` sees one atomic per workgroup.
-typedef unsigned long long isc_u64;
 #define ISC_FLT_STAGE_MAX 12288
 #define ISC_FLT_MAX_GRID 768            // 3 workgroups of ~47 KB LDS per CU
 #define ISC_FLT_MASS_SPAN 23.0f         // exp(-23) * 2^32 < 1/2: beyond (max - x) / T = 23 a mass rounds to zero
@@ -614,14 +613,13 @@ struct DevFilter {
     float top_p;       // >= 1: off
     float *slp;        // optional [B,T]: log-probability under the sampled distribution
     int staged;        // row in LDS
+    // isc_rollout_finalize_saved (all or none; ban optional): what the backward of `slp` reads, per (b, t)
+    long long *sv_kstar;
+    float *sv_gmax, *sv_logz;
+    int *sv_ban;       // [B,T,ISC_CON_MAX]
 };
 
-__device__ __forceinline__ isc_u64 flt_key(float x, int i) {
-    unsigned b = __float_as_uint(x);
-    if (b == 0x80000000u) b = 0u;                                     // -0 ranks with +0
-    const unsigned dk = (b & 0x80000000u) ? b : (~b & 0x7fffffffu);   // larger x -> smaller dk
-    return ((isc_u64)dk << 32) | (unsigned)i;
-}
+// (flt_key: flt_key.h - shared with the backward)
 
 __device__ __forceinline__ unsigned flt_mass(float x, float gmax, float c_exp) {
     const float e = __builtin_amdgcn_exp2f(fminf((x - gmax) * c_exp, 0.f)) * 4294967296.0f;
@@ -890,9 +888,16 @@ __device__ __forceinline__ void rollout_finalize_filtered_body(const DevRollout 
         if (tid == 0) {
             const float xi = xs_[it];
             lp = (xi - lp_max) - logf(S);                            // the MODEL's log-probability of the token
-            if (F.slp)
-                F.slp[(long long)b * R.T + R.t] =
-                    (float)(((double)xi - (double)gmax) / (double)F.tau - log((double)Wk * (1.0 / 4294967296.0)));
+            const double logz = F.slp || F.sv_kstar ? log((double)Wk * (1.0 / 4294967296.0)) : 0.0;
+            if (F.slp) F.slp[(long long)b * R.T + R.t] = (float)(((double)xi - (double)gmax) / (double)F.tau - logz);
+            if (F.sv_kstar) {
+                const long long o = (long long)b * R.T + R.t;
+                F.sv_kstar[o] = (long long)Kstar; F.sv_gmax[o] = gmax; F.sv_logz[o] = (float)logz;
+                if (CON && F.sv_ban) {
+#pragma unroll
+                    for (int k = 0; k < ISC_CON_MAX; ++k) F.sv_ban[o * ISC_CON_MAX + k] = ids[k];
+                }
+            }
         }
         const int u2 = finalize_commit<256>(R, b, it, lp, unf, tid);
         if (tid == 0) alive += u2;
@@ -920,31 +925,38 @@ static size_t flt_lds(const isc_rollout_step *s) {
     return s->V <= ISC_FLT_STAGE_MAX ? (size_t)((s->V + 3) & ~3) * sizeof(float) : 0;
 }
 
-static DevFilter dev_filter(const isc_rollout_step *s, const isc_sample_filter *f) {
+static DevFilter dev_filter(const isc_rollout_step *s, const isc_sample_filter *f, const isc_filter_saved *sv) {
     DevFilter F;
     F.c_exp = (float)(1.4426950408889634 / (double)f->temperature);
     F.tau = f->temperature; F.top_k = f->top_k; F.top_p = f->top_p; F.slp = f->sampling_logprobs;
     F.staged = flt_lds(s) != 0;
+    F.sv_kstar = sv ? (long long *)sv->kstar : nullptr;
+    F.sv_gmax = sv ? sv->gmax : nullptr; F.sv_logz = sv ? sv->logz : nullptr; F.sv_ban = sv ? sv->ban : nullptr;
     return F;
 }
 
-extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, void *stream) {
+static int finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, const isc_filter_saved *sv,
+                             void *stream) {
     if (!s || !f) return ISC_E_NULL;
     if (const int rc = rollout_step_check(s, !s->logits || !s->sample_u,
                                           !flt_params_ok(f) || s->V <= 0 || s->n_tile <= 0 || s->ld_logits < s->V || s->forced))
         return rc;
     hipLaunchKernelGGL(rollout_finalize_filtered_kernel, flt_grid(s), dim3(256), flt_lds(s), (hipStream_t)stream,
-                       dev_rollout(s), dev_filter(s, f));
+                       dev_rollout(s), dev_filter(s, f, sv));
     ISC_LAUNCH_CHECK();
     ++g_finalize_launches;
     return ISC_OK;
 }
 
+extern "C" int isc_rollout_finalize_filtered(const isc_rollout_step *s, const isc_sample_filter *f, void *stream) {
+    return finalize_filtered(s, f, nullptr, stream);
+}
+
 // The roll-out's finalize under token constraints (include/insenticap_hip.h: isc_decode_constraints).  `f` NULL: the
 // plain finalize's choice (arg-max, or sample_u) over the allowed ids; given: the filtered one's.  A step at which
 // nothing is banned IS the unconstrained step: it goes to the two entry points above, bit for bit.
-extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const isc_sample_filter *f,
-                                                const isc_decode_constraints *c, void *stream) {
+static int finalize_constrained(const isc_rollout_step *s, const isc_sample_filter *f, const isc_decode_constraints *c,
+                                const isc_filter_saved *sv, void *stream) {
     if (!s || !c) return ISC_E_NULL;
     if (c->n_ban < 0 || c->n_ban > 8 || c->min_len < 0 || c->min_len > s->T) return ISC_E_SHAPE;
     const bool any = c->n_ban > 0 || c->no_repeat || c->min_len > 0;
@@ -962,7 +974,7 @@ extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const
     for (; n < c->n_ban; ++n) C.ban[n] = (int)c->ban_ids[n];
     if (s->t >= 0 && s->t < c->min_len) C.ban[n++] = (int)s->eos_id;
     C.no_repeat = c->no_repeat != 0; C.first_id = (int)c->first_id;
-    if (n == 0 && !C.no_repeat) return f ? isc_rollout_finalize_filtered(s, f, stream) : isc_rollout_finalize(s, stream);
+    if (n == 0 && !C.no_repeat) return f ? finalize_filtered(s, f, sv, stream) : isc_rollout_finalize(s, stream);
     for (; n < ISC_CON_MAX - 1; ++n) C.ban[n] = -1;
     if (const int rc = rollout_step_check(s, f && !s->sample_u,
                                           (f && !flt_params_ok(f)) || s->V <= 0 || s->n_tile != (s->V + 127) / 128 ||
@@ -971,7 +983,7 @@ extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const
     const DevRollout R = dev_rollout(s);
     if (f) {
         hipLaunchKernelGGL(rollout_finalize_filtered_con_kernel, flt_grid(s), dim3(256), flt_lds(s), (hipStream_t)stream, R,
-                           dev_filter(s, f), C);
+                           dev_filter(s, f, sv), C);
     } else if (s->B > 1024) {
         hipLaunchKernelGGL(rollout_finalize_con_kernel<16>, dim3((s->B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, R, C);
     } else {
@@ -980,6 +992,21 @@ extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const
     ISC_LAUNCH_CHECK();
     ++g_finalize_launches;
     return ISC_OK;
+}
+
+extern "C" int isc_rollout_finalize_constrained(const isc_rollout_step *s, const isc_sample_filter *f,
+                                                const isc_decode_constraints *c, void *stream) {
+    return finalize_constrained(s, f, c, nullptr, stream);
+}
+
+// The filtered finalize (c NULL) or the constrained filtered one, additionally keeping per (b, t) what the backward of
+// the sampling log-probability reads (isc_logsoftmax_bwd_raw_filtered): the boundary key K*, the largest allowed logit,
+// log(kept mass) and - under constraints - the row's banned ids.  Same kernels, same choice, same outputs; a step the
+// early break skips (alive[t] == 0) writes nothing: the caller zero-fills (ban: -1) up front.
+extern "C" int isc_rollout_finalize_saved(const isc_rollout_step *s, const isc_sample_filter *f,
+                                          const isc_decode_constraints *c, const isc_filter_saved *sv, void *stream) {
+    if (!s || !f || !sv || !sv->kstar || !sv->gmax || !sv->logz) return ISC_E_NULL;
+    return c ? finalize_constrained(s, f, c, sv, stream) : finalize_filtered(s, f, sv, stream);
 }
 
 // ------------------------------------------------------------------ scheduled sampling (captioner.py:219-228)

@@ -68,6 +68,13 @@ class Detector(nn.Module):
         # of Captioner.forward_rl's keywords `suppress_special`, `decoding_constraint`, `min_len`.  While it is set every
         # iteration runs the eager sequence (capture under constraints is not built).
         self.rollout_constraints = None
+        # Sampling controls of the TRAINING iterations' sampled roll-out: None, or a dict of Captioner.forward_rl's keywords
+        # `temperature`, `top_k`, `top_p`.  A token drawn from the filtered distribution q is on-policy for q: while the
+        # controls are on, the REINFORCE loss is taken on the SAMPLING log-probabilities log q(token) (differentiable:
+        # isc_logsoftmax_bwd_raw_filtered), for n = 1 and for rl_samples_per_image > 1 alike; the greedy baseline and
+        # evaluation are untouched, and the iteration runs the eager sequence (a graph-served filtered iteration is not
+        # built).  None or all-default controls change nothing, graphs included.
+        self.rollout_sampling = None
         # Sampled captions per image of a TRAINING iteration (1: the reference's iteration, sample + greedy baseline).
         # n > 1: self-critical RL on n samples per image whose baseline is the mean CIDEr-D of the image's other n - 1
         # samples - one grouped differentiable roll-out (Captioner.forward_rl captions_per_image=n: the image is not
@@ -305,6 +312,15 @@ class Detector(nn.Module):
                              % sorted(rl_kw))
         if not any(rl_kw.values()):
             rl_kw = {}                       # (all off: the unconstrained iteration, graphs included)
+        rs_kw = dict(self.rollout_sampling or {})
+        if set(rs_kw) - {'temperature', 'top_k', 'top_p'}:
+            raise ValueError('rollout_sampling takes temperature / top_k / top_p, got %r' % sorted(rs_kw))
+        tau, top_k, top_p = ops.check_sample_filter(rs_kw.get('temperature', 1.0), rs_kw.get('top_k', 0),
+                                                    rs_kw.get('top_p', 1.0))
+        if not training or (tau == 1.0 and not 0 < top_k < cap.vocab_size and top_p >= 1.0):
+            rs_kw = {}                       # (all default: today's iteration, graphs included; evaluation: untouched)
+        else:
+            rs_kw = dict(temperature=tau, top_k=top_k, top_p=top_p, return_sampling_logprobs=True)
         # data-parallel branches: taken whenever DP is enabled and a process group exists - also a one-rank group
         # (shares are then exactly 1.0), so a one-GPU RCCL run crosses the code an 8-rank run does
         dist_on = self.dp_arena is not None and dp.distributed(self.dp_group)
@@ -362,7 +378,8 @@ class Detector(nn.Module):
                 """One iteration (models/decoder.py:69-167).  `exact`: on the exact-fp32 GEMM engine, eagerly - the retry of
                 an iteration whose roll-outs left the split-f16 operand domain (OutOfDomain is raised at the iteration's
                 own synchronisation point, before anything is updated)."""
-                if (training and self.train_graphs and not rl_kw and n_rl == 1 and not lm_on and device.type == 'cuda'
+                if (training and self.train_graphs and not rl_kw and not rs_kw and n_rl == 1 and not lm_on
+                        and device.type == 'cuda'
                         and ops.TIMER.arm_step is None and ops.graphs_allowed_here() and not exact):
                     # the same iteration from HIP graphs (train_graph.RLTrainGraph): same calls in the same order
                     from .train_graph import RLTrainGraph
@@ -398,9 +415,12 @@ class Detector(nn.Module):
                 # sampled roll-out (graph kept in train mode) and the domain-alignment loss on its prologue
                 # (grouped: n_rl rows per image, [I*n, T]; the prologue and its attributes stay per image, [I, E])
                 grouped = n_rl > 1
-                sample_captions, sample_logprobs, seq_masks = cap(
+                sampled = cap(
                     fc_feats, att_feats, cpts_tensor, sentis_tensor, senti_labels, self.max_seq_len,
-                    sample_max=0, mode='rl', **(dict(captions_per_image=n_rl) if grouped else {}), **rl_kw)
+                    sample_max=0, mode='rl', **(dict(captions_per_image=n_rl) if grouped else {}), **rl_kw, **rs_kw)
+                sample_captions, sample_logprobs, seq_masks = sampled[:3]
+                if rs_kw:           # drawn from q: the on-policy REINFORCE term is on log q(token), not on the model's log p
+                    sample_logprobs = sampled[3]
                 da_loss = self.cap_da_crit(cap.cpt_feats, cap.fc_feats.detach())
                 # DP: each term's share of the global normaliser (mask sum, XE tokens, seq2seq tokens, rows)
                 w_rl = w_xe = w_s2s = w_rows = None

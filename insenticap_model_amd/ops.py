@@ -908,14 +908,30 @@ def rollout_finalize_constrained(step, cons, filt=None, sampling_logprobs=None):
               4.0 * step.B * ((step.V if f is not None else 0) + 3 * step.n_tile + 2 * step.W))
 
 
-def rollout_finalize_step(step, cons=None, filt=None, sampling_logprobs=None):
+def rollout_finalize_saved(step, cons, filt, sampling_logprobs, saved):
+    """isc_rollout_finalize_saved: the filtered finalize (under `cons` when given) that also keeps what the backward of
+    the sampling log-probabilities reads - saved: a mapping with 'kstar', 'gmax', 'logz' [B,T] and 'ban' ([B,T,10] or
+    None).  One launch."""
+    f, sv = _lib.SampleFilter(), _lib.FilterSaved()
+    f.temperature, f.top_k, f.top_p = check_sample_filter(*filt)
+    f.sampling_logprobs = ptr(sampling_logprobs)
+    sv.kstar, sv.gmax, sv.logz, sv.ban = (ptr(saved.get(k)) for k in ('kstar', 'gmax', 'logz', 'ban'))
+    e0 = TIMER.begin()
+    check(_lib.load().isc_rollout_finalize_saved(C.byref(step), C.byref(f), None if cons is None else C.byref(cons),
+                                                 C.byref(sv), stream()), 'isc_rollout_finalize_saved')
+    TIMER.end(e0, 'rollout_finalize_saved[%d]' % step.B, 0.0, 4.0 * step.B * (step.V + 2 * step.n_tile + 2 * step.W))
+
+
+def rollout_finalize_step(step, cons=None, filt=None, sampling_logprobs=None, saved=None):
     """One decode step's finalize in whichever of the three forms above it takes.  cons: decode_constraints or None;
     filt: the sampling controls (a mapping with 'temperature', 'top_k', 'top_p' and 'filtered' = any of them is on) or
     None.  Under constraints the sampled distribution is the restricted one, so a wanted `sampling_logprobs` sends the
-    controls along even when they are the defaults."""
+    controls along even when they are the defaults.  saved (the differentiable roll-out): rollout_finalize_saved."""
     filtered = filt is not None and filt['filtered']
     controls = None if filt is None else (filt['temperature'], filt['top_k'], filt['top_p'])
-    if cons is not None:
+    if saved is not None:
+        rollout_finalize_saved(step, cons, controls, sampling_logprobs, saved)
+    elif cons is not None:
         rollout_finalize_constrained(step, cons, controls if filtered or sampling_logprobs is not None else None,
                                      sampling_logprobs)
     elif filtered:
@@ -1495,6 +1511,31 @@ def logsoftmax_bwd_raw(raw, ld_b, ld_t, B, T, V, part_max, part_sum, step_rows, 
     check(_lib.load().isc_logsoftmax_bwd_raw(raw.data_ptr(), int(ld_b), int(ld_t), B, T, V, part_max.data_ptr(),
                                              part_sum.data_ptr(), int(step_rows), ids, cf, n, ptr(scale), dlogits.data_ptr(),
                                              dlogits.stride(0), int(out_step_rows), stream()), 'isc_logsoftmax_bwd_raw')
+
+
+def logsoftmax_bwd_raw_filtered(raw, ld_b, ld_t, B, T, V, part_max, part_sum, step_rows, sparse, flt, dlogits, scale=None,
+                                out_step_rows=0):
+    """isc_logsoftmax_bwd_raw_filtered: logsoftmax_bwd_raw's d logits (zero to two model pairs) plus, in the same pass,
+    the gradient of the sampled distribution's log-probability.  flt: a mapping with 'tok' (int64 [B,T]), 'coef' (fp32
+    [B,T]), 'inv_tau' and the forward's saved 'kstar' (int64), 'gmax', 'logz' (fp32) [B,T], 'ban' (int32 [B,T,10] or
+    None)."""
+    n = len(sparse)
+    assert 0 <= n <= 2 and dlogits.stride(1) == 1
+    for i, c in sparse:
+        assert i.dtype == torch.int64 and c.dtype == torch.float32 and i.is_contiguous() and c.is_contiguous()
+        assert i.numel() == B * T and c.numel() == B * T
+    for k, dt in (('tok', torch.int64), ('kstar', torch.int64), ('coef', torch.float32), ('gmax', torch.float32),
+                  ('logz', torch.float32)):
+        assert flt[k].dtype == dt and flt[k].is_contiguous() and flt[k].numel() == B * T, k
+    ban = flt.get('ban')
+    assert ban is None or (ban.dtype == torch.int32 and ban.is_contiguous() and ban.numel() == B * T * 10)
+    ids = (C.c_void_p * max(n, 1))(*[i.data_ptr() for i, _ in sparse])
+    cf = (C.c_void_p * max(n, 1))(*[c.data_ptr() for _, c in sparse])
+    check(_lib.load().isc_logsoftmax_bwd_raw_filtered(
+        raw.data_ptr(), int(ld_b), int(ld_t), B, T, V, ptr(part_max), ptr(part_sum), int(step_rows), ids, cf, n,
+        flt['tok'].data_ptr(), flt['coef'].data_ptr(), float(flt['inv_tau']), flt['kstar'].data_ptr(),
+        flt['gmax'].data_ptr(), flt['logz'].data_ptr(), ptr(ban), ptr(scale), dlogits.data_ptr(), dlogits.stride(0),
+        int(out_step_rows), stream()), 'isc_logsoftmax_bwd_raw_filtered')
 
 
 def grad_scale(sources, out2, maxima=()):
