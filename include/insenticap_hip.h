@@ -294,7 +294,11 @@ int isc_attn_scan_fwd(const isc_scan_problem *probs_host, int n_prob, int B, voi
  * come out of the scan's own attention weights: the step's gate GEMM and gate-mix launches disappear, for R x A more
  * floats streamed per row (why the host uses it for few rows only).  scan[0] = content, scan[1] = sentiment words; their
  * .out / planes are optional here (v and s are only needed through f); A == D <= 1024 for both; zh [B,A] is the h-term
- * incl. its bias.  alpha outputs as in isc_attn_scan_fwd. */
+ * incl. its bias.  alpha outputs as in isc_attn_scan_fwd.
+ * scan[i].row_div is honoured per scan, independently: the rows of a group of scan[0].row_div rows share ONE entry of the
+ * content scan's P / V / G[0]; the rows of a group of scan[1].row_div rows share one entry of the sentiment scan's q2,
+ * row_ids and per-row P / V / G[1] (one image captioned under several sentiment labels: isc_step_plan.senti_div).
+ * B % row_div == 0, else ISC_E_SHAPE with nothing launched.  q, zh, f, beta and the alphas stay per row. */
 typedef struct {
     isc_scan_problem scan[2];
     const float *G[2];
@@ -555,14 +559,21 @@ typedef struct {
      * gate; s must equal v + pair_rows_c * E (one [rows,E] attended-feature block feeds the lang-LSTM).  Both LSTM cells
      * and the classifier then run once over all rows, the two h-projections as two problems of one launch and the two
      * scans as the two problems of one isc_attn_scan_fwd launch.  fp32 rows only (no state planes).  0 = off. */
-    int32_t pair_rows_c, _pad2;
+    /* senti_div (with row_div > 1): inside an image the rows come in LABEL GROUPS of senti_div consecutive rows - the
+     * beams of one (image, sentiment) search, when one image is captioned under several sentiment labels.  The
+     * content-side tensors (att_p, att_e, gate_Gc) keep one entry per IMAGE, row r reads entry r / row_div; the
+     * sentiment-side tensors (pre1, label_w, words_ids, per-row words_p / words_e, per-row gate_Gs) hold one entry per
+     * label group, row r reads entry r / senti_div.  row_div % senti_div == 0; 0 = as row_div (one label per image);
+     * 1 = a label per row.  Every output is, per row, bit for bit that of the plain step on the expanded tensors. */
+    int32_t pair_rows_c, senti_div;
     /* row_div > 1: `rows` = images x row_div decode rows, row r belongs to image r / row_div (the captions drawn per
      * image by a sampled roll-out), and the step-invariant tensors of an image - pre1, att_p, att_e, label_w, words_ids
      * (per-row words_p / words_e as well) - hold one entry per IMAGE, as documented for isc_rows_ext.row_div.
      * isc_step_fwd hands it to the att-LSTM (isc_lstm_problem.pre_div) and to both scans (isc_scan_problem.row_div);
-     * everything else of the step is per row as always.  rows % row_div == 0; not with pair_rows_c and not with the
-     * fused gate scan (gate_Gc / gate_Gs) of the general kernels.  isc_rows_step_fwd ignores it: the few-row step
-     * takes isc_rows_ext.row_div.  0 or 1 = off.
+     * everything else of the step is per row as always.  rows % row_div == 0; not with pair_rows_c.  With the fused gate
+     * scan (gate_Gc / gate_Gs) gate_Gc is per image as well.  isc_rows_step_fwd ignores it: the few-row step
+     * takes isc_rows_ext.row_div.  0 or 1 = off.  A violated divisibility, or row_div > 1 without pre1
+     * (the rule of isc_lstm_problem.pre_div), is ISC_E_SHAPE with nothing launched.
      * pre_rows != 0 (with row_div > 1, isc_step_fwd only): pre1 holds one row per decode ROW all the same - grouped
      * teacher-forced training, whose sentiment labels (part of the hoisted term) differ between an image's captions. */
     int32_t row_div, pre_rows;
@@ -605,6 +616,10 @@ int isc_set_stream_gate(const int32_t *flag, void *stream);
  *    words_ids; per-row words_p / words_e / gate_Gs as well) hold one entry per image and row r uses entry r / row_div -
  *    the `beam` rows of an image share its regions (captioner.py:366-377 expands nothing either: it decodes candidate by
  *    candidate), so a search keeps one copy per image instead of `beam`; rows % row_div == 0;
+ *  - senti_div (with row_div > 1): label groups of senti_div consecutive rows inside an image, as isc_step_plan.senti_div -
+ *    att_p / att_e / gate_Gc stay per image, pre1 / label_w / words_ids / per-row words_p / words_e / gate_Gs are per label
+ *    group and row r uses entry r / senti_div (one image searched under two labels: row_div = 2 * beam, senti_div = beam);
+ *    row_div % senti_div == 0, else ISC_E_SHAPE with nothing launched; 0 = as row_div;
  *  - live_in: optional device int; when it reads 0 every launch of the step returns at once (and isc_beam_select with it):
  *    a search captured as ONE graph of T steps ends itself on the device (live[t] of isc_beam_select: images still
  *    searching before step t) instead of the host reading that counter between graphs of a few steps.
@@ -617,7 +632,7 @@ typedef struct {
     const int64_t *last_word;     /* [rows] required iff decoding_constraint */
     int64_t pad_id, sos_id, unk_id;
     int32_t mask_special, decoding_constraint;
-    int32_t row_div, _pad;
+    int32_t row_div, senti_div;   /* senti_div: label groups inside an image, as isc_step_plan.senti_div (0 = as row_div) */
     const int32_t *live_in;
     /* optional: the PREVIOUS step's greedy roll-out finalize folded into this step's first launch (a roll-out of T steps is
      * then T finalize launches shorter but one: only the last step's runs on its own).  fin_prev describes that step as

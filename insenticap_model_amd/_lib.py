@@ -83,7 +83,7 @@ class StepPlan(C.Structure):
                  ('splitk_ws', C.c_void_p), ('splitk_ws_floats', C.c_int64)] +
                 _f('h1_prev_hi h1_prev_lo h2_prev_hi h2_prev_lo h1_hi h1_lo h2_hi h2_lo '
                    'v_hi v_lo s_hi s_lo f_hi f_lo words_ids', C.c_void_p) + [('words_ids_ld', C.c_int64)] +
-                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c _pad2 row_div pre_rows', C.c_int32))
+                _f('gate_Gc gate_Gs', C.c_void_p) + _f('pair_rows_c senti_div row_div pre_rows', C.c_int32))
 
 
 class StepBwdPlan(C.Structure):
@@ -110,7 +110,7 @@ class RowsExt(C.Structure):
     _fields_ = [('src_row', C.c_void_p), ('stats_tile', C.c_int32), ('beam', C.c_int32), ('cand_val', C.c_void_p),
                 ('cand_idx', C.c_void_p), ('last_word', C.c_void_p), ('pad_id', C.c_int64), ('sos_id', C.c_int64),
                 ('unk_id', C.c_int64), ('mask_special', C.c_int32), ('decoding_constraint', C.c_int32),
-                ('row_div', C.c_int32), ('_pad', C.c_int32), ('live_in', C.c_void_p), ('fin_prev', C.c_void_p),
+                ('row_div', C.c_int32), ('senti_div', C.c_int32), ('live_in', C.c_void_p), ('fin_prev', C.c_void_p),
                 ('fin_unfinished_out', C.c_void_p)]
 
 

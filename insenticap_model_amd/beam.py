@@ -136,15 +136,24 @@ class _VectorMerge:
         return out
 
 
-def beam_search_batch(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, graphs=True):
+def beam_search_batch(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, graphs=True,
+                      share=False):
+    """share: the rows of an image read ONE entry of its step-invariant tensors (nothing is expanded `beam`-fold); with
+    senti_labels [I, S] an image is searched under S labels at once (Captioner.sample_sentiments: I*S searches)."""
     if (graphs and cap.__dict__.get('_beam_graphs') is not None and getattr(cap, 'beam_device_merge', True) and beam <= 8
             and ops.TIMER.arm_step is None and ops.graphs_allowed_here()):
-        return _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T)
-    return _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T)
+        return _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
+    return _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
 
 
-def _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T):
-    s = _Search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T)
+def _n_search(fc_feats, senti_labels):
+    """Searches of one call: images x labels per image (senti_labels [I, S]; [I] or None: one)."""
+    S = senti_labels.shape[1] if senti_labels is not None and senti_labels.dim() == 2 else 1
+    return fc_feats.shape[0] * S
+
+
+def _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
+    s = _Search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
     if s.device_merge:
         with ops.h3_weights_scope(cap._dev):
             for t in range(T):
@@ -162,12 +171,13 @@ FEW_ROW_PLANE_BYTES = 24 << 20
 
 
 def _few_rows(cap, n_img, beam):
-    """One image's beam on at most ROWS_STEP_MAX rows: the few-row step (csrc/rows.hip)."""
+    """The beams of n_img searches (one image's, or one image's under two or three labels) on at most ROWS_STEP_MAX rows:
+    the few-row step (csrc/rows.hip)."""
     return (n_img * beam <= cap.ROWS_STEP_MAX and beam <= 8 and getattr(cap, 'rows_step', True)
             and getattr(cap, 'beam_device_merge', True) and cap._rows_vocab_ok())
 
 
-def _graph_key(cap, ins, beam, decoding_constraint, T):
+def _graph_key(cap, ins, beam, decoding_constraint, T, share=False):
     # (the cached tables a captured graph points at are functions of these weights: token table, sentiment-word tables,
     # and - gated scan - the sentiment-word table through attention.senti2att)
     # ... and - few-row searches - the prologue's weight planes, which such a graph keeps instead of re-splitting them
@@ -175,7 +185,8 @@ def _graph_key(cap, ins, beam, decoding_constraint, T):
                                           cap.senti2att[0].bias, cap.attention.senti2att.weight, cap.att_embed[0].weight,
                                           cap.att2att[0].weight, cap.attention.cont2att.weight))
     return (tuple(None if x is None else (tuple(x.shape), x.dtype) for x in ins), beam, decoding_constraint, T, versions,
-            ops.WEIGHT_EPOCH, cap.eos_id, torch.cuda.current_device(), bool(getattr(cap, 'beam_step_gate', True)))
+            ops.WEIGHT_EPOCH, cap.eos_id, torch.cuda.current_device(), bool(getattr(cap, 'beam_step_gate', True)),
+            bool(share))
 
 
 def _replay(cap, entry, ins, T):
@@ -189,7 +200,7 @@ def _replay(cap, entry, ins, T):
     return search.finish()
 
 
-def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T):
+def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
     """Captioner.sample_batch's short cut: a search whose graphs exist is one key look-up, the input copies, the replay
     and the read-back - none of the per-call set-up of the eager path (parameter dictionary, weights scope, mode walk:
     ~100 us of host time in front of a 1 ms search).  None when there is nothing to replay."""
@@ -200,7 +211,7 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
     if not (fc_feats.is_cuda and att_feats.is_cuda):
         return None
     ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
-    key = _graph_key(cap, ins, beam, decoding_constraint, T)
+    key = _graph_key(cap, ins, beam, decoding_constraint, T, share)
     entry = cache.get(key)
     if not isinstance(entry, tuple):
         return None
@@ -208,7 +219,7 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
     return _replay(cap, entry, ins, T)
 
 
-def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T):
+def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
     """The search served from captured HIP graphs (Captioner.enable_beam_graphs).  A single-image beam-5 step is
     ~14 small launches behind four FFI calls and the host needs longer to enqueue them than the device to run them;
     the loop has no host read except the live-image counter every CHUNK steps, so the prologue + steps 0..3 capture
@@ -216,21 +227,22 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
     <= ceil(T / CHUNK) graph launches with one counter read between them, and the read-back."""
     dev = cap._dev
     ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
-    key = _graph_key(cap, ins, beam, decoding_constraint, T)
+    key = _graph_key(cap, ins, beam, decoding_constraint, T, share)
     cache = cap._beam_graphs
     entry = cache.get(key)
     if entry is None:                       # first sight: run eagerly (builds the cached tables, warms the kernels)
         while len(cache) >= cap._beam_graphs_max:
             cap._graph_evicted(cache.pop(next(iter(cache))), 'beam')    # least recently used
             if cap._beam_graphs is None:
-                return _search(cap, *ins, beam, decoding_constraint, T)
+                return _search(cap, *ins, beam, decoding_constraint, T, share)
         cache[key] = 'seen'
-        return _search(cap, *ins, beam, decoding_constraint, T)
+        return _search(cap, *ins, beam, decoding_constraint, T, share)
     cache[key] = cache.pop(key)             # LRU order
     if entry == 'seen':
         static = [None if x is None else x.clone() for x in ins]
         ws, wp = cap._graph_buffers()          # ONE workspace / plane-buffer pair for all graphs of this captioner
-        few = _few_rows(cap, ins[0].shape[0], beam)
+        n_search = _n_search(ins[0], ins[3])
+        few = _few_rows(cap, n_search, beam)
         if few:
             # ... except the planes of a few-row search: its graph is ONE replay of ~1 ms, and the three split launches
             # of its prologue's weights (att_embed, att2att / senti2att, the gate projections: 8 MB of planes) are 2 % of
@@ -246,20 +258,20 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
         pool = torch.cuda.graph_pool_handle()
         graphs = []
         # (few-row searches are ONE graph: its last node copies the results into this pinned buffer)
-        pinned = torch.empty(_Search.result_bytes(ins[0].shape[0], beam, T), dtype=torch.uint8).pin_memory() if few else None
+        pinned = torch.empty(_Search.result_bytes(n_search, beam, T), dtype=torch.uint8).pin_memory() if few else None
         torch.cuda.synchronize()
         with ops.capture_buffers(ws, wp), torch.cuda.stream(stream):
             scope = ops.h3_weights_scope(dev)      # ONE scope over all the captures (its planes live in `wp`,
             scope.__enter__()                      # are split inside graph 0 and read by the later graphs)
             try:
                 if few:                            # (the eager prologue leaves the planes in the scope)
-                    _Search(cap, *static, beam, decoding_constraint, T)
+                    _Search(cap, *static, beam, decoding_constraint, T, share)
                 search, t0 = None, 0
                 while t0 < T:
                     g = torch.cuda.CUDAGraph()
                     with ops.graph_capture(g, pool=pool, stream=stream):
                         if search is None:
-                            search = _Search(cap, *static, beam, decoding_constraint, T)
+                            search = _Search(cap, *static, beam, decoding_constraint, T, share)
                         # few-row searches end themselves on the device (isc_rows_ext.live_in): ONE graph, no counter
                         # read in between; the general kernels run CHUNK steps per graph with a look at the counter after
                         # each - their steps are gated as well (isc_set_stream_gate), so the up to CHUNK - 1 steps a graph
@@ -284,15 +296,22 @@ class _Search:
     """State of one batched search: the prologue, the per-row copies, the device-side candidate table; step(t)
     enqueues decode step t (preceded by the state re-ordering that step t - 1 decided)."""
 
-    def __init__(self, cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T):
+    def __init__(self, cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
         p = cap._p()
-        n_img = fc_feats.shape[0]
+        # A search is an (image, label) pair: senti_labels [I, S] (Captioner.sample_sentiments) runs n_img = I * S searches
+        # of `beam` rows - the merge kernels think in searches - over I images' region tensors (share is then implied).
+        images = fc_feats.shape[0]
+        S = senti_labels.shape[1] if senti_labels is not None and senti_labels.dim() == 2 else 1
+        share = bool(share) or S > 1 or (senti_labels is not None and senti_labels.dim() == 2)
+        n_img = images * S
+        self.images, self.n_senti, self.share = images, S, share
         # few rows (one image's beam): the image's sentiment-word features as per-image tensors - the vocabulary-sized
         # tables would put an id -> row index chain in front of every step's sentiment scan, and there is one image
-        few = _few_rows(cap, fc_feats.shape[0], beam)
+        few = _few_rows(cap, n_img, beam)
         P = cap._prologue(p, 'beam', fc_feats, att_feats, None, senti_words,
                           senti_labels if senti_words is not None else None, want_table='build',
-                          words_table=getattr(cap, 'words_table', True) and not few, gate_rows=fc_feats.shape[0] * beam)
+                          words_table=getattr(cap, 'words_table', True) and not few, gate_rows=n_img * beam,
+                          label_group=S)
         dev = cap._dev
         H, Wd, V = cap.att_lstm.hidden_size, cap.settings['word_emb_dim'], cap.vocab_size
         rows = n_img * beam
@@ -306,6 +325,12 @@ class _Search:
         self.gated = self.device_merge and not self.rows_mode and getattr(cap, 'beam_step_gate', True)
         if self.rows_mode:
             Pb = P
+        elif share:
+            # the general kernels on the prologue's own tensors: row r reads the image's entry r / (S * beam) of the region
+            # tensors and gate_Gc, the label group's entry r / beam of pre1 / label_w / the word tensors
+            # (isc_step_plan.row_div / senti_div); fused gate scan or grouped scan + gate GEMM, as the prologue decided
+            Pb = P
+            Pb.row_div, Pb.senti_div = S * beam, beam
         else:
             # expand the step-invariant tensors to one copy per beam row (row = img*beam + k)
             rep = torch.arange(n_img, device=dev).repeat_interleave(beam)
@@ -327,6 +352,8 @@ class _Search:
                 Pb.gate_Gc = expand(gc.view(n_img, P.R, -1)).view(rows * P.R, -1)
                 Pb.gate_Gs = gs if P.words_ids is not None else expand(gs.view(n_img, P.Mw, -1)).view(rows * P.Mw, -1)
         self.cap, self.p, self.Pb = cap, p, Pb
+        # (observable: entries of the search's region tensor - images when shared, rows when expanded)
+        cap.last_beam_region_entries = None if Pb.att_e3 is None else int(Pb.att_e3.shape[0])
         self.n_img, self.beam, self.T, self.rows, self.dc = n_img, beam, T, rows, decoding_constraint
         self.stats_tile = ops.rows_stats_tile(V) if self.rows_mode else 128
         self.ws = cap._alloc_step_ws(rows, Pb, self.stats_tile)
@@ -386,7 +413,8 @@ class _Search:
                 self.cand_idx = cap._new(rows, n_tile, 8, dtype=torch.int32)
                 self.src_row = self.gather                  # written by step t's select, read by step t + 1
                 x = self.ext = RowsExt()
-                x.src_row, x.stats_tile, x.beam, x.row_div = None, self.stats_tile, beam, beam   # (step 0: the identity)
+                x.src_row, x.stats_tile, x.beam, x.row_div = None, self.stats_tile, beam, S * beam   # (step 0: the identity)
+                x.senti_div = beam if S > 1 else 0           # label groups inside the image: one search's beams
                 x.cand_val, x.cand_idx = self.cand_val.data_ptr(), self.cand_idx.data_ptr()
                 x.pad_id, x.sos_id, x.unk_id = cap.pad_id, cap.sos_id, cap.unk_id
                 x.mask_special, x.decoding_constraint = int(self.mask_special), int(decoding_constraint)

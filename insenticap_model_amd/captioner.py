@@ -57,6 +57,8 @@ class _Pro:
     pre1 = None      # [B,4H]  fc_e W_fc^T + label_e W_x^T + b_ih + b_hh: step-invariant att-LSTM input
     row_div = 1      # decode rows per image (captions_per_image of forward_rl / forward_xe): the image's tensors above
                      # hold one entry per IMAGE
+    senti_div = 0    # row_div > 1: rows per LABEL GROUP inside an image (isc_step_plan.senti_div) - label_e, label_w, pre1 and
+                     # the word tensors then hold one entry per group (`_prologue(label_group=S)`: I*S of them); 0 = row_div
     pre_rows = False  # row_div > 1, forward_xe: label_e / pre1 (and fc_rows) are per ROW all the same - the labels differ
                       # between an image's captions
     fc_rows = None   # [B*row_div,E] fc_e, each image's row repeated (forward_xe captions_per_image: pre1's GEMM operand)
@@ -230,10 +232,14 @@ class Captioner(nn.Module):
     ROLLOUT_GRAPH_MAX_ROWS = 256   # greedy eval roll-outs up to this many captions are served from HIP graphs
 
     def _prologue(self, p, mode, fc=None, att=None, cpt_words=None, senti_words=None, senti_labels=None,
-                  masks=None, want_table=False, words_table=False, gate_rows=0, pre1_out=None, group=1):
+                  masks=None, want_table=False, words_table=False, gate_rows=0, pre1_out=None, group=1, label_group=1):
         """group = n > 1 (forward_xe captions_per_image, 'xe' only): fc / att / cpt_words hold one entry per image and so
         does everything derived from them (dropout masks 'fc' [I,E] and 'att' [I*R,E] included); senti_labels, the 'label'
         mask, label_e and the hoisted att-LSTM term pre1 are per caption row, [I*n, ...] (P.pre_rows).
+        label_group = S > 1 (inference: one image under S sentiment labels - `sample_sentiments`, grouped roll-outs with a
+        label per row): fc / att hold one entry per image, senti_labels is [I,S] and senti_words [I,M] (shared by the
+        image's labels) or [I,S,M]; label_e, label_w, pre1 and the word tensors get I*S entries (entry i*S + s), the region
+        tensors and gate_Gc keep I.  The caller sets P.row_div / P.senti_div to its rows per image / per label group.
         want_table: False | 'cached' (use the embedding table only if already built) | 'build'.
         words_table: serve the sentiment words from the vocabulary-sized tables (no dropout on them, no autograd).
         gate_rows: number of decode rows of an INFERENCE call (0: training / not applicable): up to
@@ -279,7 +285,9 @@ class Captioner(nn.Module):
                 first.append(ops.linear_problem([(cmean, p['cpt2fc.0.weight'])], cpt, p['cpt2fc.0.bias'],
                                                 relu=True))
         ops.linear_fwd(first)
-        Bl = B * group                                    # rows of the per-caption tensors
+        S = int(label_group)
+        Bl = B * group * S                                # rows of the per-caption (per-label-group) tensors
+        Bs = B * S                                        # entries of the sentiment-word tensors
         if senti_labels is not None:
             P.label_e = self._new(Bl, Wd)
             P.label_ids = self._ids(senti_labels).reshape(-1)
@@ -291,7 +299,7 @@ class Captioner(nn.Module):
             if m is not None:
                 P.label_e = P.label_e * (m.float() * sc)   # [B,W] elementwise, train mode only
             if senti_words is not None:
-                P.label_w = self._new(B, A)
+                P.label_w = self._new(Bl, A)
                 ops.linear_fwd([ops.linear_problem(
                     [(P.label_e, p['attention.senti_att.label2word.weight'])], P.label_w,
                     p['attention.senti_att.label2word.bias'])])
@@ -307,22 +315,25 @@ class Captioner(nn.Module):
                                              p['att2att.0.bias'], relu=True))
             P.att_e3, P.att_p3 = att_e.view(B, R, E), att_p.view(B, R, A)
         if senti_words is not None:
-            sw = self._ids(senti_words).reshape(B, -1)
+            sw = self._ids(senti_words)
+            if S > 1 and sw.dim() == 2:                    # the image's words under each of its labels
+                sw = sw.unsqueeze(1).expand(B, S, sw.shape[-1])
+            sw = sw.reshape(Bs, -1).contiguous()
             P.Mw = sw.shape[1] + 1
-            m, sc = mask_for('words', B * P.Mw, Wd)
+            m, sc = mask_for('words', Bs * P.Mw, Wd)
             P.sw_ids, P.m_words, P.sc = sw, m, sc
         if senti_words is not None and words_table and m is None:
             # captioner.py:307-312 without dropout: word_embed(id) and senti2att(word_embed(id)) are functions of the
             # id alone -> two [V,.] tables (41 MB, cache-resident) instead of [B,M,.] copies re-read every step
             P.words_e3, P.words_p3 = self._senti_tables(p)
-            P.words_ids = torch.cat([sw.new_full((B, 1), self.pad_id), sw], dim=1).contiguous()
+            P.words_ids = torch.cat([sw.new_full((Bs, 1), self.pad_id), sw], dim=1).contiguous()
         elif senti_words is not None:
-            words_e = self._new(B * P.Mw, Wd)
+            words_e = self._new(Bs * P.Mw, Wd)
             ops.embed_senti_words_fwd(p['word_embed.0.weight'], sw, self.pad_id, words_e, m, sc)
-            words_p = self._new(B * P.Mw, A)
+            words_p = self._new(Bs * P.Mw, A)
             second.append(ops.linear_problem([(words_e, p['senti2att.0.weight'])], words_p,
                                              p['senti2att.0.bias'], relu=True))
-            P.words_e3, P.words_p3 = words_e.view(B, P.Mw, Wd), words_p.view(B, P.Mw, A)
+            P.words_e3, P.words_p3 = words_e.view(Bs, P.Mw, Wd), words_p.view(Bs, P.Mw, A)
         if second:
             ops.linear_fwd(second)
         if (0 < gate_rows <= self.GATE_FUSED_MAX_ROWS and getattr(self, 'gate_fused', True) and masks is None
@@ -334,8 +345,8 @@ class Captioner(nn.Module):
             if P.words_ids is not None:
                 P.gate_Gs = self._gate_senti_table(p, P.words_e3)
             else:
-                P.gate_Gs = self._new(B * P.Mw, A)
-                gl.append(ops.linear_problem([(P.words_e3.view(B * P.Mw, Wd), p['attention.senti2att.weight'])],
+                P.gate_Gs = self._new(Bs * P.Mw, A)
+                gl.append(ops.linear_problem([(P.words_e3.view(Bs * P.Mw, Wd), p['attention.senti2att.weight'])],
                                              P.gate_Gs))
             ops.linear_fwd(gl)
         # Hoist the step-invariant inputs of the att-LSTM (captioner.py:174: cat[h_lang, fc, xt] with
@@ -344,7 +355,9 @@ class Captioner(nn.Module):
         Wih = p['att_lstm.weight_ih']
         if group > 1:
             P.row_div, P.pre_rows, P.fc_rows = group, True, P.fc_e.repeat_interleave(group, 0)
-        segs = [(P.fc_e if group == 1 else P.fc_rows, Wih[:, H:H + E])]
+        elif S > 1:                                       # (one GEMM row per label group: the image's fc row under each label)
+            P.fc_rows = P.fc_e.unsqueeze(1).expand(B, S, E).reshape(Bs, E).contiguous()
+        segs = [(P.fc_e if P.fc_rows is None else P.fc_rows, Wih[:, H:H + E])]
         if P.label_e is not None:
             segs.append((P.label_e, Wih[:, H + E:]))
         # (pre1_out: the caller's [B,4H] row block of a larger buffer - the merged unroll of two sibling calls keeps
@@ -486,6 +499,7 @@ class Captioner(nn.Module):
         ws = ops.splitk_ws(self._dev)
         pl.splitk_ws, pl.splitk_ws_floats = ws.data_ptr(), ws.numel()
         pl.row_div = P.row_div if P.row_div > 1 else 0       # rows = images x row_div: P holds one entry per image
+        pl.senti_div = P.senti_div if P.row_div > 1 else 0   # (... sentiment side one per label group of senti_div rows)
         pl.pre_rows = int(P.pre_rows)                        # (... but pre1 one per row: forward_xe captions_per_image)
         return pl
 
@@ -573,7 +587,7 @@ class Captioner(nn.Module):
             segs.insert(1, (xt, Wih[:, H + E:]))
         ops.lstm_fwd(segs, None, None, c_cur[0], h_nxt[0], c_nxt[0], gates_out=save.get('g1'),
                      pre=P.pre1, tab=P.tab, tab_ids=tok if P.tab is not None else None, h_planes=pn(0),
-                     pre_div=1 if P.pre_rows else P.row_div)
+                     pre_div=1 if P.pre_rows else (P.senti_div or P.row_div))
         h1 = h_nxt[0]
         has_cont, has_senti = P.att_e3 is not None, P.words_e3 is not None
         probs, scans = [], []
@@ -591,7 +605,7 @@ class Captioner(nn.Module):
                                           p['attention.senti_att.word_alpha.weight'],
                                           p['attention.senti_att.word_alpha.bias'], ws['s'], alpha_s,
                                           q2=P.label_w, out_planes=wp('s'), row_ids=P.words_ids,
-                                          row_div=P.row_div))
+                                          row_div=P.senti_div or P.row_div))
         gate = has_cont and has_senti
         if gate:   # the h2att(h1) term of the gate rides in the same launch as the two projections
             probs.append(ops.linear_problem([(h1, p['attention.h2att.weight'], pn(0))], ws['z'],
@@ -884,7 +898,10 @@ class Captioner(nn.Module):
         term) is computed and kept once per image, and the decode runs on I*n rows that share it (the scan loads a
         region row once for an image's rows).  `_uniforms`, `_replay`, the returned tensors, the sampling log-probs and
         the attention-weight attributes are [I*n, ...], row i*n + j = draw j of image i - the layout of the same call on
-        inputs repeated with `repeat_interleave(n, 0)`; `fc_feats` / `cpt_feats` stay [I, ...].  Sampled roll-outs only
+        inputs repeated with `repeat_interleave(n, 0)`; `fc_feats` / `cpt_feats` stay [I, ...].  In the inference form
+        `senti_labels` may also hold a label per ROW, [I*n] or [I, n] (row i*n + j under label [i, j]: the label, its
+        label2word term and the hoisted att-LSTM term are then per row, isc_step_plan.senti_div = 1, the regions still
+        per image).  Sampled roll-outs only
         (n equal greedy captions would be a mistake), in one of two forms: inference (eval mode under torch.no_grad(),
         no `_masks`), or the differentiable training roll-out (training mode with gradients enabled: self-critical RL
         on n samples per image).  In the training form `senti_labels` is [I] - the labels come from the image - and
@@ -990,6 +1007,14 @@ class Captioner(nn.Module):
         if masks is not None and not grad:
             raise ValueError('captions_per_image > 1 without gradients does not take _masks (dropout masks belong to '
                              'training)')
+        if not grad and fc_feats is not None and senti_labels is not None:
+            # inference form: one label per image, or one per caption row ([I*n] or [I, n]: row i*n + j under label [i, j])
+            images, labels = int(fc_feats.shape[0]), int(senti_labels.numel())
+            if labels not in (images, images * n) or (senti_labels.dim() == 2 and labels == images * n
+                                                      and tuple(senti_labels.shape) != (images, n)):
+                raise ValueError('captions_per_image=%d: senti_labels must hold one label per image (%d) or per caption row '
+                                 '(%d, as [I*n] or [I, n]), got shape %s' % (n, images, images * n,
+                                                                            tuple(senti_labels.shape)))
         if grad and fc_feats is not None and senti_labels is not None:
             images, labels = int(fc_feats.shape[0]), int(senti_labels.numel())
             if labels != images:
@@ -1231,11 +1256,15 @@ class Captioner(nn.Module):
         want = False
         if not torch.is_grad_enabled() or not any(q.requires_grad for q in self.parameters()):
             want = 'build' if n_rows * T >= self.vocab_size // 4 else 'cached'
+        # a label per caption row (inference, captions_per_image with [I*n] / [I, n] labels): the sentiment side per row
+        row_labels = (group > 1 and senti_labels is not None and not torch.is_grad_enabled()
+                      and senti_labels.numel() == n_rows)
         P = self._prologue(p, 'rl', fc_feats, att_feats, cpt_words, senti_words, senti_labels, masks,
                            want_table=want, words_table=bool(want) and getattr(self, 'words_table', True),
-                           gate_rows=n_rows if want and group == 1 else 0)
+                           gate_rows=n_rows if want and group == 1 else 0, label_group=group if row_labels else 1)
         ops.TIMER.armed, ops.TIMER.phase = False, 'step'
         P.row_div = group
+        P.senti_div = 1 if row_labels else 0
         B, V = P.B * group, self.vocab_size
         H, Wd = self.att_lstm.hidden_size, self.settings['word_emb_dim']
         # a handful of captions, no sampling: the few-row kernels (statistics per isc_rows_stats_tile columns)
@@ -1351,11 +1380,78 @@ class Captioner(nn.Module):
 
     @torch.no_grad()
     def sample_batch(self, fc_feats, att_feats, senti_words=None, senti_labels=None,
-                     beam_size=3, decoding_constraint=1, max_seq_len=16):
+                     beam_size=3, decoding_constraint=1, max_seq_len=16, share_image=False):
         """Beam search for I images at once: every step runs ONE batched decode step over I*beam rows
         and one device top-k; candidate bookkeeping follows the reference exactly (fp64 score sums,
         stable ordering, ended beams carried, captioner.py:378-411).
-        Returns (captions[I][beam], scores[I][beam], id_sequences[I][beam])."""
+        Returns (captions[I][beam], scores[I][beam], id_sequences[I][beam]).
+        `share_image=True`: the same search without the `beam` copies of each image's region tensors - on the general
+        kernels the rows of an image read ONE entry of att_e / att_p / gate_Gc and of the label / word tensors
+        (isc_step_plan.row_div), as the few-row step always did.  Same candidates; scores to rounding."""
+        share = bool(share_image)
+        if senti_labels is not None and senti_labels.dim() != 1 and senti_labels.numel() == fc_feats.shape[0]:
+            senti_labels = senti_labels.reshape(-1)              # ([I, 1] and the like: one label per image, as always)
+        if senti_labels is not None and senti_labels.dim() != 1:
+            raise ValueError('sample_batch: senti_labels must be [I] (one label per image; several labels per image: '
+                             'sample_sentiments), got shape %s' % (tuple(senti_labels.shape),))
+        return self._beam_call(fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
+                               max_seq_len, share)
+
+    @staticmethod
+    def _check_sentiments(n_cat, fc_feats, senti_words, senti_labels, beam_size, device_merge, labels_known=False):
+        """sample_sentiments' arguments, checked before anything touches the device.  Returns (I, S)."""
+        images = int(fc_feats.shape[0])
+        if senti_labels is None or not torch.is_tensor(senti_labels) or senti_labels.dim() != 2 \
+                or int(senti_labels.shape[0]) != images or int(senti_labels.shape[1]) < 1:
+            raise ValueError('sample_sentiments: senti_labels must be an integer tensor [I, S] = [%d, S >= 1] (row i: the '
+                             'labels image i is captioned under), got %s'
+                             % (images, None if senti_labels is None else tuple(getattr(senti_labels, 'shape', ()))))
+        if senti_labels.is_floating_point() or senti_labels.dtype == torch.bool:
+            raise ValueError('sample_sentiments: senti_labels must hold integer category ids, got %s' % senti_labels.dtype)
+        S = int(senti_labels.shape[1])
+        # (the caller's [I, S] ids: a tiny read; labels_known: the caller formed them from category names itself)
+        lo, hi = (0, 0) if labels_known else (int(senti_labels.min()), int(senti_labels.max()))
+        if lo < 0 or hi >= n_cat:
+            raise ValueError('sample_sentiments: label %d is outside the %d sentiment categories'
+                             % (lo if lo < 0 else hi, n_cat))
+        if senti_words is None or not torch.is_tensor(senti_words) or not (
+                (senti_words.dim() == 2 and int(senti_words.shape[0]) == images) or
+                (senti_words.dim() == 3 and tuple(senti_words.shape[:2]) == (images, S))):
+            raise ValueError('sample_sentiments: senti_words must be [I, M] (shared by the image\'s sentiments) or '
+                             '[I, S, M] = [%d, %d, M], got %s'
+                             % (images, S, None if senti_words is None else tuple(getattr(senti_words, 'shape', ()))))
+        if isinstance(beam_size, bool) or not hasattr(beam_size, '__index__') or int(beam_size) < 1:
+            raise ValueError('sample_sentiments: beam_size must be an integer >= 1, got %r' % (beam_size,))
+        if device_merge and int(beam_size) > 8:
+            raise ValueError('sample_sentiments: %d sentiments x beam %d rows per image share the image under the '
+                             'device-side merge, which holds at most 8 beams per search (beam_device_merge = False keeps '
+                             'the host merge)' % (S, int(beam_size)))
+        return images, S
+
+    @torch.no_grad()
+    def sample_sentiments(self, fc_feats, att_feats, senti_words, senti_labels, beam_size=3, decoding_constraint=1,
+                          max_seq_len=16, _labels_known=False):
+        """Beam search of I images under S sentiment labels each, the image's tensors shared: senti_labels [I, S] (row i:
+        the category ids image i is captioned under, any order), senti_words [I, M] (the image's words under every label)
+        or [I, S, M].  A search is an (image, label) pair: I*S searches of `beam_size` rows advance together, the
+        prologue's region work (att_embed / att2att over all regions, the gate's cont2att rows) runs once per IMAGE and
+        nothing is copied per beam - row r reads the image's entry r / (S*beam) and the label's entry r / beam
+        (isc_step_plan.row_div / senti_div).  Up to 8 rows (1 image x 2 labels x beam 3 or 4, 1 x 3 x 2) the search runs on
+        the few-row step, from ONE graph when beam graphs are enabled; more rows run on the general kernels.  Each
+        (image, label) result is that of `sample` under that label: same candidates, scores to rounding.
+        Returns (captions[I][S][beam], scores[I][S][beam], id_sequences[I][S][beam])."""
+        I, S = self._check_sentiments(self.senti_label_embed[0].num_embeddings, fc_feats, senti_words, senti_labels, beam_size,
+                                      getattr(self, 'beam_device_merge', True), _labels_known)
+        caps, scores, ids = self._beam_call(fc_feats, att_feats, senti_words, senti_labels, int(beam_size),
+                                            decoding_constraint, max_seq_len, True)
+
+        def nest(x):
+            return [x[i * S:(i + 1) * S] for i in range(I)]
+        return nest(caps), nest(scores), nest(ids)
+
+    def _beam_call(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint, max_seq_len,
+                   share):
+        """sample_batch / sample_sentiments: graph serving, engine fallback and numerics checks around the search."""
         from .beam import beam_search_batch, replay_if_captured
         if self.training:
             self.eval()
@@ -1367,7 +1463,7 @@ class Captioner(nn.Module):
             self._p()
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 res = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
-                                        decoding_constraint, max_seq_len, graphs=False)
+                                        decoding_constraint, max_seq_len, graphs=False, share=share)
             ops.device_status(reset=True)          # (NaN / inf features flag there as well: decoded as they are)
             return res
         # A search ends with a host read of its results, so the numerics flags are visible right behind it: no pass over
@@ -1376,12 +1472,12 @@ class Captioner(nn.Module):
         if checks and ops.h3_mode() != 0 and self._known_out_of_domain(fc_feats, att_feats):
             return on_exact_engine()
         out = replay_if_captured(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
-                                 max_seq_len)
+                                 max_seq_len, share)
         if out is None:
             self._p()                              # raises on CPU parameters before anything touches the device
             with ops.h3_weights_scope(self._dev, key=self._weights_key()):     # prologue + search: weights split once
                 out = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
-                                        decoding_constraint, max_seq_len)
+                                        decoding_constraint, max_seq_len, share=share)
         if checks:                                 # the host has the results, i.e. has waited: read the status too
             if ops.h3_mode() != 0 and ops.device_status(reset=True):
                 self._known_out_of_domain(fc_feats, att_feats, remember=True)
@@ -1401,6 +1497,8 @@ class Captioner(nn.Module):
         `_uniforms` [I*n, max_seq_len]: test hook, as in `forward_rl`.
         `share_image=True` repeats nothing: the roll-out runs with `captions_per_image=n` on the I images' inputs (same
         rows, same layout; `fc_feats` / `cpt_feats` are then [I, ...]).
+        `senti_labels` [I] gives every caption of an image its label; [I, n] (or [I*n]) gives caption j of image i the
+        label [i, j] - in both forms.
         `suppress_special`, `decoding_constraint`, `min_len`: the token constraints of `forward_rl`, in both forms."""
         n = int(n)
         if n < 1:
@@ -1413,13 +1511,14 @@ class Captioner(nn.Module):
 
         def rep(x):
             return None if x is None else x.repeat_interleave(n, dim=0)
+        row_labels = (n > 1 and senti_labels is not None and senti_labels.numel() == fc_feats.shape[0] * n)
         if share_image and n > 1:
             seq, _, masks = self.forward_rl(fc_feats, att_feats, cpt_words, senti_words, senti_labels, max_seq_len, 0,
                                             temperature=temperature, top_k=top_k, top_p=top_p, generator=generator,
                                             _uniforms=_uniforms, captions_per_image=n, **cons)
         else:
             seq, _, masks = self.forward_rl(rep(fc_feats), rep(att_feats), rep(cpt_words), rep(senti_words),
-                                            rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
+                                            senti_labels.reshape(-1) if row_labels else rep(senti_labels), max_seq_len, 0, temperature=temperature, top_k=top_k,
                                             top_p=top_p, generator=generator, _uniforms=_uniforms, **cons)
         seq_h, len_h = seq.cpu().tolist(), masks.sum(1).long().cpu().tolist()      # the call's one host read
         i2w, eos = self.idx2word, self.eos_id

@@ -513,6 +513,7 @@ struct DevScanGate {
     long long beta_ld;
     _Float16 *f_hi, *f_lo;
     int lds_half;              // floats of LDS per scan (the two scans of a row run side by side)
+    int div[2];                // rows per entry of scan i's P / V / G / q2 / ids (isc_scan_problem.row_div; 1: per row)
     const int *gate;           // optional: *gate == 0 -> the launch returns at once (isc_set_stream_gate)
 };
 
@@ -528,6 +529,7 @@ __global__ __launch_bounds__(512) void attn_scan_gate_kernel(const DevScanGate L
     const int half = threadIdx.x >> 8;                   // 0: content scan, 1: sentiment scan (wave-uniform)
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const DevScan &S = L.p[half];
+    const long long bi = b / L.div[half];                // (wave-uniform) the entry of this row in the scan's own tensors
     const int A = S.A, D = S.D;                          // equal for both scans; A == D (checked by the host)
     const int na4 = A >> 2, nd4 = D >> 2;
     const int ngrp = 256 / nd4;                          // region groups of the weighted sums (nd4 <= 256)
@@ -539,7 +541,7 @@ __global__ __launch_bounds__(512) void attn_scan_gate_kernel(const DevScanGate L
     int *rid = reinterpret_cast<int *>(smem + S.rid_off);
     const bool gather = S.ids != nullptr;
     if (gather) {
-        for (int r = tid; r < R; r += 256) rid[r] = (int)S.ids[(long long)b * S.ids_ld + r];
+        for (int r = tid; r < R; r += 256) rid[r] = (int)S.ids[bi * S.ids_ld + r];
     }
     __syncthreads();
     // ---- scores: wave w of the half scores regions w, w+4, ...; three regions per wave-iteration
@@ -550,7 +552,7 @@ __global__ __launch_bounds__(512) void attn_scan_gate_kernel(const DevScanGate L
         if (a4 < na4) {
             qv[i] = reinterpret_cast<const float4 *>(S.q + (long long)b * A)[a4];
             if (S.q2) {
-                const float4 t = reinterpret_cast<const float4 *>(S.q2 + (long long)b * A)[a4];
+                const float4 t = reinterpret_cast<const float4 *>(S.q2 + bi * A)[a4];
                 qv[i].x += t.x; qv[i].y += t.y; qv[i].z += t.z; qv[i].w += t.w;
             }
             wv[i] = reinterpret_cast<const float4 *>(S.w)[a4];
@@ -559,7 +561,7 @@ __global__ __launch_bounds__(512) void attn_scan_gate_kernel(const DevScanGate L
             wv[i] = qv[i];
         }
     }
-    const float4 *Pb = reinterpret_cast<const float4 *>(gather ? S.P : S.P + (long long)b * R * A);
+    const float4 *Pb = reinterpret_cast<const float4 *>(gather ? S.P : S.P + bi * R * A);
     const float w_bias = S.w_bias ? S.w_bias[0] : 0.f;
     for (int r0 = wave; r0 < R; r0 += 12) {
         float4 pp[3][NA];
@@ -610,8 +612,8 @@ __global__ __launch_bounds__(512) void attn_scan_gate_kernel(const DevScanGate L
     }
     __syncthreads();
     // ---- weighted sums of V and of G (same weights, same ascending order): six regions in flight per thread
-    const float4 *Vb = reinterpret_cast<const float4 *>(gather ? S.V : S.V + (long long)b * R * D);
-    const float4 *Gb = reinterpret_cast<const float4 *>(gather ? L.G[half] : L.G[half] + (long long)b * R * A);
+    const float4 *Vb = reinterpret_cast<const float4 *>(gather ? S.V : S.V + bi * R * D);
+    const float4 *Gb = reinterpret_cast<const float4 *>(gather ? L.G[half] : L.G[half] + bi * R * A);
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f), g = o;
     if (grp < ngrp) {
         for (int r0 = grp; r0 < R; r0 += 6 * ngrp) {
@@ -691,6 +693,10 @@ extern "C" int isc_attn_scan_gate_fwd(const isc_scan_gate_args *a, int B, void *
     if (B <= 0) return ISC_E_SHAPE;
     if (!a->zh || !a->b_gc || !a->b_gs || !a->w_gate || !a->f || !a->G[0] || !a->G[1]) return ISC_E_NULL;
     if ((a->f_hi == nullptr) != (a->f_lo == nullptr)) return ISC_E_NULL;
+    // scan[i].row_div > 1: rows come in groups that share ONE entry of scan i's P / V / G / q2 / row_ids - the two scans
+    // independently (content: an image's rows; sentiment words: a label group's)
+    for (int i = 0; i < 2; ++i)
+        if (a->scan[i].row_div < 0 || (a->scan[i].row_div > 1 && B % a->scan[i].row_div)) return ISC_E_SHAPE;
     {   // few hundred rows, <= 36 regions / 12 words: one 1024-thread workgroup per row (rows.hip)
         int rc = ISC_OK;
         if (rows_scan_gate_try(a, B, (hipStream_t)stream, &rc)) return rc;
@@ -718,6 +724,7 @@ extern "C" int isc_attn_scan_gate_fwd(const isc_scan_gate_args *a, int B, void *
         if (q.row_ids) need += ((size_t)q.R + 3) & ~(size_t)3;
         if (need > lds) lds = need;
         L.G[i] = a->G[i];
+        L.div[i] = q.row_div > 1 ? q.row_div : 1;
     }
     if (!isc_aligned16(a->zh) || !isc_aligned16(a->b_gc) || !isc_aligned16(a->b_gs) || !isc_aligned16(a->w_gate) ||
         !isc_aligned16(a->f))

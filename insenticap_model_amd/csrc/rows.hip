@@ -202,7 +202,8 @@ extern "C" long long isc_rows_launches(void) { return g_rows_launches.load(); }
 // units at kernel start; it applies the cell once the partials are in LDS.
 struct RLstmArgs {
     RSegs g;
-    int S, J, has_src, M, H, row_div;   // row_div: rows per image of the per-image hoisted term `pre` (1: per row)
+    int S, J, has_src, M, H, row_div;   // row_div: rows per entry of the hoisted term `pre` (1: per row; a search's label
+                                        // group, isc_rows_ext.senti_div, otherwise)
     const int *skip;                 // optional: *skip == 0 -> nothing to do (the search has ended; see isc_rows_ext.live_in)
     const long long *src;            // never null (identity when the caller has no re-ordering)
     const RowsConst *rc;
@@ -862,7 +863,8 @@ struct RScanArgs {
     const float *q[2], *q2, *w[2], *wb[2];
     const long long *ids;                      // sentiment gather mode: word row ids [rows, ids_ld]
     long long ids_ld;
-    int R[2], A, row_div;                      // row_div: rows per image of the per-image P / V / G / ids / q2 (1: per row)
+    int R[2], A, div[2];                       // rows per entry of the content half's P / V / G (div[0]: an image's rows) and
+                                               // of the sentiment half's ids / q2 / per-row P / V / G (div[1]: a label group's)
     const int *skip;
     const float *zh, *b_c, *b_s, *w_g, *b_g;
     float *f, *alpha[2], *beta;
@@ -890,7 +892,8 @@ __global__ __launch_bounds__(1024) void rows_scan_gate_kernel(const RScanArgs a)
 #define RSTAMP_KID 2
     RSTAMP(0);
     const bool gather = half && a.ids;
-    const int bi = b / a.row_div;                              // the image of this row: P / V / G / ids / q2 are per image
+    const int bi = b / (half ? a.div[1] : a.div[0]);           // (wave-uniform) the entry of this row: its image (content
+                                                               // waves), its label group (sentiment waves: ids, q2, P / V / G)
     const float *Pb = (half ? a.P[1] : a.P[0]), *Vb = (half ? a.V[1] : a.V[0]), *Gb = (half ? a.G[1] : a.G[0]);
     if (!gather) {
         Pb += (long long)bi * R * A; Vb += (long long)bi * R * A; Gb += (long long)bi * R * A;
@@ -1133,9 +1136,9 @@ static int rows_scan_gate_launch(const RScanArgs &a, int rows, hipStream_t st) {
     return ISC_OK;
 }
 
-static int rows_scan_gate(const isc_step_plan *p, int row_div, const int *skip, hipStream_t st) {
+static int rows_scan_gate(const isc_step_plan *p, int row_div, int senti_div, const int *skip, hipStream_t st) {
     RScanArgs a = {};
-    a.row_div = row_div > 1 ? row_div : 1; a.skip = skip;
+    a.div[0] = row_div > 1 ? row_div : 1; a.div[1] = senti_div > 1 ? senti_div : 1; a.skip = skip;
     a.P[0] = p->att_p; a.V[0] = p->att_e; a.G[0] = p->gate_Gc; a.q[0] = p->qa; a.w[0] = p->w_alpha_c; a.wb[0] = p->b_alpha_c;
     a.P[1] = p->words_p; a.V[1] = p->words_e; a.G[1] = p->gate_Gs; a.q[1] = p->qw; a.w[1] = p->w_alpha_s; a.wb[1] = p->b_alpha_s;
     a.q2 = p->label_w;
@@ -1176,7 +1179,8 @@ int rows_scan_gate_try(const isc_scan_gate_args *g, int rows, hipStream_t st, in
     if (c.R > g_rows_scan_regions.load() || s.R > RS_NWS * RS_RPW) return 0;
     if (!c.P || !c.V || !c.q || !c.w || !s.P || !s.V || !s.q || !s.w || !g->G[0] || !g->G[1]) return 0;
     RScanArgs a = {};
-    a.row_div = 1;
+    a.div[0] = c.row_div > 1 ? c.row_div : 1;      // (isc_attn_scan_gate_fwd has checked rows % div)
+    a.div[1] = s.row_div > 1 ? s.row_div : 1;
     a.skip = isc_stream_gate_(st);         // (isc_set_stream_gate: a batched search that has ended skips its remaining steps)
     a.P[0] = c.P; a.V[0] = c.V; a.G[0] = g->G[0]; a.q[0] = c.q; a.w[0] = c.w; a.wb[0] = c.w_bias;
     a.P[1] = s.P; a.V[1] = s.V; a.G[1] = g->G[1]; a.q[1] = s.q; a.w[1] = s.w; a.wb[1] = s.w_bias;
@@ -1225,8 +1229,10 @@ extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, 
     const int ld1 = H + E + W, ld2 = E + H;
     const int64_t *src = x->src_row;
     const int row_div = x->row_div > 1 ? x->row_div : 1;
+    // label groups inside an image (isc_rows_ext.senti_div): the sentiment-side tensors hold one entry per group
+    const int senti_div = x->senti_div > 0 ? x->senti_div : row_div;
     const int *skip = x->live_in;
-    if (rows % row_div) return ISC_E_SHAPE;
+    if (x->senti_div < 0 || rows % row_div || row_div % senti_div) return ISC_E_SHAPE;
     {   // att-LSTM over cat[h_lang_prev, fc, xt] (captioner.py:174-175); fc / label / biases are in pre1
         const float *As[3], *Ws[3];
         int lda[3], ldw[3], K[3], ind[3], n = 0;
@@ -1236,7 +1242,7 @@ extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, 
         RLstmArgs::Fin fin = {};
         const isc_rollout_step *f = x->fin_prev;
         if (f) {        // the previous step's greedy finalize rides on this launch (isc_rows_ext.fin_prev)
-            if (!p->tab || row_div != 1 || src || skip || rows > ROWS_FIN_MAX) return ISC_E_SHAPE;
+            if (!p->tab || row_div != 1 || senti_div != 1 || src || skip || rows > ROWS_FIN_MAX) return ISC_E_SHAPE;
             if (f->forced || f->sample_u || f->xt_next) return ISC_E_SHAPE;
             if (!f->part_max || !f->part_sum || !f->part_idx || !f->seq || !f->seq_logprobs || !f->seq_masks ||
                 !f->unfinished || !f->alive || !x->fin_unfinished_out)
@@ -1249,7 +1255,7 @@ extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, 
             fin.unf_in = f->unfinished; fin.unf_out = x->fin_unfinished_out; fin.alive = f->alive;
         }
         RET(rows_lstm(As, lda, Ws, ldw, K, ind, n, rows, H, src, p->c1_prev, p->h1, p->c1, nullptr, nullptr, p->pre1,
-                      p->tab, p->tok, p->tok_stride, row_div, skip, st, f ? &fin : nullptr));
+                      p->tab, p->tok, p->tok_stride, senti_div, skip, st, f ? &fin : nullptr));
     }
     {   // projections of h_att: h2att (content), h2word (sentiment), the gate's h-term
         const float *Ws[3] = {p->W_h2att, p->W_h2word, p->W_gh}, *bs[3] = {p->b_h2att, p->b_h2word, p->b_gh};
@@ -1257,7 +1263,7 @@ extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, 
         const int N[3] = {A, A, A}, ldc[3] = {A, A, A};
         RET(rows_linear3(p->h1, H, H, rows, Ws, bs, Cs, N, ldc, 3, skip, st));
     }
-    RET(rows_scan_gate(p, row_div, skip, st));
+    RET(rows_scan_gate(p, row_div, senti_div, skip, st));
     {   // lang-LSTM over cat[f, h_att] (captioner.py:180-181)
         const float *As[3] = {p->f, p->h1, p->h2_prev}, *Ws[3] = {p->Wih2, p->Wih2 + E, p->Whh2};
         const int lda[3] = {E, H, H}, ldw[3] = {ld2, ld2, H}, K[3] = {E, H, H}, ind[3] = {0, 0, 1};

@@ -32,7 +32,12 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
     if (pair && (p->s != p->v + off_s * E || p->gate_Gc || p->gate_Gs)) return ISC_E_SHAPE;
     // captions per image (isc_step_plan.row_div): the image's tensors hold one entry per image
     const int row_div = p->row_div > 1 ? p->row_div : 1;
-    if (row_div > 1 && (rows % row_div || pair || p->gate_Gc || p->gate_Gs)) return ISC_E_SHAPE;
+    // label groups inside an image (isc_step_plan.senti_div): the sentiment-side tensors hold one entry per group
+    const int senti_div = p->senti_div > 0 ? p->senti_div : row_div;
+    if (p->senti_div < 0 || rows % row_div || row_div % senti_div || (row_div > 1 && pair)) return ISC_E_SHAPE;
+    // a grouped step's rows take the hoisted att-LSTM term of their image / label group: without pre1 the divisors index
+    // nothing (isc_lstm_fwd's own rule for pre_div, checked here with the other divisor rules, in front of the first launch)
+    if (row_div > 1 && !p->pre1) return ISC_E_SHAPE;
     const int ld1 = H + E + W, ld2 = E + H;
     // f16 planes of the recurrent state (split-f16 path): all eight or none
     const bool planes = p->h1_prev_hi && p->h1_prev_lo && p->h2_prev_hi && p->h2_prev_lo && p->h1_hi && p->h1_lo &&
@@ -57,7 +62,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
         l.h_hi = PL(p->h1_hi); l.h_lo = PL(p->h1_lo);
         l.c_prev = p->c1_prev; l.h_out = p->h1; l.c_out = p->c1; l.gates_out = p->g1;
         l.pre = p->pre1; l.tab = p->tab; l.tab_ids = p->tok; l.tab_ids_stride = p->tok_stride;
-        l.pre_div = p->pre_rows ? 1 : row_div;
+        l.pre_div = p->pre_rows ? 1 : senti_div;
         l.splitk_ws = p->splitk_ws; l.splitk_ws_floats = p->splitk_ws_floats;
         RET(isc_lstm_fwd(&l, stream));
     }
@@ -96,7 +101,7 @@ extern "C" int isc_step_fwd(const isc_step_plan *p, void *stream) {
             x.alpha_ld = p->alpha_s_ld;
             x.out_hi = PW(p->s_hi); x.out_lo = PW(p->s_lo);
             x.row_ids = p->words_ids; x.row_ids_ld = p->words_ids_ld;
-            x.rows = rows_s; x.row_div = row_div;
+            x.rows = rows_s; x.row_div = senti_div;
         }
         if (fused_gate) {
             isc_scan_gate_args g = {};

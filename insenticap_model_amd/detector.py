@@ -643,16 +643,50 @@ class Detector(nn.Module):
                                             decoding_constraint, self.max_seq_len)
         return captions, self.senti_detector.names(senti_label)
 
+    def sample_sentiments(self, fc_feats, att_feats, sentis_tensor=None, sentiments=None, beam_size=3,
+                          decoding_constraint=1):
+        """One image captioned under several sentiments at once: `sentiments` is a list of category names (default: all of
+        the detector's sentiment_categories, in their order); the searches share the image's region tensors
+        (Captioner.sample_sentiments).  The sentiment words are `sentis_tensor` or, when None, derived from the image's
+        detected concepts as in `sample`; they are the image's and serve every sentiment.  Returns
+        ({sentiment: captions}, detected) - `detected` is the image's own detected sentiment, as `sample` returns it.
+        An unknown or repeated name, or an empty list, is a ValueError before anything touches the device."""
+        cats = list(self.senti_detector.sentiment_categories)
+        names = cats if sentiments is None else list(sentiments)
+        if isinstance(sentiments, str) or not names:
+            raise ValueError('Detector.sample_sentiments: sentiments must be a non-empty list of category names out of %r, '
+                             'got %r' % (cats, sentiments))
+        for s in names:
+            if s not in cats:
+                raise ValueError('Detector.sample_sentiments: %r is not one of the sentiment categories %r' % (s, cats))
+        if len(set(names)) != len(names):
+            raise ValueError('Detector.sample_sentiments: a sentiment is named twice in %r' % (names,))
+        self.eval()
+        if sentis_tensor is None:
+            if self.__dict__.get('concept_detector') is None or self.__dict__.get('senti_table') is None:
+                raise ValueError('Detector.sample_sentiments: sentis_tensor=None needs set_concept_detector with a '
+                                 'SentimentWordTable')
+            sentis_tensor = self.tag(fc_feats.reshape(1, -1))[1]
+        att_feats = att_feats.unsqueeze(0)
+        detected, _, _ = self.senti_detector.sample_device(self._detector_input(att_feats), self.senti_threshold)
+        labels = ops.upload([[cats.index(s) for s in names]], torch.int64, fc_feats.device)       # [1, S]
+        captions, _, _ = self.captioner.sample_sentiments(fc_feats.reshape(1, -1), att_feats, sentis_tensor.reshape(1, -1),
+                                                          labels, beam_size, decoding_constraint, self.max_seq_len,
+                                                          _labels_known=True)
+        return dict(zip(names, captions[0])), self.senti_detector.names(detected)
+
     def set_encoder(self, enc):
         """The image encoder (encoder.Encoder) behind sample_image; kept outside the module tree, as the concept detector
         is: the encoder is frozen and has its own checkpoint."""
         self.__dict__['encoder'] = enc
         return self
 
-    def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14):
+    def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14, sentiments=None):
         """One image from its pixels: uint8 [H, W, 3] / [H, W] as decoded (the normalisation is fused into the encoder's
         first kernel) or a `preprocess`ed fp32 tensor [3, H, W] -> encoder -> sample(fc, att).  The sentiment words come
-        from the concept detector (set_concept_detector with a table); no host read between the encoder and the search."""
+        from the concept detector (set_concept_detector with a table); no host read between the encoder and the search.
+        `sentiments` (a list of category names): the image is captioned under each of them instead of under its detected
+        sentiment - `sample_sentiments(fc, att, None, sentiments)`, which returns ({sentiment: captions}, detected)."""
         enc = self.__dict__.get('encoder')
         if enc is None:
             raise ValueError('Detector.sample_image needs set_encoder')
@@ -661,4 +695,6 @@ class Detector(nn.Module):
                 fc, att = enc(image.to(enc.resnet.conv1.weight.device), att_size)
             else:
                 fc, att = enc.encode_uint8(image, att_size)
+        if sentiments is not None:
+            return self.sample_sentiments(fc, att, None, sentiments, beam_size, decoding_constraint)
         return self.sample(fc, att, None, beam_size, decoding_constraint)
