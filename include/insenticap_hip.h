@@ -977,6 +977,32 @@ int isc_lm_dev_score(const int64_t *hyp, int64_t N, int T, const int64_t *labels
                      int unk_as_word, int64_t sos_id, int64_t eos_id, double *score, int32_t *n_scored, int32_t *n_oov,
                      double *tok_logp, void *stream);
 
+/* Sentiment-word reward (self_critical/utils.py:154-166): every position of a caption row is paid the weight of its word
+ * where the word belongs to the lexicon of the row's sentiment label; the words that were paid are marked, and
+ * isc_sw_decay later multiplies the marked words' weights (models/decoder.py:174-176).  All pointers are device memory.
+ *   tok [N, T] int64, contiguous; every position is looked at (also those behind <EOS>: the criterion masks).  An id is
+ *     compared as a 64-bit integer before it becomes an index: an id outside [0, V) - negative, or >= 2^32 with low bits
+ *     that are a valid index - reads nothing and is paid 0.
+ *   labels [N] int64.  weights [n_labels, V] float64; state [n_labels, V] uint8: 0 = not in the lexicon, 1 = in it, 2 = in
+ *     it and used since the last decay.  Membership is the state, never "weight != 0".
+ *   w = weights[label, tok] where state[label, tok] != 0, else 0.  reward64 [N, T] float64 or NULL gets w.  reward_io
+ *     [N, T] float32 or NULL: accumulate == 0 -> (float)w (`flag` is not applied); accumulate != 0 -> reward_io +
+ *     (float)flag * (float)w, the product rounded to float32 before the addition, never contracted: the bits of torch's
+ *     `rewards + flag * sw` on float32 tensors.  row_hits [N] int32 or NULL: the row's number of paid positions.
+ *   mark != 0: a paid position stores 2 into state[label, tok] - a plain store of a constant; many lanes and rows may
+ *     store it to the same byte.
+ *   A label outside [0, n_labels): NaN in the row of reward_io and reward64, -1 in row_hits, no table is read, nothing is
+ *     marked (the convention of isc_lm_dev_score).
+ * One wave64 per row, four rows per workgroup, lanes stride over the positions (any T >= 1); row_hits from ballots.  No
+ * LDS, no atomics, no workspace, no host read; one launch: capturable.
+ * N < 1, T < 1, n_labels < 1, V < 1: ISC_E_SHAPE, nothing is launched or written. */
+int isc_sw_reward(const int64_t *tok, int64_t N, int T, const int64_t *labels, int n_labels, int V, const double *weights,
+                  uint8_t *state, double flag, float *reward_io, int accumulate, double *reward64, int32_t *row_hits,
+                  int mark, void *stream);
+/* Where state[i] == 2: weights[i] *= factor in float64 (the bits of Python's `w *= factor`) and state[i] = 1; i < n (=
+ * n_labels * V).  n < 1: ISC_E_SHAPE, nothing is launched. */
+int isc_sw_decay(double *weights, uint8_t *state, int64_t n, double factor, void *stream);
+
 /* Log-softmax backward with the criteria's gradient handed over SPARSE: XECriterion (captioner.py:427-440) and the
  * REINFORCE gather (captioner.py:336) touch one column per (caption, step) row, so their d log-prob is `coef[m]` at
  * column `ids[m]` - up to ISC_SPARSE_MAX such (ids, coef) pairs (HOST arrays of device pointers to [M] vectors, rows

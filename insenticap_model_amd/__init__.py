@@ -21,8 +21,9 @@ from .rewards import RewardCriterion, get_ciderd_scorer, get_cls_reward, get_sel
 from .rewards import get_group_self_critical_reward, group_self_critical_scores  # noqa: F401,E402
 from .rewards import Bleu, DeviceBleu, get_bleu_scorer  # noqa: F401,E402
 from .rewards import NgramLM, NgramLMSet, DeviceNgramLMSet, get_lm_reward, get_lm_reward_device, lm_perplexity  # noqa: F401,E402
+from .rewards import SentimentWordWeights, get_senti_words_reward, senti_word_stats  # noqa: F401,E402
 
-__all__ = ['Captioner', 'XECriterion', 'Detector', 'FusedClampAdam', 'clip_gradient', 'RewardCriterion',
+__all__ = ['SentimentWordWeights', 'get_senti_words_reward', 'senti_word_stats','Captioner', 'XECriterion', 'Detector', 'FusedClampAdam', 'clip_gradient', 'RewardCriterion',
            'get_ciderd_scorer', 'get_self_critical_reward', 'get_cls_reward', 'get_group_self_critical_reward',
            'group_self_critical_scores', 'Bleu', 'DeviceBleu', 'get_bleu_scorer', 'ConceptDetector', 'MultiLabelClsLoss',
            'SentimentWordTable', 'tag_concepts', 'concept_train_step', 'NgramLM', 'NgramLMSet', 'DeviceNgramLMSet',

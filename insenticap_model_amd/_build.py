@@ -11,7 +11,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libinsenticap_hip.so')
 SOURCES = ['gemm_f32.hip', 'attention.hip', 'pointwise.hip', 'backward.hip', 'step.hip', 'rows.hip', 'sent_cls.hip',
-           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'lm_dev.hip', 'concept.hip', 'encoder.hip']
+           'senti_det.hip', 'cider_dev.hip', 'bleu_dev.hip', 'lm_dev.hip', 'sw_reward.hip', 'concept.hip',
+           'encoder.hip']
 CIDER_KEY_H = os.path.join(CSRC, 'cider_key.h')      # the n-gram key: read by cider_dev.hip, bleu_dev.hip AND cider.cpp
 LM_SLOT_H = os.path.join(CSRC, 'lm_slot.h')          # the language-model slot: read by lm_dev.hip AND lm.cpp
 FLT_KEY_H = os.path.join(CSRC, 'flt_key.h')          # the filtered sampling's rank key: pointwise.hip AND backward.hip

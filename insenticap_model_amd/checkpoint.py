@@ -34,10 +34,22 @@ def save_rl_checkpoint(directory, epoch, detector, settings, idx2word, max_seq_l
     chk = {'epoch': epoch, 'model': detector.state_dict(), 'settings': settings, 'idx2word': idx2word,
            'max_seq_len': max_seq_len, 'sentiment_categories': sentiment_categories,
            'dataset_name': dataset_name, 'corpus_type': corpus_type}
+    words = getattr(detector, 'sentiment_words', None)
+    if getattr(detector, 'senti_words_flag', 0) != 0 and isinstance(words, dict):
+        # the sentiment-word reward is on: its (decayed) weights, so that a resumed run goes on with them; otherwise the
+        # file is key for key the reference's
+        chk['sentiment_words'] = {int(lab): {int(w): float(v) for w, v in ws.items()} for lab, ws in words.items()}
     os.makedirs(directory, exist_ok=True)
     path = os.path.join(directory, 'model_%d_%s.pth' % (epoch, time.strftime('%m%d-%H%M')))
     torch.save(chk, path)
     return path
+
+
+def load_sentiment_words(path):
+    """The lexicon weights an RL checkpoint carries ({label id: {word id: float}}: written while the sentiment-word
+    reward was on) for Detector.set_sentiment_words, or None where the file has none."""
+    chk = torch.load(path, map_location=lambda s, l: s, weights_only=False)
+    return chk.get('sentiment_words')
 
 
 def _check_meta(chk, expected):

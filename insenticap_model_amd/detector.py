@@ -24,9 +24,10 @@ from .helper_nets import SentenceSentimentClassifier, SentimentDetector
 from .optim import clip_gradient
 from .train import run_on_side_stream
 from .ops import OutOfDomain
-from .rewards import (CIDER_DEV_MAX_T, LM_DEV_MAX_T, Bleu, NgramLM, NgramLMSet, RewardCriterion, get_bleu_scorer,
-                      get_ciderd_scorer, get_cls_reward, get_lm_reward, get_lm_reward_device, get_self_critical_reward,
-                      get_self_critical_reward_device, group_self_critical_scores, lm_perplexity)
+from .rewards import (CIDER_DEV_MAX_T, LM_DEV_MAX_T, Bleu, NgramLM, NgramLMSet, RewardCriterion, SentimentWordWeights,
+                      get_bleu_scorer, get_ciderd_scorer, get_cls_reward, get_lm_reward, get_lm_reward_device,
+                      get_self_critical_reward, get_self_critical_reward_device, get_senti_words_reward,
+                      group_self_critical_scores, lm_perplexity)
 
 
 def _helper_input(feats):
@@ -101,6 +102,29 @@ class Detector(nn.Module):
         self.lm_flag = 0.0
         self.lm_reward_form = 'sign'
         self._lms_dev, self._lms_dev_warned = None, False
+        # The reference's dormant sentiment-word reward (decoder.py:120-126,174-176, utils.py:154-166), opt-in: with
+        # senti_words_flag != 0 (the reference's commented value: 0.05) every iteration - 'fact' and 'senti', training and
+        # evaluation, n = 1, grouped, constrained, filtered and graph-served - adds senti_words_flag * senti_words_reward
+        # to `rewards` after the other terms and logs 'senti_words_reward' (a sum); at the end of the forward() call the
+        # weights of the words that were paid are multiplied by senti_words_decay (1.0: no decay) and the caller's dict
+        # (set_sentiment_words) is updated in place.  senti_words_form 'device': isc_sw_reward on the roll-out's token
+        # matrix, the lexicon a rewards.SentimentWordWeights built lazily from the dict; 'host': the reference's function
+        # on a host copy of the tokens - the yardstick, eager sequence only.  Not built under a process group.
+        self.senti_words_flag = 0.0
+        self.senti_words_decay = 0.9
+        self.senti_words_form = 'device'
+        self._sw_table = None
+
+    def _device_sw(self, device):
+        """The device table of `sentiment_words` (rewards.SentimentWordWeights): built on first use, rebuilt when
+        set_sentiment_words replaced the dict object or the module moved."""
+        words = self.__dict__.get('sentiment_words')
+        twin = self._sw_table
+        if twin is None or twin[0] is not words or twin[1] != device:
+            n_labels = len(self.senti_detector.sentiment_categories)
+            twin = self._sw_table = (words, device, SentimentWordWeights.from_dict(
+                words, self.captioner.vocab_size, n_labels, device))
+        return twin[2]
 
     def _device_ciderd(self, device, T):
         """The device twin of `ciderd_scorer` for rows of T tokens, or None: the flag is off, or this vocabulary / length
@@ -334,6 +358,18 @@ class Detector(nn.Module):
         if n_rl > 1 and dist_on:
             raise ValueError('rl_samples_per_image=%d is not built for data-parallel training (a process group is '
                              'active): set it to 1' % n_rl)
+        sw_on = self.senti_words_flag != 0
+        sw_host = sw_on and self.senti_words_form == 'host'
+        if sw_on and self.senti_words_form not in ('device', 'host'):
+            raise ValueError("senti_words_form is 'device' or 'host', got %r" % (self.senti_words_form,))
+        if sw_on and not isinstance(self.__dict__.get('sentiment_words'), dict):
+            raise ValueError('senti_words_flag != 0 needs set_sentiment_words with the lexicon '
+                             '{label id: {word id: weight}}')
+        if sw_on and dist_on:
+            raise ValueError('senti_words_flag != 0 is not built for data-parallel training (a process group is active): '
+                             'the marks of the used words would have to be reduced across the ranks first')
+        sw_table = self._device_sw(device) if sw_on and not sw_host else None
+        accur_ws = defaultdict(set)                       # ('host' form: the words paid in this call, decoder.py:63)
         seq2seq_iter = iter(data[1]) if training else None
         caption_iter = iter(data[0])
         n_iter = min(self.MAX_BATCHES_PER_CALL, len(data[0]))
@@ -379,7 +415,7 @@ class Detector(nn.Module):
                 an iteration whose roll-outs left the split-f16 operand domain (OutOfDomain is raised at the iteration's
                 own synchronisation point, before anything is updated)."""
                 if (training and self.train_graphs and not rl_kw and not rs_kw and n_rl == 1 and not lm_on
-                        and device.type == 'cuda'
+                        and not sw_host and device.type == 'cuda'
                         and ops.TIMER.arm_step is None and ops.graphs_allowed_here() and not exact):
                     # the same iteration from HIP graphs (train_graph.RLTrainGraph): same calls in the same order
                     from .train_graph import RLTrainGraph
@@ -454,7 +490,7 @@ class Detector(nn.Module):
                 host_tokens = dev_cider is None and not (self.device_cider and data_type != 'fact')
                 # (the LM reward: on the device with device_cider where the rows fit, else from host tokens)
                 dev_lms = self._device_lms(device, sample_captions.shape[1]) if lm_on else None
-                host_tokens = host_tokens or (lm_on and dev_lms is None)
+                host_tokens = host_tokens or (lm_on and dev_lms is None) or sw_host
                 if dev_cider is not None:
                     ref_pack = dev_cider.pack_refs([ground_truth[fn] for fn in fns], keys=list(fns))
                 if host_tokens:
@@ -534,7 +570,8 @@ class Detector(nn.Module):
                     put('sample_score', stats4[0])
                     put('fact_reward', stats4[1])            # the mean advantage: 0 up to rounding by construction
                     put('cls_reward', stats4[2])
-                    put('all_rewards', stats4[3])
+                    if not sw_on:                            # (else: from the final tensor, below)
+                        put('all_rewards', stats4[3])
                 elif dev_cider is not None:
                     fact_reward = get_self_critical_reward_device(sample_captions, greedy_captions, ref_pack, dev_cider)
                     put('fact_reward', share(fact_reward[:, 0].mean(), w_rows))
@@ -559,6 +596,24 @@ class Detector(nn.Module):
                             lm_reward = ops.upload(lm_reward.astype('float32'), torch.float32, device)
                         put('lm_reward', lm_reward[:, 0].sum())      # (a sum, as decoder.py:118 logs it)
                         rewards = rewards + self.lm_flag * lm_reward
+                if sw_on:
+                    # the sentiment-word reward of the sampled rows (decoder.py:120-126), after the other terms; one torch
+                    # expression on the device for both forms: the same bits
+                    sw_labels = senti_labels.repeat_interleave(n_rl) if grouped else senti_labels
+                    if sw_host:
+                        sw_reward, accur_w = get_senti_words_reward(host_sample.numpy(), sw_labels.cpu().numpy(),
+                                                                    self.sentiment_words)
+                        for senti, words in accur_w.items():
+                            accur_ws[senti].update(words)
+                        sw_reward = ops.upload(torch.from_numpy(sw_reward).float(), torch.float32, device)
+                    else:
+                        sw_reward = sw_table.reward(sample_captions.contiguous(),
+                                                    sw_labels.to(torch.int64).contiguous())
+                    put('senti_words_reward', sw_reward.sum())       # (a sum, as decoder.py:124 logs it)
+                    rewards = rewards + self.senti_words_flag * sw_reward
+                    if grouped:                              # (isc_group_reward's mean was taken before this term)
+                        put('all_rewards', rewards.mean(-1).mean(-1))
+                if not grouped:
                     put('all_rewards', share(rewards.mean(-1).mean(-1), w_rows))
                 cap_loss = share(self.cap_rl_crit(sample_logprobs, seq_masks, rewards), w_rl)
                 put('cap_loss', cap_loss)
@@ -592,6 +647,17 @@ class Detector(nn.Module):
                     run_iteration(True, lambda k, v: stats_it.append((k, v)))
             for k, v in stats_it:
                 add(k, v)
+
+        if sw_on:
+            # the words this call paid are paid less from now on (decoder.py:174-176: no `training` condition there)
+            if sw_host:
+                for senti, words in accur_ws.items():
+                    for w in words:
+                        self.sentiment_words[senti][w] *= self.senti_words_decay
+                self._sw_table = None                    # (a device table of this dict is stale now)
+            else:
+                sw_table.decay(self.senti_words_decay)
+                sw_table.update_dict(self.sentiment_words)       # (one small copy; the states are back to 1)
 
         if dist_on and sums:                             # global statistics: one small all-reduce per call
             keys = sorted(sums)                          # (same keys on every rank: data_type / training were checked)

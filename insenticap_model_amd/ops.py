@@ -1692,6 +1692,40 @@ def lm_dev_score(hyps, labels, slots, lm_off, lm_capacity, lm_order, vocab_size,
     return out, n_scored, n_oov
 
 
+def sw_reward(tok, labels, weights, state, flag=0.0, reward_io=None, accumulate=False, reward64=None, row_hits=None,
+              mark=True):
+    """isc_sw_reward: the sentiment-word reward of the rows `tok` int64 [N, T] on the device, row r under the lexicon of
+    labels[r]: weights float64 [n_labels, V], state uint8 [n_labels, V] (rewards.SentimentWordWeights holds them).
+    `reward_io` float32 [N, T]: written ((float)w) or, `accumulate`, added to (+ (float)flag * (float)w); `reward64`
+    float64 [N, T] and `row_hits` int32 [N]: filled where given.  `mark`: the words that were paid get state 2.  Nothing is
+    allocated and nothing is returned: every output is the caller's."""
+    require_device(tok, labels, weights, state, reward_io, reward64, row_hits)
+    assert tok.dtype == torch.int64 and tok.dim() == 2 and tok.is_contiguous()
+    N, T = tok.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == N
+    assert weights.dtype == torch.float64 and weights.dim() == 2 and weights.is_contiguous()
+    assert state.dtype == torch.uint8 and state.shape == weights.shape and state.is_contiguous()
+    n_labels, V = weights.shape
+    if reward_io is not None:
+        assert reward_io.dtype == torch.float32 and reward_io.is_contiguous() and tuple(reward_io.shape) == (N, T)
+    if reward64 is not None:
+        assert reward64.dtype == torch.float64 and reward64.is_contiguous() and tuple(reward64.shape) == (N, T)
+    if row_hits is not None:
+        assert row_hits.dtype == torch.int32 and row_hits.is_contiguous() and row_hits.numel() == N
+    check(_lib.load().isc_sw_reward(tok.data_ptr(), N, T, labels.data_ptr(), n_labels, V, weights.data_ptr(),
+                                    state.data_ptr(), float(flag), ptr(reward_io), int(bool(accumulate)), ptr(reward64),
+                                    ptr(row_hits), int(bool(mark)), stream()), 'isc_sw_reward')
+
+
+def sw_decay(weights, state, factor):
+    """isc_sw_decay: weights *= factor (float64) where state == 2, and those states back to 1, in place."""
+    require_device(weights, state)
+    assert weights.dtype == torch.float64 and weights.is_contiguous()
+    assert state.dtype == torch.uint8 and state.shape == weights.shape and state.is_contiguous()
+    check(_lib.load().isc_sw_decay(weights.data_ptr(), state.data_ptr(), weights.numel(), float(factor), stream()),
+          'isc_sw_decay')
+
+
 def lstm_bwd(dh, dh2, dc_next, gates, c_prev, c, dgates, dc_prev, dgates_sum=None):
     lib = _lib.load()
     M, H = c.shape

@@ -14,6 +14,8 @@
 * `read_arpa` / `NgramLM` / `NgramLMSet` / `DeviceNgramLMSet`, `get_lm_reward` / `get_lm_reward_device`, `lm_perplexity` -
   the per-sentiment back-off n-gram language models: the reference's dormant LM reward (utils.py:86-100) and its `ppl`
   metric (eval_ppl.py), on the host (isc_lm_score) and on the device (isc_lm_dev_score); opt-in (Detector.lm_flag).
+* `get_senti_words_reward` / `SentimentWordWeights` / `senti_word_stats` - the reference's dormant sentiment-word reward
+  (utils.py:154-166) on the host and on the device (isc_sw_reward, isc_sw_decay); opt-in (Detector.senti_words_flag).
 """
 import ctypes as C
 import math
@@ -966,4 +968,137 @@ def lm_perplexity(scores, n_scored, n_oov, labels, n_labels=None):
         out[lab] = {'ppl': 10.0 ** (-total / count) if count > 0 else float('nan'),
                     'ppl1': 10.0 ** (-total / (count - sent)) if count - sent > 0 else float('nan'),
                     'logprob': total, 'sentences': sent, 'words': count - sent, 'oovs': oov}
+    return out
+
+
+# ---- the sentiment-word reward (utils.py:154-166) ---------------------------------------------------------------------
+def get_senti_words_reward(sample_captions, senti_labels, sentiment_words):
+    """utils.py:154-166 as it stands: sample_captions int [B, T] (tensor or ndarray), senti_labels [B], sentiment_words
+    {label id: {word id: weight}} -> (float64 ndarray [B, T], accur_w).  Position (i, j) is paid the weight of its word
+    where the word is in the lexicon of row i's label - EVERY position, also those behind <EOS> and <PAD> ids the lexicon
+    happens to hold: nothing is masked here (RewardCriterion masks).  accur_w: defaultdict(set) {label id: the words that
+    were paid}.  A label without an entry raises KeyError, as the reference does."""
+    from collections import defaultdict
+    if torch.is_tensor(sample_captions):
+        sample_captions = sample_captions.cpu().numpy()
+    sample_captions = np.asarray(sample_captions)
+    rewards = np.zeros(sample_captions.shape, dtype=float)
+    accur_w = defaultdict(set)
+    for i in range(sample_captions.shape[0]):
+        senti_id = int(senti_labels[i])
+        words = sentiment_words[senti_id]
+        for j, w in enumerate(sample_captions[i]):
+            if w in words:
+                rewards[i, j] = words[w]
+                accur_w[senti_id].add(w)
+    return rewards, accur_w
+
+
+class SentimentWordWeights:
+    """The lexicon of the sentiment-word reward as a dense table: `weights` float64 [n_labels, V] and `state` uint8
+    [n_labels, V] - 0 = not in the lexicon, 1 = in it, 2 = in it and used since the last decay.  Membership is the state,
+    never "weight != 0": a weight may be 0.0 or negative.  On a device the reward and the decay are isc_sw_reward /
+    isc_sw_decay; a table in host memory serves from_dict / to_dict and the host statement of the decay."""
+
+    def __init__(self, weights, state):
+        assert weights.dtype == torch.float64 and weights.dim() == 2 and state.dtype == torch.uint8
+        assert state.shape == weights.shape and weights.device == state.device
+        self.weights, self.state = weights.contiguous(), state.contiguous()
+
+    n_labels = property(lambda self: self.weights.shape[0])
+    vocab_size = property(lambda self: self.weights.shape[1])
+    device = property(lambda self: self.weights.device)
+
+    @classmethod
+    def from_dict(cls, sentiment_words, vocab_size, n_labels, device=None):
+        """{label id: {word id: weight}} -> the table.  A label of [0, n_labels) without an entry is an EMPTY lexicon here
+        (the host function raises KeyError for it; the kernel pays such rows nothing); a label outside [0, n_labels) or a
+        word id outside [0, vocab_size) raises ValueError."""
+        V, n_labels = int(vocab_size), int(n_labels)
+        if V < 1 or n_labels < 1:
+            raise ValueError('SentimentWordWeights: vocab_size and n_labels must be >= 1')
+        weights = np.zeros((n_labels, V), dtype=np.float64)
+        state = np.zeros((n_labels, V), dtype=np.uint8)
+        for lab, words in sentiment_words.items():
+            if not 0 <= int(lab) < n_labels:
+                raise ValueError('SentimentWordWeights: label %r is outside [0, %d)' % (lab, n_labels))
+            for w, weight in words.items():
+                if not 0 <= int(w) < V:
+                    raise ValueError('SentimentWordWeights: word id %r of label %r is outside [0, %d)' % (w, lab, V))
+                weights[int(lab), int(w)] = float(weight)
+                state[int(lab), int(w)] = 1
+        table = cls(torch.from_numpy(weights), torch.from_numpy(state))
+        return table if device is None else table.to(device)
+
+    def to(self, device):
+        from . import ops
+        device = torch.device(device)
+        if device.type == 'cuda':                          # (through pinned memory: the host does not wait for the queue)
+            return SentimentWordWeights(ops.upload(self.weights, torch.float64, device),
+                                        ops.upload(self.state, torch.uint8, device))
+        return SentimentWordWeights(self.weights.to(device), self.state.to(device))
+
+    def to_dict(self):
+        """{label id: {word id: Python float}} over every label of the table, the word ids ascending."""
+        w, s = self.weights.cpu().numpy(), self.state.cpu().numpy()
+        return {lab: {int(i): float(w[lab, i]) for i in np.nonzero(s[lab])[0]} for lab in range(self.n_labels)}
+
+    def update_dict(self, sentiment_words):
+        """Writes the table's weights into the entries `sentiment_words` already has, in place (one copy of `weights`)."""
+        w = self.weights.cpu().numpy()
+        for lab, words in sentiment_words.items():
+            for k in words:
+                words[k] = float(w[int(lab), int(k)])
+        return sentiment_words
+
+    def reward(self, tok, labels, flag=0.0, reward_io=None, accumulate=False, reward64=None, row_hits=None, mark=True):
+        """isc_sw_reward on device rows tok int64 [N, T] / labels int64 [N] -> reward_io float32 [N, T] (allocated when
+        None and not accumulating: the reward itself, (float)w).  See ops.sw_reward."""
+        from . import ops
+        if reward_io is None and not accumulate:
+            reward_io = torch.empty(tok.shape, dtype=torch.float32, device=tok.device)
+        ops.sw_reward(tok, labels, self.weights, self.state, flag, reward_io, accumulate, reward64, row_hits, mark)
+        return reward_io
+
+    def mark(self, accur_w):
+        """The host statement of the marks: accur_w {label id: words} as get_senti_words_reward returns it."""
+        if self.weights.is_cuda:
+            raise ValueError('SentimentWordWeights.mark is the host statement; on the device isc_sw_reward marks')
+        s = self.state.numpy()
+        for lab, words in accur_w.items():
+            for w in words:
+                if s[int(lab), int(w)]:
+                    s[int(lab), int(w)] = 2
+
+    def decay(self, factor):
+        """weights *= factor where state == 2 and those states back to 1: isc_sw_decay on the device, numpy in host memory
+        (float64 either way: the bits of the reference's `w *= 0.9`)."""
+        if self.weights.is_cuda:
+            from . import ops
+            ops.sw_decay(self.weights, self.state, factor)
+            return self
+        w, s = self.weights.numpy(), self.state.numpy()
+        used = s == 2
+        w[used] = w[used] * float(factor)
+        s[used] = 1
+        return self
+
+
+def senti_word_stats(captions, labels, weights):
+    """How far the captions use the lexicon: captions int64 [N, T] and labels int64 [N] on the device of `weights` (a
+    SentimentWordWeights) -> {label: {'captions', 'with_word' (captions with at least one lexicon word), 'hits' (positions
+    paid), 'distinct' (lexicon words used)}} over the table's labels.  isc_sw_reward on a scratch copy of the state, no
+    reward written; rows of a label outside the table are left out."""
+    from . import ops
+    captions = captions.to(torch.int64).contiguous()
+    labels = labels.to(torch.int64).contiguous()
+    state = (weights.state != 0).to(torch.uint8)
+    hits = torch.empty(captions.shape[0], dtype=torch.int32, device=captions.device)
+    ops.sw_reward(captions, labels, weights.weights, state, 0.0, None, False, None, hits, True)
+    hits, labels, distinct = hits.cpu().numpy(), labels.cpu().numpy(), (state == 2).sum(dim=1).cpu().numpy()
+    out = {}
+    for lab in range(weights.n_labels):
+        h = hits[labels == lab]
+        out[lab] = {'captions': int(h.size), 'with_word': int((h > 0).sum()), 'hits': int(h.sum()),
+                    'distinct': int(distinct[lab])}
     return out

@@ -425,6 +425,7 @@ class _RLGeometry(_Geometry):
         self.reward = None          # static [B, T] reward the REINFORCE loss reads
         self.late = {}              # inputs handed over as callables, still to be produced this iteration
         self.stats = None           # static [7] device statistics of the iteration
+        self.sw64 = self.sw_sum = None      # the sentiment-word term of the iteration (float64) and its logged sum
 
 
 class RLTrainGraph(XETrainGraph):
@@ -662,12 +663,31 @@ class RLTrainGraph(XETrainGraph):
         if not fact:
             self.stream.wait_stream(self.side)
             geo.reward.copy_(0 + det.cls_flag * geo.cls)     # (`fact_reward = 0` there: the same expression as the eager path's)
+            self._sw_reward(geo, roll)
             return
         greedy = self_critical_scores(geo.host[1].numpy(), fns, ground_truth, det.ciderd_scorer)
         fact0 = ops.upload((sampled - greedy).astype('float32'), torch.float32, self.device)     # (utils.py:56-83: one per row)
         geo.fact0.copy_(fact0)
         self.stream.wait_stream(self.side)
         geo.reward.copy_(fact0.unsqueeze(1) + det.cls_flag * geo.cls)
+        self._sw_reward(geo, roll)
+
+    def _sw_reward(self, geo, roll):
+        """Detector.senti_words_flag != 0: geo.reward += flag * the sentiment-word reward of the sampled rows - one eager
+        launch (isc_sw_reward, accumulating: the bits of torch's `rewards + flag * sw`) behind the copy above, on the same
+        stream, from the roll-out's token buffer and the staged labels; the words that are paid are marked in the
+        detector's device table.  geo.sw_sum: the logged sum of the float32 term."""
+        det = self.det
+        geo.sw_sum = None
+        if det.senti_words_flag == 0:
+            return
+        table = det._device_sw(self.device)
+        seq = roll[0].contiguous()
+        if geo.sw64 is None:
+            geo.sw64 = torch.empty(seq.shape, dtype=torch.float64, device=self.device)
+        labels = geo.inputs['labels'].to(torch.int64).contiguous()       # (the staged buffer itself where it is int64)
+        table.reward(seq, labels, det.senti_words_flag, geo.reward, accumulate=True, reward64=geo.sw64)
+        geo.sw_sum = geo.sw64.float().sum()
 
     def _fork_fwd(self, geo, roll, lengths, s_lengths):
         """self.xe_stream may start g_fwd: it reads the staged inputs and the weights only - not the roll-outs - so it runs
@@ -872,6 +892,8 @@ class RLTrainGraph(XETrainGraph):
                 out = dict(zip(self.KEYS, stats.clone().unbind(0)))
                 if lengths is None:                  # ('senti': no fact_reward, no xe_loss - decoder.py:120-158)
                     out = {k: v for k, v in out.items() if k not in ('fact_reward', 'xe_loss')}
+                if geo.sw_sum is not None:           # (Detector.senti_words_flag != 0: the term's logged sum)
+                    out['senti_words_reward'] = geo.sw_sum
         except ops.OutOfDomain:
             caller.wait_stream(self.stream)          # the caller redoes the iteration on ITS stream: behind what was queued
             self.cap.cpt_feats = self.cap.fc_feats = self.cap.s2s_cpt_feats = None
