@@ -448,6 +448,40 @@ int isc_beam_topk(const float *logits, int64_t ld_logits, const float *part_max,
                   const int64_t *last_word, int64_t pad_id, int64_t sos_id, int64_t unk_id,
                   int mask_special, int decoding_constraint, float *top_val, int64_t *top_idx,
                   void *stream);
+/* isc_beam_topk with a per-row list of further banned ids (isc_beam_ngram_ban's output): row r also masks
+ * ban_ids[r * ban_ld + 0 .. min(ban_cnt[r], 256)) to -inf - for the top-`beam` only, the log-softmax normaliser stays
+ * that of the whole row.  Both kernels of isc_beam_topk take the list (the tile-selecting one admits ban_cnt[r] more
+ * tiles).  Duplicates and ids outside [0, V) are harmless.  ban_ids / ban_cnt NULL -> ISC_E_NULL, ban_ld < 1 ->
+ * ISC_E_SHAPE, V <= 4 + beam (the masks could leave fewer than `beam` words) is the caller's to exclude. */
+int isc_beam_topk_banned(const float *logits, int64_t ld_logits, const float *part_max,
+                         const float *part_sum, int n_tile, int rows, int V, int beam,
+                         const int64_t *last_word, int64_t pad_id, int64_t sos_id, int64_t unk_id,
+                         int mask_special, int decoding_constraint, const int64_t *ban_ids, const int32_t *ban_cnt,
+                         int64_t ban_ld, float *top_val, int64_t *top_idx, void *stream);
+
+/* Ban lists of a beam step (no reference counterpart: its only token rule is decoding_constraint, captioner.py:394-399):
+ * no n-gram twice in a caption, no <EOS> before min_len words.  Row r holds a candidate with the generated words
+ * w = words[r, 0 .. L), L = min(len[r], t) (a live candidate has L == t at step t; <SOS> is not among them).  With
+ * n = no_repeat_ngram >= 1 and L >= n - 1, pre = w[L - n + 1 .. L) (empty for n = 1): for every position j in [n - 1, L)
+ * with w[j - n + 1 .. j) == pre, ascending, w[j] is appended to the row's list (duplicates kept); then eos_id when
+ * t < min_len.  ban_cnt[r] = entries written (at most T).  One wave64 per row: lanes test 64 positions at a time, a ballot
+ * and a prefix population count place the matches in order - no atomics, no LDS, bit-repeatable, capturable.
+ * The list of step t is built from the tables the merge / select of step t - 1 wrote (t = 0: the empty tables) and is
+ * read by isc_rows_step_banned_fwd / isc_beam_topk_banned at step t.  live_in (optional): reads 0 -> nothing is written.
+ * Before any launch: a null struct or table -> ISC_E_NULL; rows < 1, T outside [1, 256], no_repeat_ngram outside [0, 4],
+ * min_len outside [0, T], t outside [0, T), ban_ld < T -> ISC_E_SHAPE. */
+typedef struct {
+    int32_t rows, T, t;
+    int32_t no_repeat_ngram, min_len, _pad;
+    int64_t eos_id;
+    const int64_t *words;     /* [rows, T] */
+    const int32_t *len;       /* [rows] */
+    int64_t *ban_ids;         /* [rows, ban_ld] */
+    int32_t *ban_cnt;         /* [rows] */
+    int64_t ban_ld;
+    const int32_t *live_in;
+} isc_beam_ngram_ban_args;
+int isc_beam_ngram_ban(const isc_beam_ngram_ban_args *args_host, void *stream);
 
 /* Candidate merge of a batched beam search on the device (captioner.py:378-411), one step: from the step's top-`beam`
  * (value, id) pairs per live row, form every image's candidates in the reference's insertion order (an ended
@@ -645,13 +679,31 @@ typedef struct {
     const isc_rollout_step *fin_prev;
     int32_t *fin_unfinished_out;
 } isc_rows_ext;
+/* A per-row list of further banned ids for the step's tile candidates (ext->beam > 0), as isc_beam_ngram_ban writes it: row
+ * r's candidate mask also bans ids[r * ld + 0 .. cnt[r]) (duplicates and ids outside [0, V) are harmless).  Only cand_val /
+ * cand_idx change: pmax / psum / pidx and `logits` are those of the launch without a list.  The first 8 entries of every
+ * row are fetched ahead of the weight stream like the row's last word, a longer list is walked in the epilogue.  The list
+ * travels next to isc_rows_ext, not inside it (that struct's size is pinned): isc_rows_step_banned_fwd /
+ * isc_rows_vocab_banned_fwd are isc_rows_step_fwd / isc_rows_vocab_fwd with it; the entry points without it launch the
+ * kernels without it, which are the kernels as they were.  A null list, ids or cnt -> ISC_E_NULL; ld < 1 or ext->beam <= 0 ->
+ * ISC_E_SHAPE; nothing is launched then. */
+typedef struct {
+    const int64_t *ids;       /* [rows, ld] */
+    const int32_t *cnt;       /* [rows] */
+    int64_t ld;
+} isc_rows_ban;
 int isc_rows_stats_tile(int V);
 int isc_rows_step_supported(const isc_step_plan *plan_host);
 int isc_rows_step_fwd(const isc_step_plan *plan_host, const isc_rows_ext *ext_host, void *stream);
+int isc_rows_step_banned_fwd(const isc_step_plan *plan_host, const isc_rows_ext *ext_host, const isc_rows_ban *ban_host,
+                             void *stream);
 /* The classifier launch of that step alone (tests, tools): statistics per stats_tile columns (+ tile candidates). */
 int isc_rows_vocab_fwd(const float *h, int ldh, const float *W, int ldw, const float *bias, int M, int V, int K,
                        float *part_max, float *part_sum, int32_t *part_idx, float *logits, int64_t ld_logits,
                        const isc_rows_ext *ext_host, void *stream);
+int isc_rows_vocab_banned_fwd(const float *h, int ldh, const float *W, int ldw, const float *bias, int M, int V, int K,
+                              float *part_max, float *part_sum, int32_t *part_idx, float *logits, int64_t ld_logits,
+                              const isc_rows_ext *ext_host, const isc_rows_ban *ban_host, void *stream);
 /* Cache policy of the rows kernels' weight streams: 0 = default policy everywhere, 1 (default) = the classifier's weights
  * non-temporal (read once per step: they pass through without evicting the LSTM / projection weights that the XCD L2s
  * keep from step to step), 2 = every stream non-temporal.  Returns the previous value. */

@@ -114,6 +114,17 @@ class RowsExt(C.Structure):
                 ('fin_unfinished_out', C.c_void_p)]
 
 
+class RowsBan(C.Structure):
+    """isc_rows_ban: the rows' ban lists next to isc_rows_ext (isc_rows_step_banned_fwd / isc_rows_vocab_banned_fwd)."""
+    _fields_ = [('ids', C.c_void_p), ('cnt', C.c_void_p), ('ld', C.c_int64)]
+
+
+class BeamNgramBanArgs(C.Structure):
+    """isc_beam_ngram_ban_args: the ban lists of a beam step (no-repeat n-gram, minimum length)."""
+    _fields_ = (_f('rows T t no_repeat_ngram min_len _pad', C.c_int32) + [('eos_id', C.c_int64)] +
+                _f('words len ban_ids ban_cnt', C.c_void_p) + [('ban_ld', C.c_int64), ('live_in', C.c_void_p)])
+
+
 class BeamSelectArgs(C.Structure):
     _fields_ = ([('n_img', C.c_int32), ('beam', C.c_int32), ('T', C.c_int32), ('t', C.c_int32), ('n_tile', C.c_int32),
                  ('V', C.c_int32), ('eos_id', C.c_int64)] +
@@ -282,6 +293,10 @@ SIGNATURES = {
     'isc_rows_vocab_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RowsExt),
                                      C.c_void_p]),
+    'isc_rows_step_banned_fwd': (C.c_int, [C.POINTER(StepPlan), C.POINTER(RowsExt), C.POINTER(RowsBan), C.c_void_p]),
+    'isc_rows_vocab_banned_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RowsExt),
+                                            C.POINTER(RowsBan), C.c_void_p]),
     'isc_set_rows_nt': (C.c_int, [C.c_int]),
     'isc_set_rows_scan_max': (C.c_int, [C.c_int]),
     'isc_set_rows_scan_regions': (C.c_int, [C.c_int]),
@@ -325,6 +340,10 @@ SIGNATURES = {
     'isc_beam_topk': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_beam_topk_banned': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'isc_beam_ngram_ban': (C.c_int, [C.POINTER(BeamNgramBanArgs), C.c_void_p]),
     'isc_xe_loss_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     'isc_logsoftmax_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,

@@ -137,13 +137,27 @@ class _VectorMerge:
 
 
 def beam_search_batch(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, graphs=True,
-                      share=False):
+                      share=False, no_repeat_ngram=0, min_len=0):
     """share: the rows of an image read ONE entry of its step-invariant tensors (nothing is expanded `beam`-fold); with
-    senti_labels [I, S] an image is searched under S labels at once (Captioner.sample_sentiments: I*S searches)."""
+    senti_labels [I, S] an image is searched under S labels at once (Captioner.sample_sentiments: I*S searches).
+    no_repeat_ngram (0 = off, up to 4): no n-gram twice in a candidate; min_len: no <EOS> before that many words.  Both
+    act inside the per-step top-k (isc_beam_ngram_ban's lists); device-side merge only.  The two values arrive checked
+    (check_controls: the Captioner's public calls do it once, first thing)."""
+    ctrl = (no_repeat_ngram, min_len)
     if (graphs and cap.__dict__.get('_beam_graphs') is not None and getattr(cap, 'beam_device_merge', True) and beam <= 8
             and ops.TIMER.arm_step is None and ops.graphs_allowed_here()):
-        return _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
-    return _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
+        return _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share,
+                               ctrl)
+    return _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share, ctrl)
+
+
+def check_controls(cap, beam, T, no_repeat_ngram, min_len):
+    """(no_repeat_ngram, min_len) as checked ints, ValueError otherwise (ops.check_beam_controls); the defaults cost two
+    type looks."""
+    if no_repeat_ngram.__class__ is int and min_len.__class__ is int and not no_repeat_ngram and not min_len:
+        return (0, 0)
+    return ops.check_beam_controls(no_repeat_ngram, min_len, T, cap.vocab_size, beam,
+                                   getattr(cap, 'beam_device_merge', True))
 
 
 def _n_search(fc_feats, senti_labels):
@@ -152,8 +166,8 @@ def _n_search(fc_feats, senti_labels):
     return fc_feats.shape[0] * S
 
 
-def _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
-    s = _Search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share)
+def _search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False, ctrl=(0, 0)):
+    s = _Search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share, ctrl)
     if s.device_merge:
         with ops.h3_weights_scope(cap._dev):
             for t in range(T):
@@ -177,7 +191,7 @@ def _few_rows(cap, n_img, beam):
             and getattr(cap, 'beam_device_merge', True) and cap._rows_vocab_ok())
 
 
-def _graph_key(cap, ins, beam, decoding_constraint, T, share=False):
+def _graph_key(cap, ins, beam, decoding_constraint, T, share=False, ctrl=(0, 0)):
     # (the cached tables a captured graph points at are functions of these weights: token table, sentiment-word tables,
     # and - gated scan - the sentiment-word table through attention.senti2att)
     # ... and - few-row searches - the prologue's weight planes, which such a graph keeps instead of re-splitting them
@@ -186,7 +200,7 @@ def _graph_key(cap, ins, beam, decoding_constraint, T, share=False):
                                           cap.att2att[0].weight, cap.attention.cont2att.weight))
     return (tuple(None if x is None else (tuple(x.shape), x.dtype) for x in ins), beam, decoding_constraint, T, versions,
             ops.WEIGHT_EPOCH, cap.eos_id, torch.cuda.current_device(), bool(getattr(cap, 'beam_step_gate', True)),
-            bool(share))
+            bool(share), ctrl)
 
 
 def _replay(cap, entry, ins, T):
@@ -200,10 +214,12 @@ def _replay(cap, entry, ins, T):
     return search.finish()
 
 
-def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
+def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False,
+                       no_repeat_ngram=0, min_len=0):
     """Captioner.sample_batch's short cut: a search whose graphs exist is one key look-up, the input copies, the replay
     and the read-back - none of the per-call set-up of the eager path (parameter dictionary, weights scope, mode walk:
-    ~100 us of host time in front of a 1 ms search).  None when there is nothing to replay."""
+    ~100 us of host time in front of a 1 ms search).  None when there is nothing to replay.  no_repeat_ngram / min_len: checked
+    values, as for beam_search_batch."""
     cache = cap.__dict__.get('_beam_graphs')
     if (not cache or not getattr(cap, 'beam_device_merge', True) or beam > 8 or ops.TIMER.arm_step is not None
             or not ops.graphs_allowed_here()):
@@ -211,7 +227,7 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
     if not (fc_feats.is_cuda and att_feats.is_cuda):
         return None
     ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
-    key = _graph_key(cap, ins, beam, decoding_constraint, T, share)
+    key = _graph_key(cap, ins, beam, decoding_constraint, T, share, (no_repeat_ngram, min_len))
     entry = cache.get(key)
     if not isinstance(entry, tuple):
         return None
@@ -219,7 +235,8 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
     return _replay(cap, entry, ins, T)
 
 
-def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
+def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False,
+                    ctrl=(0, 0)):
     """The search served from captured HIP graphs (Captioner.enable_beam_graphs).  A single-image beam-5 step is
     ~14 small launches behind four FFI calls and the host needs longer to enqueue them than the device to run them;
     the loop has no host read except the live-image counter every CHUNK steps, so the prologue + steps 0..3 capture
@@ -227,16 +244,16 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
     <= ceil(T / CHUNK) graph launches with one counter read between them, and the read-back."""
     dev = cap._dev
     ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
-    key = _graph_key(cap, ins, beam, decoding_constraint, T, share)
+    key = _graph_key(cap, ins, beam, decoding_constraint, T, share, ctrl)
     cache = cap._beam_graphs
     entry = cache.get(key)
     if entry is None:                       # first sight: run eagerly (builds the cached tables, warms the kernels)
         while len(cache) >= cap._beam_graphs_max:
             cap._graph_evicted(cache.pop(next(iter(cache))), 'beam')    # least recently used
             if cap._beam_graphs is None:
-                return _search(cap, *ins, beam, decoding_constraint, T, share)
+                return _search(cap, *ins, beam, decoding_constraint, T, share, ctrl)
         cache[key] = 'seen'
-        return _search(cap, *ins, beam, decoding_constraint, T, share)
+        return _search(cap, *ins, beam, decoding_constraint, T, share, ctrl)
     cache[key] = cache.pop(key)             # LRU order
     if entry == 'seen':
         static = [None if x is None else x.clone() for x in ins]
@@ -265,13 +282,13 @@ def _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, d
             scope.__enter__()                      # are split inside graph 0 and read by the later graphs)
             try:
                 if few:                            # (the eager prologue leaves the planes in the scope)
-                    _Search(cap, *static, beam, decoding_constraint, T, share)
+                    _Search(cap, *static, beam, decoding_constraint, T, share, ctrl)
                 search, t0 = None, 0
                 while t0 < T:
                     g = torch.cuda.CUDAGraph()
                     with ops.graph_capture(g, pool=pool, stream=stream):
                         if search is None:
-                            search = _Search(cap, *static, beam, decoding_constraint, T, share)
+                            search = _Search(cap, *static, beam, decoding_constraint, T, share, ctrl)
                         # few-row searches end themselves on the device (isc_rows_ext.live_in): ONE graph, no counter
                         # read in between; the general kernels run CHUNK steps per graph with a look at the counter after
                         # each - their steps are gated as well (isc_set_stream_gate), so the up to CHUNK - 1 steps a graph
@@ -296,7 +313,8 @@ class _Search:
     """State of one batched search: the prologue, the per-row copies, the device-side candidate table; step(t)
     enqueues decode step t (preceded by the state re-ordering that step t - 1 decided)."""
 
-    def __init__(self, cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False):
+    def __init__(self, cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False,
+                 ctrl=(0, 0)):
         p = cap._p()
         # A search is an (image, label) pair: senti_labels [I, S] (Captioner.sample_sentiments) runs n_img = I * S searches
         # of `beam` rows - the merge kernels think in searches - over I images' region tensors (share is then implied).
@@ -407,6 +425,22 @@ class _Search:
             a.done, a.gather, a.live = self.done.data_ptr(), self.gather.data_ptr(), self.live.data_ptr()
             self.cur = 0
             self._plans = [None, None]                     # (step plan, merge arguments) of the even / odd steps
+            # no_repeat_ngram / min_len: two ban buffers that ping-pong with the candidate tables - the list of step t is
+            # built from the tables step t - 1 wrote (isc_beam_ngram_ban, behind its merge / select; in front of step 0
+            # from the empty tables) and read by step t's candidate masks.  Pointers repeat with period 2, as the tables'.
+            self.ban = None
+            if ctrl != (0, 0):
+                from ._lib import BeamNgramBanArgs, RowsBan
+                self.ban_ids = torch.zeros(2, rows, T, dtype=torch.int64, device=dev)
+                self.ban_cnt = torch.zeros(2, rows, dtype=torch.int32, device=dev)
+                self.ban = [None, None]
+                for k in (0, 1):
+                    g = self.ban[k] = BeamNgramBanArgs()
+                    g.rows, g.T, g.no_repeat_ngram, g.min_len, g.eos_id, g.ban_ld = rows, T, ctrl[0], ctrl[1], cap.eos_id, T
+                    g.words, g.len = self.words[k].data_ptr(), self.length[k].data_ptr()
+                    g.ban_ids, g.ban_cnt = self.ban_ids[k].data_ptr(), self.ban_cnt[k].data_ptr()
+                # (the few-row step's view of buffer k: isc_rows_ban)
+                self.rows_ban = [RowsBan(self.ban_ids[k].data_ptr(), self.ban_cnt[k].data_ptr(), T) for k in (0, 1)]
             if self.rows_mode:
                 n_tile = self.ws['pmax'].shape[1]
                 self.cand_val = cap._new(rows, n_tile, 8)
@@ -444,6 +478,8 @@ class _Search:
         cap.last_beam_steps = t + 1
         cur = self.cur
         last_d = self.last[cur]
+        if self.ban is not None and t == 0:
+            self._ban_lists(0, 0, None)
         if self.Pb.tab is None:
             ops.embed_relu_fwd(self.emb, last_d, self.xt)
         # Every pointer of a step repeats with period 2 (token / candidate tables ping-pong, the recurrent state
@@ -462,8 +498,13 @@ class _Search:
             else:
                 h_cur, c_cur, h_nxt, c_nxt = self.st_cur[0], self.st_cur[1], self.st_nxt[0], self.st_nxt[1]
                 cap._step(self.p, self.Pb, self.ws, self.xt, h_cur, c_cur, h_nxt, c_nxt, logits=self.logits, tok=last_d)
-            ops.beam_topk(self.logits, self.ws['pmax'], self.ws['psum'], last_d, self.beam, cap.pad_id, cap.sos_id,
-                          cap.unk_id, self.mask_special, self.dc, self.top_val, self.top_idx)
+            if self.ban is not None:
+                ops.beam_topk_banned(self.logits, self.ws['pmax'], self.ws['psum'], last_d, self.beam, cap.pad_id,
+                                     cap.sos_id, cap.unk_id, self.mask_special, self.dc, self.ban_ids[cur],
+                                     self.ban_cnt[cur], self.top_val, self.top_idx)
+            else:
+                ops.beam_topk(self.logits, self.ws['pmax'], self.ws['psum'], last_d, self.beam, cap.pad_id, cap.sos_id,
+                              cap.unk_id, self.mask_special, self.dc, self.top_val, self.top_idx)
         nxt = cur ^ 1
         if fast is not None:
             a = fast[1]
@@ -478,7 +519,15 @@ class _Search:
                 plan = self.ws['_plan']
                 self._plans[t] = (type(plan).from_buffer_copy(plan), type(a).from_buffer_copy(a))
         ops.beam_merge(a)
+        if self.ban is not None and t + 1 < self.T:
+            self._ban_lists(nxt, t + 1, self.live.data_ptr() + 4 * (t + 1) if self.gated else None)
         self.cur = nxt
+
+    def _ban_lists(self, k, t, live_in):
+        """The ban lists of step t from candidate tables k into ban buffer k (isc_beam_ngram_ban)."""
+        g = self.ban[k]
+        g.t, g.live_in = t, live_in
+        ops.beam_ngram_ban(g)
 
     def _step_rows(self, t):
         """Step t on the few-row kernels: the step reads st_cur and writes st_nxt, the select that closes it gathers the
@@ -487,6 +536,8 @@ class _Search:
         cap.last_beam_steps = t + 1
         cur = self.cur
         last_d = self.last[cur]
+        if self.ban is not None and t == 0:
+            self._ban_lists(0, 0, None)
         if self.Pb.tab is None:
             ops.embed_relu_fwd(self.emb, last_d, self.xt)
         fast = self._plans[t & 1] if t >= 2 else None
@@ -494,12 +545,13 @@ class _Search:
         if fast is not None:
             plan, x, a = fast
             x.live_in = a.live_in = live_in
-            ops.rows_step_fwd(plan, x)
+            ops.rows_step_fwd(plan, x, None if self.ban is None else self.rows_ban[cur])
         else:
             x.last_word = last_d.data_ptr()
             x.live_in = a.live_in = live_in
             sc, sn = self.st_cur, self.st_nxt
-            cap._step(self.p, self.Pb, self.ws, self.xt, sc[0], sc[1], sn[0], sn[1], logits=None, tok=last_d, rows_ext=x)
+            cap._step(self.p, self.Pb, self.ws, self.xt, sc[0], sc[1], sn[0], sn[1], logits=None, tok=last_d, rows_ext=x,
+                      rows_ban=None if self.ban is None else self.rows_ban[cur])
         nxt = cur ^ 1
         a.t = t
         if fast is None:
@@ -511,6 +563,8 @@ class _Search:
                 plan = self.ws['_plan']
                 self._plans[t & 1] = (type(plan).from_buffer_copy(plan), type(x).from_buffer_copy(x), type(a).from_buffer_copy(a))
         ops.beam_select(a)
+        if self.ban is not None and t + 1 < self.T:
+            self._ban_lists(nxt, t + 1, self.live.data_ptr() + 4 * (t + 1))
         self.cur = nxt
 
     def all_done(self, t):

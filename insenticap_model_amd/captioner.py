@@ -505,9 +505,10 @@ class Captioner(nn.Module):
 
     def _step(self, p, P, ws, xt, h_cur, c_cur, h_nxt, c_nxt, alpha_c=None, alpha_s=None, beta=None,
               logits=None, out_mask=None, out_scale=1.0, save=None, tok=None, normalize=False,
-              hp_cur=None, hp_nxt=None, rows_ext=None):
+              hp_cur=None, hp_nxt=None, rows_ext=None, rows_ban=None):
         """forward_step (captioner.py:168-186) on `rows` sequences: ONE library call (isc_step_fwd; with `rows_ext`, an
-        isc_rows_ext, isc_rows_step_fwd: the few-row kernels, `ws` then holds statistics per rows_ext.stats_tile columns)
+        isc_rows_ext, isc_rows_step_fwd: the few-row kernels, `ws` then holds statistics per rows_ext.stats_tile columns;
+        `rows_ban`, an isc_rows_ban, adds the rows' ban lists to the tile candidates)
         that enqueues every kernel of the step. h/c arguments are indexable pairs (0 = att-LSTM,
         1 = lang-LSTM) of [rows,H] tensors; `save` (training) holds 'g1','g2' [rows,4H] and 'hdrop'
         [rows,H] buffers kept for the backward pass; `xt` = relu(Emb[token]) or None when P.tab
@@ -559,7 +560,7 @@ class Captioner(nn.Module):
         pl.pmax, pl.psum, pl.pidx = ptr(ws.get('pmax')), ptr(ws.get('psum')), ptr(ws.get('pidx'))   # None: no classifier
         pl.gate_Gc, pl.gate_Gs = ptr(getattr(P, 'gate_Gc', None)), ptr(getattr(P, 'gate_Gs', None))
         if rows_ext is not None:
-            ops.rows_step_fwd(pl, rows_ext)
+            ops.rows_step_fwd(pl, rows_ext, rows_ban)
         else:
             ops.step_fwd(pl)
 
@@ -1369,25 +1370,34 @@ class Captioner(nn.Module):
 
     # ------------------------------------------------------------------ beam search
     def sample(self, fc_feat, att_feat, senti_words=None, senti_label=None,
-               beam_size=3, decoding_constraint=1, max_seq_len=16):
-        """Beam search for ONE image (captioner.py:351-420): returns (captions, scores)."""
+               beam_size=3, decoding_constraint=1, max_seq_len=16, no_repeat_ngram=0, min_len=0):
+        """Beam search for ONE image (captioner.py:351-420): returns (captions, scores).  `no_repeat_ngram` / `min_len`:
+        see sample_batch."""
         caps, scores, _ = self.sample_batch(
             fc_feat.reshape(1, -1), att_feat.reshape(1, -1, att_feat.shape[-1]),
             None if senti_words is None else senti_words.reshape(1, -1),
             None if senti_label is None else senti_label.reshape(1),
-            beam_size, decoding_constraint, max_seq_len)
+            beam_size, decoding_constraint, max_seq_len, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
         return caps[0], scores[0]
 
     @torch.no_grad()
     def sample_batch(self, fc_feats, att_feats, senti_words=None, senti_labels=None,
-                     beam_size=3, decoding_constraint=1, max_seq_len=16, share_image=False):
+                     beam_size=3, decoding_constraint=1, max_seq_len=16, share_image=False, no_repeat_ngram=0,
+                     min_len=0):
         """Beam search for I images at once: every step runs ONE batched decode step over I*beam rows
         and one device top-k; candidate bookkeeping follows the reference exactly (fp64 score sums,
         stable ordering, ended beams carried, captioner.py:378-411).
         Returns (captions[I][beam], scores[I][beam], id_sequences[I][beam]).
         `share_image=True`: the same search without the `beam` copies of each image's region tensors - on the general
         kernels the rows of an image read ONE entry of att_e / att_p / gate_Gc and of the label / word tensors
-        (isc_step_plan.row_div), as the few-row step always did.  Same candidates; scores to rounding."""
+        (isc_step_plan.row_div), as the few-row step always did.  Same candidates; scores to rounding.
+        `no_repeat_ngram=n` (1..4; 0 = off): no candidate holds an n-gram twice - at every step the words that would
+        complete a second occurrence are banned like <PAD> / <SOS> / <UNK> (log-prob -inf for the top-`beam` only, the
+        log-softmax untouched).  `min_len=m`: <EOS> is banned before m words.  Both act inside the per-step top-k on the
+        device (isc_beam_ngram_ban); the reference has neither.  They need the device-side merge and a vocabulary of more
+        than max_seq_len + 4 + beam_size words (ValueError otherwise, before anything touches the device)."""
+        from .beam import check_controls
+        ctrl = check_controls(self, beam_size, max_seq_len, no_repeat_ngram, min_len)      # (raises first)
         share = bool(share_image)
         if senti_labels is not None and senti_labels.dim() != 1 and senti_labels.numel() == fc_feats.shape[0]:
             senti_labels = senti_labels.reshape(-1)              # ([I, 1] and the like: one label per image, as always)
@@ -1395,7 +1405,7 @@ class Captioner(nn.Module):
             raise ValueError('sample_batch: senti_labels must be [I] (one label per image; several labels per image: '
                              'sample_sentiments), got shape %s' % (tuple(senti_labels.shape),))
         return self._beam_call(fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
-                               max_seq_len, share)
+                               max_seq_len, share, *ctrl)
 
     @staticmethod
     def _check_sentiments(n_cat, fc_feats, senti_words, senti_labels, beam_size, device_merge, labels_known=False):
@@ -1430,7 +1440,7 @@ class Captioner(nn.Module):
 
     @torch.no_grad()
     def sample_sentiments(self, fc_feats, att_feats, senti_words, senti_labels, beam_size=3, decoding_constraint=1,
-                          max_seq_len=16, _labels_known=False):
+                          max_seq_len=16, _labels_known=False, no_repeat_ngram=0, min_len=0):
         """Beam search of I images under S sentiment labels each, the image's tensors shared: senti_labels [I, S] (row i:
         the category ids image i is captioned under, any order), senti_words [I, M] (the image's words under every label)
         or [I, S, M].  A search is an (image, label) pair: I*S searches of `beam_size` rows advance together, the
@@ -1439,19 +1449,23 @@ class Captioner(nn.Module):
         (isc_step_plan.row_div / senti_div).  Up to 8 rows (1 image x 2 labels x beam 3 or 4, 1 x 3 x 2) the search runs on
         the few-row step, from ONE graph when beam graphs are enabled; more rows run on the general kernels.  Each
         (image, label) result is that of `sample` under that label: same candidates, scores to rounding.
+        `no_repeat_ngram` / `min_len`: as sample_batch.
         Returns (captions[I][S][beam], scores[I][S][beam], id_sequences[I][S][beam])."""
+        from .beam import check_controls
+        ctrl = check_controls(self, beam_size, max_seq_len, no_repeat_ngram, min_len)      # (raises first)
         I, S = self._check_sentiments(self.senti_label_embed[0].num_embeddings, fc_feats, senti_words, senti_labels, beam_size,
                                       getattr(self, 'beam_device_merge', True), _labels_known)
         caps, scores, ids = self._beam_call(fc_feats, att_feats, senti_words, senti_labels, int(beam_size),
-                                            decoding_constraint, max_seq_len, True)
+                                            decoding_constraint, max_seq_len, True, *ctrl)
 
         def nest(x):
             return [x[i * S:(i + 1) * S] for i in range(I)]
         return nest(caps), nest(scores), nest(ids)
 
     def _beam_call(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint, max_seq_len,
-                   share):
-        """sample_batch / sample_sentiments: graph serving, engine fallback and numerics checks around the search."""
+                   share, no_repeat_ngram=0, min_len=0):
+        """sample_batch / sample_sentiments: graph serving, engine fallback and numerics checks around the search
+        (no_repeat_ngram / min_len: the callers' checked values)."""
         from .beam import beam_search_batch, replay_if_captured
         if self.training:
             self.eval()
@@ -1463,7 +1477,8 @@ class Captioner(nn.Module):
             self._p()
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 res = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
-                                        decoding_constraint, max_seq_len, graphs=False, share=share)
+                                        decoding_constraint, max_seq_len, graphs=False, share=share,
+                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len)
             ops.device_status(reset=True)          # (NaN / inf features flag there as well: decoded as they are)
             return res
         # A search ends with a host read of its results, so the numerics flags are visible right behind it: no pass over
@@ -1472,12 +1487,13 @@ class Captioner(nn.Module):
         if checks and ops.h3_mode() != 0 and self._known_out_of_domain(fc_feats, att_feats):
             return on_exact_engine()
         out = replay_if_captured(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
-                                 max_seq_len, share)
+                                 max_seq_len, share, no_repeat_ngram, min_len)
         if out is None:
             self._p()                              # raises on CPU parameters before anything touches the device
             with ops.h3_weights_scope(self._dev, key=self._weights_key()):     # prologue + search: weights split once
                 out = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
-                                        decoding_constraint, max_seq_len, share=share)
+                                        decoding_constraint, max_seq_len, share=share,
+                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len)
         if checks:                                 # the host has the results, i.e. has waited: read the status too
             if ops.h3_mode() != 0 and ops.device_status(reset=True):
                 self._known_out_of_domain(fc_feats, att_feats, remember=True)

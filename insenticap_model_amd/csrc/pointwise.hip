@@ -255,6 +255,60 @@ extern "C" int isc_beam_gather(const float *state_next, const float *state_cur, 
     return ISC_OK;
 }
 
+// ------------------------------------------------------------------ beam search: ban lists (n-gram blocking, minimum length)
+// isc_beam_ngram_ban: one wave64 per candidate row.  The row's last n - 1 words (`pre`) sit in registers; lane l of
+// chunk c tests position j = 64 c + l: does the (n - 1)-gram in front of w[j] equal `pre`?  The ballot of a chunk
+// and the population count of the lanes below place every match at its rank, so the list is in ascending j with
+// duplicates kept - the order the host restatement produces - without atomics or LDS.
+__global__ __launch_bounds__(64) void beam_ngram_ban_kernel(const isc_beam_ngram_ban_args a) {
+    if (a.live_in != nullptr && *a.live_in == 0) return;      // (uniform: the search has ended)
+    const int row = blockIdx.x, lane = threadIdx.x, n = a.no_repeat_ngram, T = a.T;
+    const int64_t *w = a.words + (long long)row * T;
+    int64_t *out = a.ban_ids + (long long)row * a.ban_ld;
+    int L = a.len[row];
+    L = L < 0 ? 0 : L;
+    L = L > a.t ? a.t : L;                                    // (t < T: every index below stays inside the row)
+    int cnt = 0;
+    if (n >= 1 && L >= n - 1) {
+        int64_t pre[3] = {0, 0, 0};                           // pre[k] = w[L - 1 - k], k < n - 1
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < n - 1) pre[k] = w[L - 1 - k];
+        for (int j0 = 0; j0 < L; j0 += 64) {
+            const int j = j0 + lane;
+            bool match = j >= n - 1 && j < L;
+            int64_t wj = 0;
+            if (match) {
+                wj = w[j];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (k < n - 1) match = match && (w[j - 1 - k] == pre[k]);
+            }
+            const unsigned long long bal = __ballot(match);
+            const int pos = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+            if (match && pos < a.ban_ld) out[pos] = wj;
+            cnt += __popcll(bal);
+        }
+    }
+    if (a.t < a.min_len) {
+        if (lane == 0 && cnt < a.ban_ld) out[cnt] = a.eos_id;
+        ++cnt;
+    }
+    if (lane == 0) a.ban_cnt[row] = cnt < a.ban_ld ? cnt : (int)a.ban_ld;
+}
+
+extern "C" int isc_beam_ngram_ban(const isc_beam_ngram_ban_args *args, void *stream) {
+    if (!args) return ISC_E_NULL;
+    const isc_beam_ngram_ban_args &a = *args;
+    if (!a.words || !a.len || !a.ban_ids || !a.ban_cnt) return ISC_E_NULL;
+    if (a.rows <= 0 || a.T <= 0 || a.T > 256 || a.t < 0 || a.t >= a.T || a.no_repeat_ngram < 0 || a.no_repeat_ngram > 4 ||
+        a.min_len < 0 || a.min_len > a.T || a.ban_ld < a.T)
+        return ISC_E_SHAPE;
+    hipLaunchKernelGGL(beam_ngram_ban_kernel, dim3(a.rows), dim3(64), 0, (hipStream_t)stream, a);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
 // ------------------------------------------------------------------ row statistics helper
 // Folds the per-tile (max, sumexp, argmax) triples of one row: returns the global max, its
 // vocabulary index (smallest index on ties) and S = sum exp(x - gmax).  All 64 lanes get
@@ -1265,14 +1319,39 @@ extern "C" int isc_logsoftmax_apply_steps(float *logits, int64_t ld_b, int64_t l
 // `beam` rounds of a block-wide arg-max over the threads' list heads.  Same values and order as the kernel below
 // (descending value, ties to the smaller word id, masked entries as -inf): [5 x 10000] 78 us -> ~10 us, which was
 // 40 % of a one-image search.
+// BAN (isc_beam_topk_banned): the row's ban list (at most 256 ids) is staged in LDS and masks like the specials; a row
+// with c listed ids admits c more tiles, since up to 4 + c of the words above the threshold may be masked.
+// (the instantiations without a list take an empty argument: their code and kernarg layout are what they were)
+template <bool BAN>
+struct BeamBan {
+    const int64_t *ids;
+    const int32_t *cnt;
+    long long ld;
+};
+template <>
+struct BeamBan<false> {};
+#define ISC_BAN_MAX 256
+template <bool BAN>
 __global__ __launch_bounds__(256) void beam_topk8_kernel(const float *logits, long long ld,
                                                          const float *pmax, const float *psum, int n_tile,
                                                          int V, int beam, const int64_t *last_word,
                                                          long long pad_id, long long sos_id,
                                                          long long unk_id, int mask_special, int cons,
-                                                         float *top_val, int64_t *top_idx, const int *gate) {
+                                                         float *top_val, int64_t *top_idx, const int *gate,
+                                                         const BeamBan<BAN> ban) {
     if (gate != nullptr && *gate == 0) return;      // (uniform; isc_set_stream_gate: the search has ended)
     constexpr int K = 8;
+    __shared__ int sban[BAN ? ISC_BAN_MAX : 1];
+    int nban = 0;
+    if constexpr (BAN) {
+        nban = ban.cnt[blockIdx.x];
+        nban = nban < 0 ? 0 : (nban > ISC_BAN_MAX ? ISC_BAN_MAX : nban);
+        nban = nban > ban.ld ? (int)ban.ld : nban;
+        if ((int)threadIdx.x < nban) {
+            const long long b = ban.ids[(long long)blockIdx.x * ban.ld + threadIdx.x];
+            sban[threadIdx.x] = (b >= 0 && b < V) ? (int)b : -1;
+        }
+    }
     __shared__ float sv[2][4];
     __shared__ int si[2][4];
     __shared__ float sh[2];
@@ -1294,7 +1373,7 @@ __global__ __launch_bounds__(256) void beam_topk8_kernel(const float *logits, lo
     const float gmax = sh[0], logS = sh[1];
     // tile selection: rank of this thread's tile among the tile maxima (ties by tile id); tiles tied with the last
     // admitted maximum are admitted as well because the comparison below is on values, not ranks
-    const int want = beam + 4;
+    const int want = beam + 4 + nban;
     if (tid < n_tile) {
         const float mine = spm[tid];
         int larger = 0;
@@ -1313,6 +1392,8 @@ __global__ __launch_bounds__(256) void beam_topk8_kernel(const float *logits, lo
         bool banned = false;
         if (mask_special && (i == pad_id || i == sos_id || i == unk_id)) banned = true;
         if (cons && i == last) banned = true;
+        if constexpr (BAN)
+            for (int b = 0; b < nban; ++b) banned |= (sban[b] == i);
         float v = banned ? -INFINITY : (raw - gmax) - logS;
         int id = i;
 #pragma unroll
@@ -1372,13 +1453,26 @@ __global__ __launch_bounds__(256) void beam_topk8_kernel(const float *logits, lo
 
 // One workgroup per live beam row; `beam` rounds of a block-wide arg-max over the masked
 // log-probabilities (rows are few: images x beam).  Ties resolve to the smaller word id.
+template <bool BAN>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const float *logits, long long ld,
                                                         const float *pmax, const float *psum, int n_tile,
                                                         int V, int beam, const int64_t *last_word,
                                                         long long pad_id, long long sos_id,
                                                         long long unk_id, int mask_special, int cons,
-                                                        float *top_val, int64_t *top_idx, const int *gate) {
+                                                        float *top_val, int64_t *top_idx, const int *gate,
+                                                        const BeamBan<BAN> ban) {
     if (gate != nullptr && *gate == 0) return;      // (uniform; isc_set_stream_gate: the search has ended)
+    __shared__ int sban[BAN ? ISC_BAN_MAX : 1];
+    int nban = 0;
+    if constexpr (BAN) {
+        nban = ban.cnt[blockIdx.x];
+        nban = nban < 0 ? 0 : (nban > ISC_BAN_MAX ? ISC_BAN_MAX : nban);
+        nban = nban > ban.ld ? (int)ban.ld : nban;
+        if ((int)threadIdx.x < nban) {
+            const long long b = ban.ids[(long long)blockIdx.x * ban.ld + threadIdx.x];
+            sban[threadIdx.x] = (b >= 0 && b < V) ? (int)b : -1;
+        }
+    }
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ float sh[2];
@@ -1403,6 +1497,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float *logits, lon
             if (mask_special && (i == pad_id || i == sos_id || i == unk_id)) banned = true;
             if (cons && i == last) banned = true;
             for (int j = 0; j < k; ++j) banned |= (chosen[j] == i);
+            if constexpr (BAN)
+                for (int b = 0; b < nban; ++b) banned |= (sban[b] == i);
             const float v = banned ? -INFINITY : (x[i] - gmax) - logS;
             // banned entries still take part as -inf (torch.sort keeps them, at the tail)
             if (v > mx || (v == mx && i < ix)) { mx = v; ix = i; }
@@ -1423,26 +1519,49 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float *logits, lon
     }
 }
 
+template <bool BAN>
+static int beam_topk_launch(const float *logits, int64_t ld_logits, const float *part_max, const float *part_sum,
+                            int n_tile, int rows, int V, int beam, const int64_t *last_word, int64_t pad_id,
+                            int64_t sos_id, int64_t unk_id, int mask_special, int decoding_constraint, const BeamBan<BAN> ban,
+                            float *top_val, int64_t *top_idx, void *stream) {
+    if (!logits || !part_max || !part_sum || !last_word || !top_val || !top_idx) return ISC_E_NULL;
+    if (rows <= 0 || V <= 0 || beam <= 0 || beam > 16 || beam > V) return ISC_E_SHAPE;
+    const int *gate = isc_stream_gate_(stream);
+    if (beam <= 8 && n_tile <= 256 && V >= (beam + 4) * 128)
+        hipLaunchKernelGGL(beam_topk8_kernel<BAN>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits,
+                           (long long)ld_logits, part_max, part_sum, n_tile, V, beam, last_word,
+                           (long long)pad_id, (long long)sos_id, (long long)unk_id, mask_special,
+                           decoding_constraint, top_val, top_idx, gate, ban);
+    else
+        hipLaunchKernelGGL(beam_topk_kernel<BAN>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits,
+                           (long long)ld_logits, part_max, part_sum, n_tile, V, beam, last_word,
+                           (long long)pad_id, (long long)sos_id, (long long)unk_id, mask_special,
+                           decoding_constraint, top_val, top_idx, gate, ban);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
 extern "C" int isc_beam_topk(const float *logits, int64_t ld_logits, const float *part_max,
                              const float *part_sum, int n_tile, int rows, int V, int beam,
                              const int64_t *last_word, int64_t pad_id, int64_t sos_id, int64_t unk_id,
                              int mask_special, int decoding_constraint, float *top_val,
                              int64_t *top_idx, void *stream) {
-    if (!logits || !part_max || !part_sum || !last_word || !top_val || !top_idx) return ISC_E_NULL;
-    if (rows <= 0 || V <= 0 || beam <= 0 || beam > 16 || beam > V) return ISC_E_SHAPE;
-    const int *gate = isc_stream_gate_(stream);
-    if (beam <= 8 && n_tile <= 256 && V >= (beam + 4) * 128)
-        hipLaunchKernelGGL(beam_topk8_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits,
-                           (long long)ld_logits, part_max, part_sum, n_tile, V, beam, last_word,
-                           (long long)pad_id, (long long)sos_id, (long long)unk_id, mask_special,
-                           decoding_constraint, top_val, top_idx, gate);
-    else
-        hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits,
-                           (long long)ld_logits, part_max, part_sum, n_tile, V, beam, last_word,
-                           (long long)pad_id, (long long)sos_id, (long long)unk_id, mask_special,
-                           decoding_constraint, top_val, top_idx, gate);
-    ISC_LAUNCH_CHECK();
-    return ISC_OK;
+    return beam_topk_launch<false>(logits, ld_logits, part_max, part_sum, n_tile, rows, V, beam, last_word, pad_id, sos_id,
+                                   unk_id, mask_special, decoding_constraint, BeamBan<false>{}, top_val, top_idx,
+                                   stream);
+}
+
+extern "C" int isc_beam_topk_banned(const float *logits, int64_t ld_logits, const float *part_max,
+                                    const float *part_sum, int n_tile, int rows, int V, int beam,
+                                    const int64_t *last_word, int64_t pad_id, int64_t sos_id, int64_t unk_id,
+                                    int mask_special, int decoding_constraint, const int64_t *ban_ids,
+                                    const int32_t *ban_cnt, int64_t ban_ld, float *top_val, int64_t *top_idx,
+                                    void *stream) {
+    if (!ban_ids || !ban_cnt) return ISC_E_NULL;
+    if (ban_ld < 1) return ISC_E_SHAPE;
+    return beam_topk_launch<true>(logits, ld_logits, part_max, part_sum, n_tile, rows, V, beam, last_word, pad_id, sos_id,
+                                  unk_id, mask_special, decoding_constraint, BeamBan<true>{ban_ids, ban_cnt, (long long)ban_ld},
+                                  top_val, top_idx, stream);
 }
 
 // ------------------------------------------------------------------ beam step tail in one launch

@@ -669,11 +669,24 @@ struct RVocabArgs {
     float *cand_val;
     int *cand_idx;
 };
+// ... and the per-row ban lists (isc_rows_ban) of the BAN instantiations; the others keep the argument block they had
+struct RVocabBanArgs : RVocabArgs {
+    const long long *ban_ids;
+    const int *ban_cnt;
+    long long ban_ld;
+};
+template <bool BAN>
+struct RVocabArgsOf { typedef RVocabArgs type; };
+template <>
+struct RVocabArgsOf<true> { typedef RVocabBanArgs type; };
 
-template <int MR, int NP, bool NT>
-__global__ __launch_bounds__(768) void rows_vocab_kernel(const RVocabArgs a) {
+// BAN: the candidate mask also bans the row's list.  Lane l holds entry l >> 3 of row l & 7 - the first 8 entries of every
+// row, fetched with the row's count ahead of the weight stream like `lastv` - so the epilogue tests them with lane reads;
+// only a list of more than 8 entries is walked from memory there.
+template <int MR, int NP, bool NT, bool BAN>
+__global__ __launch_bounds__(768) void rows_vocab_kernel(const typename RVocabArgsOf<BAN>::type a) {
     constexpr int TWC = 16 * NP;                            // columns a workgroup can hold: 4 (J) x NP passes x 4 lane groups
-    rows_kernarg_warm<ROWS_KERNARG_LINES(RVocabArgs)>();
+    rows_kernarg_warm<ROWS_KERNARG_LINES(typename RVocabArgsOf<BAN>::type)>();
     extern __shared__ __attribute__((aligned(16))) float As[];
     __shared__ float red[8 * NP * 4 * ROWS_MAX];            // [S*J waves][NP][4][MR]
     __shared__ __attribute__((aligned(16))) unsigned long long kk[ROWS_MAX][64];
@@ -688,6 +701,16 @@ __global__ __launch_bounds__(768) void rows_vocab_kernel(const RVocabArgs a) {
     // epilogue operands, fetched ahead of the weight stream: this lane's column bias, its row's last word
     const float bias_c = (lane < tw) ? a.bias[col0 + lane] : 0.f;
     const int lastv = (a.cons && a.last_word) ? (int)a.last_word[(lane & 7) < M ? (lane & 7) : M - 1] : -1;   // lane q: row q's
+    int banv = -1, bancnt = 0;
+    if constexpr (BAN) {
+        const int q = (lane & 7) < M ? (lane & 7) : M - 1, e = lane >> 3;
+        bancnt = a.ban_cnt[q];
+        bancnt = bancnt < a.ban_ld ? bancnt : (int)a.ban_ld;
+        if (e < a.ban_ld) {                                               // (masked by the count where it is used)
+            const long long b = a.ban_ids[q * a.ban_ld + e];
+            banv = (b >= 0 && b < V) ? (int)b : -1;                       // an id outside [0, V) bans nothing, as in the walk below
+        }
+    }
     if (a.skip && *a.skip == 0) return;                     // (uniform)
     {
         const int sw = wave % S, j = wave / S;
@@ -739,6 +762,13 @@ __global__ __launch_bounds__(768) void rows_vocab_kernel(const RVocabArgs a) {
     for (int m = wave; m < M; m += nw) {
         const int c = lane;
         float x = -INFINITY, mk = -INFINITY;
+        bool listed = false;
+        if constexpr (BAN) {
+            const int id = col0 + c, nb = __builtin_amdgcn_readlane(bancnt, m);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) listed |= (e < nb) && (id == __builtin_amdgcn_readlane(banv, 8 * e + m));
+            for (int e = 8; e < nb; ++e) listed |= ((long long)id == a.ban_ids[m * a.ban_ld + e]);       // (uniform loads)
+        }
         if (c < tw) {
             const int q4 = c >> 2, gg = c & 3, jj = q4 % J, p = q4 / J;
             float v = red[(((jj * S) * NP + p) * 4 + gg) * MR + m];
@@ -748,6 +778,7 @@ __global__ __launch_bounds__(768) void rows_vocab_kernel(const RVocabArgs a) {
             if (a.logits) a.logits[(long long)m * a.ld_logits + id] = x;
             bool banned = a.mask_special && (id == a.pad_id || id == a.sos_id || id == a.unk_id);
             if (id == (long long)__builtin_amdgcn_readlane(lastv, m)) banned = true;
+            if constexpr (BAN) banned |= listed;
             mk = banned ? -INFINITY : x;
         }
         if (a.beam > 0) {
@@ -802,10 +833,10 @@ extern "C" int isc_rows_stats_tile(int V) {
 
 static int rows_vocab(const float *h, int ldh, const float *W, int ldw, const float *bias, int M, int V, int K,
                       int TW, float *pmax, float *psum, int *pidx, float *logits, int64_t ld_logits,
-                      const isc_rows_ext *x, hipStream_t st) {
+                      const isc_rows_ext *x, hipStream_t st, const isc_rows_ban *ban = nullptr) {
     if (!h || !W || !bias || !pmax || !psum || !pidx) return ISC_E_NULL;
     if (M < 1 || M > ROWS_MAX || V < 1 || TW < 16 || TW > 64 || (TW & 3)) return ISC_E_SHAPE;
-    RVocabArgs a = {};
+    RVocabBanArgs a = {};
     const int ind = 0;
     const int nslice = rows_make_segs(a.g, &h, &ldh, &W, &ldw, &K, &ind, 1, 8);
     if (nslice < 1) return ISC_E_SHAPE;
@@ -830,14 +861,19 @@ static int rows_vocab(const float *h, int ldh, const float *W, int ldw, const fl
         a.last_word = reinterpret_cast<const long long *>(x->last_word);
         a.cand_val = x->cand_val; a.cand_idx = x->cand_idx;
         if (a.cons && !a.last_word) return ISC_E_NULL;
+        if (ban) { a.ban_ids = reinterpret_cast<const long long *>(ban->ids); a.ban_cnt = ban->cnt; a.ban_ld = ban->ld; }
     }
     const int threads = 64 * a.S * J, MR = rows_mr(M), nt = g_rows_nt.load();
     const size_t lds = (size_t)nslice * MR * ROWS_SK * sizeof(float);
     if (lds > ROWS_LDS_MAX) return ISC_E_SHAPE;
+    const RVocabArgs a0 = a;                               // (the kernels without a list take the block without it)
 #define RV_LAUNCH(MRV, NPV)                                                                                     \
     do {                                                                                                        \
-        if (nt) ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, true>), a.n_tile, threads, lds, st, a);                  \
-        else ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, false>), a.n_tile, threads, lds, st, a);                    \
+        if (a.ban_ids) {                                                                                        \
+            if (nt) ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, true, true>), a.n_tile, threads, lds, st, a);        \
+            else ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, false, true>), a.n_tile, threads, lds, st, a);          \
+        } else if (nt) ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, true, false>), a.n_tile, threads, lds, st, a0);   \
+        else ROWS_LAUNCH((rows_vocab_kernel<MRV, NPV, false, false>), a.n_tile, threads, lds, st, a0);            \
     } while (0)
 #define RV_NP(MRV)                                                                          \
     do {                                                                                    \
@@ -1220,7 +1256,13 @@ extern "C" int isc_rows_step_supported(const isc_step_plan *p) {
         if (rc__) return rc__; \
     } while (0)
 
-extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, void *stream) {
+static int rows_ban_check(const isc_rows_ext *x, const isc_rows_ban *ban) {
+    if (!x || !ban || !ban->ids || !ban->cnt) return ISC_E_NULL;
+    if (ban->ld < 1 || x->beam <= 0) return ISC_E_SHAPE;
+    return ISC_OK;
+}
+
+static int rows_step(const isc_step_plan *p, const isc_rows_ext *x, const isc_rows_ban *ban, void *stream) {
     if (!p || !x) return ISC_E_NULL;
     if (!isc_rows_step_supported(p)) return ISC_E_SHAPE;
     if (!p->pmax || !p->psum || !p->pidx) return ISC_E_NULL;
@@ -1271,8 +1313,19 @@ extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, 
                       nullptr, nullptr, 0, 1, skip, st));
     }
     RET(rows_vocab(p->h2, H, p->W_cls, H, p->b_cls, rows, V, H, x->stats_tile, p->pmax, p->psum, p->pidx, p->logits,
-                   p->ld_logits, x, st));
+                   p->ld_logits, x, st, ban));
     return ISC_OK;
+}
+
+extern "C" int isc_rows_step_fwd(const isc_step_plan *p, const isc_rows_ext *x, void *stream) {
+    return rows_step(p, x, nullptr, stream);
+}
+
+extern "C" int isc_rows_step_banned_fwd(const isc_step_plan *p, const isc_rows_ext *x, const isc_rows_ban *ban,
+                                        void *stream) {
+    if (!p) return ISC_E_NULL;
+    RET(rows_ban_check(x, ban));
+    return rows_step(p, x, ban, stream);
 }
 
 // Single kernels of the step behind their own entry points (tests, tools/rows_lab.py)
@@ -1282,4 +1335,12 @@ extern "C" int isc_rows_vocab_fwd(const float *h, int ldh, const float *W, int l
     if (!ext) return ISC_E_NULL;
     return rows_vocab(h, ldh, W, ldw, bias, M, V, K, ext->stats_tile, part_max, part_sum, part_idx, logits, ld_logits,
                       ext, (hipStream_t)stream);
+}
+
+extern "C" int isc_rows_vocab_banned_fwd(const float *h, int ldh, const float *W, int ldw, const float *bias, int M, int V,
+                                         int K, float *part_max, float *part_sum, int32_t *part_idx, float *logits,
+                                         int64_t ld_logits, const isc_rows_ext *ext, const isc_rows_ban *ban, void *stream) {
+    RET(rows_ban_check(ext, ban));
+    return rows_vocab(h, ldh, W, ldw, bias, M, V, K, ext->stats_tile, part_max, part_sum, part_idx, logits, ld_logits,
+                      ext, (hipStream_t)stream, ban);
 }

@@ -692,10 +692,12 @@ class Detector(nn.Module):
             cache[fn] = lab
         return labels
 
-    def sample(self, fc_feats, att_feats, sentis_tensor=None, beam_size=3, decoding_constraint=1):
+    def sample(self, fc_feats, att_feats, sentis_tensor=None, beam_size=3, decoding_constraint=1, no_repeat_ngram=0,
+               min_len=0):
         """One image: detect its sentiment, then beam search (decoder.py:182-192).  sentis_tensor=None: the image's
         sentiment words are derived on the device from its detected concepts (set_concept_detector with a table) and the
-        search is queued behind them without a host read; without a table ValueError."""
+        search is queued behind them without a host read; without a table ValueError.  `no_repeat_ngram` / `min_len`: the
+        beam search's controls (Captioner.sample_batch)."""
         self.eval()
         if sentis_tensor is None:
             if self.__dict__.get('concept_detector') is None or self.__dict__.get('senti_table') is None:
@@ -706,11 +708,12 @@ class Detector(nn.Module):
         # search's own read-back instead of draining the device between the two (tools/eval_loop_probe.py)
         senti_label, _, _ = self.senti_detector.sample_device(self._detector_input(att_feats), self.senti_threshold)
         captions, _ = self.captioner.sample(fc_feats, att_feats, sentis_tensor, senti_label, beam_size,
-                                            decoding_constraint, self.max_seq_len)
+                                            decoding_constraint, self.max_seq_len, no_repeat_ngram=no_repeat_ngram,
+                                            min_len=min_len)
         return captions, self.senti_detector.names(senti_label)
 
     def sample_sentiments(self, fc_feats, att_feats, sentis_tensor=None, sentiments=None, beam_size=3,
-                          decoding_constraint=1):
+                          decoding_constraint=1, no_repeat_ngram=0, min_len=0):
         """One image captioned under several sentiments at once: `sentiments` is a list of category names (default: all of
         the detector's sentiment_categories, in their order); the searches share the image's region tensors
         (Captioner.sample_sentiments).  The sentiment words are `sentis_tensor` or, when None, derived from the image's
@@ -738,7 +741,8 @@ class Detector(nn.Module):
         labels = ops.upload([[cats.index(s) for s in names]], torch.int64, fc_feats.device)       # [1, S]
         captions, _, _ = self.captioner.sample_sentiments(fc_feats.reshape(1, -1), att_feats, sentis_tensor.reshape(1, -1),
                                                           labels, beam_size, decoding_constraint, self.max_seq_len,
-                                                          _labels_known=True)
+                                                          _labels_known=True, no_repeat_ngram=no_repeat_ngram,
+                                                          min_len=min_len)
         return dict(zip(names, captions[0])), self.senti_detector.names(detected)
 
     def set_encoder(self, enc):
@@ -747,7 +751,8 @@ class Detector(nn.Module):
         self.__dict__['encoder'] = enc
         return self
 
-    def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14, sentiments=None):
+    def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14, sentiments=None, no_repeat_ngram=0,
+                     min_len=0):
         """One image from its pixels: uint8 [H, W, 3] / [H, W] as decoded (the normalisation is fused into the encoder's
         first kernel) or a `preprocess`ed fp32 tensor [3, H, W] -> encoder -> sample(fc, att).  The sentiment words come
         from the concept detector (set_concept_detector with a table); no host read between the encoder and the search.
@@ -762,5 +767,6 @@ class Detector(nn.Module):
             else:
                 fc, att = enc.encode_uint8(image, att_size)
         if sentiments is not None:
-            return self.sample_sentiments(fc, att, None, sentiments, beam_size, decoding_constraint)
-        return self.sample(fc, att, None, beam_size, decoding_constraint)
+            return self.sample_sentiments(fc, att, None, sentiments, beam_size, decoding_constraint, no_repeat_ngram,
+                                          min_len)
+        return self.sample(fc, att, None, beam_size, decoding_constraint, no_repeat_ngram, min_len)

@@ -645,20 +645,25 @@ def rows_step_supported(plan):
     return bool(_lib.load().isc_rows_step_supported(C.byref(plan)))
 
 
-def rows_step_fwd(plan, ext):
-    """One decode step on <= 8 rows from a prepared isc_step_plan + isc_rows_ext (csrc/rows.hip: five launches)."""
+def rows_step_fwd(plan, ext, ban=None):
+    """One decode step on <= 8 rows from a prepared isc_step_plan + isc_rows_ext (csrc/rows.hip: five launches); `ban`
+    (an isc_rows_ban): the rows' ban lists in the tile candidates (isc_rows_step_banned_fwd)."""
+    if ban is not None:
+        return check(_lib.load().isc_rows_step_banned_fwd(C.byref(plan), C.byref(ext), C.byref(ban), stream()),
+                     'isc_rows_step_banned_fwd')
     check(_lib.load().isc_rows_step_fwd(C.byref(plan), C.byref(ext), stream()), 'isc_rows_step_fwd')
 
 
-def rows_vocab_fwd(h, W, bias, part_max, part_sum, part_idx, ext, logits=None):
+def rows_vocab_fwd(h, W, bias, part_max, part_sum, part_idx, ext, logits=None, ban=None):
     lib = _lib.load()
     M, K = h.shape
     V = W.shape[0]
     assert h.stride(1) == 1 and W.stride(1) == 1
-    check(lib.isc_rows_vocab_fwd(h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr(), M, V, K,
-                                 part_max.data_ptr(), part_sum.data_ptr(), part_idx.data_ptr(), ptr(logits),
-                                 logits.stride(0) if logits is not None else 0, C.byref(ext), stream()),
-          'isc_rows_vocab_fwd')
+    args = (h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr(), M, V, K, part_max.data_ptr(),
+            part_sum.data_ptr(), part_idx.data_ptr(), ptr(logits), logits.stride(0) if logits is not None else 0, C.byref(ext))
+    if ban is not None:
+        return check(lib.isc_rows_vocab_banned_fwd(*args, C.byref(ban), stream()), 'isc_rows_vocab_banned_fwd')
+    check(lib.isc_rows_vocab_fwd(*args, stream()), 'isc_rows_vocab_fwd')
 
 
 def beam_select(args):
@@ -961,6 +966,53 @@ def beam_topk(logits, part_max, part_sum, last_word, beam, pad_id, sos_id, unk_i
                             n_tile, rows, V, beam, last_word.data_ptr(), pad_id, sos_id, unk_id,
                             int(mask_special), int(decoding_constraint), top_val.data_ptr(),
                             top_idx.data_ptr(), stream()), 'isc_beam_topk')
+
+
+def beam_topk_banned(logits, part_max, part_sum, last_word, beam, pad_id, sos_id, unk_id, mask_special,
+                     decoding_constraint, ban_ids, ban_cnt, top_val, top_idx):
+    """beam_topk with the rows' ban lists (isc_beam_topk_banned): ban_ids int64 [rows, ld], ban_cnt int32 [rows]."""
+    lib = _lib.load()
+    rows, V = logits.shape
+    n_tile = part_max.shape[1]
+    assert ban_ids.dtype == torch.int64 and ban_cnt.dtype == torch.int32 and ban_ids.stride(1) == 1
+    check(lib.isc_beam_topk_banned(logits.data_ptr(), logits.stride(0), part_max.data_ptr(), part_sum.data_ptr(),
+                                   n_tile, rows, V, beam, last_word.data_ptr(), pad_id, sos_id, unk_id,
+                                   int(mask_special), int(decoding_constraint), ban_ids.data_ptr(), ban_cnt.data_ptr(),
+                                   ban_ids.stride(0), top_val.data_ptr(), top_idx.data_ptr(), stream()),
+          'isc_beam_topk_banned')
+
+
+def beam_ngram_ban(args):
+    """The ban lists of a beam step from its candidate tables (isc_beam_ngram_ban)."""
+    check(_lib.load().isc_beam_ngram_ban(C.byref(args), stream()), 'isc_beam_ngram_ban')
+
+
+def check_beam_controls(no_repeat_ngram, min_len, max_seq_len, vocab_size, beam, device_merge):
+    """The beam search's keywords `no_repeat_ngram` / `min_len`, checked before anything touches the device.  Returns
+    them as plain ints; (0, 0) is the search without controls and asks nothing of the other arguments.  With a control on:
+    vocab_size > max_seq_len + 4 + beam, the device-side merge (beam <= 8), and max_seq_len <= 256 (isc_beam_ngram_ban's
+    bound, which the general merge alone does not have) - ValueError otherwise.  A `beam` that is no integer is left to the
+    caller's own check."""
+    def integer(name, v, lo, hi):
+        if isinstance(v, bool) or not hasattr(v, '__index__') or not lo <= int(v) <= hi:
+            raise ValueError('%s must be an integer in [%d, %d], got %r' % (name, lo, hi, v))
+        return int(v)
+    n = integer('no_repeat_ngram', no_repeat_ngram, 0, 4)
+    m = integer('min_len', min_len, 0, int(max_seq_len))
+    if n == 0 and m == 0:
+        return 0, 0
+    beam = int(beam) if hasattr(beam, '__index__') and not isinstance(beam, bool) else 1
+    if vocab_size <= int(max_seq_len) + 4 + int(beam):
+        raise ValueError('no_repeat_ngram / min_len can ban up to max_seq_len + 4 words of a step: a vocabulary of %d words '
+                         'leaves fewer than beam_size = %d candidates at max_seq_len = %d'
+                         % (vocab_size, beam, max_seq_len))
+    if not device_merge or int(beam) > 8:
+        raise ValueError('no_repeat_ngram / min_len are not built for the host merge (beam_device_merge = False or '
+                         'beam_size > 8): the ban lists are formed on the device, behind the device-side merge')
+    if int(max_seq_len) > 256:
+        raise ValueError('no_repeat_ngram / min_len are not built for max_seq_len = %d > 256 (the ban-list kernel tests a '
+                         'candidate in chunks of 64 positions up to 256)' % max_seq_len)
+    return n, m
 
 
 def beam_merge(args):
