@@ -694,6 +694,16 @@ typedef struct {
 } isc_rows_ban;
 int isc_rows_stats_tile(int V);
 int isc_rows_step_supported(const isc_step_plan *plan_host);
+/* The same answer from a plan's integers alone, and the launches' own shape conditions one by one (the launch functions
+ * take their geometry from the code behind these: a step isc_rows_step_supported accepts is a step all five launches
+ * take).  Host arithmetic only: nothing is issued, no pointer is read.  1 = accepted.
+ *  - isc_rows_vocab_supported: the classifier on M rows of width K over V columns at isc_rows_stats_tile(V);
+ *  - isc_rows_lstm_supported: an LSTM cell of H units over up to three K-segments (0 = absent), each cut at 256;
+ *  - isc_rows_linear_supported: the grouped projections of K inputs onto Ntot outputs in all. */
+int isc_rows_shape_supported(int rows, int H, int E, int A, int W, int V, int R, int Mw, int has_tab);
+int isc_rows_vocab_supported(int M, int V, int K);
+int isc_rows_lstm_supported(int M, int H, int K0, int K1, int K2);
+int isc_rows_linear_supported(int M, int K, int Ntot);
 int isc_rows_step_fwd(const isc_step_plan *plan_host, const isc_rows_ext *ext_host, void *stream);
 int isc_rows_step_banned_fwd(const isc_step_plan *plan_host, const isc_rows_ext *ext_host, const isc_rows_ban *ban_host,
                              void *stream);
@@ -709,6 +719,12 @@ int isc_rows_vocab_banned_fwd(const float *h, int ldh, const float *W, int ldw, 
  * keep from step to step), 2 = every stream non-temporal.  Returns the previous value. */
 int isc_set_rows_nt(int mode);
 long long isc_rows_launches(void);    /* launches of rows kernels so far (tests assert the path was taken) */
+/* Which instantiation the last launches took (tests assert the route of every launch they make).  Writes the most recent
+ * min(n, 16, launches so far) records, oldest first, 8 ints each: kernel (0 = rows_lstm_kernel, 1 = rows_linear_kernel,
+ * 2 = rows_scan_gate_kernel, 3 = rows_vocab_kernel), MR (0 for the scan), UPW (LSTM) / NP (classifier) / 1 when every
+ * region is in flight at once (scan), NT, BAN, S, J, K-slices.  Returns the launches recorded so far; `out` may be
+ * NULL.  Host bookkeeping: reading touches no device. */
+long long isc_rows_routes(int32_t *out, int n);
 /* isc_attn_scan_gate_fwd (and with it isc_step_fwd's gated scan) runs launches of up to this many rows on the rows scan
  * kernel - one 1024-thread workgroup per row, the row's rows of P / V / G in flight at once - when the shape is its own
  * (v / s not wanted on their own, R <= isc_set_rows_scan_regions, Mw <= 12, A = D <= 512); default 256, 0 = never (attn_scan_gate_kernel walks

@@ -289,6 +289,11 @@ SIGNATURES = {
     'isc_step_bwd': (C.c_int, [C.POINTER(StepBwdPlan), C.c_void_p]),
     'isc_rows_stats_tile': (C.c_int, [C.c_int]),
     'isc_rows_step_supported': (C.c_int, [C.POINTER(StepPlan)]),
+    'isc_rows_shape_supported': (C.c_int, [C.c_int] * 9),
+    'isc_rows_vocab_supported': (C.c_int, [C.c_int] * 3),
+    'isc_rows_lstm_supported': (C.c_int, [C.c_int] * 5),
+    'isc_rows_linear_supported': (C.c_int, [C.c_int] * 3),
+    'isc_rows_routes': (C.c_longlong, [C.POINTER(C.c_int32), C.c_int]),
     'isc_rows_step_fwd': (C.c_int, [C.POINTER(StepPlan), C.POINTER(RowsExt), C.c_void_p]),
     'isc_rows_vocab_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RowsExt),

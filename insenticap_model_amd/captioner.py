@@ -432,21 +432,28 @@ class Captioner(nn.Module):
 
     def _rows_step_ok(self, rows, P):
         """The conditions of isc_rows_step_supported that are known before a plan exists (both attentions with the
-        pre-projected gate rows, equal widths <= 512); `self.rows_step = False` keeps the general kernels."""
+        pre-projected gate rows, equal widths <= 512, and the library's own word on the widths and the vocabulary:
+        isc_rows_shape_supported); `self.rows_step = False` keeps the general kernels."""
         st = self.settings
         E, A, Wd, H = st['feat_emb_dim'], st['att_hid_dim'], st['word_emb_dim'], st['rnn_hid_dim']
         return (getattr(self, 'rows_step', True) and 0 < rows <= self.ROWS_STEP_MAX and not ops.TIMER.armed
                 and self._rows_vocab_ok()
                 and ops.TIMER.arm_step is None and getattr(P, 'gate_Gc', None) is not None
                 and getattr(P, 'gate_Gs', None) is not None and A == E == Wd and A <= 512 and A % 4 == 0 and H % 4 == 0
-                and H <= 1024)
+                and H <= self.ROWS_STEP_MAX_H
+                and ops.rows_shape_supported(rows, H, E, A, Wd, self.vocab_size, has_tab=getattr(P, 'tab', None) is not None))
+
+    ROWS_STEP_MAX_H = 1024         # the widest LSTM the searches and roll-outs send to the few-row kernels (the kernels
+                                   # themselves reach 1280 at V <= 4096: isc_rows_shape_supported; nothing end to end runs there)
 
     def _rows_vocab_ok(self):
         """The few-row classifier keeps statistics per isc_rows_stats_tile(V) <= 64 columns and isc_beam_select holds at
-        most 256 tile lists (64 lanes x 4): vocabularies beyond 16384 words take the general kernels."""
+        most 256 tile lists (64 lanes x 4): vocabularies beyond 16384 words take the general kernels.  So do the
+        vocabularies whose tile the classifier cannot hold at this LSTM width (isc_rows_vocab_supported: beyond 8192 words
+        from H = 516 on): the general kernels take them, nothing raises halfway through a step."""
         V = self.vocab_size
         tw = ops.rows_stats_tile(V)
-        return tw > 0 and (V + tw - 1) // tw <= 256
+        return tw > 0 and (V + tw - 1) // tw <= 256 and ops.rows_vocab_supported(1, V, self.settings['rnn_hid_dim'])
 
     def _alloc_step_ws(self, rows, P, stats_tile=128):
         st = self.settings

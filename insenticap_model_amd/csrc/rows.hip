@@ -21,6 +21,7 @@
 //   * the gated attention scan runs one 1024-thread workgroup per row with every region's loads in flight at once.
 // All arithmetic is exact fp32 FMA in a fixed order.
 #include <atomic>
+#include <mutex>
 
 #include "common.h"
 
@@ -192,6 +193,93 @@ extern "C" int isc_set_rows_nt(int mode) { return g_rows_nt.exchange(mode < 0 ? 
 static std::atomic<long long> g_rows_launches{0};
 extern "C" long long isc_rows_launches(void) { return g_rows_launches.load(); }
 #define ROWS_LDS_MAX 110000
+
+// Which instantiation each launch took (tests; host side only, nothing on the device knows of it): the last
+// ROWS_ROUTE_RING launches as (kernel, MR, UPW | NP | single, NT, BAN, S, J, slices); kernel 0 = rows_lstm_kernel,
+// 1 = rows_linear_kernel, 2 = rows_scan_gate_kernel (MR = 0; third field 1 = every region in flight at once), 3 =
+// rows_vocab_kernel.
+#define ROWS_ROUTE_RING 16
+#define ROWS_ROUTE_INTS 8
+static std::mutex g_rows_route_mu;
+static int g_rows_route[ROWS_ROUTE_RING][ROWS_ROUTE_INTS];
+static long long g_rows_route_n = 0;
+static void rows_note_route(int kernel, int mr, int x, int nt, int ban, int S, int J, int nslice) {
+    std::lock_guard<std::mutex> lk(g_rows_route_mu);
+    int *r = g_rows_route[g_rows_route_n % ROWS_ROUTE_RING];
+    r[0] = kernel; r[1] = mr; r[2] = x; r[3] = nt; r[4] = ban; r[5] = S; r[6] = J; r[7] = nslice;
+    ++g_rows_route_n;
+}
+extern "C" long long isc_rows_routes(int32_t *out, int n) {
+    std::lock_guard<std::mutex> lk(g_rows_route_mu);
+    if (out && n > 0) {
+        long long have = g_rows_route_n < ROWS_ROUTE_RING ? g_rows_route_n : ROWS_ROUTE_RING;
+        if (n < have) have = n;
+        for (long long i = 0; i < have; ++i)
+            for (int k = 0; k < ROWS_ROUTE_INTS; ++k)
+                out[i * ROWS_ROUTE_INTS + k] = g_rows_route[(g_rows_route_n - have + i) % ROWS_ROUTE_RING][k];
+    }
+    return g_rows_route_n;
+}
+
+// ------------------------------------------------------------------ launch geometry, decided in one place
+// What a launch function launches and what isc_rows_step_supported promises come from these: a shape the predicate
+// accepts is a shape every one of the five launches takes.
+static int rows_mr(int M) { return M <= 2 ? 2 : M <= 4 ? 4 : M <= 6 ? 6 : 8; }
+struct RowsGrid {
+    int S, J, X;                     // K-slices in flight, column / unit groups per workgroup, UPW (LSTM) or NP (classifier)
+};
+static bool rows_slices_fit(int nslice, int M) {
+    return nslice >= 1 && nslice <= ROWS_MAX_SLICE && (size_t)nslice * rows_mr(M) * ROWS_SK * sizeof(float) <= ROWS_LDS_MAX;
+}
+static int rows_nslice(int K, int cut_shift) { return K > 0 ? (K + (1 << cut_shift) - 1) >> cut_shift : 0; }
+// LSTM cell over `nslice` slices of 256: units per workgroup U = J * UPW - about 256 workgroups, at most 8 streaming waves,
+// U * MR <= 64 epilogue lanes
+static bool rows_lstm_grid(int nslice, int M, int H, RowsGrid &r) {
+    if (M < 1 || M > ROWS_MAX || H < 1 || !rows_slices_fit(nslice, M)) return false;
+    const int MR = rows_mr(M);
+    r.S = nslice < 8 ? nslice : 8;
+    int want = (H + 255) / 256;                       // units per workgroup that fill 256 CUs once
+    if (want < 1) want = 1;
+    int J = 8 / r.S;
+    if (J < 1) J = 1;
+    int upw = 1;
+    if (J > want) J = want;
+    if (J < want) upw = 2;
+    while (J > 1 && J * upw * MR > 64) --J;
+    if (J * upw * MR > 64) upw = 1;
+    r.J = J; r.X = upw;
+    return true;
+}
+// grouped projections: slices of 128 from K = 256 on (twice the waves per output column: the launch is latency-bound)
+static int rows_linear_cut_shift(int K) { return K >= 256 ? 7 : 8; }
+static bool rows_linear_grid(int K, int M, int Ntot, RowsGrid &r) {
+    const int nslice = rows_nslice(K, rows_linear_cut_shift(K));
+    if (M < 1 || M > ROWS_MAX || Ntot < 4 || !rows_slices_fit(nslice, M)) return false;
+    r.S = nslice < 8 ? nslice : 8;
+    int J = 8 / r.S;
+    if (J < 1) J = 1;
+    while (J > 1 && (Ntot / 4 + J - 1) / J < 192) --J;     // enough workgroups for the chip before fat ones
+    r.J = J; r.X = 1;
+    return true;
+}
+// classifier: a workgroup holds a tile of TW columns as J waves x NP passes x 4 lane groups, NP <= 4.  J = 8 / S falls
+// with the width (K > 512: J = 2, K > 1024: J = 1), and with it the widest tile the kernel can hold: a tile beyond
+// 16 * J columns (V > 4096 * J) is refused, here and therefore by the predicate.
+static bool rows_vocab_grid(int M, int V, int K, int TW, RowsGrid &r) {
+    const int nslice = rows_nslice(K, 8);
+    if (M < 1 || M > ROWS_MAX || V < 1 || TW < 16 || TW > 64 || (TW & 3) || !rows_slices_fit(nslice, M)) return false;
+    r.S = nslice < 8 ? nslice : 8;
+    int J = 8 / r.S;
+    if (J < 1) J = 1;
+    if (J > 4) J = 4;                                      // the kernel ranks a tile of at most 16 * NP columns
+    const int passes = (TW + 3) / 4;
+    if (J > passes) J = passes;
+    int np = (passes + J - 1) / J;
+    if (16 * np < TW) np = (TW + 15) / 16;
+    if (np > 4) return false;
+    r.J = J; r.X = np;
+    return true;
+}
 
 // ------------------------------------------------------------------ LSTM cell
 // gates[m, g*H + u] = sum over slices; c' = sig(f) c + sig(i) tanh(g), h' = sig(o) tanh(c')  (captioner.py:175,181)
@@ -457,8 +545,6 @@ static int rows_make_segs(RSegs &g, const float *const *A, const int *lda, const
     return n;
 }
 
-static int rows_mr(int M) { return M <= 2 ? 2 : M <= 4 ? 4 : M <= 6 ? 6 : 8; }
-
 template <typename K>
 static int rows_lds_attr(K kernel, std::atomic<bool> &done) {
     if (!done.load()) {
@@ -503,18 +589,10 @@ static int rows_lstm(const float *const *A, const int *lda, const float *const *
     if ((b_ih == nullptr) != (b_hh == nullptr)) return ISC_E_NULL;
     if (tab && !tab_ids) return ISC_E_NULL;
     const int MR = rows_mr(M);
-    a.S = nslice < 8 ? nslice : 8;
-    // units per workgroup U = J * UPW: about 256 workgroups, at most 8 streaming waves, U * MR <= 64 epilogue lanes
-    int want = (H + 255) / 256;                       // units per workgroup that fill 256 CUs once
-    if (want < 1) want = 1;
-    int J = 8 / a.S;
-    if (J < 1) J = 1;
-    int upw = 1;
-    if (J > want) J = want;
-    if (J < want) upw = 2;
-    while (J > 1 && J * upw * MR > 64) --J;
-    if (J * upw * MR > 64) upw = 1;
-    a.J = J;
+    RowsGrid gr;
+    if (!rows_lstm_grid(nslice, M, H, gr)) return ISC_E_SHAPE;
+    const int J = gr.J, upw = gr.X;
+    a.S = gr.S; a.J = J;
     a.has_src = src != nullptr;
     a.M = M; a.H = H; a.row_div = row_div > 1 ? row_div : 1; a.skip = skip;
     a.rc = rows_const();
@@ -524,12 +602,13 @@ static int rows_lstm(const float *const *A, const int *lda, const float *const *
     a.tab_ids = reinterpret_cast<const long long *>(tab_ids); a.tab_ids_stride = tab_ids_stride;
     const int U = J * upw, grid = (H + U - 1) / U, threads = 64 * (a.S * J + 1);
     const size_t lds = (size_t)nslice * MR * ROWS_SK * sizeof(float);
-    if (lds > ROWS_LDS_MAX) return ISC_E_SHAPE;
+    const int nt = g_rows_nt.load() >= 2;
     int rc;
-    if (g_rows_nt.load() >= 2) rc = upw == 2 ? rows_lstm_launch<2, true>(a, grid, threads, lds, st) : rows_lstm_launch<1, true>(a, grid, threads, lds, st);
+    if (nt) rc = upw == 2 ? rows_lstm_launch<2, true>(a, grid, threads, lds, st) : rows_lstm_launch<1, true>(a, grid, threads, lds, st);
     else rc = upw == 2 ? rows_lstm_launch<2, false>(a, grid, threads, lds, st) : rows_lstm_launch<1, false>(a, grid, threads, lds, st);
     if (rc) return rc;
     ISC_LAUNCH_CHECK();
+    rows_note_route(0, MR, upw, nt, 0, a.S, J, nslice);
     ++g_rows_launches;
     return ISC_OK;
 }
@@ -616,7 +695,7 @@ static int rows_linear3(const float *A, int lda, int K, int M, const float *cons
     RLinArgs a = {};
     const int ldw = K, ind = 0;
     // slices of 128: twice the waves per output column, the launch is latency-bound (3 MB of weights)
-    const int nslice = rows_make_segs(a.g, &A, &lda, &W[0], &ldw, &K, &ind, 1, K >= 256 ? 7 : 8);
+    const int nslice = rows_make_segs(a.g, &A, &lda, &W[0], &ldw, &K, &ind, 1, rows_linear_cut_shift(K));
     if (nslice < 1) return ISC_E_SHAPE;
     int Ntot = 0;
     for (int i = 0; i < nprob; ++i) {
@@ -628,14 +707,12 @@ static int rows_linear3(const float *A, int lda, int K, int M, const float *cons
     a.nprob = nprob; a.M = M; a.skip = skip;
     a.rc = rows_const();
     if (!a.rc) return ISC_E_STATE;
-    a.S = nslice < 8 ? nslice : 8;
-    int J = 8 / a.S;
-    if (J < 1) J = 1;
-    while (J > 1 && (Ntot / 4 + J - 1) / J < 192) --J;     // enough workgroups for the chip before fat ones
-    a.J = J;
+    RowsGrid gr;
+    if (!rows_linear_grid(K, M, Ntot, gr)) return ISC_E_SHAPE;
+    const int J = gr.J;
+    a.S = gr.S; a.J = J;
     const int grid = (Ntot / 4 + J - 1) / J, threads = 64 * a.S * J, MR = rows_mr(M);
     const size_t lds = (size_t)nslice * MR * ROWS_SK * sizeof(float);
-    if (lds > ROWS_LDS_MAX) return ISC_E_SHAPE;
     switch (MR) {
         case 2: ROWS_LAUNCH((rows_linear_kernel<2>), grid, threads, lds, st, a); break;
         case 4: ROWS_LAUNCH((rows_linear_kernel<4>), grid, threads, lds, st, a); break;
@@ -643,6 +720,7 @@ static int rows_linear3(const float *A, int lda, int K, int M, const float *cons
         default: ROWS_LAUNCH((rows_linear_kernel<8>), grid, threads, lds, st, a); break;
     }
     ISC_LAUNCH_CHECK();
+    rows_note_route(1, MR, 1, 0, 0, a.S, J, nslice);
     ++g_rows_launches;
     return ISC_OK;
 }
@@ -840,16 +918,10 @@ static int rows_vocab(const float *h, int ldh, const float *W, int ldw, const fl
     const int ind = 0;
     const int nslice = rows_make_segs(a.g, &h, &ldh, &W, &ldw, &K, &ind, 1, 8);
     if (nslice < 1) return ISC_E_SHAPE;
-    a.S = nslice < 8 ? nslice : 8;
-    int J = 8 / a.S;
-    if (J < 1) J = 1;
-    if (J > 4) J = 4;                                      // the kernel ranks a tile of at most 16 * NP columns
-    const int passes = (TW + 3) / 4;
-    if (J > passes) J = passes;
-    int np = (passes + J - 1) / J;
-    if (16 * np < TW) np = (TW + 15) / 16;
-    if (np > 4) return ISC_E_SHAPE;
-    a.J = J; a.M = M; a.V = V; a.TW = TW; a.n_tile = (V + TW - 1) / TW; a.skip = x ? x->live_in : nullptr;
+    RowsGrid gr;
+    if (!rows_vocab_grid(M, V, K, TW, gr)) return ISC_E_SHAPE;
+    const int J = gr.J, np = gr.X;
+    a.S = gr.S; a.J = J; a.M = M; a.V = V; a.TW = TW; a.n_tile = (V + TW - 1) / TW; a.skip = x ? x->live_in : nullptr;
     a.rc = rows_const();
     if (!a.rc) return ISC_E_STATE;
     a.bias = bias; a.pmax = pmax; a.psum = psum; a.pidx = pidx; a.logits = logits; a.ld_logits = ld_logits;
@@ -865,7 +937,6 @@ static int rows_vocab(const float *h, int ldh, const float *W, int ldw, const fl
     }
     const int threads = 64 * a.S * J, MR = rows_mr(M), nt = g_rows_nt.load();
     const size_t lds = (size_t)nslice * MR * ROWS_SK * sizeof(float);
-    if (lds > ROWS_LDS_MAX) return ISC_E_SHAPE;
     const RVocabArgs a0 = a;                               // (the kernels without a list take the block without it)
 #define RV_LAUNCH(MRV, NPV)                                                                                     \
     do {                                                                                                        \
@@ -884,6 +955,7 @@ static int rows_vocab(const float *h, int ldh, const float *W, int ldw, const fl
 #undef RV_NP
 #undef RV_LAUNCH
     ISC_LAUNCH_CHECK();
+    rows_note_route(3, MR, np, nt != 0, a.ban_ids != nullptr, a.S, J, nslice);
     ++g_rows_launches;
     return ISC_OK;
 }
@@ -1150,24 +1222,32 @@ __global__ __launch_bounds__(1024) void rows_scan_gate_kernel(const RScanArgs a)
 #undef RSTAMP_KID
 }
 
+#define ROWS_SCAN_LDS_MAX 150000
+static size_t rows_scan_lds(int R, int Mw, int A) {
+    return ((size_t)((R + 3) & ~3) + ((Mw + 3) & ~3) + (size_t)(32 + 4) * A + 16) * sizeof(float);
+}
+static bool rows_scan_shape_ok(int E, int A, int W, int R, int Mw) {
+    return A == E && A == W && A >= 4 && A <= 512 && (A & 3) == 0 && R >= 1 && Mw >= 1 && R <= (1 << 20) && Mw <= (1 << 20) &&
+           rows_scan_lds(R, Mw, A) <= ROWS_SCAN_LDS_MAX;
+}
 static bool rows_scan_ok(const isc_step_plan *p) {
-    return p->att_e && p->words_e && p->gate_Gc && p->gate_Gs && p->A == p->E && p->A == p->W && p->A <= 512 &&
-           (p->A & 3) == 0 && p->R >= 1 && p->Mw >= 1;
+    return p->att_e && p->words_e && p->gate_Gc && p->gate_Gs && rows_scan_shape_ok(p->E, p->A, p->W, p->R, p->Mw);
 }
 
 static int rows_scan_gate_launch(const RScanArgs &a, int rows, hipStream_t st) {
     if (!a.q[0] || !a.q[1] || !a.zh || !a.f || !a.w[0] || !a.w[1] || !a.b_c || !a.b_s || !a.w_g) return ISC_E_NULL;
-    const size_t lds = ((size_t)((a.R[0] + 3) & ~3) + ((a.R[1] + 3) & ~3) + (size_t)(32 + 4) * a.A + 16) * sizeof(float);
-    if (lds > 150000) return ISC_E_SHAPE;
+    const size_t lds = rows_scan_lds(a.R[0], a.R[1], a.A);
+    if (lds > ROWS_SCAN_LDS_MAX) return ISC_E_SHAPE;
     static std::atomic<bool> attr_set{false};
     if (!attr_set.load()) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rows_scan_gate_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150000);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_SCAN_LDS_MAX);
         if (e != hipSuccess) return (int)e;
         attr_set.store(true);
     }
     hipLaunchKernelGGL(rows_scan_gate_kernel, dim3(rows), dim3(1024), lds, st, a);
     ISC_LAUNCH_CHECK();
+    rows_note_route(2, 0, a.R[0] <= RS_NWC * RS_RPW && a.R[1] <= RS_NWS * RS_RPW, 0, 0, 0, 0, 0);
     ++g_rows_launches;
     return ISC_OK;
 }
@@ -1232,22 +1312,48 @@ int rows_scan_gate_try(const isc_scan_gate_args *g, int rows, hipStream_t st, in
 }
 
 // ------------------------------------------------------------------ the step
-extern "C" int isc_rows_step_supported(const isc_step_plan *p) {
-    if (!p) return 0;
-    if (p->rows < 1 || p->rows > ROWS_MAX) return 0;
-    if (!rows_scan_ok(p)) return 0;
-    if (p->g1 || p->g2 || p->out_mask || p->apply_logsoftmax || p->pair_rows_c) return 0;   // training / teacher-forced forms: isc_step_fwd
+// The pure predicates (host arithmetic only: nothing is issued, no pointer is read).
+extern "C" int isc_rows_vocab_supported(int M, int V, int K) {
+    RowsGrid gr;
+    if (K < 4 || (K & 3)) return 0;
+    return rows_vocab_grid(M, V, K, isc_rows_stats_tile(V), gr) ? 1 : 0;
+}
+// an LSTM cell launch over up to three K-segments (K_i = 0: absent), each cut at 256
+extern "C" int isc_rows_lstm_supported(int M, int H, int K0, int K1, int K2) {
+    RowsGrid gr;
+    if (K0 < 4 || K1 < 0 || K2 < 0 || ((K0 | K1 | K2) & 3)) return 0;
+    return rows_lstm_grid(rows_nslice(K0, 8) + rows_nslice(K1, 8) + rows_nslice(K2, 8), M, H, gr) ? 1 : 0;
+}
+extern "C" int isc_rows_linear_supported(int M, int K, int Ntot) {
+    RowsGrid gr;
+    if (K < 4 || (K & 3) || (Ntot & 3)) return 0;
+    return rows_linear_grid(K, M, Ntot, gr) ? 1 : 0;
+}
+// The widths and counts of a step that the five launches take: what isc_rows_step_supported says of a plan's integers.
+// The bound on H is the kernels' own: 2 ceil(H / 256) (+ ceil(W / 256) without the token table) <= 12 slices for the
+// att-LSTM, ceil(E / 256) + 2 ceil(H / 256) <= 12 for the lang-LSTM, ceil(H / 128) <= 12 for the projections - H <= 1280
+// in all - and the classifier's tile: V <= 4096 * min(4, 8 / ceil(H / 256)) (H <= 512: 16384, <= 1024: 8192, beyond: 4096).
+extern "C" int isc_rows_shape_supported(int rows, int H, int E, int A, int W, int V, int R, int Mw, int has_tab) {
+    if (rows < 1 || rows > ROWS_MAX) return 0;
+    if (H < 4 || (H & 3) || (E & 3) || (W & 3) || (A & 3)) return 0;
+    if (!rows_scan_shape_ok(E, A, W, R, Mw)) return 0;
     {   // the classifier's statistics tiles (<= 64 columns each) must fit isc_beam_select's register-resident tile lists
         // (64 lanes x 4 tiles): V <= 16384.  Larger vocabularies take the general kernels.
-        const int tw = isc_rows_stats_tile(p->V);
-        if (tw <= 0 || (p->V + tw - 1) / tw > 256) return 0;
+        const int tw = isc_rows_stats_tile(V);
+        if (tw <= 0 || (V + tw - 1) / tw > 256) return 0;
     }
-    if ((p->H & 3) || (p->E & 3) || (p->W & 3) || (p->A & 3)) return 0;
-    // slices: att-LSTM H (+ W) + H, lang-LSTM E + H + H, each cut at 256
-    const int s1 = (p->H + 255) / 256 * 2 + (p->tab ? 0 : (p->W + 255) / 256);
-    const int s2 = (p->E + 255) / 256 + (p->H + 255) / 256 * 2;
-    if (s1 > ROWS_MAX_SLICE || s2 > ROWS_MAX_SLICE || (p->H + 255) / 256 > ROWS_MAX_SLICE) return 0;
+    if (!isc_rows_lstm_supported(rows, H, H, has_tab ? 0 : W, H)) return 0;         // att-LSTM: h_lang (, xt), h_att
+    if (!isc_rows_linear_supported(rows, H, 3 * A)) return 0;
+    if (!isc_rows_lstm_supported(rows, H, E, H, H)) return 0;                       // lang-LSTM: f, h_att, h_lang
+    if (!isc_rows_vocab_supported(rows, V, H)) return 0;
     return 1;
+}
+
+extern "C" int isc_rows_step_supported(const isc_step_plan *p) {
+    if (!p) return 0;
+    if (!rows_scan_ok(p)) return 0;
+    if (p->g1 || p->g2 || p->out_mask || p->apply_logsoftmax || p->pair_rows_c) return 0;   // training / teacher-forced forms: isc_step_fwd
+    return isc_rows_shape_supported(p->rows, p->H, p->E, p->A, p->W, p->V, p->R, p->Mw, p->tab != nullptr);
 }
 
 #define RET(x)                 \

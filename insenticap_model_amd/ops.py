@@ -645,6 +645,35 @@ def rows_step_supported(plan):
     return bool(_lib.load().isc_rows_step_supported(C.byref(plan)))
 
 
+def rows_shape_supported(rows, H, E, A, W, V, R=1, Mw=1, has_tab=True):
+    """isc_rows_step_supported's answer from the widths and counts alone (isc_rows_shape_supported; nothing is issued)."""
+    return bool(_lib.load().isc_rows_shape_supported(int(rows), int(H), int(E), int(A), int(W), int(V), int(R), int(Mw),
+                                                     int(bool(has_tab))))
+
+
+def rows_vocab_supported(M, V, K):
+    """Whether the few-row classifier takes M rows of width K over V columns (isc_rows_vocab_supported)."""
+    return bool(_lib.load().isc_rows_vocab_supported(int(M), int(V), int(K)))
+
+
+ROWS_ROUTE_KERNELS = ('lstm', 'linear', 'scan', 'vocab')
+
+
+def rows_routes(n=0):
+    """(launches of rows kernels recorded so far, the last min(n, 16) of them, oldest first) - isc_rows_routes; a
+    record is (kernel name, MR, UPW | NP | single, NT, BAN, S, J, K-slices)."""
+    n = max(0, min(int(n), 16))
+    buf = (C.c_int32 * (8 * max(n, 1)))()
+    total = _lib.load().isc_rows_routes(buf, n)
+    have = min(n, total)
+    return total, [(ROWS_ROUTE_KERNELS[buf[8 * i]],) + tuple(buf[8 * i + 1:8 * i + 8]) for i in range(have)]
+
+
+def set_rows_nt(mode):
+    """Cache policy of the rows kernels' weight streams (isc_set_rows_nt: 0 / 1 / 2).  Returns the previous mode."""
+    return _lib.load().isc_set_rows_nt(int(mode))
+
+
 def rows_step_fwd(plan, ext, ban=None):
     """One decode step on <= 8 rows from a prepared isc_step_plan + isc_rows_ext (csrc/rows.hip: five launches); `ban`
     (an isc_rows_ban): the rows' ban lists in the tile candidates (isc_rows_step_banned_fwd)."""

@@ -82,20 +82,21 @@ def scan_fwd_ref(dt, P, V, q, w, w_bias=None, q2=None, row_ids=None):
 
 
 # ------------------------------------------------------------------------------------------------ tile statistics
-def tile_stats(x):
-    """(pmax, psum, pidx) per 128-column tile of the float32 rows x [M, V], made on the host: pmax the tile maximum
+def tile_stats(x, tile=TILE):
+    """(pmax, psum, pidx) per `tile`-column tile of the float32 rows x [M, V] (128: isc_vocab_fwd's; the few-row
+    classifier's is isc_rows_stats_tile(V)), made on the host: pmax the tile maximum
     (exact), psum = float32(sum in float64 of exp(x - pmax)), pidx the GLOBAL index of the tile maximum, the smallest on
     ties.  [M, n_tile] float32, float32, int32 - what isc_vocab_fwd leaves for its consumers."""
     x = x.detach().cpu()
     assert x.dtype == F32 and x.dim() == 2
     M, V = x.shape
-    nt = (V + TILE - 1) // TILE
-    pad = np.full((M, nt * TILE), -np.inf, dtype=np.float64)
+    nt = (V + tile - 1) // tile
+    pad = np.full((M, nt * tile), -np.inf, dtype=np.float64)
     pad[:, :V] = x.numpy()
-    t = pad.reshape(M, nt, TILE)
+    t = pad.reshape(M, nt, tile)
     pmax = t.max(axis=2)
     psum = np.exp(t - pmax[:, :, None]).sum(axis=2)
-    pidx = t.argmax(axis=2) + np.arange(nt)[None, :] * TILE          # numpy: the first maximum
+    pidx = t.argmax(axis=2) + np.arange(nt)[None, :] * tile          # numpy: the first maximum
     return (torch.from_numpy(pmax.astype(np.float32)), torch.from_numpy(psum.astype(np.float32)),
             torch.from_numpy(pidx.astype(np.int32)))
 

@@ -302,6 +302,47 @@ def test_a_vocabulary_beyond_the_tile_lists_takes_the_general_kernels():
     assert not ops.rows_step_supported(plan)           # the library says so too
 
 
+def test_a_vocabulary_the_classifier_cannot_hold_at_this_width_takes_the_general_kernels():
+    """H = 768 with V = 8196: the few-row classifier holds 16 columns per column group and has two groups at this width
+    (J = 8 / ceil(H / 256)): a tile of 32 columns, and isc_rows_stats_tile(8196) = 36.  isc_rows_step_supported and the Python gates used to accept the shape
+    and the step's fifth launch refused it (ISC_E_SHAPE from ops.rows_step_fwd, four launches issued): a beam search and
+    a 4-row greedy roll-out raised.  Now they complete on the general kernels - no launch of the few-row step - and equal
+    the same calls with the path switched off, under the criteria of the tests above; V = 8192 keeps the path."""
+    V, st = 8196, Wd.H_768
+    cap = _captioner(V, st, seed=2)
+    assert not cap._rows_vocab_ok() and not ops.rows_vocab_supported(5, V, st['rnn_hid_dim'])
+    assert _captioner(8192, st, seed=2)._rows_vocab_ok()
+    cap.enable_beam_graphs(False)
+    cap.enable_rollout_graphs(False)
+    d = _inputs(4, V, st, 7, seed=5)
+    res = {}
+    for on in (True, False):
+        cap.rows_step = on
+        n0 = _n()
+        with _region_walk_scan(True), torch.no_grad():     # (the general step's own use of the row scan kernel off: it counts too)
+            beams = cap.sample_batch(d['fc_feats'][:1], d['att_feats'][:1], d['senti_words'][:1], d['senti_labels'][:1], 3, 1, 20)
+            seq, lp, mk = cap(d['fc_feats'], d['att_feats'], d['cpt_words'], d['senti_words'], d['senti_labels'], 20, 1, mode='rl')
+        torch.cuda.synchronize()
+        assert _n() == n0                                   # nothing went to the few-row kernels
+        res[on] = (beams, seq.cpu(), lp.cpu(), mk.cpu())
+    (_, s1, i1), (_, s0, i0) = res[True][0], res[False][0]
+    assert i1 == i0
+    np.testing.assert_allclose(s1, s0, atol=2e-4)
+    assert torch.equal(res[True][1], res[False][1]) and torch.equal(res[True][3], res[False][3])
+    assert float((res[True][2] - res[False][2]).abs().max()) < 1e-4
+    # ... and with everything at its default (graphs, the general step's scan on the row kernel)
+    cap.rows_step = True
+    cap.enable_beam_graphs(True)
+    cap.enable_rollout_graphs(True)
+    for _ in range(2):
+        out = cap.sample_batch(d['fc_feats'][:1], d['att_feats'][:1], d['senti_words'][:1], d['senti_labels'][:1], 3, 1, 20)
+        for a, b, sa, sb in zip(out[2], i0, out[1], s0):
+            if a != b:      # a near-tie between the two scan kernels may reorder candidates: then the scores must tie too
+                assert abs(sa[0] - sb[0]) < 1e-3, (a, b, sa, sb)
+            else:
+                np.testing.assert_allclose(sa, sb, atol=2e-4)
+
+
 def test_beam_graphs_replay_equals_eager_on_this_path():
     cap = _captioner(10000, synth.DEFAULT_SETTINGS, seed=4)
     d = _inputs(1, 10000, synth.DEFAULT_SETTINGS, 36, seed=6)
