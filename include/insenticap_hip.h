@@ -509,6 +509,17 @@ typedef struct {
 } isc_beam_merge_args;
 
 int isc_beam_merge(const isc_beam_merge_args *args_host, void *stream);
+/* Diverse beam search (Vijayakumar et al. 2016; no reference counterpart): isc_beam_merge with the search's `beam` rows
+ * split into `groups` groups of B' = beam / groups ranks (group g owns ranks g B' .. (g + 1) B' - 1), handled in this
+ * order.  Group g's candidates, in insertion order: its parents by rank, an ended one carried as ONE candidate, a live
+ * one contributing its `beam` children in the row's top-`beam` order (at t == 0: the group's first row alone).  A
+ * child's key is (s_parent + (double)logp) - lambda * (double)c, c = candidates selected AT THIS STEP by the groups in
+ * front of g that appended the same token (carried ones appended nothing); a carried candidate's key is its score; one
+ * fp64 add, one multiply, one subtract, never contracted.  The group keeps the first B' of a stable descending sort by
+ * key; score_out holds the un-augmented sum.  done / live / gather as isc_beam_merge; new rows are group-major.
+ * One wave64 per search, a loop over the groups, no atomics beyond the live counter: bit-repeatable.
+ * groups < 1, beam % groups != 0, lambda negative or not finite -> ISC_E_SHAPE. */
+int isc_beam_merge_groups(const isc_beam_merge_args *args_host, int groups, double lambda, void *stream);
 /* State re-ordering of a beam step: out[p, r, :] = (gather[r] < rows ? state_next : state_cur)[p, gather[r] % rows, :]
  * for the `planes` [rows, H] planes of the recurrent state (h|c x layer), gather as written by isc_beam_merge. */
 int isc_beam_gather(const float *state_next, const float *state_cur, const int64_t *gather, float *out,
@@ -790,6 +801,12 @@ typedef struct {
     int32_t state_planes, H;
 } isc_beam_select_args;
 int isc_beam_select(const isc_beam_select_args *args_host, void *stream);
+/* isc_beam_select under isc_beam_merge_groups' rule: the same launch (tile-list merges, side waves, state re-ordering),
+ * its rank phase a chain of `groups` rounds - round g ranks group g's candidates by their keys, eight lanes per
+ * candidate, and leaves its B' winners' tokens in LDS for the rounds behind it.  groups == 1 (the plain search for any
+ * lambda) launches isc_beam_select's kernel.  Same refusals as isc_beam_select, and
+ * ISC_E_SHAPE for groups < 1, beam % groups != 0, lambda negative or not finite. */
+int isc_beam_select_groups(const isc_beam_select_args *args_host, int groups, double lambda, void *stream);
 
 /* Reverse-sweep counterpart (one BPTT step, see autograd.py): lang-LSTM cell backward, input-gradient
  * contractions, gate / scan backward, att-LSTM cell backward, recurrent gradients for step t-1.

@@ -311,6 +311,7 @@ SIGNATURES = {
     'isc_copy_multi': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     'isc_rows_launches': (C.c_longlong, []),
     'isc_beam_select': (C.c_int, [C.POINTER(BeamSelectArgs), C.c_void_p]),
+    'isc_beam_select_groups': (C.c_int, [C.POINTER(BeamSelectArgs), C.c_int, C.c_double, C.c_void_p]),
     'isc_vocab_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                 C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -341,6 +342,7 @@ SIGNATURES = {
     'isc_rollout_finalize_constrained': (C.c_int, [C.POINTER(RolloutStep), C.POINTER(SampleFilter),
                                                    C.POINTER(DecodeConstraints), C.c_void_p]),
     'isc_beam_merge': (C.c_int, [C.POINTER(BeamMergeArgs), C.c_void_p]),
+    'isc_beam_merge_groups': (C.c_int, [C.POINTER(BeamMergeArgs), C.c_int, C.c_double, C.c_void_p]),
     'isc_beam_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'isc_beam_topk': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,

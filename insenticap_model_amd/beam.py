@@ -137,13 +137,17 @@ class _VectorMerge:
 
 
 def beam_search_batch(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, graphs=True,
-                      share=False, no_repeat_ngram=0, min_len=0):
+                      share=False, no_repeat_ngram=0, min_len=0, groups=(1, 0.0)):
     """share: the rows of an image read ONE entry of its step-invariant tensors (nothing is expanded `beam`-fold); with
     senti_labels [I, S] an image is searched under S labels at once (Captioner.sample_sentiments: I*S searches).
     no_repeat_ngram (0 = off, up to 4): no n-gram twice in a candidate; min_len: no <EOS> before that many words.  Both
     act inside the per-step top-k (isc_beam_ngram_ban's lists); device-side merge only.  The two values arrive checked
-    (check_controls: the Captioner's public calls do it once, first thing)."""
-    ctrl = (no_repeat_ngram, min_len)
+    (check_controls: the Captioner's public calls do it once, first thing).
+    groups = (G, lambda), checked (check_groups): diverse beam search - the `beam` rows of a search form G groups of
+    beam / G ranks, handled in order; a child's key loses lambda for every candidate a group in front selected at this
+    step with the same token (isc_beam_merge_groups / isc_beam_select_groups; scores stay the model's log-probabilities,
+    results come group-major).  G = 1 is the plain search: same calls, same graph key."""
+    ctrl = _ctrl(no_repeat_ngram, min_len, groups)
     if (graphs and cap.__dict__.get('_beam_graphs') is not None and getattr(cap, 'beam_device_merge', True) and beam <= 8
             and ops.TIMER.arm_step is None and ops.graphs_allowed_here()):
         return _graphed_search(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share,
@@ -158,6 +162,19 @@ def check_controls(cap, beam, T, no_repeat_ngram, min_len):
         return (0, 0)
     return ops.check_beam_controls(no_repeat_ngram, min_len, T, cap.vocab_size, beam,
                                    getattr(cap, 'beam_device_merge', True))
+
+
+def check_groups(cap, beam, beam_groups, diversity):
+    """(beam_groups, diversity) as a checked (int, float), ValueError otherwise (ops.check_beam_groups); the defaults cost
+    two type looks."""
+    if beam_groups.__class__ is int and beam_groups == 1 and diversity.__class__ is float and diversity == 0.0:
+        return (1, 0.0)
+    return ops.check_beam_groups(beam_groups, diversity, beam, getattr(cap, 'beam_device_merge', True))
+
+
+def _ctrl(no_repeat_ngram, min_len, groups):
+    """The search's controls as one tuple: (no_repeat_ngram, min_len), and (G, lambda) behind them when G > 1."""
+    return (no_repeat_ngram, min_len) + (tuple(groups) if groups[0] > 1 else ())
 
 
 def _n_search(fc_feats, senti_labels):
@@ -215,7 +232,7 @@ def _replay(cap, entry, ins, T):
 
 
 def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam, decoding_constraint, T, share=False,
-                       no_repeat_ngram=0, min_len=0):
+                       no_repeat_ngram=0, min_len=0, groups=(1, 0.0)):
     """Captioner.sample_batch's short cut: a search whose graphs exist is one key look-up, the input copies, the replay
     and the read-back - none of the per-call set-up of the eager path (parameter dictionary, weights scope, mode walk:
     ~100 us of host time in front of a 1 ms search).  None when there is nothing to replay.  no_repeat_ngram / min_len: checked
@@ -227,7 +244,7 @@ def replay_if_captured(cap, fc_feats, att_feats, senti_words, senti_labels, beam
     if not (fc_feats.is_cuda and att_feats.is_cuda):
         return None
     ins = [cap._feat(fc_feats), cap._feat(att_feats), senti_words, senti_labels]
-    key = _graph_key(cap, ins, beam, decoding_constraint, T, share, (no_repeat_ngram, min_len))
+    key = _graph_key(cap, ins, beam, decoding_constraint, T, share, _ctrl(no_repeat_ngram, min_len, groups))
     entry = cache.get(key)
     if not isinstance(entry, tuple):
         return None
@@ -334,6 +351,8 @@ class _Search:
         H, Wd, V = cap.att_lstm.hidden_size, cap.settings['word_emb_dim'], cap.vocab_size
         rows = n_img * beam
         self.device_merge = getattr(cap, 'beam_device_merge', True) and beam <= 8
+        if ctrl[2:] and not self.device_merge:
+            raise ValueError('beam groups need the device-side merge (beam_device_merge, beam_size <= 8)')
         # <= 8 rows (one image's beam): the few-row step (csrc/rows.hip) - state re-ordering as an index on its loads,
         # per-tile candidates out of the classifier, top-k + merge in one launch (isc_beam_select): six launches per step.
         # The rows of an image share its step-invariant tensors there (isc_rows_ext.row_div): nothing is expanded.
@@ -425,11 +444,12 @@ class _Search:
             a.done, a.gather, a.live = self.done.data_ptr(), self.gather.data_ptr(), self.live.data_ptr()
             self.cur = 0
             self._plans = [None, None]                     # (step plan, merge arguments) of the even / odd steps
+            self.div = ctrl[2:] or None                    # (G, lambda) of a diverse search: the group-aware merge / select
             # no_repeat_ngram / min_len: two ban buffers that ping-pong with the candidate tables - the list of step t is
             # built from the tables step t - 1 wrote (isc_beam_ngram_ban, behind its merge / select; in front of step 0
             # from the empty tables) and read by step t's candidate masks.  Pointers repeat with period 2, as the tables'.
             self.ban = None
-            if ctrl != (0, 0):
+            if ctrl[:2] != (0, 0):
                 from ._lib import BeamNgramBanArgs, RowsBan
                 self.ban_ids = torch.zeros(2, rows, T, dtype=torch.int64, device=dev)
                 self.ban_cnt = torch.zeros(2, rows, dtype=torch.int32, device=dev)
@@ -518,7 +538,10 @@ class _Search:
             if t < 2 and not ops.TIMER.armed and '_plan' in self.ws:
                 plan = self.ws['_plan']
                 self._plans[t] = (type(plan).from_buffer_copy(plan), type(a).from_buffer_copy(a))
-        ops.beam_merge(a)
+        if self.div is None:
+            ops.beam_merge(a)
+        else:
+            ops.beam_merge_groups(a, *self.div)
         if self.ban is not None and t + 1 < self.T:
             self._ban_lists(nxt, t + 1, self.live.data_ptr() + 4 * (t + 1) if self.gated else None)
         self.cur = nxt
@@ -562,7 +585,10 @@ class _Search:
             if t < 2 and '_plan' in self.ws:
                 plan = self.ws['_plan']
                 self._plans[t & 1] = (type(plan).from_buffer_copy(plan), type(x).from_buffer_copy(x), type(a).from_buffer_copy(a))
-        ops.beam_select(a)
+        if self.div is None:
+            ops.beam_select(a)
+        else:
+            ops.beam_select_groups(a, *self.div)
         if self.ban is not None and t + 1 < self.T:
             self._ban_lists(nxt, t + 1, self.live.data_ptr() + 4 * (t + 1))
         self.cur = nxt

@@ -1377,20 +1377,22 @@ class Captioner(nn.Module):
 
     # ------------------------------------------------------------------ beam search
     def sample(self, fc_feat, att_feat, senti_words=None, senti_label=None,
-               beam_size=3, decoding_constraint=1, max_seq_len=16, no_repeat_ngram=0, min_len=0):
-        """Beam search for ONE image (captioner.py:351-420): returns (captions, scores).  `no_repeat_ngram` / `min_len`:
-        see sample_batch."""
+               beam_size=3, decoding_constraint=1, max_seq_len=16, no_repeat_ngram=0, min_len=0, beam_groups=1,
+               diversity=0.0):
+        """Beam search for ONE image (captioner.py:351-420): returns (captions, scores).  `no_repeat_ngram` / `min_len` /
+        `beam_groups` / `diversity`: see sample_batch."""
         caps, scores, _ = self.sample_batch(
             fc_feat.reshape(1, -1), att_feat.reshape(1, -1, att_feat.shape[-1]),
             None if senti_words is None else senti_words.reshape(1, -1),
             None if senti_label is None else senti_label.reshape(1),
-            beam_size, decoding_constraint, max_seq_len, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+            beam_size, decoding_constraint, max_seq_len, no_repeat_ngram=no_repeat_ngram, min_len=min_len,
+            beam_groups=beam_groups, diversity=diversity)
         return caps[0], scores[0]
 
     @torch.no_grad()
     def sample_batch(self, fc_feats, att_feats, senti_words=None, senti_labels=None,
                      beam_size=3, decoding_constraint=1, max_seq_len=16, share_image=False, no_repeat_ngram=0,
-                     min_len=0):
+                     min_len=0, beam_groups=1, diversity=0.0):
         """Beam search for I images at once: every step runs ONE batched decode step over I*beam rows
         and one device top-k; candidate bookkeeping follows the reference exactly (fp64 score sums,
         stable ordering, ended beams carried, captioner.py:378-411).
@@ -1402,9 +1404,16 @@ class Captioner(nn.Module):
         complete a second occurrence are banned like <PAD> / <SOS> / <UNK> (log-prob -inf for the top-`beam` only, the
         log-softmax untouched).  `min_len=m`: <EOS> is banned before m words.  Both act inside the per-step top-k on the
         device (isc_beam_ngram_ban); the reference has neither.  They need the device-side merge and a vocabulary of more
-        than max_seq_len + 4 + beam_size words (ValueError otherwise, before anything touches the device)."""
-        from .beam import check_controls
+        than max_seq_len + 4 + beam_size words (ValueError otherwise, before anything touches the device).
+        `beam_groups=G, diversity=lambda` (diverse beam search, Vijayakumar et al. 2016; the reference has none): the
+        `beam_size` ranks of a search form G groups of beam_size / G, handled in order at every step; a child's key is
+        its score minus lambda for every candidate the groups in front selected at this step with the same token, a group
+        keeps its best beam_size / G by key.  Scores stay the model's log-probability sums; the results come group-major
+        (group 0's captions, then group 1's, ...).  G must divide beam_size, lambda is a finite number >= 0; G > 1 needs
+        the device-side merge (ValueError otherwise).  G = 1 is the plain search for any lambda."""
+        from .beam import check_controls, check_groups
         ctrl = check_controls(self, beam_size, max_seq_len, no_repeat_ngram, min_len)      # (raises first)
+        grp = check_groups(self, beam_size, beam_groups, diversity)
         share = bool(share_image)
         if senti_labels is not None and senti_labels.dim() != 1 and senti_labels.numel() == fc_feats.shape[0]:
             senti_labels = senti_labels.reshape(-1)              # ([I, 1] and the like: one label per image, as always)
@@ -1412,7 +1421,7 @@ class Captioner(nn.Module):
             raise ValueError('sample_batch: senti_labels must be [I] (one label per image; several labels per image: '
                              'sample_sentiments), got shape %s' % (tuple(senti_labels.shape),))
         return self._beam_call(fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
-                               max_seq_len, share, *ctrl)
+                               max_seq_len, share, *ctrl, groups=grp)
 
     @staticmethod
     def _check_sentiments(n_cat, fc_feats, senti_words, senti_labels, beam_size, device_merge, labels_known=False):
@@ -1447,7 +1456,8 @@ class Captioner(nn.Module):
 
     @torch.no_grad()
     def sample_sentiments(self, fc_feats, att_feats, senti_words, senti_labels, beam_size=3, decoding_constraint=1,
-                          max_seq_len=16, _labels_known=False, no_repeat_ngram=0, min_len=0):
+                          max_seq_len=16, _labels_known=False, no_repeat_ngram=0, min_len=0, beam_groups=1,
+                          diversity=0.0):
         """Beam search of I images under S sentiment labels each, the image's tensors shared: senti_labels [I, S] (row i:
         the category ids image i is captioned under, any order), senti_words [I, M] (the image's words under every label)
         or [I, S, M].  A search is an (image, label) pair: I*S searches of `beam_size` rows advance together, the
@@ -1456,23 +1466,24 @@ class Captioner(nn.Module):
         (isc_step_plan.row_div / senti_div).  Up to 8 rows (1 image x 2 labels x beam 3 or 4, 1 x 3 x 2) the search runs on
         the few-row step, from ONE graph when beam graphs are enabled; more rows run on the general kernels.  Each
         (image, label) result is that of `sample` under that label: same candidates, scores to rounding.
-        `no_repeat_ngram` / `min_len`: as sample_batch.
+        `no_repeat_ngram` / `min_len` / `beam_groups` / `diversity`: as sample_batch (the groups are each search's own).
         Returns (captions[I][S][beam], scores[I][S][beam], id_sequences[I][S][beam])."""
-        from .beam import check_controls
+        from .beam import check_controls, check_groups
         ctrl = check_controls(self, beam_size, max_seq_len, no_repeat_ngram, min_len)      # (raises first)
+        grp = check_groups(self, beam_size, beam_groups, diversity)
         I, S = self._check_sentiments(self.senti_label_embed[0].num_embeddings, fc_feats, senti_words, senti_labels, beam_size,
                                       getattr(self, 'beam_device_merge', True), _labels_known)
         caps, scores, ids = self._beam_call(fc_feats, att_feats, senti_words, senti_labels, int(beam_size),
-                                            decoding_constraint, max_seq_len, True, *ctrl)
+                                            decoding_constraint, max_seq_len, True, *ctrl, groups=grp)
 
         def nest(x):
             return [x[i * S:(i + 1) * S] for i in range(I)]
         return nest(caps), nest(scores), nest(ids)
 
     def _beam_call(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint, max_seq_len,
-                   share, no_repeat_ngram=0, min_len=0):
+                   share, no_repeat_ngram=0, min_len=0, groups=(1, 0.0)):
         """sample_batch / sample_sentiments: graph serving, engine fallback and numerics checks around the search
-        (no_repeat_ngram / min_len: the callers' checked values)."""
+        (no_repeat_ngram / min_len / groups: the callers' checked values)."""
         from .beam import beam_search_batch, replay_if_captured
         if self.training:
             self.eval()
@@ -1485,7 +1496,7 @@ class Captioner(nn.Module):
             with ops.exact_fp32_engine(), ops.h3_weights_scope(self._dev, key=self._weights_key()):
                 res = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
                                         decoding_constraint, max_seq_len, graphs=False, share=share,
-                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len, groups=groups)
             ops.device_status(reset=True)          # (NaN / inf features flag there as well: decoded as they are)
             return res
         # A search ends with a host read of its results, so the numerics flags are visible right behind it: no pass over
@@ -1494,13 +1505,13 @@ class Captioner(nn.Module):
         if checks and ops.h3_mode() != 0 and self._known_out_of_domain(fc_feats, att_feats):
             return on_exact_engine()
         out = replay_if_captured(self, fc_feats, att_feats, senti_words, senti_labels, beam_size, decoding_constraint,
-                                 max_seq_len, share, no_repeat_ngram, min_len)
+                                 max_seq_len, share, no_repeat_ngram, min_len, groups)
         if out is None:
             self._p()                              # raises on CPU parameters before anything touches the device
             with ops.h3_weights_scope(self._dev, key=self._weights_key()):     # prologue + search: weights split once
                 out = beam_search_batch(self, fc_feats, att_feats, senti_words, senti_labels, beam_size,
                                         decoding_constraint, max_seq_len, share=share,
-                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+                                        no_repeat_ngram=no_repeat_ngram, min_len=min_len, groups=groups)
         if checks:                                 # the host has the results, i.e. has waited: read the status too
             if ops.h3_mode() != 0 and ops.device_status(reset=True):
                 self._known_out_of_domain(fc_feats, att_feats, remember=True)

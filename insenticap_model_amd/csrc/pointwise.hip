@@ -232,6 +232,113 @@ extern "C" int isc_beam_merge(const isc_beam_merge_args *args, void *stream) {
     return ISC_OK;
 }
 
+// ------------------------------------------------------------------ diverse beam search: the merge, group by group
+// The search's `beam` rows form `groups` groups of bp = beam / groups ranks; group g's candidates are those of its own
+// parents (insertion order as above: a contiguous range of the candidate table), ranked by
+//     key = (s_parent + (double)logp) - lambda * (double)c,    c = tokens appended by the winners of groups < g that equal
+// the candidate's (a carried candidate: its score).  One add, one multiply, one subtract - never an FMA, so that the host
+// restatement and both kernels agree in bits.  The stored score is the un-augmented sum.
+__device__ __forceinline__ double beam_group_key(double s, double lambda, int c) {
+#pragma clang fp contract(off)
+    const double pen = lambda * (double)c;
+    return s - pen;
+}
+static inline bool beam_groups_ok(int beam, int groups, double lambda) {
+    return groups >= 1 && beam % groups == 0 && lambda >= 0.0 && lambda <= 1.79769313486231570e308;   // (NaN fails both)
+}
+
+__global__ __launch_bounds__(64) void beam_merge_groups_kernel(const isc_beam_merge_args a, const int groups,
+                                                               const double lambda) {
+    __shared__ double cs[ISC_BEAM_MAX * ISC_BEAM_MAX], ckey[ISC_BEAM_MAX * ISC_BEAM_MAX];
+    __shared__ long long ctok[ISC_BEAM_MAX * ISC_BEAM_MAX], chosen[ISC_BEAM_MAX];    // chosen: appended token by rank, -1 = carried
+    __shared__ int cpar[ISC_BEAM_MAX * ISC_BEAM_MAX], ccar[ISC_BEAM_MAX * ISC_BEAM_MAX], coff[ISC_BEAM_MAX + 1];
+    __shared__ int s_all_ended;
+    const int i = blockIdx.x, tid = threadIdx.x, beam = a.beam, T = a.T, rows = a.n_img * beam, base = i * beam;
+    const int bp = beam / groups;
+    if (a.done[i]) {                      // frozen image: as beam_merge_kernel
+        for (int k = tid; k < beam; k += 64) {
+            a.gather[base + k] = base + k + rows;
+            a.last_out[base + k] = a.last_in[base + k];
+            a.score_out[base + k] = a.score_in[base + k];
+            a.len_out[base + k] = a.len_in[base + k];
+        }
+        for (int e = tid; e < beam * T; e += 64) a.words_out[(long long)base * T + e] = a.words_in[(long long)base * T + e];
+        return;
+    }
+    // parents: every row; at t == 0 the first row of every group (the rows of a search all decode the same step 0)
+    if (tid == 0) {
+        int off = 0, all_ended = 1;
+        for (int k = 0; k < beam; ++k) {
+            coff[k] = off;
+            if (a.t == 0 && k % bp != 0) continue;
+            const int ended = a.t > 0 && a.last_in[base + k] == a.eos_id;
+            off += ended ? 1 : beam;
+            all_ended &= ended;
+        }
+        coff[beam] = off;
+        s_all_ended = all_ended;
+    }
+    __syncthreads();
+    for (int e = tid; e < beam * beam; e += 64) {
+        const int k = e / beam, j = e % beam, row = base + k;
+        if (a.t == 0 && k % bp != 0) continue;
+        const int ended = a.t > 0 && a.last_in[row] == a.eos_id;
+        if (ended) {
+            if (j == 0) { const int c = coff[k]; cs[c] = a.score_in[row]; ctok[c] = a.last_in[row]; cpar[c] = k; ccar[c] = 1; }
+        } else {
+            const int c = coff[k] + j;
+            cs[c] = a.score_in[row] + (double)a.top_val[(long long)row * beam + j];
+            ctok[c] = a.top_idx[(long long)row * beam + j];
+            cpar[c] = k; ccar[c] = 0;
+        }
+    }
+    __syncthreads();
+    for (int g = 0; g < groups; ++g) {
+        const int lo = coff[g * bp], hi = coff[(g + 1) * bp], c = lo + tid;      // hi - lo <= bp * beam <= 32
+        if (c < hi) {
+            int cnt = 0;
+            if (!ccar[c])
+                for (int s = 0; s < g * bp; ++s) cnt += chosen[s] == ctok[c];
+            ckey[c] = ccar[c] ? cs[c] : beam_group_key(cs[c], lambda, cnt);
+        }
+        __syncthreads();
+        if (c < hi) {
+            const double key = ckey[c];
+            int rank = 0;
+            for (int j = lo; j < hi; ++j) rank += (ckey[j] > key) || (ckey[j] == key && j < c);
+            if (rank < bp) {
+                const int par = cpar[c], car = ccar[c], dst = base + g * bp + rank, srow = base + par;
+                chosen[g * bp + rank] = car ? -1 : ctok[c];
+                a.score_out[dst] = cs[c];
+                a.last_out[dst] = ctok[c];
+                a.gather[dst] = car ? srow + rows : srow;
+                const int len = a.len_in[srow];
+                for (int e = 0; e < T; ++e) a.words_out[(long long)dst * T + e] = a.words_in[(long long)srow * T + e];
+                if (!car && len < T) a.words_out[(long long)dst * T + len] = ctok[c];
+                a.len_out[dst] = len + (car ? 0 : 1);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (s_all_ended) a.done[i] = 1;
+        else atomicAdd(&a.live[a.t + 1], 1);
+    }
+}
+
+extern "C" int isc_beam_merge_groups(const isc_beam_merge_args *args, int groups, double lambda, void *stream) {
+    if (!args) return ISC_E_NULL;
+    const isc_beam_merge_args &a = *args;
+    if (!a.top_val || !a.top_idx || !a.score_in || !a.score_out || !a.last_in || !a.last_out || !a.words_in ||
+        !a.words_out || !a.len_in || !a.len_out || !a.done || !a.gather || !a.live)
+        return ISC_E_NULL;
+    if (a.n_img <= 0 || a.beam <= 0 || a.beam > ISC_BEAM_MAX || a.T <= 0 || a.t < 0 || a.t >= a.T) return ISC_E_SHAPE;
+    if (!beam_groups_ok(a.beam, groups, lambda)) return ISC_E_SHAPE;
+    hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(a.n_img), dim3(64), 0, (hipStream_t)stream, a, groups, lambda);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
 // New recurrent state of every beam row: out[p, r, :] = (gather[r] < rows ? next : current)[p, gather[r] % rows, :]
 // for the P = 4 planes (h|c x layer) of a [P, rows, H] state - one launch instead of a concatenation + index_select.
 __global__ __launch_bounds__(256) void beam_gather_kernel(const float *nxt, const float *cur, const int64_t *gather,
@@ -1626,13 +1733,23 @@ __device__ __forceinline__ float sel_wave_sum(float v) {                // == fu
         cid[Q][s_] = me##Q ? cid[Q][s_ + 1] : cid[Q][s_];                                   \
     }
 
-__global__ __launch_bounds__(1024) void beam_select_kernel(const isc_beam_select_args a) {
+// GR: the diverse search's group-sequential rank phase (isc_beam_select_groups; `groups` groups of bp = beam / groups
+// ranks, beam_group_key's keys) - everything in front of the candidates and behind the winners is the plain search's.
+struct sel_groups { int groups; double lambda; };
+__device__ __forceinline__ sel_groups sel_groups_of() { return sel_groups{1, 0.0}; }
+__device__ __forceinline__ sel_groups sel_groups_of(const sel_groups q) { return q; }
+// (GQ: empty for the plain search, whose kernel keeps its one argument; one sel_groups for the diverse one)
+template <bool GR, typename... GQ>
+__global__ __launch_bounds__(1024) void beam_select_kernel(const isc_beam_select_args a, const GQ... gq) {
+    const int groups = sel_groups_of(gq...).groups;
+    const double lambda = sel_groups_of(gq...).lambda;
     extern __shared__ __attribute__((aligned(16))) unsigned char sel_smem[];
     __shared__ double cs[64];                          // the image's candidates (<= beam x beam): score,
     __shared__ long long ctk[64];                      //   token
     __shared__ float nrm[ISC_BEAM_MAX][2];             // per row: max, log(sum)
     __shared__ int w_par[ISC_BEAM_MAX], w_car[ISC_BEAM_MAX], w_len[ISC_BEAM_MAX];     // winners by rank
     __shared__ long long w_tok[ISC_BEAM_MAX];
+    __shared__ int cpen[GR ? 64 : 1], w_pen[GR ? ISC_BEAM_MAX : 1];     // GR: appended token of a candidate (-1: carried) / winner (-2)
     rows_kernarg_warm<ROWS_KERNARG_LINES(isc_beam_select_args)>();
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1741,8 +1858,22 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const isc_beam_select
     // ---- which parents have ended, where each parent's candidates start, how many there are: scalar work on one ballot
     const int ncand = a.t == 0 ? 1 : beam;
     const unsigned endm = a.t > 0 ? (unsigned)__ballot(my_last == a.eos_id) & ((1u << beam) - 1u) : 0u;
-    const int n = ncand * beam - (beam - 1) * __builtin_popcount(endm & ((1u << ncand) - 1u));
-    const int nrow = n < beam ? n : beam;             // (t == 0: one live parent still yields `beam` rows)
+    // (GR: the parents are every row, at t == 0 the first row of every group - actm; candidates in front of parent p: gck(p))
+    const int bp = GR ? beam / groups : beam;
+    unsigned actm = (1u << ncand) - 1u;
+    if constexpr (GR) {
+        actm = (1u << beam) - 1u;
+        if (a.t == 0) {
+            actm = 0u;
+            for (int g = 0; g < groups; ++g) actm |= 1u << (g * bp);
+        }
+    }
+    auto gck = [&](int p) {
+        const unsigned below = (1u << p) - 1u;
+        return beam * __builtin_popcount(actm & below) - (beam - 1) * __builtin_popcount(endm & actm & below);
+    };
+    const int n = GR ? gck(beam) : ncand * beam - (beam - 1) * __builtin_popcount(endm & ((1u << ncand) - 1u));
+    const int nrow = GR ? beam : n < beam ? n : beam;             // (t == 0: one live parent still yields `beam` rows)
     float myraw = -INFINITY;              // lane k < beam of a merge wave: the row's k-th best (raw logit, word id)
     int myid = 0;
     if (merger) {
@@ -1813,21 +1944,69 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const isc_beam_select
         }
         // ---- parent `wave`'s candidates (captioner.py:378-411; beam_merge_kernel's rules): an ended parent is carried as
         // ONE candidate with its score, a live one expands into its `beam` best words
-        if (wave < ncand) {
+        if (GR ? (actm >> wave) & 1u : wave < ncand) {
             const int ended = (endm >> wave) & 1u;
-            const int ck = wave * beam - (beam - 1) * __builtin_popcount(endm & ((1u << wave) - 1u));
+            const int ck = GR ? gck(wave) : wave * beam - (beam - 1) * __builtin_popcount(endm & ((1u << wave) - 1u));
             const double sc_k = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_score), wave),
                                                  __builtin_amdgcn_readlane(__double2loint(my_score), wave));
             if (lane < (ended ? 1 : beam)) {
                 cs[ck + lane] = ended ? sc_k : sc_k + (double)myv;
                 ctk[ck + lane] = ended ? a.eos_id : (long long)((unsigned)myid < (unsigned)a.V ? myid : 0);
+                if constexpr (GR) cpen[ck + lane] = ended ? -1 : ((unsigned)myid < (unsigned)a.V ? myid : 0);
             }
         }
     }
     RSTAMP(4);
     __syncthreads();                                              // candidates
     RSTAMP(5);
-    if (merger) {
+    if constexpr (GR) {
+        // ---- group-sequential rank: round g is the plain rank over group g's candidates [lo, hi) (<= bp x beam <= 32: four
+        // per lane, eight lanes per candidate) by their keys; a key is formed where it is compared - the score, the
+        // candidate's appended token against the g x bp winners' in front of it (w_pen).  One barrier between rounds: the
+        // next group's waves read this round's w_pen.
+        const int wgrp = wave / bp;                       // (merge waves: the group of parent `wave`)
+        for (int g = 0; g < groups; ++g) {
+            if (merger && wgrp == g && ((actm >> wave) & 1u)) {
+                const int ended = (endm >> wave) & 1u;
+                const int ck = gck(wave), lo = gck(g * bp), hi = gck((g + 1) * bp), nch = g * bp;
+                const int j = lane >> 3, s_ = lane & 7, c = ck + j;
+                const bool mine_ok = j < (ended ? 1 : beam);
+                auto key_of = [&](int it) {
+                    const int pen = cpen[it];
+                    int cn = 0;
+                    for (int s = 0; s < nch; ++s) cn += w_pen[s] == pen;
+                    return pen < 0 ? cs[it] : beam_group_key(cs[it], lambda, cn);
+                };
+                const double mine = key_of(mine_ok ? c : lo);
+                int cnt = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int it = lo + s_ + 8 * u;
+                    const double o = key_of(it < hi ? it : lo);
+                    cnt += (it < hi) & ((int)(o > mine) | ((int)(o == mine) & (int)(it < c)));
+                }
+                cnt += isc_dpp<ISC_DPP_XOR1>(cnt);
+                cnt += isc_dpp<ISC_DPP_XOR2>(cnt);
+                cnt += isc_dpp<ISC_DPP_HALF_MIRROR>(cnt);
+                if (s_ == 0 && mine_ok && cnt < bp) {
+                    const int len = __builtin_amdgcn_readlane(my_len, wave);
+                    const int slot = nch + cnt, dst = base + slot;
+                    const long long tok = ctk[c];
+                    w_par[slot] = wave; w_car[slot] = ended; w_len[slot] = len; w_tok[slot] = tok;
+                    w_pen[slot] = ended ? -2 : cpen[c];
+                    a.score_out[dst] = cs[c];                   // the model's log-probability: un-augmented
+                    a.last_out[dst] = tok;
+                    a.src_row[dst] = base + wave;
+                    a.len_out[dst] = len + (ended ? 0 : 1);
+                }
+            }
+            if (g + 1 < groups) __syncthreads();
+        }
+        if (tid == 0) {
+            if ((endm & actm) == actm) a.done[i] = 1;
+            else atomicAdd(&a.live[a.t + 1], 1);
+        }
+    } else if (merger) {
         if (wave < ncand) {
             // stable descending rank of candidate c = ck + j: lanes 8 j .. 8 j + 7 each count an eighth of the others
             const int ended = (endm >> wave) & 1u;
@@ -1883,9 +2062,8 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const isc_beam_select
 }
 #undef SEL_SHIFT
 
-extern "C" int isc_beam_select(const isc_beam_select_args *args, void *stream) {
-    if (!args) return ISC_E_NULL;
-    const isc_beam_select_args &a = *args;
+// The argument checks of both entry points; *lds_out = the launch's dynamic LDS.
+static int beam_select_check(const isc_beam_select_args &a, size_t *lds_out) {
     if (!a.part_max || !a.part_sum || !a.cand_val || !a.cand_idx || !a.score_in || !a.score_out || !a.last_in ||
         !a.last_out || !a.words_in || !a.words_out || !a.len_in || !a.len_out || !a.done || !a.src_row || !a.live)
         return ISC_E_NULL;
@@ -1901,15 +2079,48 @@ extern "C" int isc_beam_select(const isc_beam_select_args *args, void *stream) {
     if (a.state_out) lds += (size_t)a.state_planes * a.beam * a.H * 4 + 1024;    // + the image's rows of the state (whole 1 KB pieces)
     if (lds > 150000) return ISC_E_SHAPE;
     if (a.T > 256) return ISC_E_SHAPE;
+    *lds_out = lds;
+    return ISC_OK;
+}
+
+extern "C" int isc_beam_select(const isc_beam_select_args *args, void *stream) {
+    if (!args) return ISC_E_NULL;
+    const isc_beam_select_args &a = *args;
+    size_t lds = 0;
+    const int rc = beam_select_check(a, &lds);
+    if (rc != ISC_OK) return rc;
     static std::atomic<bool> attr_set{false};
     if (!attr_set.load()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_select_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_select_kernel<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 150000);
         if (e != hipSuccess) return (int)e;
         attr_set.store(true);
     }
     // one merge wave + one side wave per beam row
-    hipLaunchKernelGGL(beam_select_kernel, dim3(a.n_img), dim3(128 * a.beam), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(beam_select_kernel<false>, dim3(a.n_img), dim3(128 * a.beam), lds, (hipStream_t)stream, a);
+    ISC_LAUNCH_CHECK();
+    return ISC_OK;
+}
+
+extern "C" int isc_beam_select_groups(const isc_beam_select_args *args, int groups, double lambda, void *stream) {
+    if (!args) return ISC_E_NULL;
+    const isc_beam_select_args &a = *args;
+    size_t lds = 0;
+    const int rc = beam_select_check(a, &lds);
+    if (rc != ISC_OK) return rc;
+    if (!beam_groups_ok(a.beam, groups, lambda)) return ISC_E_SHAPE;
+    // one group is the plain search for any lambda (no candidate is penalised): the plain kernel.  The group rounds below
+    // rank at most 32 candidates (four per lane), which holds for groups >= 2 only: bp x beam <= (beam / 2) x beam <= 32.
+    if (groups == 1) return isc_beam_select(args, stream);
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set.load()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_select_kernel<true, sel_groups>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150000);
+        if (e != hipSuccess) return (int)e;
+        attr_set.store(true);
+    }
+    hipLaunchKernelGGL((beam_select_kernel<true, sel_groups>), dim3(a.n_img), dim3(128 * a.beam), lds, (hipStream_t)stream, a,
+                       sel_groups{groups, lambda});
     ISC_LAUNCH_CHECK();
     return ISC_OK;
 }

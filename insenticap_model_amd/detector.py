@@ -693,11 +693,12 @@ class Detector(nn.Module):
         return labels
 
     def sample(self, fc_feats, att_feats, sentis_tensor=None, beam_size=3, decoding_constraint=1, no_repeat_ngram=0,
-               min_len=0):
+               min_len=0, beam_groups=1, diversity=0.0):
         """One image: detect its sentiment, then beam search (decoder.py:182-192).  sentis_tensor=None: the image's
         sentiment words are derived on the device from its detected concepts (set_concept_detector with a table) and the
-        search is queued behind them without a host read; without a table ValueError.  `no_repeat_ngram` / `min_len`: the
-        beam search's controls (Captioner.sample_batch)."""
+        search is queued behind them without a host read; without a table ValueError.  `no_repeat_ngram` / `min_len` /
+        `beam_groups` / `diversity`: the beam search's controls (Captioner.sample_batch)."""
+        self._check_groups(beam_size, beam_groups, diversity)
         self.eval()
         if sentis_tensor is None:
             if self.__dict__.get('concept_detector') is None or self.__dict__.get('senti_table') is None:
@@ -709,17 +710,23 @@ class Detector(nn.Module):
         senti_label, _, _ = self.senti_detector.sample_device(self._detector_input(att_feats), self.senti_threshold)
         captions, _ = self.captioner.sample(fc_feats, att_feats, sentis_tensor, senti_label, beam_size,
                                             decoding_constraint, self.max_seq_len, no_repeat_ngram=no_repeat_ngram,
-                                            min_len=min_len)
+                                            min_len=min_len, beam_groups=beam_groups, diversity=diversity)
         return captions, self.senti_detector.names(senti_label)
 
+    def _check_groups(self, beam_size, beam_groups, diversity):
+        """`beam_groups` / `diversity` checked first thing, before the detector touches the device."""
+        from .beam import check_groups
+        return check_groups(self.captioner, beam_size, beam_groups, diversity)
+
     def sample_sentiments(self, fc_feats, att_feats, sentis_tensor=None, sentiments=None, beam_size=3,
-                          decoding_constraint=1, no_repeat_ngram=0, min_len=0):
+                          decoding_constraint=1, no_repeat_ngram=0, min_len=0, beam_groups=1, diversity=0.0):
         """One image captioned under several sentiments at once: `sentiments` is a list of category names (default: all of
         the detector's sentiment_categories, in their order); the searches share the image's region tensors
         (Captioner.sample_sentiments).  The sentiment words are `sentis_tensor` or, when None, derived from the image's
         detected concepts as in `sample`; they are the image's and serve every sentiment.  Returns
         ({sentiment: captions}, detected) - `detected` is the image's own detected sentiment, as `sample` returns it.
         An unknown or repeated name, or an empty list, is a ValueError before anything touches the device."""
+        self._check_groups(beam_size, beam_groups, diversity)
         cats = list(self.senti_detector.sentiment_categories)
         names = cats if sentiments is None else list(sentiments)
         if isinstance(sentiments, str) or not names:
@@ -742,7 +749,7 @@ class Detector(nn.Module):
         captions, _, _ = self.captioner.sample_sentiments(fc_feats.reshape(1, -1), att_feats, sentis_tensor.reshape(1, -1),
                                                           labels, beam_size, decoding_constraint, self.max_seq_len,
                                                           _labels_known=True, no_repeat_ngram=no_repeat_ngram,
-                                                          min_len=min_len)
+                                                          min_len=min_len, beam_groups=beam_groups, diversity=diversity)
         return dict(zip(names, captions[0])), self.senti_detector.names(detected)
 
     def set_encoder(self, enc):
@@ -752,12 +759,13 @@ class Detector(nn.Module):
         return self
 
     def sample_image(self, image, beam_size=3, decoding_constraint=1, att_size=14, sentiments=None, no_repeat_ngram=0,
-                     min_len=0):
+                     min_len=0, beam_groups=1, diversity=0.0):
         """One image from its pixels: uint8 [H, W, 3] / [H, W] as decoded (the normalisation is fused into the encoder's
         first kernel) or a `preprocess`ed fp32 tensor [3, H, W] -> encoder -> sample(fc, att).  The sentiment words come
         from the concept detector (set_concept_detector with a table); no host read between the encoder and the search.
         `sentiments` (a list of category names): the image is captioned under each of them instead of under its detected
         sentiment - `sample_sentiments(fc, att, None, sentiments)`, which returns ({sentiment: captions}, detected)."""
+        self._check_groups(beam_size, beam_groups, diversity)
         enc = self.__dict__.get('encoder')
         if enc is None:
             raise ValueError('Detector.sample_image needs set_encoder')
@@ -768,5 +776,5 @@ class Detector(nn.Module):
                 fc, att = enc.encode_uint8(image, att_size)
         if sentiments is not None:
             return self.sample_sentiments(fc, att, None, sentiments, beam_size, decoding_constraint, no_repeat_ngram,
-                                          min_len)
-        return self.sample(fc, att, None, beam_size, decoding_constraint, no_repeat_ngram, min_len)
+                                          min_len, beam_groups, diversity)
+        return self.sample(fc, att, None, beam_size, decoding_constraint, no_repeat_ngram, min_len, beam_groups, diversity)

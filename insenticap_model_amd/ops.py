@@ -700,6 +700,11 @@ def beam_select(args):
     check(_lib.load().isc_beam_select(C.byref(args), stream()), 'isc_beam_select')
 
 
+def beam_select_groups(args, groups, diversity):
+    """isc_beam_select under the diverse search's rule (isc_beam_select_groups; see beam_merge_groups)."""
+    check(_lib.load().isc_beam_select_groups(C.byref(args), groups, diversity, stream()), 'isc_beam_select_groups')
+
+
 def step_bwd(plan):
     check(_lib.load().isc_step_bwd(C.byref(plan), stream()), 'isc_step_bwd')
 
@@ -1047,6 +1052,32 @@ def check_beam_controls(no_repeat_ngram, min_len, max_seq_len, vocab_size, beam,
 def beam_merge(args):
     """One candidate-merge step of a batched beam search on the device (isc_beam_merge)."""
     check(_lib.load().isc_beam_merge(C.byref(args), stream()), 'isc_beam_merge')
+
+
+def beam_merge_groups(args, groups, diversity):
+    """isc_beam_merge under the diverse search's rule: `groups` groups, Hamming penalty `diversity` per token already
+    chosen at this step by a group in front (isc_beam_merge_groups)."""
+    check(_lib.load().isc_beam_merge_groups(C.byref(args), groups, diversity, stream()), 'isc_beam_merge_groups')
+
+
+def check_beam_groups(beam_groups, diversity, beam, device_merge):
+    """The beam search's keywords `beam_groups` / `diversity`, checked before anything touches the device.  Returns
+    (G, lambda) as a plain int and float.  G = 1 is the plain search for any lambda and asks nothing of the other
+    arguments; G > 1 must divide `beam` and needs the device-side merge (beam <= 8) - ValueError otherwise.  A `beam` that
+    is no integer is left to the caller's own check."""
+    if isinstance(beam_groups, bool) or not hasattr(beam_groups, '__index__') or int(beam_groups) < 1:
+        raise ValueError('beam_groups must be an integer >= 1, got %r' % (beam_groups,))
+    G = int(beam_groups)
+    if isinstance(diversity, bool) or not isinstance(diversity, (int, float)) or not 0.0 <= float(diversity) < float('inf'):
+        raise ValueError('diversity must be a finite number >= 0, got %r' % (diversity,))
+    lam = float(diversity)
+    beam = int(beam) if hasattr(beam, '__index__') and not isinstance(beam, bool) else G
+    if beam % G:
+        raise ValueError('beam_groups = %d does not divide beam_size = %d' % (G, beam))
+    if G > 1 and (not device_merge or beam > 8):
+        raise ValueError('beam_groups > 1 is not built for the host merge (beam_device_merge = False or beam_size > 8): '
+                         'the groups are ranked on the device, inside the device-side merge')
+    return G, lam
 
 
 def beam_gather(state_next, state_cur, gather, out):
